@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/s of the dense-to-sparse ViT step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs if --dump-outputs is given, and prints
+the line (headline figure, ms_per_step and what the timed region itself counts).  --full adds everything else the benchmark measures:
+the per-kernel pass (roofline and HBM rates), the standalone gather and HBM copy measurements and the CPU baseline.
 
 N > 1: one process per GPU.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`:
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment), or - when WORLD_SIZE is not set - this process starts them itself
@@ -14,7 +18,7 @@ selection, kept-token gather, pruned blocks), MaskLoss + BackboneLoss, backward,
 resident in HBM.  Workload: DeiT-Small 224x224, single-stage pruning keep_ratio 0.5 at block 3, per-GPU batch 128
 (weak scaling: the global batch is 128 * N), fp32 (the reference computes in fp32).  Prints ONE JSON line on rank 0.
 
-Extra objects on the line:
+Extra objects on the line with --full:
   roofline      the dominant kernel (fp32 MFMA GEMM family): algorithmic FLOPs of every launch in the timed region /
                 their HIP-event durations, against the 157.3 TFLOP/s fp32 matrix peak of gfx950.
   gather        the kept-token gather/pack kernel: algorithmic bytes / HIP-event time, against 8 TB/s.
@@ -49,6 +53,8 @@ GEMM_MODE_ROOFLINE = {
 }
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E spec peak
 LARGE_LAUNCH_BYTES = 64e6      # HBM-bound kernels: launches that move at least this much are also reported on their own (`large_launches`)
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: an output with more elements is stored as this many elements at seeded positions
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
 
 
 def parse():
@@ -87,7 +93,15 @@ def parse():
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the instrumented pass (no per-kernel figures in the line)")
     ap.add_argument("--time-kernels-in-region", action="store_true",
                     help="put the per-kernel HIP events inside the timed region itself (they cost ~5 %% of the step: ~900 event records)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run the per-kernel pass (roofline, HBM rates), the standalone gather and HBM copy "
+                         "measurements and the CPU baseline (off: the run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned and the updated parameters to DIR/<name>.npy "
+                         "(float32 / float64; outputs of more than %d elements as a fixed, seeded sample)" % DUMP_SAMPLE)
     a = ap.parse_args()
+    if not a.full and (a.gemm_shapes_out or a.time_kernels_in_region):
+        ap.error("--gemm-shapes-out and --time-kernels-in-region come from the per-kernel pass: add --full")
     a.locs, a.keeps, a.arch, a.img = [3], [a.keep], "deit_small", 224
     if a.config == "c2":
         a.keeps = [0.7]
@@ -339,6 +353,34 @@ def gather_back_to_back(device, B, n=197, k=98, D=384, iters=100, nbuf=16):
     return {"us_per_launch": round(us, 2), "achieved": round(nbytes / us / 1e3, 1), "unit": "GB/s", "frac": round(nbytes / us / 1e3 / PEAK_HBM_GBS, 4)}
 
 
+def dump_outputs(out_dir, info, params):
+    """--dump-outputs: what the timed path handed its caller in the last timed step - TrainStep's return value (losses, logits, kept-token
+    ids, the features and attention rows the losses read) and the student's parameters after that step's AdamW update - as
+    out_dir/<name>.npy; list entries are <name>_<i>.  Floating-point outputs are stored in float32, integer ones in float64 (exact).
+    An output of more than DUMP_SAMPLE elements is stored as DUMP_SAMPLE elements at sorted positions drawn from a fixed seed: the
+    same positions for every run of the same shape, so two builds can be compared file by file."""
+    import numpy as np
+    arrays = {}
+    for key, val in sorted(list(info.items()) + [("student_params", params)]):
+        seq = val if isinstance(val, (list, tuple)) else [val]
+        for i, t in enumerate(seq):
+            if torch.is_tensor(t):
+                arrays[f"{key}_{i}" if isinstance(val, (list, tuple)) else key] = t.detach()
+    out = {}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            pos = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort()[0]
+            t = t.reshape(-1)[pos.to(t.device)]
+        out[name] = t.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def log(msg):
     print(f"[bench +{time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
@@ -470,7 +512,7 @@ def main():
     # The timed region runs WITHOUT per-kernel events: ~900 event records per step between the kernels cost about 5 % of the step
     # (measured: 42.5 vs 40.4 ms), i.e. they would perturb the throughput they sit beside.  The per-kernel figures come from an
     # identical instrumented pass of the same K steps right after it (same process, same stream, same inputs).
-    in_region = args.time_kernels_in_region and not args.no_kernel_timing
+    in_region = args.full and args.time_kernels_in_region and not args.no_kernel_timing
     timer.enabled = in_region
     timer.counting = True
     if in_region:
@@ -494,8 +536,11 @@ def main():
     captured = ts.last_step_captured
     loss = float(info["loss"])
     log(f"timed region done: {args.steps} steps in {elapsed:.3f} s, loss {loss:.5f}")
+    if args.dump_outputs and rank == 0:        # before the instrumented pass, which steps the model further
+        nbytes = dump_outputs(args.dump_outputs, info, ts.arena.params)
+        log(f"outputs of the last timed step written to {args.dump_outputs} ({nbytes / 2**20:.1f} MiB)")
     instr_elapsed = elapsed if in_region else None
-    if not args.no_kernel_timing and not in_region:
+    if args.full and not args.no_kernel_timing and not in_region:
         timer.enabled = True
         # per-kernel durations are only meaningful when kernels do not share the GPU: the instrumented pass runs the teacher's forward
         # in series with the student's (the timed region above overlaps them on two streams)
@@ -623,17 +668,18 @@ def main():
                     lgbs = lg["work"] / (lg["ms"] * 1e-3) / 1e9
                     line[key[0]]["large_launches"] = {"min_bytes": LARGE_LAUNCH_BYTES, "achieved": round(lgbs, 1), "frac": round(lgbs / PEAK_HBM_GBS, 4),
                                                       "launches_per_step": lg["launches"] / args.steps, "ms_per_step": round(lg["ms"] / args.steps, 3)}
-        line["hbm_copy_GBps_measured"] = hbm_copy_gbs(device)
-        # the same device-to-device copy at the size of ONE gather / LayerNorm launch of this workload (19.5 MB read + 19.5 MB written):
-        # what a 39 MB transfer can reach at all, launch ramp included - the yardstick for the in-step gather / scatter / LayerNorm rates
-        line["hbm_copy_GBps_at_39MB"] = hbm_copy_gbs(device, mbytes=19, reps=64, nbuf=16)      # 16 x 38 MB > the Infinity Cache
+        if args.full:
+            line["hbm_copy_GBps_measured"] = hbm_copy_gbs(device)
+            # the same device-to-device copy at the size of ONE gather / LayerNorm launch of this workload (19.5 MB read + 19.5 MB written):
+            # what a 39 MB transfer can reach at all, launch ramp included - the yardstick for the in-step gather / scatter / LayerNorm rates
+            line["hbm_copy_GBps_at_39MB"] = hbm_copy_gbs(device, mbytes=19, reps=64, nbuf=16)      # 16 x 38 MB > the Infinity Cache
         if distributed:
             c = ts.reducer.comm_summary(args.steps * (2 if (instr_elapsed is not None and not in_region) else 1))   # both passes all-reduce
             if c:
                 line["comm"] = c
                 # did the stream the step is issued on share a hardware queue with the process group's RCCL stream, and was the step moved
                 line["comm"]["rccl_stream_probe"] = ts.pg_probe
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             log("timing the CPU oracle (bounded sample)")
             line["cpu_baseline"] = cpu_baseline(args.keep)
         sys.stdout.flush()

@@ -184,13 +184,13 @@ def test_soft_target_cross_entropy_under_mixup():
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line with the driver's contract keys plus the `roofline` / `cpu_baseline`-style objects of this
-    scope (a short run: 2 timed steps, no CPU leg), and the per-kernel figures hang together (achieved <= peak, frac = achieved / peak, the
-    dominant kernel's launches per step is what the model issues)."""
+    """`python bench.py --full` prints ONE JSON line with the driver's contract keys plus the `roofline` / `cpu_baseline`-style objects of
+    this scope (a short run: 2 timed steps, no CPU leg), and the per-kernel figures hang together (achieved <= peak, frac = achieved / peak,
+    the dominant kernel's launches per step is what the model issues)."""
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(cases.REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(cases.REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -206,3 +206,32 @@ def test_bench_line_contract():
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and 0 < r["achieved"] <= r["peak"] == 157.3
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and r["launches_per_step"] == 159.0
     assert d["gather"]["bound"] == "hbm" and 0 < d["gather"]["frac"] < 1 and d["c_abi_calls_per_step"] < 200
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain `python bench.py` run (no --full) prints the headline line without the extra measurements, and --dump-outputs writes what
+    the last timed step returned (float32 / float64, within 64 MB, large outputs as a fixed-size sample)."""
+    import json
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(cases.REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "images/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 128 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-3
+    for key in ("roofline", "kernel_timing", "gather", "cpu_baseline", "hbm_copy_GBps_measured"):
+        assert key not in d, key
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(f.endswith(".npy") for f in os.listdir(tmp_path))
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["logits_s"].shape == (128, 1000) and files["logits_t"].shape == (128, 1000) and np.isfinite(files["logits_s"]).all()
+    kept = files["kept_0"]
+    assert kept.dtype == np.float64 and kept.shape == (128, 98) and (kept == np.round(kept)).all() and 0 <= kept.min() and kept.max() < 196
+    assert files["student_params"].shape == (1 << 20,) and files["student_params"].dtype == np.float32
+    assert abs(float(files["loss"]) - d["config"]["final_loss"]) < 1e-4
