@@ -1056,3 +1056,37 @@ class gemm_mode:
     def __exit__(self, *exc):
         _tls.stack.pop()
         return False
+
+
+# ---- input pipeline (csrc/augment.hip; d2s/data.py packs the batch) ------------------------------------------------------------------
+AUG_DESC_INTS = 64        # == d2s_augment_desc_ints(), checked by augment_images
+
+
+def augment_images(pix, desc, meta, size):
+    """Crop + resize (Pillow-exact) + flip + Normalize + RandomErasing + Mixup / CutMix of a packed batch, on the current stream.
+    pix: uint8 device buffer (a multiple of 16 bytes), desc: [B, AUG_DESC_INTS] int32 device descriptors, meta: the host maxima written
+    by d2s.data.pack_batch.  Returns fp32 [B, 3, size, size].  The scratch and the output are allocated on the current stream."""
+    if lib.query("d2s_augment_desc_ints") != AUG_DESC_INTS:
+        raise lib.D2SError("augment descriptor layout of the library and of d2s.ops disagree")
+    assert pix.dtype == torch.uint8 and pix.is_contiguous() and desc.dtype == torch.int32 and desc.is_contiguous()
+    B = desc.shape[0]
+    assert desc.shape == (B, AUG_DESC_INTS), desc.shape
+    inter = torch.empty(max(int(meta["total_rows"]) * size * 3, 16), dtype=torch.uint8, device=pix.device)
+    out = torch.empty((B, 3, size, size), dtype=torch.float32, device=pix.device)
+    rc = lib._fn("d2s_augment_images")(lib.ptr(pix), pix.numel(), lib.ptr(desc), B, int(size), int(meta["max_rows"]), int(meta["kmax_h"]),
+                                        int(meta["kmax_v"]), int(meta["rowbytes"]), int(meta["seed"]) & 0xFFFFFFFFFFFFFFFF,
+                                        lib.ptr(inter), lib.ptr(out), lib.stream())
+    if rc != 0:
+        raise lib.D2SError(f"d2s_augment_images failed with code {rc} (a crop more than ~40x the output size does not fit the "
+                           "coefficient tables)" if rc == -1 else f"d2s_augment_images failed with code {rc}")
+    return out
+
+
+def augment_labels(desc, num_classes, smoothing):
+    """timm's mixup_target from the per-sample (label, lam) of the descriptors: fp32 [B, num_classes]."""
+    B = desc.shape[0]
+    off = smoothing / num_classes                  # in double, then rounded to fp32 by the kernel argument, as torch.full does
+    on = 1. - smoothing + off
+    out = torch.empty((B, num_classes), dtype=torch.float32, device=desc.device)
+    lib.call("d2s_augment_labels", lib.ptr(desc), B, int(num_classes), on, off, lib.ptr(out))
+    return out

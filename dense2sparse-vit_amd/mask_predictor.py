@@ -1,11 +1,14 @@
 """Counterpart of the reference's entry script (mask_predictor.py:56-330): the same flags (utils.parse_args), the same sequence
 - student / teacher from the arch factories (:170-202), parameter groups + AdamW (:213-230), optional backbone freeze
 (:218-224), per epoch adjust_learning_rate -> train_one_epoch -> evaluate_performance (:295-310), best-accuracy tracking -
-on the accelerated path with synthetic batches (the image has no data set and no network; the reference's ImageNet folders,
-mixup transforms, wandb / tensorboard tracking and visualisations are outside the path).
+on the accelerated path, with synthetic batches by default or, with --data-source folder, the reference's ImageFolder split, training
+transform and Mixup/CutMix on the GPU input pipeline (d2s.data, csrc/augment.hip); wandb / tensorboard tracking and visualisations
+are outside the path.
 
     python dense2sparse-vit_amd/mask_predictor.py --arch deit_small --pruning-locs 3 --keep-ratios 0.5 --epochs 3 \\
         --warmup-steps 1 --batch-size 64 --steps-per-epoch 10
+    python dense2sparse-vit_amd/mask_predictor.py --arch deit_small --pruning-locs 3 --keep-ratios 0.5 --topk-selection \\
+        --data-source folder --imgnet-val-dir /path/to/imagefolder --batch-size 128
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         dense2sparse-vit_amd/mask_predictor.py --use-ddp ...        (one process per GPU, RCCL)
 """
@@ -48,10 +51,30 @@ def check_supported(args):
         bad.append(f"--mask-loss-type {args.mask_loss_type} (kl_div and mse are on the path; bce is broken in the reference)")
     if args.use_dp:
         bad.append("--use-dp (one process per GPU only: --use-ddp under torch.distributed.run)")
+    folder = getattr(args, "data_source", "synthetic") == "folder"
+    if folder:
+        if not args.imgnet_val_dir:
+            bad.append("--data-source folder needs --imgnet-val-dir DIR (an ImageFolder: one sub-directory per class)")
+        if args.train_interpolation not in ("bilinear", "bicubic", "random"):
+            bad.append(f"--train-interpolation {args.train_interpolation} (bilinear, bicubic and random are built)")
+        if (args.cutmix > 0 or args.cutmix_minmax is not None) and not args.mixup > 0:
+            bad.append("--cutmix without --mixup > 0 (BackboneLoss takes soft targets only when mixup > 0, as the reference does, and "
+                       "would read the soft labels as hard ones)")
+        if args.mixup_mode not in ("batch", "pair", "elem"):
+            bad.append(f"--mixup-mode {args.mixup_mode} (batch, pair or elem)")
+        if args.recount > 8:
+            bad.append("--recount above 8 (erase boxes per image)")
+        if not 0 <= args.num_workers <= 16:
+            bad.append("--num-workers outside 0..16")
     if bad:
         raise SystemExit("not on the accelerated path: " + "; ".join(bad))
     if args.predictor_bn and args.use_ddp:
         print("Attention: --predictor-bn keeps per-rank batch statistics (not synchronised), exactly like the reference")
+    if folder:
+        if (args.aa and args.aa.lower() != "none") or args.color_jitter > 0:
+            print("Attention: --aa / --color-jitter: RandAugment and ColorJitter are not built; the training transform is "
+                  "RandomResizedCrop + flip + Normalize + RandomErasing (+ Mixup/CutMix)")
+        return
     if args.mixup > 0 or args.cutmix > 0 or args.cutmix_minmax is not None:
         print("Attention: mixup/cutmix are not used (synthetic batches)")
     args.mixup, args.cutmix, args.cutmix_minmax = 0.0, 0.0, None
@@ -68,6 +91,23 @@ def build_models(args):
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
+
+
+def folder_loaders(args, samples, split, epoch, rank, world):
+    """The reference's ImageFolder loaders (mask_predictor.py:234-259, ddp_training.py:15-20) on the GPU input pipeline (d2s.data): the
+    training subset in a new order per epoch, one DistributedSampler-style shard per rank; Mixup when the reference enables it."""
+    from d2s import data
+    train_idx, val_idx = split
+    mix = None
+    if args.mixup > 0 or args.cutmix > 0 or args.cutmix_minmax is not None:                                # :261-267
+        mix = data.MixConfig(args.mixup, args.cutmix, tuple(args.cutmix_minmax) if args.cutmix_minmax else None, args.mixup_prob,
+                             args.mixup_switch_prob, args.mixup_mode, args.smoothing, args.nb_classes)
+    opts = data.AugmentOptions(args.train_interpolation, args.reprob, args.remode, args.recount)
+    common = dict(seed=42, epoch=epoch, rank=rank, num_workers=args.num_workers)
+    train = data.FolderLoader(samples, data.shard(data.epoch_order(train_idx, 42, epoch), rank, world), args.batch_size, args.device,
+                              train=True, opts=opts, mix=mix, **common)
+    val = data.FolderLoader(samples, data.shard(val_idx, rank, world), args.batch_size, args.device, train=False, **common)
+    return train, val
 
 
 def main(argv=None):
@@ -109,6 +149,14 @@ def main(argv=None):
             dist.broadcast(optim.arena.params, src=0)
     n_pred = sum(p.numel() for n, p in student.named_parameters() if 'predictor' in n and p.requires_grad)
     print(f'Total number of trainable parameters in predictor network in millions: {n_pred / 1e6}')
+    folder = args.data_source == "folder"
+    if folder:
+        from d2s import data
+        samples, classes = data.image_folder(args.imgnet_val_dir)
+        if len(classes) > args.nb_classes:
+            raise SystemExit(f"{len(classes)} classes in {args.imgnet_val_dir}, the heads have {args.nb_classes}")
+        split = data.split_indices(len(samples))
+        print(f"{len(samples)} images in {len(classes)} classes: {len(split[0])} train / {len(split[1])} val")
     print(f"Start training for {args.epochs} epochs, with batch size of {args.batch_size}")
     img = 224
     since, best_acc = time.time(), 0.0
@@ -123,8 +171,13 @@ def main(argv=None):
             optim.set_epoch(epoch)
         if args.topk_selection and hasattr(args, "current_sigma"):
             student.current_sigma = args.current_sigma
-        train_loader = utils.SyntheticLoader(args.steps_per_epoch, args.batch_size, img, seed=1000 * epoch + rank, device=args.device)
-        val_loader = utils.SyntheticLoader(args.val_steps, args.batch_size, img, seed=777 + rank, device=args.device)
+        if folder:
+            train_loader, val_loader = folder_loaders(args, samples, split, epoch, rank, world)
+            n_images = len(train_loader.set.order)
+        else:
+            train_loader = utils.SyntheticLoader(args.steps_per_epoch, args.batch_size, img, seed=1000 * epoch + rank, device=args.device)
+            val_loader = utils.SyntheticLoader(args.val_steps, args.batch_size, img, seed=777 + rank, device=args.device)
+            n_images = args.steps_per_epoch * args.batch_size
         t0 = time.time()
         train_metrics = train_one_epoch(args, student, teacher, train_loader, optim, None)                  # :308
         torch.cuda.synchronize()
@@ -138,7 +191,7 @@ def main(argv=None):
             dist.barrier()
         best_acc = max(best_acc, epoch_metrics['val_acc'])
         if rank == 0:
-            print(f"epoch {epoch + 1}: {args.steps_per_epoch * args.batch_size * world / dt:.1f} train images/s, " +
+            print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))
     elapsed = time.time() - since
     print(f'Training complete in {(elapsed // 60):.0f}m {(elapsed % 60):.0f}s')

@@ -72,8 +72,9 @@ class SyntheticLoader:
 
 def parse_args(argv=None):
     """The reference's command line (utils.py:182-317): same flag names, types and defaults, so job scripts written for the
-    reference run unchanged.  Data-set / augmentation / tracking flags are accepted and ignored (inputs are synthetic here:
-    no data set or network in the image); four synthetic-run flags are added at the end."""
+    reference run unchanged.  With the default --data-source synthetic the data-set / augmentation flags are accepted and ignored;
+    with --data-source folder they drive d2s.data (the tracking flags are always ignored).  The run flags added at the end are not in
+    the reference."""
     import argparse
     p = argparse.ArgumentParser(description='Transformers')
     p.add_argument('--arch', default='deit_small', type=str)
@@ -141,6 +142,9 @@ def parse_args(argv=None):
     p.add_argument('--torch-optim', action='store_true', default=False,
                    help="the reference's recipe (torch.optim.AdamW over get_param_groups) instead of the fused arena step")
     p.add_argument('--gemm-mode', choices=['exact', 'split', 'bf16'], default='exact')
+    p.add_argument('--data-source', choices=['synthetic', 'folder'], default='synthetic',
+                   help='synthetic N(0,1) batches, or an ImageFolder at --imgnet-val-dir (80/20 train/val split, GPU augmentation)')
+    p.add_argument('--num-workers', type=int, default=8, help='JPEG-decoding DataLoader workers of --data-source folder (at most 16)')
     return p.parse_args(argv)
 
 

@@ -287,6 +287,17 @@ int d2s_adamw_chunk_elems(void);
 int d2s_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* chunk_desc, int n_chunks,
                    float beta1, float beta2, float eps, int step, float grad_scale, int* chunk_steps, d2s_stream_t stream);
 
+/* ---- input pipeline: crop + resize (bit-exact with Pillow), flip, Normalize, RandomErasing, Mixup / CutMix (build_data_sets.py:8-34,
+ * train.py:29-31; d2s/data.py packs the batch) ------------------------------------------------------------------------------------ */
+int d2s_augment_desc_ints(void);
+/* pix: uint8 HWC images packed into one buffer (pix_bytes a multiple of 16); desc: [B, d2s_augment_desc_ints()] int32 per-sample
+ * descriptors (layout in csrc/augment.hip).  Host maxima over the batch: max_rows (source rows read per sample), kmax_h / kmax_v (filter
+ * taps), rowbytes (staged row segment bytes, a multiple of 16).  inter: scratch of sum(rows) * S * 3 bytes.  out: [B, 3, S, S] fp32. */
+int d2s_augment_images(const unsigned char* pix, long pix_bytes, const int* desc, int B, int S, int max_rows, int kmax_h, int kmax_v,
+                       int rowbytes, unsigned long long seed, unsigned char* inter, float* out, d2s_stream_t stream);
+/* out: [B, C] fp32 soft labels, timm's mixup_target (partner of sample i: B-1-i). */
+int d2s_augment_labels(const int* desc, int B, int C, float on, float off, float* out, d2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
