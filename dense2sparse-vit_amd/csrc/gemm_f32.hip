@@ -15,8 +15,6 @@
 // transposing ds_write_b32 of k-contiguous operands and the ds_read_b32 fragment reads conflict-free.
 // Global->register prefetch of tile t+1 is issued before the 32 MFMAs of tile t; one barrier per K-step.
 #include "gemm_common.h"
-#include <cstdio>
-#include <cstdlib>
 
 namespace {
 using namespace d2s_gemm;
@@ -97,8 +95,8 @@ __device__ __forceinline__ void load_tile_fast(const float* __restrict__ P, long
 
 template <int LAY, int BR>
 __device__ __forceinline__ void store_tile(float* __restrict__ S, int tid, const f32x4 (&r)[BR / 64]) {
-    // S: [BK][BR] floats, element (k,row) at k*BR + (row ^ (((k>>2)&3)<<3) ^ ((k&1)<<4)).  The (k&1)<<4 term makes the fragment reads of
-    // the 16x16x4 form (lanes l and l+16 of a half-wave read rows k and k+1 of the same 16 columns) conflict-free as well
+    // S: [BK][BR] floats, element (k,row) at k*BR + (row ^ (((k>>2)&3)<<3) ^ ((k&1)<<4)).  The (k&1)<<4 term was added for a 16x16x4 form of
+    // the kernel (since removed); the fragment reads below apply the same swizzle
 #pragma unroll
     for (int i = 0; i < BR / 64; ++i) {
         const int f = tid + i * 256;
@@ -293,131 +291,6 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 128) ? 3 : 1) void gemm_f3
         case EPI_ACCUM: store_tile_out<EPI_ACCUM, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
         default: store_tile_out<EPI_NONE, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
     }
-}
-
-// The same GEMM on v_mfma_f32_16x16x4_f32 (same FLOP per cycle as 32x32x2 - 64 per clock and SIMD - and the same exact fp32 fma chain,
-// k-ordered): a wave's 64x64 (32x32) sub-tile is 4x4 (2x2) accumulator blocks of 16x16.  Lane l feeds A[row = l & 15][k = l >> 4] and
-// B[k = l >> 4][col = l & 15], so one fragment register covers FOUR k values: per 16-deep K-step the wave issues the same 32 ds_read_b32 as
-// the 32x32x2 form but 64 MFMAs of 32 cycles instead of 32 of 64.  Used for the guard-free (FAST) shapes with the 16-byte epilogue; whether
-// it is the default is a measured choice (the chip may hold a different clock on the two shapes, MI355X_MICROARCH.md 'DVFS give-back' 7).
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-template <int ALAY, int BLAY, int BM, int BN>
-__global__ __launch_bounds__(256, (BM == 128 && BN == 128) ? 3 : 1) void gemm_f32_kernel16(GemmArgs p) {
-    constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 16, NT = WN / 16;   // 2x2 waves, each MT x NT MFMA blocks of 16x16
-    __shared__ __attribute__((aligned(16))) float smem[2 * BK * (BM + BN)];
-    float* As = smem;
-    float* Bs = smem + 2 * BK * BM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lq = lane >> 4, l15 = lane & 15;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int bm = bid / nbn, bn = bid % nbn;
-    const int row0 = bm * BM, col0 = bn * BN;
-    const int kbeg = blockIdx.z * p.k_per_slice;
-    const int kend = min(p.K, kbeg + p.k_per_slice);
-    const int nk = (kend - kbeg + BK - 1) / BK;
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const bool do_colsum = (ALAY == 1) && p.colsum != nullptr && bn == 0;
-    f32x4 csum[BM / 64];
-#pragma unroll
-    for (int i = 0; i < BM / 64; ++i) csum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    f32x4 ra[BM / 64], rb[BN / 64];
-    long offa[BM / 64], offb[BN / 64];
-    tile_offsets<ALAY, BM>(p.lda, row0, p.M, tid, offa);
-    tile_offsets<BLAY, BN>(p.ldb, col0, p.N, tid, offb);
-    if (nk > 0) {
-        load_tile_fast<ALAY, BM>(p.A, p.lda, kbeg, offa, ra);
-        load_tile_fast<BLAY, BN>(p.B, p.ldb, kbeg, offb, rb);
-        if (ALAY == 1 && do_colsum) {
-#pragma unroll
-            for (int i = 0; i < BM / 64; ++i) csum[i] += ra[i];
-        }
-        store_tile<ALAY, BM>(As, tid, ra);
-        store_tile<BLAY, BN>(Bs, tid, rb);
-    }
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        const int kn = kbeg + min(kt + 1, nk - 1) * BK;       // branch-free prefetch (the last trip re-reads the last slab and discards it)
-        load_tile_fast<ALAY, BM>(p.A, p.lda, kn, offa, ra);
-        load_tile_fast<BLAY, BN>(p.B, p.ldb, kn, offb, rb);
-        const float* Ac = As + cur * BK * BM;
-        const float* Bc = Bs + cur * BK * BN;
-        float a[2][MT], b[2][NT];
-        auto read_frags = [&](int q, float (&af)[MT], float (&bf)[NT]) {
-            const int k = 4 * q + lq;
-            const int sw = ((q & 3) << 3) ^ ((lq & 1) << 4);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) af[i] = Ac[k * BM + ((wm * WM + i * 16 + l15) ^ sw)];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bf[j] = Bc[k * BN + ((wn * WN + j * 16 + l15) ^ sw)];
-        };
-        read_frags(0, a[0], b[0]);
-#pragma unroll
-        for (int q = 0; q < BK / 4; ++q) {
-            if (q + 1 < BK / 4) read_frags(q + 1, a[(q + 1) & 1], b[(q + 1) & 1]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = mfma16(a[q & 1][i], b[q & 1][j], acc[i][j]);
-        }
-        {   // issue order of the K-step: fragment reads of quad q + 1 ahead of the MFMAs of quad q, global loads spread over the quads
-            constexpr int NL = BM / 64 + BN / 64, NQ = BK / 4;
-            __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                if (q + 1 < NQ) __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, MT * NT / 2, 0);
-                if (q < NL) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, MT * NT - MT * NT / 2, 0);
-            }
-        }
-        if (kt + 1 < nk) {
-            store_tile<ALAY, BM>(As + (cur ^ 1) * BK * BM, tid, ra);
-            store_tile<BLAY, BN>(Bs + (cur ^ 1) * BK * BN, tid, rb);
-            if (ALAY == 1 && do_colsum) {
-#pragma unroll
-                for (int i = 0; i < BM / 64; ++i) csum[i] += ra[i];
-            }
-        }
-        __syncthreads();
-    }
-
-    if (ALAY == 1 && do_colsum) {
-        constexpr int CH = BM / 4, G = 256 / CH;
-        f32x4 t = csum[0];
-#pragma unroll
-        for (int i = 1; i < BM / 64; ++i) t += csum[i];
-        *reinterpret_cast<f32x4*>(&smem[(tid / CH) * BM + (tid % CH) * 4]) = t;
-        __syncthreads();
-        if (tid < BM && row0 + tid < p.M) {
-            float s = 0.f;
-#pragma unroll
-            for (int g = 0; g < G; ++g) s += smem[g * BM + tid];
-            float* o = p.colsum + (long)blockIdx.z * p.M + row0 + tid;
-            *o = (gridDim.z == 1 && p.colsum_accumulate) ? *o + s : s;
-        }
-        __syncthreads();
-    }
-    float* Cb = p.C + (long)blockIdx.z * p.slab_stride;
-    const int epi = (gridDim.z > 1) ? (int)EPI_NONE : p.epi;
-    static_assert(4 * 16 * (WN + 4) <= 2 * BK * (BM + BN), "epilogue staging must fit the operand buffers");
-    store_tile_dispatch_lds16<MT, NT>(epi, p, Cb, acc, row0 + wm * WM, col0 + wn * WN, lane, smem + wave * 16 * (WN + 4));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -751,11 +624,9 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 // fill with 128x128 tiles (297 workgroups) to 93 % with 64x64 (1188).
 struct Tile { int bm, bn; float penalty; };
 inline Tile pick_tile(int M, int N) {
-    static const int forced = [] { const char* e = getenv("D2S_GEMM_TILE"); return e ? atoi(e) : 0; }();   // tuning aid: 1..4 = candidate index
-    // per-tile cost factors, re-measured on the [row][k]-image kernel (D2S_GEMM_TILE sweep, profiles/r02_d_gemm_tile_sweep.txt; SQ counters:
+    // per-tile cost factors, re-measured on the [row][k]-image kernel (forced-tile sweep, profiles/r02_d_gemm_tile_sweep.txt; SQ counters:
     // the 64x64 tile spends 1.9 vector + 2.1 scalar instructions per MFMA on addressing / loop control, the 128x64 tile 1.1 + 1.1)
     const Tile cand[4] = {{128, 128, 1.00f}, {128, 64, 1.04f}, {64, 128, 1.05f}, {64, 64, 1.10f}};
-    if (forced >= 1 && forced <= 4) return cand[forced - 1];
     Tile best = cand[0];
     float best_cost = 1e30f;
     for (const Tile& t : cand) {
@@ -770,59 +641,28 @@ inline Tile pick_tile(int M, int N) {
     return best;
 }
 
-// Residency cap: a bare loop of f32 MFMAs issues at 0.99 of the pipe's rate with one or two waves per SIMD and at 0.80 with four
-// (tools/micro/mfma_shape_f32.hip, profiles/r02_mfma_residency.txt), so more co-resident workgroups than the latency hiding needs cost
-// matrix throughput.  Unused dynamic LDS is the knob: asking for 160 KB / k - static bytes per workgroup lets a CU hold exactly k.
-inline unsigned residency_pad(int bm, int bn) {
-    static const int cap = [] { const char* e = getenv("D2S_GEMM_WG_PER_CU"); return e ? atoi(e) : 0; }();
-    if (cap <= 0) return 0;
-    const int static_bytes = 2 * BK * (bm + bn) * (int)sizeof(float) + 64;
-    const int want = (160 * 1024) / cap - static_bytes - 512;
-    return want > 0 ? (unsigned)(want & ~255) : 0u;
-}
 template <int ALAY, int BLAY, bool FAST>
 inline void launch_gemm_f(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p) {
     dim3 block(256);
-    const unsigned pad = residency_pad(t.bm, t.bn);
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 128, FAST>), grid, block, pad, stream, p);
-    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 64, FAST>), grid, block, pad, stream, p);
-    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 128, FAST>), grid, block, pad, stream, p);
-    else hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 64, FAST>), grid, block, pad, stream, p);
-}
-template <int ALAY, int BLAY>
-inline void launch_gemm16(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p) {
-    dim3 block(256);
-    const unsigned pad = residency_pad(t.bm, t.bn);
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel16<ALAY, BLAY, 128, 128>), grid, block, pad, stream, p);
-    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_kernel16<ALAY, BLAY, 128, 64>), grid, block, pad, stream, p);
-    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel16<ALAY, BLAY, 64, 128>), grid, block, pad, stream, p);
-    else hipLaunchKernelGGL((gemm_f32_kernel16<ALAY, BLAY, 64, 64>), grid, block, pad, stream, p);
+    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 128, FAST>), grid, block, 0, stream, p);
+    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 64, FAST>), grid, block, 0, stream, p);
+    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 128, FAST>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 64, FAST>), grid, block, 0, stream, p);
 }
 template <int BLAY>
 inline void launch_gemm_rk(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p) {
     dim3 block(256);
-    const unsigned pad = residency_pad(t.bm, t.bn);
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 128>), grid, block, pad, stream, p);
-    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 64>), grid, block, pad, stream, p);
-    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 128>), grid, block, pad, stream, p);
-    else hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 64>), grid, block, pad, stream, p);
+    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 128>), grid, block, 0, stream, p);
+    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 64>), grid, block, 0, stream, p);
+    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 128>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 64>), grid, block, 0, stream, p);
 }
-// D2S_GEMM_RK [1]: k-contiguous A operands (NT / NN layouts, guard-free shapes) use the [row][k] LDS image (ds_*_b128); 0 = the [k][row]
-// image everywhere.  Measured on the model's shapes at B = 128 (tools/gemm_bench.py, profiles/r02_c_gemm_rk_vs_krow.txt): +20...30 % on
-// the N = 384 outputs and the K = 1536 / 1152 reductions, +4...7 % on the wide outputs, within +-2 % on the n = 99 input-gradient shapes
-inline bool use_rk() {
-    static const int on = [] { const char* e = getenv("D2S_GEMM_RK"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
-// D2S_GEMM_MFMA16: 1 = run the guard-free shapes on the 16x16x4 form, 0 = always the 32x32x2 form
-inline bool use_mfma16() {
-    static const int on = [] { const char* e = getenv("D2S_GEMM_MFMA16"); return e ? atoi(e) : 0; }();
-    return on != 0;
-}
+// k-contiguous A operands (NT / NN layouts) of guard-free shapes with the 16-byte epilogue use the [row][k] LDS image (ds_*_b128), every
+// other call the [k][row] image.  Measured on the model's shapes at B = 128 (tools/gemm_bench.py, profiles/r02_c_gemm_rk_vs_krow.txt): +20...30 %
+// on the N = 384 outputs and the K = 1536 / 1152 reductions, +4...7 % on the wide outputs, within +-2 % on the n = 99 input-gradient shapes
 template <int ALAY, int BLAY>
 inline void launch_gemm(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p, bool fast) {
-    if (fast && p.vec_epilogue && ALAY == 0 && use_rk()) launch_gemm_rk<BLAY>(t, grid, stream, p);
-    else if (fast && p.vec_epilogue && use_mfma16()) launch_gemm16<ALAY, BLAY>(t, grid, stream, p);
+    if (fast && p.vec_epilogue && ALAY == 0) launch_gemm_rk<BLAY>(t, grid, stream, p);
     else if (fast) launch_gemm_f<ALAY, BLAY, true>(t, grid, stream, p);
     else launch_gemm_f<ALAY, BLAY, false>(t, grid, stream, p);
 }
@@ -838,16 +678,14 @@ bool split_tn_use_dma(int M, int N, int K);
 int split_tn_dma_slices(int M, int N, int K);
 int launch_split_gemm_tn(const GemmArgs& p, int split, int slices, void* pieces_ws, float* colsum_part, hipStream_t stream, int* colsum_parts);
 }
-// Workgroups the wgrad launch aims for (tiles x K slices, rounded down).  Run alone, exactly 2 per CU is best (tools/gemm_bench.py,
-// D2S_SPLITK_TARGET sweep in round 1: 512 beats 768 / 1024 by 4-15 % - fewer, longer K slices mean less slab traffic for the ordered
+// Workgroups the wgrad launch aims for (tiles x K slices, rounded down): 3 per CU.  Run alone, exactly 2 per CU is best (tools/gemm_bench.py,
+// split-K target sweep in round 1: 512 beats 768 / 1024 by 4-15 % - fewer, longer K slices mean less slab traffic for the ordered
 // combine - and any count that is not a multiple of the CU count loses 10-40 % to imbalance).  Inside the training step the weight
 // gradients run on their own stream BESIDE the dgrad / attention kernels (d2s.ops.async_weight_grads), where shorter workgroups interleave
 // better: 3 per CU measured best there (step: 256 -> 3483, 384 -> 3470, 512 -> 3513, 768 -> 3556, 1024 -> 3526, 1536 -> 3508, 2048 -> 3490
-// images/s on one box), so that is the default.
+// images/s on one box).
 static int splitk_target() {
     static const int t = [] {
-        const char* e = getenv("D2S_SPLITK_TARGET");
-        if (e) return atoi(e);
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
             cus = 256;
@@ -856,11 +694,6 @@ static int splitk_target() {
     return t;
 }
 static inline size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
-// mode 2 only: run the weight gradient on the bf16 matrix cores too (D2S_BF16_WGRAD=0 keeps it on the exact fp32 kernel)
-static bool bf16_wgrad(int mode) {
-    static const int on = [] { const char* e = getenv("D2S_BF16_WGRAD"); return e ? atoi(e) : 1; }();
-    return mode == 2 && on;
-}
 extern "C" size_t d2s_colsum_workspace_bytes(int M, int N);
 extern "C" int d2s_colsum_f32(const float* X, long ldx, int M, int N, float* out, int accumulate, void* workspace,
                               size_t workspace_bytes, hipStream_t stream);
@@ -868,10 +701,9 @@ extern "C" int d2s_colsum_f32(const float* X, long ldx, int M, int N, float* out
 // split K: the choice minimises (workgroups on the busiest CU) x (K share per workgroup) / (matrix-pipe use at that residency) plus a
 // per-slice cost for the extra slab traffic.  Large grids get 1 (no split).
 static int nt_slices(int tiles, int K) {
-    static const int enabled = [] { const char* e = getenv("D2S_NT_SPLITK"); return e ? atoi(e) : 1; }();
     // only grids that leave the busiest CU with at most 2 workgroups: with more, dispatch evens the load out by itself and the split
     // only adds slab traffic (measured at B=128: -4...-19 % on the shapes an unrestricted model chose to split)
-    if (!enabled || K < 512 || tiles > 512) return 1;
+    if (K < 512 || tiles > 512) return 1;
     int best = 1;
     float best_cost = 1e30f;
     const int smax = K / 256 < 8 ? K / 256 : 8;
@@ -884,8 +716,7 @@ static int nt_slices(int tiles, int K) {
     return best;
 }
 static int splitk_slices(int tiles, int K) {
-    const int target = splitk_target();
-    int slices = target >= 100000 ? (target - 100000 + tiles - 1) / tiles : target / tiles;   // >= 100000: round up, else round down
+    int slices = splitk_target() / tiles;
     const int max_slices = (K + 255) / 256;
     if (slices > max_slices) slices = max_slices;
     if (slices < 1) slices = 1;
@@ -913,12 +744,13 @@ size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode) {
         return sl > 1 ? (size_t)sl * M * N * sizeof(float) : 0;
     }
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);      // (64x64 wgrad tiles for the small 384x384 weights: measured slower)
-    int slices = splitk_slices(tiles, K);
-    size_t bytes = slices <= 1 ? 0 : ((size_t)slices * M * N + (size_t)slices * M) * sizeof(float);   // C slabs + fused bias-gradient slabs
-    if (bf16_wgrad(mode) && split_tn_use_dma(M, N, K)) slices = split_tn_dma_slices(M, N, K);
-    if (bf16_wgrad(mode))   // + bf16 pieces of both operands + scratch of the separate bias-gradient pass (see gemm_impl)
-        bytes = ws_align(((size_t)(slices + 1) * M * N) * sizeof(float)) + ws_align(split_tn_pieces_bytes(1, M, N, K)) + (size_t)split_tn_colsum_partials(K) * M * sizeof(float);
-    return bytes;
+    if (mode != 2) {      // C slabs + fused bias-gradient slabs
+        const int slices = splitk_slices(tiles, K);
+        return slices <= 1 ? 0 : ((size_t)slices * M * N + (size_t)slices * M) * sizeof(float);
+    }
+    // mode 2: C slabs + bf16 pieces of both operands + scratch of the separate bias-gradient pass (see gemm_impl)
+    const int slices = split_tn_use_dma(M, N, K) ? split_tn_dma_slices(M, N, K) : splitk_slices(tiles, K);
+    return ws_align(((size_t)(slices + 1) * M * N) * sizeof(float)) + ws_align(split_tn_pieces_bytes(1, M, N, K)) + (size_t)split_tn_colsum_partials(K) * M * sizeof(float);
 }
 
 // layout 0 = NT (A[M,K], B[N,K]); 1 = NN (A[M,K], B[K,N]); 2 = TN (A[K,M], B[K,N]).
@@ -929,10 +761,10 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
                      hipStream_t stream, float* colsum_out, int mode, const void* a16 = nullptr, void* c16 = nullptr, const void* b16 = nullptr) {
     // layout 2 (weight gradient): a16 is the bf16 form of the SECOND operand (the layer input x); B may then be NULL
     // layout 2: b16 is the bf16 form of the FIRST operand (dy); A may then be NULL
-    if (b16 && (mode != 2 || (layout != 2 && (K % 32 != 0 || !aligned16(b16))) || (layout == 2 && (!bf16_wgrad(mode) || (reinterpret_cast<uintptr_t>(b16) & 7))))) return D2S_ERR_ARG;
+    if (b16 && (mode != 2 || (layout != 2 && (K % 32 != 0 || !aligned16(b16))) || (layout == 2 && (reinterpret_cast<uintptr_t>(b16) & 7)))) return D2S_ERR_ARG;
     if ((!A && !(a16 && layout != 2) && !(b16 && layout == 2)) || (!B && !(a16 && layout == 2) && !(b16 && layout != 2)) || (!C && !c16) || M <= 0 || N <= 0 || K <= 0 || layout < 0 || layout > 2 || mode < 0 || mode > 2) return D2S_ERR_ARG;
     if ((a16 || c16) && (mode != 2 || (layout != 2 && accumulate) || remap_rows_per_img > 0)) return D2S_ERR_ARG;   // bf16 operands / copies exist in bf16 mode only
-    if (layout == 2 && (c16 || (a16 && !bf16_wgrad(mode)))) return D2S_ERR_ARG;
+    if (layout == 2 && c16) return D2S_ERR_ARG;
     if (layout == 2 && a16) {
         if ((reinterpret_cast<uintptr_t>(a16) & 7) != 0) return D2S_ERR_ARG;
     }
@@ -971,7 +803,7 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
         p.slab_stride = 0;
         return launch_split_gemm(p, layout == 1 ? 1 : 0, mode == 1 ? 3 : 1, workspace, workspace_bytes, stream);
     }
-    if (layout == 2 && bf16_wgrad(mode)) {
+    if (layout == 2 && mode == 2) {
         // wgrad in bf16 mode: transposing split of dy and x into K-contiguous bf16 pieces, K-sliced pieces kernel into fp32 slabs,
         // the same ordered slab combine as the exact path; the bias gradient is a separate exact fp32 column-sum pass over dy.
         const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -1033,15 +865,11 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
         if (accumulate) p.epi = EPI_ACCUM;
         p.colsum = colsum_out;
     }
-    {
-        static const int vec_epi_env = [] { const char* e = getenv("D2S_GEMM_VEC_EPILOGUE"); return e ? atoi(e) : 1; }();
-        p.vec_epilogue = (vec_epi_env && epilogue_vec_ok(p) && (p.slab_stride % 4 == 0)) ? 1 : 0;
-    }
+    p.vec_epilogue = (epilogue_vec_ok(p) && (p.slab_stride % 4 == 0)) ? 1 : 0;
     dim3 grid(tiles, 1, slices), block(256);
     // guard-free instantiation: both operands 16-byte loadable, every K slice a whole number of K-steps, and at least one full
     // 4-row chunk where rows are the contiguous dimension (the clamp needs rows - 4 >= 0)
-    static const int fast_env = [] { const char* e = getenv("D2S_GEMM_FAST"); return e ? atoi(e) : 1; }();
-    const bool fast = fast_env && p.vecA && p.vecB && (K % BK == 0) && (alay == 0 || M >= 4) && (blay == 0 || N >= 4);
+    const bool fast = p.vecA && p.vecB && (K % BK == 0) && (alay == 0 || M >= 4) && (blay == 0 || N >= 4);
     if (layout == 0) launch_gemm<0, 0>(tile, grid, stream, p, fast);
     else if (layout == 1) launch_gemm<0, 1>(tile, grid, stream, p, fast);
     else launch_gemm<1, 1>(tile, grid, stream, p, fast);

@@ -20,7 +20,6 @@
 // LDS-DMA), and stage 1 disappears for every operand whose producer already wrote it in bf16 (d2s_gemm_f32_bf16io: a_bf16 from
 // LayerNorm / attention / a GEMM epilogue, b_bf16 from the per-step weight conversion, c_bf16 for the next GEMM).
 #include "gemm_common.h"
-#include <cstdlib>
 
 namespace {
 using namespace d2s_gemm;
@@ -188,8 +187,8 @@ __device__ __forceinline__ void store_pieces(__bf16* __restrict__ S, int tid, co
     }
 }
 
-// ---- activation operand straight from fp32 (split in registers on its way to LDS): 4 B/element of L2->CU traffic instead of
-// 2*SPLIT, and no separate split pass over the big operand.  Thread item = 8 consecutive k of one row (two 16-byte loads).
+// ---- activation operand straight from fp32 (rounded to bf16 in registers on its way to LDS; bf16 mode only): 4 B/element of L2->CU
+// traffic instead of 2, and no separate conversion pass over the big operand.  Thread item = 8 consecutive k of one row (two 16-byte loads).
 template <int BK>
 __device__ __forceinline__ void load_a_f32(const float* __restrict__ A, long lda, int M, int K, int row0, int k0, int tid,
                                            f32x4 (&r)[BK / 16][2]) {
@@ -213,26 +212,17 @@ __device__ __forceinline__ void load_a_f32(const float* __restrict__ A, long lda
         }
     }
 }
-template <int SPLIT, int BK>
-__device__ __forceinline__ void store_a_split(__bf16* __restrict__ S, int tid, const f32x4 (&r)[BK / 16][2]) {
+template <int BK>
+__device__ __forceinline__ void store_a_bf16(__bf16* __restrict__ S, int tid, const f32x4 (&r)[BK / 16][2]) {
     constexpr int CH = BK / 8, PITCH = BK + 8;
 #pragma unroll
     for (int i = 0; i < BK / 16; ++i) {
         const int f = tid + i * 256;
         const int row = f / CH, ch = f % CH;
-        bf16x8 h, m, l;
+        bf16x8 h;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            __bf16 hh, mm = (__bf16)0.f, ll = (__bf16)0.f;
-            if constexpr (SPLIT == 3) split3(r[i][j >> 2][j & 3], hh, mm, ll);
-            else hh = (__bf16)r[i][j >> 2][j & 3];
-            h[j] = hh; m[j] = mm; l[j] = ll;
-        }
+        for (int j = 0; j < 8; ++j) h[j] = (__bf16)r[i][j >> 2][j & 3];
         *reinterpret_cast<bf16x8*>(S + row * PITCH + ch * 8) = h;
-        if constexpr (SPLIT == 3) {
-            *reinterpret_cast<bf16x8*>(S + (128 + row) * PITCH + ch * 8) = m;
-            *reinterpret_cast<bf16x8*>(S + (256 + row) * PITCH + ch * 8) = l;
-        }
     }
 }
 
@@ -256,7 +246,8 @@ __device__ unsigned long long g_stamps[16 * 32768];
 
 template <int SPLIT, int BK, bool AF32>
 __global__ __launch_bounds__(256, 2) void gemm_pieces_nt_kernel(GemmArgs p, PieceArgs q) {
-    constexpr int SBK = BK, PITCH = BK + 8;   // LDS row pitch in bf16: 80 B (BK 32) / 48 B (BK 16), both conflict-free for b128 reads
+    static_assert(!AF32 || SPLIT == 1, "the activation operand is converted in the kernel in the bf16 mode only");
+    constexpr int SBK = BK, PITCH = BK + 8;   // LDS row pitch in bf16: 80 B (BK 32), conflict-free for b128 reads
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __bf16* As = reinterpret_cast<__bf16*>(smem_raw);   // [SPLIT][128][PITCH]
     __bf16* Bs = As + SPLIT * SBM * PITCH;               // [SPLIT][128][PITCH]
@@ -298,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pieces_nt_kernel(GemmArgs p, Piec
     STAMP(1); STAMPC(4);
     for (int kt = 0; kt < nk; ++kt) {
         STAMPK(8);
-        if constexpr (AF32) store_a_split<SPLIT, BK>(As, tid, fa);
+        if constexpr (AF32) store_a_bf16<BK>(As, tid, fa);
         else store_pieces<SPLIT, BK>(As, tid, ra);
         store_pieces<SPLIT, BK>(Bs, tid, rb);
         STAMPK(9);
@@ -662,9 +653,8 @@ inline void launch_dma(const GemmArgs& pv, const PieceArgs& q, hipStream_t strea
         attr_set = true;
     }
     const int tiles = ((pv.M + 255) / 256) * ((pv.N + BN - 1) / BN) * ((q.Kp + pv.k_per_slice - 1) / pv.k_per_slice);
-    static const int persist_env = [] { const char* e = getenv("D2S_DMA_PERSISTENT"); return e ? atoi(e) : 1; }();
     const int resident = gemm_cus() * (WGN == 4 ? 1 : 2);      // one 256x256 or two 256x128 workgroups per CU
-    const int grid = (persist_env && tiles > resident) ? resident : tiles;
+    const int grid = tiles > resident ? resident : tiles;
     hipLaunchKernelGGL((gemm_bf16_dma_kernel<WGN, BK, NS, TOK>), dim3(grid), dim3(WGN * 128), lds, stream, pv, q);
 }
 
@@ -694,17 +684,14 @@ int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace,
     // The activation operand can be converted inside the matrix kernel (read as fp32 with 16-byte loads, no split pass over it) instead
     // of being pre-split.  bf16x3 (mode 1): alone, a GEMM with <= 4 column tiles runs 9-12 % faster that way and one with 9-12 column tiles
     // 4 % slower (each panel element is re-split per column tile); inside the training step pre-splitting is 0.5-1 % faster overall, so
-    // it stays the default there.  bf16 (mode 2): the conversion is one instruction per two values; with at most 12 column tiles
+    // mode 1 always pre-splits.  bf16 (mode 2): the conversion is one instruction per two values; with at most 12 column tiles
     // (every DeiT-S GEMM) in-kernel conversion wins (+2.7 % on the step), with 18-24 (DeiT-B qkv / fc1) the fp32 re-reads lose (-2.7 %).
-    // D2S_SPLIT_A_INKERNEL = 0 / 1 forces one or the other.
-    static const int a_inkernel_env = [] { const char* e = getenv("D2S_SPLIT_A_INKERNEL"); return e ? atoi(e) : -1; }();
     const int col_tiles = (p.N + SBN - 1) / SBN;
-    // bf16 (one piece): LDS-DMA kernel for large shapes; D2S_SPLIT_DMA = 0 off, 1 automatic tile choice, 2 / 3 force 256x128 / 256x256
-    static const int dma_env = [] { const char* e = getenv("D2S_SPLIT_DMA"); return e ? atoi(e) : 1; }();
+    // bf16 (one piece): LDS-DMA kernel for large shapes, 256x256 or 256x128 tiles by the cost rule below
     // Without a caller-provided bf16 A the kernel needs a conversion pass over A first (6 bytes per element of A against the 2 of reading
     // it in the matrix kernel): that pays from N ~ 900 on (measured: DeiT-B fc1 / qkv yes, proj / fc2 no).
     const bool have_a16 = p.a16 != nullptr && split == 1;      // the caller's bf16 copy of A is the piece matrix (Kp == K)
-    const bool dma_shape = dma_env && split == 1 && p.M >= 2048 && p.N >= 128 && epilogue_vec_ok(p) && (have_a16 || p.N >= 1024 || dma_env > 1);
+    const bool dma_shape = split == 1 && p.M >= 2048 && p.N >= 128 && epilogue_vec_ok(p) && (have_a16 || p.N >= 1024);
     bool dma_wide = false;
     if (dma_shape) {
         if (Kp % 64 == 0 && p.N >= 256) {
@@ -716,13 +703,13 @@ int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace,
             const long f128 = t128 / (2 * cus), r128 = t128 % (2 * cus);
             const double c256 = (double)((t256 + cus - 1) / cus);
             const double c128 = f128 * 1.17 + (r128 == 0 ? 0.0 : r128 <= cus ? 0.62 : 1.17);
-            dma_wide = dma_env == 3 || (dma_env != 2 && c256 <= c128);
+            dma_wide = c256 <= c128;
         }
     }
     if ((p.c16 || !p.C) && (!epilogue_vec_ok(p) || split != 1)) return D2S_ERR_ARG;      // the bf16 copy is written by the 16-byte epilogue only
     if (!p.A && !have_a16) return D2S_ERR_ARG;
     if (have_a16) Ap = static_cast<__bf16*>(const_cast<void*>(p.a16));
-    const bool af32 = !have_a16 && p.vecA && (a_inkernel_env >= 0 ? a_inkernel_env != 0 : (split == 1 && col_tiles <= 12 && !dma_shape));
+    const bool af32 = !have_a16 && p.vecA && split == 1 && col_tiles <= 12 && !dma_shape;
     if (split == 3) {
         if (!af32) hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)((ea + 255) / 256)), block, 0, stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA);
         if (b_cols) hipLaunchKernelGGL(split_cols_kernel<3>, dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
@@ -744,27 +731,16 @@ int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace,
         return d2s_check_launch();
     }
     const int tiles = ((p.M + SBM - 1) / SBM) * ((p.N + SBN - 1) / SBN);
-    static const int bk = [] { const char* e = getenv("D2S_SPLIT_BK"); return (e && atoi(e) == 16) ? 16 : 32; }();   // 32 measured faster than 16 on every model shape
-    size_t lds = (size_t)split * (SBM + SBN) * (bk + 8) * sizeof(__bf16);
+    size_t lds = (size_t)split * (SBM + SBN) * (32 + 8) * sizeof(__bf16);      // K-step 32 (measured faster than 16 on every model shape)
     if (lds < 4 * epi_stage_floats(2) * sizeof(float)) lds = 4 * epi_stage_floats(2) * sizeof(float);
     GemmArgs pv = p;
     pv.vec_epilogue = epilogue_vec_ok(p) ? 1 : 0;
     pv.k_per_slice = Kp;      // one K slice over the padded reduction length
     pv.slab_stride = 0;
     PieceArgs q{Ap, Bp, Kp};
-#define D2S_LAUNCH_PIECES(S, K_, F) hipLaunchKernelGGL((gemm_pieces_nt_kernel<S, K_, F>), dim3(tiles), block, lds, stream, pv, q)
-    if (af32) {
-        if (split == 3 && bk == 32) D2S_LAUNCH_PIECES(3, 32, true);
-        else if (split == 3) D2S_LAUNCH_PIECES(3, 16, true);
-        else if (bk == 32) D2S_LAUNCH_PIECES(1, 32, true);
-        else D2S_LAUNCH_PIECES(1, 16, true);
-    } else {
-        if (split == 3 && bk == 32) D2S_LAUNCH_PIECES(3, 32, false);
-        else if (split == 3) D2S_LAUNCH_PIECES(3, 16, false);
-        else if (bk == 32) D2S_LAUNCH_PIECES(1, 32, false);
-        else D2S_LAUNCH_PIECES(1, 16, false);
-    }
-#undef D2S_LAUNCH_PIECES
+    if (af32) hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, true>), dim3(tiles), block, lds, stream, pv, q);
+    else if (split == 3) hipLaunchKernelGGL((gemm_pieces_nt_kernel<3, 32, false>), dim3(tiles), block, lds, stream, pv, q);
+    else hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, false>), dim3(tiles), block, lds, stream, pv, q);
     return d2s_check_launch();
 }
 
@@ -778,9 +754,8 @@ size_t split_tn_pieces_bytes(int split, int M, int N, int K) {
 }
 // 256x256 LDS-DMA tiles for weight gradients whose output fills them (every DeiT-S / DeiT-B Linear; not the predictor's narrow layers)
 bool split_tn_use_dma(int M, int N, int K) {
-    static const int env = [] { const char* e = getenv("D2S_SPLIT_DMA_TN"); return e ? atoi(e) : 1; }();
     const long padded = (long)((M + 255) / 256) * 256 * ((N + 255) / 256) * 256;
-    return env && M >= 256 && N >= 256 && K >= 2048 && padded * 5 <= (long)M * N * 6;      // at most 20 % of the tile area past the edges
+    return M >= 256 && N >= 256 && K >= 2048 && padded * 5 <= (long)M * N * 6;      // at most 20 % of the tile area past the edges
 }
 // K slices for the LDS-DMA form: about one 256x256 workgroup per CU, at least 8 slabs of 64 per slice
 int split_tn_dma_slices(int M, int N, int K) {
@@ -831,7 +806,7 @@ __global__ __launch_bounds__(256) void colsum_tok_kernel(const ST* __restrict__ 
 // pass that reads dy anyway; the caller folds them in order into the bias gradient.
 int split_tn_colsum_partials(int K) { return tn_kp(K) / 64; }
 int launch_split_gemm_tn(const GemmArgs& p, int split, int slices, void* pieces_ws, float* colsum_part, hipStream_t stream, int* colsum_parts) {
-    if (colsum_parts) *colsum_parts = split_tn_colsum_partials(p.K);      // partial rows written to colsum_part (the caller folds that many)
+    *colsum_parts = split_tn_colsum_partials(p.K);      // partial rows written to colsum_part (the caller folds that many)
     const int Kp = tn_kp(p.K);
     if (split != 1) return D2S_ERR_ARG;
     if ((long)p.M * Kp * 2 >= (1L << 32) || (long)p.N * Kp * 2 >= (1L << 32)) return D2S_ERR_ARG;
@@ -839,21 +814,18 @@ int launch_split_gemm_tn(const GemmArgs& p, int split, int slices, void* pieces_
     __bf16* Bp = reinterpret_cast<__bf16*>(static_cast<unsigned char*>(pieces_ws) + align256((size_t)split * p.M * Kp * sizeof(__bf16)));
     dim3 block(256);
     // Both operands at hand in bf16 (the bf16 data path's fc1 / qkv, and proj / fc2 where the caller kept the bf16 forms): the matrix kernel
-    // reads them token-major as they lie (gemm_bf16_dma_kernel<.., TOK>) - no transposing pass, no piece matrices.  D2S_TN_TOKEN_MAJOR=0: A/B.
-    static const int tok_env = [] { const char* e = getenv("D2S_TN_TOKEN_MAJOR"); return e ? atoi(e) : 1; }();
-    if (tok_env && p.b16 && p.a16 && p.K % 64 == 0 && p.M % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
+    // reads them token-major as they lie (gemm_bf16_dma_kernel<.., TOK>) - no transposing pass, no piece matrices.
+    if (p.b16 && p.a16 && p.K % 64 == 0 && p.M % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
         (reinterpret_cast<uintptr_t>(p.b16) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.a16) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && split_tn_use_dma(p.M, p.N, p.K) &&
         epilogue_vec_ok(p) && p.slab_stride % 4 == 0 && p.k_per_slice % 64 == 0 && (long)p.K * p.lda * 2 < (1L << 32) && (long)p.K * p.ldb * 2 < (1L << 32)) {
-        static const int cs_env = [] { const char* e = getenv("D2S_TN_COLSUM_INKERNEL"); return e ? atoi(e) : 1; }();
         GemmArgs pt = p;
         pt.colsum = nullptr;
         if (colsum_part && p.A)       // the fp32 gradient exists too: the bias gradient stays its exact column sum
             hipLaunchKernelGGL(colsum_tok_kernel<float>, dim3((p.M + 255) / 256, p.K / 64), block, 0, stream, p.A, p.lda, p.M, colsum_part);
-        else if (colsum_part && cs_env && colsum_parts) {      // bf16-only gradient: summed by the matrix kernel itself, one partial row per K slice
+        else if (colsum_part) {      // bf16-only gradient: summed by the matrix kernel itself, one partial row per K slice
             pt.colsum = colsum_part;
             *colsum_parts = slices;
-        } else if (colsum_part)
-            hipLaunchKernelGGL(colsum_tok_kernel<__bf16>, dim3((p.M + 255) / 256, p.K / 64), block, 0, stream, static_cast<const __bf16*>(p.b16), p.lda, p.M, colsum_part);
+        }
         pt.vec_epilogue = 1;
         pt.a16 = nullptr; pt.c16 = nullptr; pt.b16 = nullptr;
         PieceArgs qt{static_cast<const __bf16*>(p.b16), static_cast<const __bf16*>(p.a16), p.K};

@@ -7,7 +7,6 @@
 // Rows may be addressed through a RowMap so that the predictor can read x[:, 1:] of a [B, n, D] buffer in place
 // (dynamic_vit.py:855) and its backward can add into rows 1.. of the gradient buffer.
 #include "d2s_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -493,9 +492,8 @@ inline int pick_nv(int D) {
 inline int bwd_blocks(long rows) {
     // one wave walks its rows one after the other (load -> two wave reductions -> store), so the kernel is latency-bound unless
     // several workgroups share a CU: up to 3 per CU (measured: 256 blocks 48.8 us, 768 blocks see DESIGN.md section 7)
-    static const long cap = [] { const char* e = getenv("D2S_LN_BWD_BLOCKS"); return e ? atol(e) : 768L; }();
     long nb = (rows + 31) / 32;
-    if (nb > cap) nb = cap;
+    if (nb > 768) nb = 768;
     if (nb < 1) nb = 1;
     return (int)nb;
 }
@@ -517,8 +515,7 @@ static int layernorm_fwd_impl(const float* x, long rows_per_group, long group_st
         hipLaunchKernelGGL(ln_fwd_scalar_kernel, grid, block, 0, stream, x, m, w, b, y, mean, rstd, rows, D, eps);
         return d2s_check_launch();
     }
-    static const int pair_env = [] { const char* e = getenv("D2S_LN_PAIR"); return e ? atoi(e) : 1; }();
-    if (D == 384 && pair_env) {
+    if (D == 384) {
         hipLaunchKernelGGL(ln_fwd_pair96_kernel, dim3((unsigned)((rows + 7) / 8)), block, 0, stream, x, m, w, b, y, y16, mean, rstd, rows, eps);
         return d2s_check_launch();
     }
@@ -581,8 +578,7 @@ static int layernorm_bwd_impl(const float* x, long rows_per_group, long group_st
                                accumulate_wb);
         return d2s_check_launch();
     }
-    static const int bwd_pair_env = [] { const char* e = getenv("D2S_LN_BWD_PAIR"); return e ? atoi(e) : 1; }();
-    if (D == 384 && bwd_pair_env) {      // two rows per wave (D2S_LN_BWD_PAIR=0: the generic kernel)
+    if (D == 384) {      // two rows per wave
         hipLaunchKernelGGL(ln_bwd_pair96_kernel, grid, block, 0, stream, x, m, dy, w, mean, rstd, dx, add_src, part, rows, rpb, relu_mask, dx16);
         if (dweight)
             hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3((2 * D + FOLD_COLS - 1) / FOLD_COLS), dim3(FOLD_COLS * FOLD_LANES), 0, stream, part, nblocks, D, dweight, dbias,

@@ -169,7 +169,7 @@ class BlockFn(torch.autograd.Function):
         # bf16 arithmetic mode: LayerNorm, the attention forward and the fc1 epilogue also emit the bf16 form of what the next GEMM
         # multiplies, and that GEMM reads it instead of converting its fp32 operand (no conversion passes on the forward path)
         io = ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and x.is_cuda
-        io_attn = io and policy is None and ops._BF16_ATTENTION
+        io_attn = io and policy is None
         ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
         ctx.composite = False
         if policy is None and not io and ops.block_composite_ok(x, heads, hidden):
@@ -253,7 +253,7 @@ class BlockFn(torch.autograd.Function):
         x2d = x.view(M, D)
         x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x2d, a16=aoh)
         # GELU pre-activation for the backward: fp32, or bf16 on the bf16 data path (what autocast keeps: fc1's output is bf16 there)
-        z = torch.empty((M, hidden), dtype=torch.bfloat16 if (io and ops._BF16_PREACT) else torch.float32, device=x.device)
+        z = torch.empty((M, hidden), dtype=torch.bfloat16 if io else torch.float32, device=x.device)
         if io:
             _, mean2, rstd2, ln2h = ops.layernorm_fwd_bf16(x1, cmap, n2w, n2b, M, D, eps, want_f32=False)
             ln2 = ln2h
@@ -315,7 +315,7 @@ class BlockFn(torch.autograd.Function):
         # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
         io = ops.bf16_io() and z.shape[1] % 32 == 0 and D % 32 == 0 and gy.is_cuda
         policy, cinv = ctx.policy
-        io_attn = io and policy is None and ops._BF16_ATTENTION
+        io_attn = io and policy is None
         gyh = ops.shadow_take(gy) if io else None
         if gyh is not None:
             gyh = gyh.view(M, D)

@@ -16,8 +16,6 @@ NT, NN, TN = 0, 1, 2
 
 _ws = {}
 _WS_NEED = {}       # (layout, M, N, K, mode) -> workspace bytes of d2s_gemm_f32 (a pure function of its arguments)
-_BF16_ATTENTION = os.environ.get("D2S_BF16_ATTENTION", "1") != "0"
-_BF16_PREACT = os.environ.get("D2S_BF16_PREACT", "1") != "0"      # bf16 data path: fc1's pre-activation is saved in bf16 (0: fp32, A/B)
 
 
 def workspace(nbytes, device):
@@ -95,12 +93,11 @@ def shadow_take(t):
 # arena that does not require gradients (the frozen teacher) is converted on first use and again only when its version counter moves.
 # Anything else (a free-standing trainable tensor) has no safe invalidation signal and is converted inside each GEMM call as before.
 _W16 = {}                       # (data_ptr, transposed) -> (weakref to the weight or None for arena entries, epoch, version, shape, bf16 tensor)
-_BF16_WEIGHTS = os.environ.get("D2S_BF16_WEIGHT_CACHE", "1") != "0"
 
 
 def bf16_weight(W, transposed=False):
     """bf16 [N][K] form of the B operand of y = x W^T (transposed=False: W itself) or of dx = dy W (transposed=True: W^T), or None."""
-    if not (_BF16_WEIGHTS and _BF16_IO and W.is_cuda and W.dim() == 2 and W.shape[0 if transposed else 1] % 32 == 0):
+    if not (_BF16_IO and W.is_cuda and W.dim() == 2 and W.shape[0 if transposed else 1] % 32 == 0):
         return None
     ent = _W16.get((W.data_ptr(), transposed))
     shape = tuple(W.shape)
@@ -228,7 +225,7 @@ def _in_weight_arena(ptr):
         if lo <= ptr < hi and ref() is not None:
             return True
     return False
-_DGRAD_NT_MIN_ROWS = int(os.environ.get("D2S_DGRAD_NT_MIN_ROWS", "1024"))      # arena weights get their W^T copies once per step anyway (TransposedArena); at 3168 rows the NT form is still 5-10 % faster (profiles/r03_d_config3_tile_sweep.txt)
+_DGRAD_NT_MIN_ROWS = 1024      # arena weights get their W^T copies once per step anyway (TransposedArena); at 3168 rows the NT form is still 5-10 % faster (profiles/r03_d_config3_tile_sweep.txt)
 
 
 def bump_weights_epoch():
@@ -442,8 +439,6 @@ def recheck_weight_grad_stream(beside):
 
 _WGRAD = {"on": False, "stream": None, "used": False}
 _WGRAD_ENABLED = os.environ.get("D2S_WGRAD_STREAM", "1") != "0"
-_ATTN_BWD_STREAMS = os.environ.get("D2S_ATTN_BWD_STREAMS", "0") == "1"      # dQ and dK/dV kernels of the attention backward side by side:
-# measured +-0 on top of the weight-gradient stream (3503 / 3502 images/s), so off by default
 
 
 class async_weight_grads:
@@ -690,7 +685,7 @@ def attn_fwd(qkv, B, n, H, scale, want_cls=True):
     lse = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
     cls_row = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if want_cls else None
     # bf16 arithmetic mode: the two matrix products of the forward run on the bf16 matrix cores too (same outputs, fp32 backward)
-    entry = "d2s_attn_fwd_bf16" if (get_gemm_mode() == GEMM_BF16 and _BF16_ATTENTION) else "d2s_attn_fwd_f32"
+    entry = "d2s_attn_fwd_bf16" if get_gemm_mode() == GEMM_BF16 else "d2s_attn_fwd_f32"
     lib.call(entry, lib.ptr(qkv), lib.ptr(out), lib.ptr(lse), lib.ptr(cls_row), B, n, H, float(scale))
     return out, lse, cls_row
 
@@ -713,26 +708,13 @@ def attn_bwd(qkv, out, dout, lse, B, n, H, scale, dqkv16=None, want_f32=True):
     (needs dqkv16): only that form is written and None is returned."""
     dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device) if (want_f32 or dqkv16 is None) else None
     delta = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
-    bf16 = get_gemm_mode() == GEMM_BF16 and _BF16_ATTENTION
+    bf16 = get_gemm_mode() == GEMM_BF16
     if dqkv16 is not None:
         assert bf16 and dqkv16.dtype == torch.bfloat16 and dqkv16.is_contiguous() and dqkv16.numel() == qkv.numel()
         lib.call("d2s_attn_bwd_bf16_bf16out", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(out), lib.ptr(dout), lib.ptr(lse),
                  lib.ptr(dqkv), lib.ptr(dqkv16), lib.ptr(delta), B, n, H, float(scale))
         return dqkv
     assert qkv.dtype == torch.float32
-    if _WGRAD["on"] and _ATTN_BWD_STREAMS and not bf16 and qkv.is_cuda:
-        # inside TrainStep's backward: the dK/dV kernel on a stream of its own beside the dQ kernel (independent, disjoint outputs);
-        # both are joined again before anything reads dqkv
-        if _WGRAD.get("attn_stream") is None:
-            _WGRAD["attn_stream"] = torch.cuda.Stream()
-        side, main = _WGRAD["attn_stream"], torch.cuda.current_stream()
-        lib.call("d2s_attn_delta", lib.ptr(out), lib.ptr(dout), lib.ptr(delta), B, n, H)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            lib.call("d2s_attn_bwd_dkv_f32", lib.ptr(qkv), lib.ptr(dout), lib.ptr(lse), lib.ptr(delta), lib.ptr(dqkv), B, n, H, float(scale))
-        lib.call("d2s_attn_bwd_dq_f32", lib.ptr(qkv), lib.ptr(dout), lib.ptr(lse), lib.ptr(delta), lib.ptr(dqkv), B, n, H, float(scale))
-        main.wait_stream(side)
-        return dqkv
     entry = "d2s_attn_bwd_bf16" if bf16 else "d2s_attn_bwd_f32"
     lib.call(entry, lib.ptr(qkv), lib.ptr(out), lib.ptr(dout), lib.ptr(lse), lib.ptr(dqkv), lib.ptr(delta), B, n, H, float(scale))
     return dqkv

@@ -319,12 +319,13 @@ def test_gemm_split_modes(ops, mode, rtol, atol):
 
 
 @pytest.mark.parametrize("mode,rtol,atol", [(1, 1e-4, 2e-5), (2, 3e-2, 3e-2)])
-@pytest.mark.parametrize("M,N,K", [(4096, 1536, 384), (2500, 384, 1536), (2048, 768, 96), (3000, 1152, 384), (2304, 300, 64)])
+@pytest.mark.parametrize("M,N,K", [(4096, 1536, 384), (2500, 384, 1536), (2048, 768, 96), (3000, 1152, 384), (2304, 300, 64),
+                                   (12700, 1152, 384)])
 def test_gemm_split_modes_big_tiles(ops, mode, rtol, atol, M, N, K):
-    """Shapes that take the large-tile LDS-DMA kernel in bf16 mode (M >= 2048; 256x256 or 256x128 tiles by shape, the GPU round also
-    runs this file with D2S_SPLIT_DMA=2 / 3 to force either): forward with every epilogue the model uses on that path (bias, GELU +
-    pre-activation copy, residual, GELU-gradient mask) and the input-gradient layout, ragged edges in M and N included, in both
-    arithmetic modes at the tolerances of the 128x128 kernel."""
+    """Shapes that take the large-tile LDS-DMA kernel in bf16 mode (M >= 2048; 256x256 or 256x128 tiles by the residency cost rule of
+    launch_split_gemm: (4096, 1536) and (3000, 1152) get 256x128, (12700, 1152) gets 256x256 - 250 tiles for 256 CUs): forward with every
+    epilogue the model uses on that path (bias, GELU + pre-activation copy, residual, GELU-gradient mask) and the input-gradient layout,
+    ragged edges in M and N included, in both arithmetic modes at the tolerances of the 128x128 kernel."""
     ops.set_gemm_mode(mode)
     try:
         x, w, b = _rand("bx", (M, K), seed=M), _rand("bw", (N, K), 0.05, seed=N), _rand("bb", (N,), 0.1)

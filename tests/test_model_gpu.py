@@ -794,7 +794,7 @@ def test_full_size_config3_batch32_three_stages():
     args = types.SimpleNamespace(keep_ratios=[0.7, 0.5, 0.3], mask_loss_type="kl_div", mixup=0.0, patch_score_threshold=None, step=0)
     x = _t(synth.images(32, 3, 224, seed=3)).to(dev)
     y = _t(synth.labels(32, 1000, seed=3)).to(dev)
-    # at 32 / 16 images the GEMM grids are small enough that the forward GEMMs split K to fill the chip (gemm_f32.hip, D2S_NT_SPLITK), and
+    # at 32 / 16 images the GEMM grids are small enough that the forward GEMMs split K to fill the chip (gemm_f32.hip, nt_slices), and
     # the number of K slices depends on the row count: the same products are summed in another order (measured: 2.6e-6 on O(0.5) logits)
     _full_size_properties(student, teacher, args, x, y, half=16, rtol=1e-4, atol=1e-5)
     assert [k.shape[1] for k in student.kept_token_indices] == [137, 98, 58]
