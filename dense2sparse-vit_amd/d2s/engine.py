@@ -7,6 +7,7 @@ exp_avg_sq have arenas of the same layout.  The Functions in d2s.functional writ
 the gradient arena (ops.grad_buffer), so the optimiser is a single kernel launch and a DDP bucket is a contiguous
 slice - there is no flatten/unflatten copy anywhere.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -102,6 +103,48 @@ class FusedAdamW:
         self._desc = None
         self._dirty = True
         self._wt = None
+        # exponential moving average of the weights (enable_ema): a fifth arena, advanced inside the AdamW launch; None = off, and then
+        # neither the buffer nor the EMA entry point is ever touched
+        self.ema, self.ema_decay, self._ema_primed = None, None, False
+
+    def enable_ema(self, decay):
+        """Keep ema = decay * ema + (1 - decay) * p after every step (timm ModelEmaV2), in the launch that updates p.  The average
+        starts from the parameters as they are immediately before the NEXT step - not from what the arena holds now - so a broadcast
+        into the arena or a load_state_dict that follows this call is what it starts from."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise lib.D2SError(f"ema decay {decay}: expected 0 <= decay < 1")
+        if self.ema is None:
+            self.ema = torch.zeros_like(self.arena.params)
+        self.ema_decay, self._ema_primed = decay, False
+
+    def ema_flat(self):
+        """The EMA arena as it counts right now: before the first step after enable_ema it IS the parameters."""
+        if self.ema is None:
+            raise lib.D2SError("no EMA weights: call enable_ema(decay) first")
+        return self.ema if self._ema_primed else self.arena.params
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the parameter arena holds the EMA weights (and the EMA arena the live ones): the model evaluates its moving
+        average without a second copy of itself.  Swapped on the device and swapped back on exit, bit for bit.  No step inside."""
+        if self.ema is None:
+            raise lib.D2SError("no EMA weights: call enable_ema(decay) first")
+        swap = self._ema_primed              # not started yet: the average equals the parameters, nothing to exchange
+        if swap:
+            self._swap_ema()
+        try:
+            yield self
+        finally:
+            if swap:
+                self._swap_ema()
+
+    def _swap_ema(self):
+        a = self.arena
+        tmp = a.params.clone()
+        a.params.copy_(self.ema)
+        self.ema.copy_(tmp)
+        ops.bump_weights_epoch()        # raw write into the arena: cached W^T copies and bf16 mirrors of the weights are stale
 
     def set_lrs(self, predictor_lr, backbone_lr):
         self.group_lr.update(predictor=predictor_lr, base_no_decay=backbone_lr, base_decay=backbone_lr)
@@ -133,8 +176,15 @@ class FusedAdamW:
             self._build_desc()
         self.steps += 1
         a = self.arena
-        ops.adamw_step(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
-                       self.eps, self.steps, grad_scale, chunk_steps=self.chunk_steps)
+        if self.ema is None:
+            ops.adamw_step(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
+                           self.eps, self.steps, grad_scale, chunk_steps=self.chunk_steps)
+        else:
+            if not self._ema_primed:
+                self.ema.copy_(a.params)
+                self._ema_primed = True
+            ops.adamw_step_ema(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
+                               self.eps, self.steps, self.ema, self.ema_decay, grad_scale, chunk_steps=self.chunk_steps)
         ops.bump_weights_epoch()        # the kernel wrote the parameters through raw pointers: cached W^T copies are stale
 
     def refresh_transposed_weights(self):
@@ -154,6 +204,71 @@ class FusedAdamW:
     def zero_grad(self):
         for p in self.arena.params_list:
             p.grad = None
+
+    # ---- state in and out: per parameter NAME and in the parameter's own shape; offsets, padding and the arena order stay inside ----
+    def _unflatten(self, flat):
+        """device arena -> {name: CPU tensor of the parameter's shape, with storage of its own} (one device-to-host copy)"""
+        a = self.arena
+        host = flat.detach().cpu()
+        return {n: host[o:o + sz].reshape(p.shape).clone() for n, p, o, sz in zip(a.names, a.params_list, a.offsets, a.sizes)}
+
+    def _flatten(self, tensors):
+        """{name: tensor} -> CPU tensor in arena layout (padding zero)"""
+        a = self.arena
+        host = torch.zeros(a.total, dtype=torch.float32)
+        for n, o, sz in zip(a.names, a.offsets, a.sizes):
+            host[o:o + sz] = tensors[n].detach().to(dtype=torch.float32, device="cpu").reshape(-1)
+        return host
+
+    def state_dict(self):
+        a = self.arena
+        m, v = self._unflatten(self.exp_avg), self._unflatten(self.exp_avg_sq)
+        counts = self.chunk_steps.cpu().tolist()
+        state = {n: {"exp_avg": m[n], "exp_avg_sq": v[n], "step": int(counts[a.chunk_range(i)[0]])} for i, n in enumerate(a.names)}
+        return {"state": state, "betas": [float(self.betas[0]), float(self.betas[1])], "eps": float(self.eps), "steps": int(self.steps)}
+
+    def check_state_dict(self, sd, what="optimizer"):
+        a = self.arena
+        state = sd.get("state") if isinstance(sd, dict) else None
+        if not isinstance(state, dict):
+            raise lib.D2SError(f"checkpoint {what}: no per-parameter 'state'")
+        _check_names_shapes(what, {n: tuple(p.shape) for n, p in zip(a.names, a.params_list)},
+                            {n: tuple(e["exp_avg"].shape) for n, e in state.items()})
+        for n, e in state.items():
+            if tuple(e["exp_avg_sq"].shape) != tuple(e["exp_avg"].shape):
+                raise lib.D2SError(f"checkpoint {what}: exp_avg_sq of {n} has shape {tuple(e['exp_avg_sq'].shape)}, exp_avg {tuple(e['exp_avg'].shape)}")
+        if [float(b) for b in sd["betas"]] != [float(b) for b in self.betas] or float(sd["eps"]) != float(self.eps):
+            raise lib.D2SError(f"checkpoint {what}: betas / eps {sd['betas']} / {sd['eps']}, this optimiser has {list(self.betas)} / {self.eps}")
+
+    def load_state_dict(self, sd):
+        """Copies INTO the existing arenas (call check_state_dict first: this method assumes names and shapes fit)."""
+        a = self.arena
+        state = sd["state"]
+        self.exp_avg.copy_(self._flatten({n: state[n]["exp_avg"] for n in a.names}))
+        self.exp_avg_sq.copy_(self._flatten({n: state[n]["exp_avg_sq"] for n in a.names}))
+        counts = torch.zeros(a.n_chunks, dtype=torch.int32)
+        for i, n in enumerate(a.names):
+            c0, c1 = a.chunk_range(i)
+            counts[c0:c1] = int(state[n]["step"])
+        self.chunk_steps.copy_(counts)
+        self.steps = int(sd.get("steps", 0))
+        self._dirty = True
+
+
+def _check_names_shapes(what, want, got):
+    """want / got: {name: shape}.  One D2SError naming the first difference."""
+    for n in want:
+        if n not in got:
+            raise lib.D2SError(f"checkpoint {what}: {n} is missing")
+    for n in got:
+        if n not in want:
+            raise lib.D2SError(f"checkpoint {what}: unexpected entry {n}")
+    for n, shape in want.items():
+        if tuple(got[n]) != tuple(shape):
+            raise lib.D2SError(f"checkpoint {what}: {n} has shape {tuple(got[n])}, this model has {tuple(shape)}")
+
+
+CHECKPOINT_FORMAT = 1
 
 
 def adjust_learning_rate(optimizer, model, step, epochs, lr, min_lr, warmup_steps, frozen=()):
@@ -400,6 +515,114 @@ class TrainStep:
                 for o, sz, p, g in zip(a.offsets, a.sizes, a.params_list, self.opt.groups)
                 if p.requires_grad and g is not None and g != "early_exit")
         return out
+
+    # ---- exponential moving average of the weights (FusedAdamW.enable_ema) ----
+    def enable_ema(self, decay):
+        self.opt.enable_ema(decay)
+
+    def ema_weights(self):
+        """Context manager: the student holds its EMA weights inside the block (FusedAdamW.ema_weights)."""
+        return self.opt.ema_weights()
+
+    def ema_state_dict(self):
+        """The student's state dict with the EMA weights for its parameters (CPU tensors); buffers - the running statistics of
+        --predictor-bn - are the live model's: only parameters are averaged.  Call it outside ema_weights()."""
+        return self._model_state(self.opt.ema_flat())
+
+    def _model_state(self, flat):
+        byname = self.opt._unflatten(flat)
+        return {k: (byname[k] if k in byname else v.detach().cpu().clone()) for k, v in self.student.state_dict().items()}
+
+    # ---- checkpoints ----
+    def config(self):
+        """What a checkpoint must agree on with the run that loads it (schedule lengths and learning rates may differ: a resumed job may
+        be given more epochs)."""
+        s = self.student
+        pe = getattr(s, "patch_embed", None)
+        pred = s.score_predictor[0] if len(getattr(s, "score_predictor", [])) else None
+        thr = getattr(s, "patch_score_threshold", None)
+        return {
+            "format": CHECKPOINT_FORMAT,
+            "model": type(s).__name__,
+            "embed_dim": int(getattr(s, "embed_dim", 0)),
+            "depth": len(s.blocks),
+            "num_heads": int(getattr(getattr(s.blocks[0], "attn", None), "num_heads", 0)),
+            "num_classes": int(getattr(s, "num_classes", 0)),
+            "img_size": [int(v) for v in getattr(pe, "img_size", ())],
+            "patch_size": [int(v) for v in getattr(pe, "patch_size", ())],
+            "pruning_loc": [int(v) for v in getattr(s, "pruning_loc", [])],
+            "token_ratio": [float(v) for v in getattr(s, "token_ratio", [])],
+            "init_n": int(getattr(s, "init_n", 0)),
+            "topk_selection": bool(getattr(s, "topk_selection", False)),
+            "small_predictor": bool(getattr(pred, "small_predictor", False)),
+            "predictor_bn": bool(getattr(pred, "use_bn", False)),
+            "mask_loss_type": str(getattr(self.args, "mask_loss_type", "")),
+            "patch_score_threshold": None if thr is None else float(thr),
+            "gemm_mode": int(ops.get_gemm_mode()),
+        }
+
+    def state_dict(self, best_acc=0.0, epoch=None):
+        """Everything a later process needs to continue this run after the epoch that just ended, or to evaluate the student: a plain
+        nested dict of CPU tensors, numbers, strings and lists (torch.load(..., weights_only=True) reads it back).  Keys are the
+        student's parameter names and every tensor has its parameter's own shape - the arena layout stays an implementation detail.
+        epoch: the last finished one (default: the epoch set_epoch was last called with)."""
+        dev = self.arena.params.device
+        sd = {
+            "model": self._model_state(self.arena.params),
+            "optimizer": self.opt.state_dict(),
+            "epoch": int(self.epoch if epoch is None else epoch),
+            "best_acc": float(best_acc),
+            "rng": {"cpu": torch.get_rng_state().clone()},
+            "config": self.config(),
+        }
+        if dev.type == "cuda":
+            sd["rng"]["device"] = torch.cuda.get_rng_state(dev).clone()
+        if self.opt.ema is not None:
+            sd["model_ema"] = self.ema_state_dict()
+            sd["ema_decay"] = float(self.opt.ema_decay)
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue from TrainStep.state_dict(): config, then names and shapes are checked BEFORE anything is written (one D2SError names
+        the first mismatch and leaves this step as it was); the tensors are then copied INTO the arenas this step already owns, the
+        per-tensor AdamW counters rebuilt, EMA weights and RNG states restored, and everything that remembers the old weights (captured
+        step graphs, a teacher pass issued ahead, cached W^T / bf16 copies) dropped.  The caller continues with set_epoch(sd["epoch"] + 1)."""
+        if not isinstance(sd, dict) or not isinstance(sd.get("config"), dict) or "model" not in sd or "optimizer" not in sd:
+            raise lib.D2SError("not a training checkpoint: 'config', 'model' and 'optimizer' are expected (a weights-only file goes "
+                               "through --student-checkpoint)")
+        theirs, ours = sd["config"], self.config()
+        for k in ours:
+            if k not in theirs or theirs[k] != ours[k]:
+                raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")
+        own = self.student.state_dict()
+        _check_names_shapes("model", {k: tuple(v.shape) for k, v in own.items()}, {k: tuple(v.shape) for k, v in sd["model"].items()})
+        self.opt.check_state_dict(sd["optimizer"])
+        ema = sd.get("model_ema") if self.opt.ema is not None else None
+        if ema is not None:
+            _check_names_shapes("model_ema", {k: tuple(v.shape) for k, v in own.items()}, {k: tuple(v.shape) for k, v in ema.items()})
+        # ---- checked; from here on only copies into existing storage (parameters keep aliasing the arena) ----
+        a = self.arena
+        a.params.copy_(self.opt._flatten(sd["model"]))
+        for k, v in own.items():
+            if k not in a.grad_views:                  # buffers (BatchNorm running statistics): in place too
+                v.copy_(sd["model"][k])
+        self.opt.load_state_dict(sd["optimizer"])
+        if ema is not None:
+            self.opt.ema.copy_(self.opt._flatten(ema))
+            self.opt._ema_primed = True
+        elif self.opt.ema is not None:
+            self.opt._ema_primed = False               # a checkpoint without an average: it starts from the loaded weights
+        rng = sd.get("rng", {})
+        if "cpu" in rng:
+            torch.set_rng_state(rng["cpu"])
+        if "device" in rng and a.params.device.type == "cuda":
+            torch.cuda.set_rng_state(rng["device"], a.params.device)
+        ops.bump_weights_epoch()
+        self.opt.mark_dirty()
+        self.drop_graphs()
+        self._ahead = None
+        a.check_alias()
+        return int(sd["epoch"])
 
     @staticmethod
     def _batch_key(images):

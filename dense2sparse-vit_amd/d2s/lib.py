@@ -89,6 +89,7 @@ _SIGS = {
     "d2s_block_bwd_f32": (I, [P, P, P, P, P, I, I, I, I, I, F, P, P, P, I, P, Z, P, Z, P]),
     "d2s_adamw_chunk_elems": (I, None),
     "d2s_adamw_step": (I, [P, P, P, P, P, I, F, F, F, I, F, P]),
+    "d2s_adamw_step_ema": (I, [P, P, P, P, P, I, F, F, F, I, F, P, P, F]),
     "d2s_augment_desc_ints": (I, None),
     "d2s_augment_images": (I, [P, L, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P]),
     "d2s_augment_labels": (I, [P, I, I, F, F, P]),

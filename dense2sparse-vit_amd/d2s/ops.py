@@ -967,6 +967,15 @@ def adamw_step(params, grads, exp_avg, exp_avg_sq, desc, n_chunks, beta1, beta2,
              float(beta1), float(beta2), float(eps), int(step), float(grad_scale), lib.ptr(chunk_steps))
 
 
+def adamw_step_ema(params, grads, exp_avg, exp_avg_sq, desc, n_chunks, beta1, beta2, eps, step, ema, ema_decay, grad_scale=1.0,
+                   chunk_steps=None):
+    """adamw_step, and in the same launch ema = ema_decay * ema + (1 - ema_decay) * params (every chunk, the inactive ones included)."""
+    assert chunk_steps is None or (chunk_steps.dtype == torch.int32 and chunk_steps.numel() == n_chunks)
+    assert ema.dtype == torch.float32 and ema.numel() == params.numel() and ema.data_ptr() != params.data_ptr()
+    lib.call("d2s_adamw_step_ema", lib.ptr(params), lib.ptr(grads), lib.ptr(exp_avg), lib.ptr(exp_avg_sq), lib.ptr(desc), n_chunks,
+             float(beta1), float(beta2), float(eps), int(step), float(grad_scale), lib.ptr(chunk_steps), lib.ptr(ema), float(ema_decay))
+
+
 # ---- gradient-arena routing: the slice of a flat gradient arena that the gradient of a parameter is written into.  The record lives
 # ON the Parameter object (not in a table keyed by its address), so it dies with the parameter, an arena is freed as soon as its model
 # and TrainStep are, and a recycled device address can never alias a stale entry. ----

@@ -11,6 +11,9 @@ are outside the path.
         --data-source folder --imgnet-val-dir /path/to/imagefolder --batch-size 128
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         dense2sparse-vit_amd/mask_predictor.py --use-ddp ...        (one process per GPU, RCCL)
+    python dense2sparse-vit_amd/mask_predictor.py ... --output-dir runs/a --model-ema      (runs/a/last.pt after every epoch, best.pt)
+    python dense2sparse-vit_amd/mask_predictor.py ... --output-dir runs/a --resume runs/a/last.pt
+    python dense2sparse-vit_amd/mask_predictor.py ... --eval-only --resume runs/a/best.pt
 """
 import os
 import sys
@@ -66,8 +69,21 @@ def check_supported(args):
             bad.append("--recount above 8 (erase boxes per image)")
         if not 0 <= args.num_workers <= 16:
             bad.append("--num-workers outside 0..16")
+    if args.resume and args.torch_optim:
+        bad.append("--resume with --torch-optim (a checkpoint restores the fused step's arenas; that recipe has none)")
+    if args.model_ema and args.torch_optim:
+        bad.append("--model-ema with --torch-optim (the moving average is kept inside the fused AdamW launch)")
+    if args.model_ema and not 0.0 <= args.model_ema_decay < 1.0:
+        bad.append(f"--model-ema-decay {args.model_ema_decay} (0 <= decay < 1)")
+    if args.eval_only and not (args.resume or args.student_checkpoint):
+        bad.append("--eval-only without weights to load (--resume FILE or --student-checkpoint FILE)")
+    if args.save_every < 1:
+        bad.append(f"--save-every {args.save_every} (at least 1)")
     if bad:
         raise SystemExit("not on the accelerated path: " + "; ".join(bad))
+    if args.output_dir and args.torch_optim and not args.eval_only:
+        print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
+              "loads through --student-checkpoint, it cannot be resumed")
     if args.predictor_bn and args.use_ddp:
         print("Attention: --predictor-bn keeps per-rank batch statistics (not synchronised), exactly like the reference")
     if folder:
@@ -110,6 +126,28 @@ def folder_loaders(args, samples, split, epoch, rank, world):
     return train, val
 
 
+def save_checkpoints(args, optim, student, epoch, best_acc, improved, first):
+    """Rank 0, after an epoch: DIR/last.pt (every --save-every epochs and after the final one) and, when val_acc improved, DIR/best.pt.
+    Each goes to a temporary name first (utils.atomic_save)."""
+    last = (epoch + 1) % args.save_every == 0 or epoch == args.epochs - 1
+    if not (last or improved):
+        return first
+    t0 = time.time()
+    if args.torch_optim:
+        sd = {"model": {k: v.detach().cpu().clone() for k, v in student.state_dict().items()}, "epoch": epoch, "best_acc": float(best_acc)}
+    else:
+        sd = optim.state_dict(best_acc=best_acc, epoch=epoch)
+    os.makedirs(args.output_dir, exist_ok=True)
+    for name, wanted in (("last.pt", last), ("best.pt", improved)):
+        if wanted:
+            utils.atomic_save(sd, os.path.join(args.output_dir, name))
+            if first:       # the cost of --save-every 1, once
+                size = os.path.getsize(os.path.join(args.output_dir, name))
+                print(f"checkpoint: state_dict + write of {name} took {time.time() - t0:.3f} s ({size / 1e6:.1f} MB)")
+                first = False
+    return first
+
+
 def main(argv=None):
     args = utils.parse_args(argv)
     check_supported(args)
@@ -147,6 +185,16 @@ def main(argv=None):
                           warmup_steps=args.warmup_steps, distributed=distributed)
         if distributed:
             dist.broadcast(optim.arena.params, src=0)
+    start_epoch, best_acc = 0, 0.0
+    if not args.torch_optim:
+        if args.model_ema:
+            optim.enable_ema(args.model_ema_decay)
+        if args.resume:                   # every rank reads the file; nothing from it is executed
+            sd = torch.load(args.resume, map_location="cpu", weights_only=True)
+            start_epoch = optim.load_state_dict(sd) + 1
+            best_acc = float(sd["best_acc"])
+            print(f"Resumed {args.resume}: epoch {start_epoch} is finished, best val acc so far {best_acc:4f}")
+            del sd
     n_pred = sum(p.numel() for n, p in student.named_parameters() if 'predictor' in n and p.requires_grad)
     print(f'Total number of trainable parameters in predictor network in millions: {n_pred / 1e6}')
     folder = args.data_source == "folder"
@@ -157,10 +205,29 @@ def main(argv=None):
             raise SystemExit(f"{len(classes)} classes in {args.imgnet_val_dir}, the heads have {args.nb_classes}")
         split = data.split_indices(len(samples))
         print(f"{len(samples)} images in {len(classes)} classes: {len(split[0])} train / {len(split[1])} val")
-    print(f"Start training for {args.epochs} epochs, with batch size of {args.batch_size}")
     img = 224
-    since, best_acc = time.time(), 0.0
-    for epoch in range(args.epochs):
+    if args.eval_only:
+        if folder:
+            _, val_loader = folder_loaders(args, samples, split, 0, rank, world)
+        else:
+            val_loader = utils.SyntheticLoader(args.val_steps, args.batch_size, img, seed=777 + rank, device=args.device)
+        metrics = evaluate_performance(args, student, teacher, val_loader)
+        if args.model_ema and args.resume:
+            with optim.ema_weights():
+                metrics["val_acc_ema"] = evaluate_performance(args, student, teacher, val_loader)["val_acc"]
+        if distributed:
+            keys = [k for k in ("val_acc", "val_acc_ema") if k in metrics]
+            t = torch.tensor([metrics[k] for k in keys], device=args.device)
+            dist.all_reduce(t)
+            metrics.update(zip(keys, (t / world).tolist()))
+            dist.destroy_process_group()
+        if rank == 0:
+            print("eval only: " + ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
+        return metrics["val_acc"]
+    print(f"Start training for {args.epochs} epochs, with batch size of {args.batch_size}")
+    since = time.time()
+    first_save = True
+    for epoch in range(start_epoch, args.epochs):
         args.step = epoch
         print('Epoch {}/{}'.format(epoch + 1, args.epochs))
         print('-' * 50)
@@ -184,12 +251,29 @@ def main(argv=None):
         dt = time.time() - t0
         val_metrics = evaluate_performance(args, student, teacher, val_loader)                              # :310
         epoch_metrics = dict(train_metrics, **val_metrics)
+        if args.model_ema:                # the same student object scores its moving average: the arenas trade contents and trade back
+            with optim.ema_weights():
+                epoch_metrics["val_acc_ema"] = evaluate_performance(args, student, teacher, val_loader)["val_acc"]
         if distributed:                                                                                     # ddp_training.py:174-177,213
-            t = torch.tensor([epoch_metrics["train_loss"], epoch_metrics["val_acc"]], device=args.device)
+            keys = ["train_loss", "val_acc"] + (["val_acc_ema"] if args.model_ema else [])
+            t = torch.tensor([epoch_metrics[k] for k in keys], device=args.device)
             dist.all_reduce(t)
-            epoch_metrics["train_loss"], epoch_metrics["val_acc"] = (t / world).tolist()
+            epoch_metrics.update(zip(keys, (t / world).tolist()))
             dist.barrier()
+        if args.output_dir:
+            # best.pt follows val_acc, as the reference tracks it: written after the first evaluated epoch whatever its accuracy, replaced
+            # only by a strictly better one.  All ranks hold the same arenas after the reduced step, so rank 0 alone writes.
+            improved = epoch_metrics['val_acc'] > best_acc or not os.path.exists(os.path.join(args.output_dir, "best.pt"))
+            if distributed:
+                flag = torch.tensor([1.0 if improved else 0.0], device=args.device)
+                dist.broadcast(flag, src=0)          # only rank 0 looks at the directory
+                improved = bool(flag.item())
         best_acc = max(best_acc, epoch_metrics['val_acc'])
+        if args.output_dir:
+            if rank == 0:
+                first_save = save_checkpoints(args, optim, student, epoch, best_acc, improved, first_save)
+            if distributed:
+                dist.barrier()
         if rank == 0:
             print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))

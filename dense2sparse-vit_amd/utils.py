@@ -145,7 +145,33 @@ def parse_args(argv=None):
     p.add_argument('--data-source', choices=['synthetic', 'folder'], default='synthetic',
                    help='synthetic N(0,1) batches, or an ImageFolder at --imgnet-val-dir (80/20 train/val split, GPU augmentation)')
     p.add_argument('--num-workers', type=int, default=8, help='JPEG-decoding DataLoader workers of --data-source folder (at most 16)')
+    p.add_argument('--output-dir', type=str, default=None,
+                   help='after every epoch rank 0 writes DIR/last.pt, and DIR/best.pt when val_acc improved (default: nothing is written)')
+    p.add_argument('--save-every', type=int, default=1, help='write last.pt every N epochs, and always after the final one')
+    p.add_argument('--resume', type=str, default=None, help='continue the run saved in FILE (a last.pt / best.pt) with the epoch after it')
+    p.add_argument('--eval-only', action='store_true', default=False,
+                   help='with --resume or --student-checkpoint: load, run the evaluation once, print, exit')
+    p.add_argument('--model-ema', action='store_true', default=False,
+                   help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
+    p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
     return p.parse_args(argv)
+
+
+def atomic_save(obj, path, writer=torch.save):
+    """writer(obj, file) into a temporary name in the directory of `path`, flushed to disk, then os.replace: whoever reads `path`
+    finds the previous complete file or the new complete file, never a part of one - also when the job is killed mid-write."""
+    import os
+    tmp = os.path.join(os.path.dirname(os.path.abspath(path)), f".{os.path.basename(path)}.{os.getpid()}.tmp")
+    try:
+        with open(tmp, "wb") as f:
+            writer(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
 
 
 def keep_ratio_summary(keep_ratio_batches):

@@ -280,6 +280,14 @@ int d2s_adamw_chunk_elems(void);
  * advances the counters of the active chunks.  NULL: `step` (>= 1) is used for every chunk. */
 int d2s_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* chunk_desc, int n_chunks,
                    float beta1, float beta2, float eps, int step, float grad_scale, int* chunk_steps, d2s_stream_t stream);
+/* The same update, and in the same launch the exponential moving average of the weights (timm ModelEmaV2): ema, a fifth arena of the same
+ * layout, becomes ema_decay * ema + (1 - ema_decay) * p_new, element by element, from the fresh parameters still in registers (36 bytes
+ * per element instead of 28).  Chunks that are not active are not updated, but their average still follows their (unchanged)
+ * parameters; padding stays zero.  0 <= ema_decay < 1, anything else is D2S_ERR_ARG.  The factor 1 - ema_decay is formed on the host, in
+ * double from the float ema_decay, and passed to the kernel rounded to float: the two factors sum to 1 exactly. */
+int d2s_adamw_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* chunk_desc, int n_chunks,
+                       float beta1, float beta2, float eps, int step, float grad_scale, int* chunk_steps, float* ema, float ema_decay,
+                       d2s_stream_t stream);
 
 /* ---- input pipeline: crop + resize (bit-exact with Pillow), flip, Normalize, RandomErasing, Mixup / CutMix (build_data_sets.py:8-34,
  * train.py:29-31; d2s/data.py packs the batch) ------------------------------------------------------------------------------------ */
