@@ -35,6 +35,10 @@ int d2s_attn_bwd_f32(const float* qkv, const float* out, const float* dout, cons
                      int H, float scale, hipStream_t stream);
 int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, hipStream_t stream);
 int d2s_softmax_rows(const float* scores, float* probs, int rows, int T, hipStream_t stream);
+int d2s_gemm_f32_rowscale(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
+                          const float* bias, const float* aux, long ldaux, const float* rowscale, int rows_per_group, int mode,
+                          const void* a_bf16, const void* b_bf16, void* c_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int d2s_scale_rows(const float* g, const float* rowscale, float* out, long M, int D, int rows_per_group, hipStream_t stream);
 }
 
 namespace {
@@ -73,9 +77,11 @@ struct BlockSaved {
 
 // scratch slab of a block backward, in floats: dz, g1 and dqkv are read by the weight-gradient stream after the main stream has moved
 // on, so they get buffers of their own; dln2 / dao / dln1 live and die on the main stream one after the other and share `t`
+// with stochastic depth (drop_path): + the scaled copies of gy and g1 that enter the MLP / attention branch; each is read by that branch's
+// weight-gradient launch on the side stream, so they do not share a buffer either
 struct BlockBwdScratch {
-    long dz, g1, dqkv, delta, t, total;
-    BlockBwdScratch(long B, long n, long D, long H, long hid) {
+    long dz, g1, dqkv, delta, t, gs_mlp, gs_attn, total;
+    BlockBwdScratch(long B, long n, long D, long H, long hid, bool drop_path = false) {
         const long M = B * n;
         long o = 0;
         auto take = [&](long cnt) { const long at = o; o += seg(cnt); return at; };
@@ -84,6 +90,8 @@ struct BlockBwdScratch {
         dqkv = take(M * 3 * D);
         delta = take(B * H * n);
         t = take(M * D);
+        gs_mlp = gs_attn = -1;
+        if (drop_path) { gs_mlp = take(M * D); gs_attn = take(M * D); }
         total = o;
     }
 };
@@ -133,6 +141,13 @@ inline int linear_fwd(const Ctx& c, const float* x, const float* W, const float*
     return d2s_gemm_f32(NT, x, K, W, K, y, N, M, N, K, epi, b, aux, aux ? N : 0, aux_out, 0, 0, 0, 0, c.mode, c.ws, c.ws_bytes, c.stream);
 }
 
+// y = rowscale[m / rows_per_group] * (x W^T + b) + aux: the residual Linear of a branch under stochastic depth
+inline int linear_fwd_rowscale(const Ctx& c, const float* x, const float* W, const float* b, float* y, int M, int N, int K, const float* aux,
+                               const float* rowscale, int rows_per_group) {
+    return d2s_gemm_f32_rowscale(NT, x, K, W, K, y, N, M, N, K, b, aux, N, rowscale, rows_per_group, c.mode, nullptr, nullptr, nullptr, c.ws,
+                                 c.ws_bytes, c.stream);
+}
+
 // dx[M,K] = epi(dy[M,N] W[N,K]); with the k-contiguous copy W^T [K,N] at hand it runs as an NT product (exact mode, d2s.ops.linear_dgrad)
 inline int linear_dgrad(const Ctx& c, const float* dy, const float* W, const float* Wt, float* dx, int M, int N, int K, int epi = EPI_NONE,
                         const float* aux = nullptr) {
@@ -167,6 +182,8 @@ extern "C" {
 // floats of the slab d2s_block_fwd_f32 fills: train != 0 -> everything the backward needs; 0 -> forward-only scratch
 long d2s_block_saved_floats(int B, int n, int D, int H, int hidden, int train) { return BlockSaved(B, n, D, H, hidden, train != 0).total; }
 long d2s_block_bwd_scratch_floats(int B, int n, int D, int H, int hidden) { return BlockBwdScratch(B, n, D, H, hidden).total; }
+// the scratch of d2s_block_bwd_f32_dp when a table row is given
+long d2s_block_bwd_dp_scratch_floats(int B, int n, int D, int H, int hidden) { return BlockBwdScratch(B, n, D, H, hidden, true).total; }
 
 // scratch of the launches issued on the caller's stream (split-K slabs of small grids, LayerNorm-backward partials)
 size_t d2s_block_workspace_bytes(int B, int n, int D, int hidden, int mode) {
@@ -204,8 +221,12 @@ size_t d2s_block_wgrad_workspace_bytes(int B, int n, int D, int hidden, int mode
 //           norm2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
 //   cls_row [B, H, n] or NULL: the CLS row of the softmax (Attention.forward's second output, :234)
 //   saved: slab of d2s_block_saved_floats(.., train) floats; train != 0: it holds what d2s_block_bwd_f32 needs afterwards
-int d2s_block_fwd_f32(const float* x, const float* const* params, int B, int n, int D, int H, int hidden, float eps, float scale, float* y,
-                      float* cls_row, float* saved, int train, int mode, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// _dp: with stochastic depth.  s_attn / s_mlp: [B] rows of the d2s_drop_path_scales table (device; either may be NULL = branch not
+// dropped): x1 = x + s_attn[b] * proj(..), y = x1 + s_mlp[b] * fc2(..), the scale applied in the epilogue of the proj / fc2 GEMM.  With
+// both NULL the launches are exactly those of a block without stochastic depth (d2s_block_fwd_f32 is this call with two NULLs).
+int d2s_block_fwd_f32_dp(const float* x, const float* const* params, const float* s_attn, const float* s_mlp, int B, int n, int D, int H,
+                         int hidden, float eps, float scale, float* y, float* cls_row, float* saved, int train, int mode, void* workspace,
+                         size_t workspace_bytes, hipStream_t stream) {
     if (!x || !params || !y || !saved || B <= 0 || n <= 0 || D <= 0 || H <= 0 || hidden <= 0 || D != H * 64 || mode < 0 || mode > 1) return D2S_ERR_ARG;
     for (int i = 0; i < NPARAM; ++i)      // the four Linear biases are optional (T2T blocks: qkv_bias=False, transformer_block.py:31)
         if (!params[i] && i != QKVB && i != PROJB && i != FC1B && i != FC2B) return D2S_ERR_ARG;
@@ -222,12 +243,20 @@ int d2s_block_fwd_f32(const float* x, const float* const* params, int B, int n, 
                               M, D, eps, stream));
     D2S_TRY(linear_fwd(c, ln1, params[QKVW], params[QKVB], qkv, M, 3 * D, D, params[QKVB] ? EPI_BIAS : EPI_NONE));
     D2S_TRY(d2s_attn_fwd_f32(qkv, ao, saved + L.lse, cls_row, B, n, H, scale, stream));
-    D2S_TRY(linear_fwd(c, ao, params[PROJW], params[PROJB], x1, M, D, D, EPI_BIAS_RESID, x));
+    if (s_attn) D2S_TRY(linear_fwd_rowscale(c, ao, params[PROJW], params[PROJB], x1, M, D, D, x, s_attn, n));
+    else D2S_TRY(linear_fwd(c, ao, params[PROJW], params[PROJB], x1, M, D, D, EPI_BIAS_RESID, x));
     D2S_TRY(d2s_layernorm_fwd(x1, M, 0, D, 0, params[N2W], params[N2B], ln2, train ? saved + L.mean2 : nullptr, train ? saved + L.rstd2 : nullptr,
                               M, D, eps, stream));
     D2S_TRY(linear_fwd(c, ln2, params[FC1W], params[FC1B], h, M, hidden, D, EPI_BIAS_GELU, nullptr, train ? saved + L.z : nullptr));
-    D2S_TRY(linear_fwd(c, h, params[FC2W], params[FC2B], y, M, D, hidden, EPI_BIAS_RESID, x1));
+    if (s_mlp) D2S_TRY(linear_fwd_rowscale(c, h, params[FC2W], params[FC2B], y, M, D, hidden, x1, s_mlp, n));
+    else D2S_TRY(linear_fwd(c, h, params[FC2W], params[FC2B], y, M, D, hidden, EPI_BIAS_RESID, x1));
     return D2S_OK;
+}
+
+int d2s_block_fwd_f32(const float* x, const float* const* params, int B, int n, int D, int H, int hidden, float eps, float scale, float* y,
+                      float* cls_row, float* saved, int train, int mode, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return d2s_block_fwd_f32_dp(x, params, nullptr, nullptr, B, n, D, H, hidden, eps, scale, y, cls_row, saved, train, mode, workspace,
+                                workspace_bytes, stream);
 }
 
 // Backward of d2s_block_fwd_f32 (train slab).  gy [B, n, D] -> dx [B, n, D] (NULL: not wanted, the attention / LayerNorm-1 leg is then
@@ -238,10 +267,13 @@ int d2s_block_fwd_f32(const float* x, const float* const* params, int B, int n, 
 //   scratch: d2s_block_bwd_scratch_floats floats
 //   wgrad_stream: NULL = weight gradients in line; else every Linear's (dW, db) launch is issued there, after a fork from `stream`, with
 //            wgrad_workspace as scratch - the caller joins the two streams before anything reads a gradient
-int d2s_block_bwd_f32(const float* gy, const float* x, const float* saved, const float* const* params, const float* const* paramsT, int B,
-                      int n, int D, int H, int hidden, float scale, float* dx, float* const* dparams, float* scratch, int mode, void* workspace,
-                      size_t workspace_bytes, void* wgrad_workspace, size_t wgrad_workspace_bytes, hipStream_t wgrad_stream,
-                      hipStream_t stream) {
+// _dp: backward of d2s_block_fwd_f32_dp with the same table rows.  The gradient that enters a dropped branch is s[b] * g: one
+// d2s_scale_rows pass per given row into the scratch (d2s_block_bwd_dp_scratch_floats floats when either row is given), and the scaled copy
+// feeds that branch's weight-gradient launch and its input-gradient GEMM; the residual path (LayerNorm backward's add_src) keeps the unscaled g.
+int d2s_block_bwd_f32_dp(const float* gy, const float* x, const float* saved, const float* const* params, const float* const* paramsT,
+                         const float* s_attn, const float* s_mlp, int B, int n, int D, int H, int hidden, float scale, float* dx,
+                         float* const* dparams, float* scratch, int mode, void* workspace, size_t workspace_bytes, void* wgrad_workspace,
+                         size_t wgrad_workspace_bytes, hipStream_t wgrad_stream, hipStream_t stream) {
     if (!gy || !x || !saved || !params || !dparams || !scratch || B <= 0 || n <= 0 || D <= 0 || H <= 0 || hidden <= 0 || D != H * 64 || mode < 0 || mode > 1)
         return D2S_ERR_ARG;
     if ((dparams[N1W] == nullptr) != (dparams[N1B] == nullptr) || (dparams[N2W] == nullptr) != (dparams[N2B] == nullptr)) return D2S_ERR_ARG;
@@ -249,7 +281,7 @@ int d2s_block_bwd_f32(const float* gy, const float* x, const float* saved, const
     if (leg1 && !dx) return D2S_ERR_ARG;
     const int M = B * n;
     const BlockSaved L(B, n, D, H, hidden, true);
-    const BlockBwdScratch S(B, n, D, H, hidden);
+    const BlockBwdScratch S(B, n, D, H, hidden, s_attn || s_mlp);
     const Ctx c{mode, workspace, workspace_bytes, stream};
     Side side{stream, wgrad_stream, wgrad_stream ? wgrad_workspace : workspace, wgrad_stream ? wgrad_workspace_bytes : workspace_bytes, mode};
     const float* qkvT = paramsT ? paramsT[0] : nullptr;
@@ -261,15 +293,25 @@ int d2s_block_bwd_f32(const float* gy, const float* x, const float* saved, const
     float* dqkv = scratch + S.dqkv;
     float* t = scratch + S.t;
     // ---- MLP branch ----
-    D2S_TRY(param_grads(side, gy, saved + L.h, dparams[FC2W], dparams[FC2B], M, D, hidden));
-    D2S_TRY(linear_dgrad(c, gy, params[FC2W], fc2T, dz, M, D, hidden, EPI_MUL_GELU_GRAD, saved + L.z));
+    const float* g2 = gy;      // what enters the branch
+    if (s_mlp) {
+        D2S_TRY(d2s_scale_rows(gy, s_mlp, scratch + S.gs_mlp, M, D, n, stream));
+        g2 = scratch + S.gs_mlp;
+    }
+    D2S_TRY(param_grads(side, g2, saved + L.h, dparams[FC2W], dparams[FC2B], M, D, hidden));
+    D2S_TRY(linear_dgrad(c, g2, params[FC2W], fc2T, dz, M, D, hidden, EPI_MUL_GELU_GRAD, saved + L.z));
     D2S_TRY(param_grads(side, dz, saved + L.ln2, dparams[FC1W], dparams[FC1B], M, hidden, D));
     D2S_TRY(linear_dgrad(c, dz, params[FC1W], fc1T, t, M, hidden, D));                                   // t = dln2
     D2S_TRY(d2s_layernorm_bwd(saved + L.x1, M, 0, D, 0, t, params[N2W], saved + L.mean2, saved + L.rstd2, g1, gy, dparams[N2W], dparams[N2B], 0, 0,
                               M, D, workspace, workspace_bytes, stream));
     // ---- attention branch ----
-    D2S_TRY(param_grads(side, g1, saved + L.ao, dparams[PROJW], dparams[PROJB], M, D, D));
-    D2S_TRY(linear_dgrad(c, g1, params[PROJW], projT, t, M, D, D));                                      // t = dao
+    const float* ga = g1;
+    if (s_attn) {
+        D2S_TRY(d2s_scale_rows(g1, s_attn, scratch + S.gs_attn, M, D, n, stream));
+        ga = scratch + S.gs_attn;
+    }
+    D2S_TRY(param_grads(side, ga, saved + L.ao, dparams[PROJW], dparams[PROJB], M, D, D));
+    D2S_TRY(linear_dgrad(c, ga, params[PROJW], projT, t, M, D, D));                                      // t = dao
     D2S_TRY(d2s_attn_bwd_f32(saved + L.qkv, saved + L.ao, t, saved + L.lse, dqkv, scratch + S.delta, B, n, H, scale, stream));
     D2S_TRY(param_grads(side, dqkv, saved + L.ln1, dparams[QKVW], dparams[QKVB], M, 3 * D, D));
     if (leg1) {
@@ -278,6 +320,14 @@ int d2s_block_bwd_f32(const float* gy, const float* x, const float* saved, const
                                   workspace, workspace_bytes, stream));
     }
     return D2S_OK;
+}
+
+int d2s_block_bwd_f32(const float* gy, const float* x, const float* saved, const float* const* params, const float* const* paramsT, int B,
+                      int n, int D, int H, int hidden, float scale, float* dx, float* const* dparams, float* scratch, int mode, void* workspace,
+                      size_t workspace_bytes, void* wgrad_workspace, size_t wgrad_workspace_bytes, hipStream_t wgrad_stream,
+                      hipStream_t stream) {
+    return d2s_block_bwd_f32_dp(gy, x, saved, params, paramsT, nullptr, nullptr, B, n, D, H, hidden, scale, dx, dparams, scratch, mode,
+                                workspace, workspace_bytes, wgrad_workspace, wgrad_workspace_bytes, wgrad_stream, stream);
 }
 
 }  // extern "C"

@@ -67,3 +67,12 @@ __device__ __forceinline__ void xcd_remap_2d(int& bx, int& by) {
     by = V / gx;
     bx = V - by * gx;
 }
+
+// One round of Philox4x32 (counter c, key k); ten rounds make the counter-based generator of the perturbation noise (perturbed_topk.hip)
+// and of the stochastic-depth draws (droppath.hip).
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
+}

@@ -18,6 +18,8 @@ enum Epi : int {
     // C-ABI codes of d2s_gemm_f32_bf16io only (mapped to the two kinds above + GemmArgs::aux_bf16): the saved GELU pre-activation in bf16
     EPI_BIAS_GELU_Z16 = 9,      // as EPI_BIAS_GELU, aux_out is bf16 [M][ldc]
     EPI_MUL_GELU_GRAD_Z16 = 10, // as EPI_MUL_GELU_GRAD, aux is bf16 [M][ldaux]
+    // stochastic depth (d2s_gemm_f32_rowscale only): the branch output of sample m / rows_per_group is scaled before the residual add
+    EPI_BIAS_RESID_ROWSCALE = 11, // C = rowscale[m / rows_per_group] * (acc + bias[n]) + aux[m][n]
 };
 
 struct GemmArgs {
@@ -41,6 +43,7 @@ struct GemmArgs {
     const void* a16; void* c16;
     const void* b16;   // bf16 mode: the B operand already in bf16, [N][K] k-contiguous whatever the layout (a cached weight, or W^T for dgrad)
     int aux_bf16;      // bf16 mode: aux_out (EPI_BIAS_GELU) / aux (EPI_MUL_GELU_GRAD) point at bf16, not float
+    const float* rowscale; int rows_per_group;   // EPI_BIAS_RESID_ROWSCALE: one scale per group of rows_per_group consecutive output rows
 };
 
 typedef __bf16 bf16x4_epi __attribute__((ext_vector_type(4)));
@@ -53,7 +56,8 @@ __device__ __forceinline__ void store_tile_out(const GemmArgs& p, float* __restr
         const int n = nbase + nt * 32;
         if (n >= p.N) continue;
         float bias = 0.f;
-        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_ROWADD)
+        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_ROWADD ||
+            EPI == EPI_BIAS_RESID_ROWSCALE)
             bias = p.bias ? p.bias[n] : 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -75,6 +79,10 @@ __device__ __forceinline__ void store_tile_out(const GemmArgs& p, float* __restr
                     v = gelu_erf(v);
                 }
                 if (EPI == EPI_BIAS_RESID) v += bias + p.aux[(long)m * p.ldaux + n];
+                if (EPI == EPI_BIAS_RESID_ROWSCALE) {      // a dropped row (scale 0) is the residual bit for bit, whatever the branch holds
+                    const float s = p.rowscale[m / p.rows_per_group];
+                    v = s == 0.f ? p.aux[(long)m * p.ldaux + n] : s * (v + bias) + p.aux[(long)m * p.ldaux + n];
+                }
                 if (EPI == EPI_MUL_GELU_GRAD)
                     v *= gelu_erf_grad(p.aux_bf16 ? (float)reinterpret_cast<const __bf16*>(p.aux)[(long)m * p.ldaux + n] : p.aux[(long)m * p.ldaux + n]);
                 if (EPI == EPI_MUL_RELU_MASK) v = p.aux[(long)m * p.ldaux + n] > 0.f ? v : 0.f;
@@ -101,7 +109,8 @@ __device__ __forceinline__ void store_tile_out_lds(const GemmArgs& p, float* __r
     const int half = lane >> 5, l31 = lane & 31;
     const int rr = lane / LPR, c4 = (lane % LPR) * 4;
     const int n = ncol0 + c4;
-    constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_ROWADD;
+    constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_ROWADD ||
+                              EPI == EPI_BIAS_RESID_ROWSCALE;
     f32x4 bias = {0.f, 0.f, 0.f, 0.f};
     if (HAS_BIAS && p.bias && n < p.N) bias = *reinterpret_cast<const f32x4*>(p.bias + n);
 #pragma unroll
@@ -165,6 +174,12 @@ __device__ __forceinline__ void store_tile_out_lds(const GemmArgs& p, float* __r
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] += a[j];
                 }
+                if (EPI == EPI_BIAS_RESID_ROWSCALE) {      // one scale load per row: a lane's 4 columns share it
+                    const float s = p.rowscale[m / p.rows_per_group];
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(p.aux + (long)m * p.ldaux + n);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = s == 0.f ? a[j] : s * v[j] + a[j];
+                }
                 if (EPI == EPI_ACCUM) {
                     const f32x4 o = *reinterpret_cast<const f32x4*>(cp);
 #pragma unroll
@@ -198,6 +213,7 @@ __device__ __forceinline__ void store_tile_dispatch_lds(int epi, const GemmArgs&
         case EPI_MUL_RELU_MASK: store_tile_out_lds<EPI_MUL_RELU_MASK, MT, NT, C16>(p, Cb, acc, mr, nc, lane, stage); break;
         case EPI_BIAS_ROWADD: store_tile_out_lds<EPI_BIAS_ROWADD, MT, NT, C16>(p, Cb, acc, mr, nc, lane, stage); break;
         case EPI_ACCUM: store_tile_out_lds<EPI_ACCUM, MT, NT, C16>(p, Cb, acc, mr, nc, lane, stage); break;
+        case EPI_BIAS_RESID_ROWSCALE: store_tile_out_lds<EPI_BIAS_RESID_ROWSCALE, MT, NT, C16>(p, Cb, acc, mr, nc, lane, stage); break;
         default: store_tile_out_lds<EPI_NONE, MT, NT, C16>(p, Cb, acc, mr, nc, lane, stage); break;
     }
 }

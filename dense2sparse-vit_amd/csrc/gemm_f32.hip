@@ -289,6 +289,7 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 128) ? 3 : 1) void gemm_f3
         case EPI_MUL_RELU_MASK: store_tile_out<EPI_MUL_RELU_MASK, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
         case EPI_BIAS_ROWADD: store_tile_out<EPI_BIAS_ROWADD, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
         case EPI_ACCUM: store_tile_out<EPI_ACCUM, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
+        case EPI_BIAS_RESID_ROWSCALE: store_tile_out<EPI_BIAS_RESID_ROWSCALE, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
         default: store_tile_out<EPI_NONE, MT, NT>(p, Cb, acc, mbase, nbase, half); break;
     }
 }
@@ -485,7 +486,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(GemmArgs p, cons
     float v = 0.f;
     for (int z = 0; z < slabs; ++z) v += ws[(long)z * slab_stride + idx];
     const int e = p.epi;
-    const bool has_bias = e == EPI_BIAS || e == EPI_BIAS_RELU || e == EPI_BIAS_GELU || e == EPI_BIAS_RESID || e == EPI_BIAS_ROWADD;
+    const bool has_bias = e == EPI_BIAS || e == EPI_BIAS_RELU || e == EPI_BIAS_GELU || e == EPI_BIAS_RESID || e == EPI_BIAS_ROWADD ||
+                          e == EPI_BIAS_RESID_ROWSCALE;
     if (has_bias && p.bias) v += p.bias[n];
     long orow = m;
     if (e == EPI_BIAS_ROWADD && p.remap_rows_per_img > 0) orow = (long)m + (long)(m / p.remap_rows_per_img) * p.remap_skip + p.remap_skip;
@@ -496,6 +498,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(GemmArgs p, cons
         v = gelu_erf(v);
     }
     if (e == EPI_BIAS_RESID) v += p.aux[(long)m * p.ldaux + n];
+    if (e == EPI_BIAS_RESID_ROWSCALE) {
+        const float s = p.rowscale[m / p.rows_per_group], a = p.aux[(long)m * p.ldaux + n];
+        v = s == 0.f ? a : s * v + a;
+    }
     if (e == EPI_MUL_GELU_GRAD) v *= gelu_erf_grad(p.aux[(long)m * p.ldaux + n]);
     if (e == EPI_MUL_RELU_MASK) v = p.aux[(long)m * p.ldaux + n] > 0.f ? v : 0.f;
     if (e == EPI_BIAS_ROWADD) v += p.aux[(long)(m % p.aux_rows) * p.ldaux + n];
@@ -758,7 +764,8 @@ size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode) {
 static int gemm_impl(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                      int K, int epilogue, const float* bias, const float* aux, long ldaux, float* aux_out, int aux_rows,
                      int remap_rows_per_img, int remap_skip, int accumulate, void* workspace, size_t workspace_bytes,
-                     hipStream_t stream, float* colsum_out, int mode, const void* a16 = nullptr, void* c16 = nullptr, const void* b16 = nullptr) {
+                     hipStream_t stream, float* colsum_out, int mode, const void* a16 = nullptr, void* c16 = nullptr, const void* b16 = nullptr,
+                     const float* rowscale = nullptr, int rows_per_group = 0) {
     // layout 2 (weight gradient): a16 is the bf16 form of the SECOND operand (the layer input x); B may then be NULL
     // layout 2: b16 is the bf16 form of the FIRST operand (dy); A may then be NULL
     if (b16 && (mode != 2 || (layout != 2 && (K % 32 != 0 || !aligned16(b16))) || (layout == 2 && (reinterpret_cast<uintptr_t>(b16) & 7)))) return D2S_ERR_ARG;
@@ -778,7 +785,9 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
         aux_bf16 = 1;
         epilogue = epilogue == EPI_BIAS_GELU_Z16 ? EPI_BIAS_GELU : EPI_MUL_GELU_GRAD;
     }
-    if (epilogue < EPI_NONE || epilogue > EPI_ACCUM) return D2S_ERR_ARG;
+    if (epilogue == EPI_BIAS_RESID_ROWSCALE) {      // reachable through d2s_gemm_f32_rowscale only
+        if (!rowscale || rows_per_group <= 0 || layout == 2 || accumulate || !aux) return D2S_ERR_ARG;
+    } else if (epilogue < EPI_NONE || epilogue > EPI_ACCUM) return D2S_ERR_ARG;
     if ((epilogue == EPI_BIAS_RESID || epilogue == EPI_MUL_GELU_GRAD || epilogue == EPI_MUL_RELU_MASK ||
          epilogue == EPI_BIAS_ROWADD) && !aux)
         return D2S_ERR_ARG;
@@ -790,6 +799,7 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
     p.remap_rows_per_img = remap_rows_per_img; p.remap_skip = remap_skip;
     p.colsum = nullptr; p.colsum_accumulate = accumulate;
     p.a16 = a16; p.c16 = c16; p.b16 = b16;
+    p.rowscale = rowscale; p.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
     {
         p.stagger = 0;
         p.vec_epilogue = 0;
@@ -912,6 +922,17 @@ int d2s_gemm_f32_bf16io(int layout, const float* A, long lda, const float* B, lo
     if (layout == 2) return D2S_ERR_ARG;      // weight gradients with a bf16 input: d2s_linear_wgrad_f32_bf16x
     return gemm_impl(layout, A, lda, B, ldb, C, ldc, M, N, K, epilogue, bias, aux, ldaux, aux_out, 0, 0, 0, 0, workspace, workspace_bytes,
                      stream, nullptr, 2, a_bf16, c_bf16, b_bf16);
+}
+
+// Stochastic depth in the residual GEMMs (proj, fc2): C = rowscale[m / rows_per_group] * (A B^T + bias[n]) + aux[m][n], epilogue kind
+// EPI_BIAS_RESID_ROWSCALE.  rowscale: [ceil(M / rows_per_group)] floats, 0 or 1 / keep (a row of the d2s_drop_path_scales table); a row whose
+// scale is 0 is a bit copy of aux.  NT / NN layouts, every mode; a_bf16 / b_bf16 / c_bf16 as in d2s_gemm_f32_bf16io (mode 2 only, else NULL).
+int d2s_gemm_f32_rowscale(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
+                          const float* bias, const float* aux, long ldaux, const float* rowscale, int rows_per_group, int mode,
+                          const void* a_bf16, const void* b_bf16, void* c_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (layout == 2 || !rowscale || rows_per_group <= 0) return D2S_ERR_ARG;
+    return gemm_impl(layout, A, lda, B, ldb, C, ldc, M, N, K, EPI_BIAS_RESID_ROWSCALE, bias, aux, ldaux, nullptr, 0, 0, 0, 0, workspace,
+                     workspace_bytes, stream, nullptr, mode, a_bf16, c_bf16, b_bf16, rowscale, rows_per_group);
 }
 
 // nn.Linear backward w.r.t. its parameters in one pass over dy:  dW[n_out, n_in] (+)= dy^T x,  db[n_out] (+)= column sums of dy.

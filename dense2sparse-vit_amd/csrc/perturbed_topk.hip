@@ -117,12 +117,6 @@ __global__ __launch_bounds__(256) void ptk_bwd_kernel(const float* __restrict__ 
 // the device, peturbed_topk.py:29): Philox4x32-10 keyed by (seed), counter = element index / 4, four uniforms -> two Box-Muller pairs.
 // Stateless and order independent: element i of the stream is the same whatever the launch shape, so a test can regenerate exactly the
 // numbers a training step consumed.
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
-}
 __global__ __launch_bounds__(256) void normal_noise_kernel(float* __restrict__ out, long n, unsigned long long seed) {
     const long q = (long)blockIdx.x * 256 + threadIdx.x;      // one Philox block = 4 outputs
     if (q * 4 >= n) return;

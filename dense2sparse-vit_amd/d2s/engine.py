@@ -493,6 +493,13 @@ class TrainStep:
         if graph is None:
             graph = {"0": False, "1": True, "auto": "auto"}[os.environ.get("D2S_STEP_GRAPH", "0")]
         self.graph = None if graph == "auto" else bool(graph)      # True | False | None (auto: small per-rank batches only)
+        if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+            # the table of draws is filled inside the model's forward (seed from the CPU generator, one launch): a captured step would
+            # replay the masks of the step it was captured in.  Refilling the persistent table outside the captured region is not built.
+            if self.graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with drop_path_rate > 0 is not supported: a replayed step would reuse the "
+                                   "stochastic-depth masks it was captured with; run the step eagerly (graph=False)")
+            self.graph = False
         self.graph_auto_max_rows = int(os.environ.get("D2S_STEP_GRAPH_AUTO_ROWS", "16384"))
         self._graphs = {}                   # key -> entry (see _graph_step)
         self._capture_stream = None
@@ -559,6 +566,7 @@ class TrainStep:
             "mask_loss_type": str(getattr(self.args, "mask_loss_type", "")),
             "patch_score_threshold": None if thr is None else float(thr),
             "gemm_mode": int(ops.get_gemm_mode()),
+            "drop_path_rate": float(getattr(s, "drop_path_rate", 0.0)),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -590,7 +598,8 @@ class TrainStep:
         if not isinstance(sd, dict) or not isinstance(sd.get("config"), dict) or "model" not in sd or "optimizer" not in sd:
             raise lib.D2SError("not a training checkpoint: 'config', 'model' and 'optimizer' are expected (a weights-only file goes "
                                "through --student-checkpoint)")
-        theirs, ours = sd["config"], self.config()
+        theirs, ours = dict(sd["config"]), self.config()
+        theirs.setdefault("drop_path_rate", 0.0)       # checkpoints written before stochastic depth existed were trained without it
         for k in ours:
             if k not in theirs or theirs[k] != ours[k]:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")

@@ -158,7 +158,10 @@ class BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, heads, eps, want_cls, scale, *extra):
-        policy = extra[0] if extra else None         # optional 18th input: keep policy [B, n] of the dynamic-keep-ratio path
+        policy = extra[0] if extra else None         # optional 18th input: keep policy [B, n] of the dynamic-keep-ratio path (or None)
+        # optional 19th and 20th input, stochastic depth: the block's two rows [B] of the ops.drop_path_scales table (attention branch, MLP
+        # branch; either may be None), non-differentiable.  Only a forward that keeps something for a backward applies them.
+        s_attn, s_mlp = (extra[1], extra[2]) if len(extra) >= 3 else (None, None)
         ctx.nextra = len(extra)
         B, n, D = x.shape
         M = B * n
@@ -176,9 +179,11 @@ class BlockFn(torch.autograd.Function):
             # fp32 data path: the whole block is ONE C-ABI call (csrc/block.hip issues the same seven launches)
             train = wants_grad(ctx)
             params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
-            y, cls_row, slab = ops.block_fwd(x, params, B, n, D, heads, hidden, eps, scale, want_cls, train)
+            y, cls_row, slab = ops.block_fwd(x, params, B, n, D, heads, hidden, eps, scale, want_cls, train,
+                                             s_attn if train else None, s_mlp if train else None)
             if train:
                 ctx.save_for_backward(x, slab, *params)
+                ctx.drop_path = (s_attn, s_mlp)
                 ctx.composite = True
                 ctx.dims = (B, n, D, heads, scale)
                 ctx.hidden = hidden
@@ -251,7 +256,7 @@ class BlockFn(torch.autograd.Function):
         else:   # dynamic keep ratio: softmax_with_policy fused into the attention pass (:195-214)
             ao, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, heads, scale, want_cls=want_cls)
         x2d = x.view(M, D)
-        x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x2d, a16=aoh)
+        x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x2d, a16=aoh, rowscale=s_attn, rows_per_group=n)
         # GELU pre-activation for the backward: fp32, or bf16 on the bf16 data path (what autocast keeps: fc1's output is bf16 there)
         z = torch.empty((M, hidden), dtype=torch.bfloat16 if io else torch.float32, device=x.device)
         if io:
@@ -260,15 +265,16 @@ class BlockFn(torch.autograd.Function):
             hh = ops.bf16_buffer(M, hidden, x.device)
             ops.linear_fwd(None, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, aux_out=z, a16=ln2h, c16=hh, want_f32=False)
             h = hh
-            y = ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh)
+            y = ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh, rowscale=s_mlp, rows_per_group=n)
         else:
             ln2, mean2, rstd2 = ops.layernorm_fwd(x1, cmap, n2w, n2b, M, D, eps)
             h = ops.linear_fwd(ln2, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, aux_out=z)
-            y = ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1)
+            y = ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, rowscale=s_mlp, rows_per_group=n)
         del ln2h, hh
         ctx.save_for_backward(x, n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
                               n1b, qkvb, projb, n2b, fc1b, fc2b, aoh)      # aoh: bf16 form of ao (bf16 attention only), proj's weight gradient
         ctx.policy = (policy, cinv)
+        ctx.drop_path = (s_attn, s_mlp)
         ctx.dims = (B, n, D, heads, scale)
         if cls_row is None:
             cls_row = torch.empty((0,), device=x.device)
@@ -287,7 +293,7 @@ class BlockFn(torch.autograd.Function):
             if wants[1 + i] or wants[1 + pair]:
                 dparams[i] = ops.grad_buffer(params[i])
         want_dx = wants[0] or dparams[0] is not None
-        dx = ops.block_bwd(gy.contiguous(), x, slab, params, B, n, D, heads, ctx.hidden, scale, want_dx, dparams)
+        dx = ops.block_bwd(gy.contiguous(), x, slab, params, B, n, D, heads, ctx.hidden, scale, want_dx, dparams, *ctx.drop_path)
         grads = [dx if wants[0] else None] + [dparams[i] if wants[1 + i] else None for i in range(12)]
         return tuple(grads) + (None, None, None, None) + (None,) * ctx.nextra
 
@@ -319,6 +325,12 @@ class BlockFn(torch.autograd.Function):
         gyh = ops.shadow_take(gy) if io else None
         if gyh is not None:
             gyh = gyh.view(M, D)
+        # stochastic depth: the gradient that enters a branch is s[b] * g (one pass, ops.scale_rows); the residual path - the LayerNorm
+        # backward's add_src - keeps the unscaled one.  The bf16 shadow of the unscaled gradient does not describe the scaled copy.
+        s_attn, s_mlp = ctx.drop_path
+        g_res = gy
+        if s_mlp is not None:
+            gy, gyh = ops.scale_rows(g_res, s_mlp, n), None
         # with both operands at hand in bf16 the weight-gradient kernel reads them where they lie (token-major, no transposing pass); the
         # bias gradient is then the sum of the bf16 gradient values, as under torch.autocast
         grads[11], grads[12] = ops.linear_param_grads(gy, hx, fc2w, fc2b, wants[11], wants[12], x16=h16, dy16=gyh if h16 is not None else None)
@@ -333,14 +345,17 @@ class BlockFn(torch.autograd.Function):
         dln2 = ops.linear_dgrad(dz, fc1w, a16=dzh)
         del dzh
         g1 = torch.empty((M, D), dtype=torch.float32, device=dev)
-        g1h = ops.bf16_buffer(M, D, dev) if io else None
+        g1h = ops.bf16_buffer(M, D, dev) if (io and ctx.drop_path[0] is None) else None
         dn2w = new(n2w) if (wants[7] or wants[8]) else None
         dn2b = new(n2b) if dn2w is not None else None
-        ops.layernorm_bwd(x1, cmap, dln2, n2w, mean2, rstd2, g1, gy, dn2w, dn2b, M, D, dx16=g1h)
+        ops.layernorm_bwd(x1, cmap, dln2, n2w, mean2, rstd2, g1, g_res, dn2w, dn2b, M, D, dx16=g1h)
         grads[7], grads[8] = (dn2w if wants[7] else None), (dn2b if wants[8] else None)
         # ---- attention branch ----
-        grads[5], grads[6] = ops.linear_param_grads(g1, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
-        dao = ops.linear_dgrad(g1, projw, a16=g1h)
+        ga = g1
+        if s_attn is not None:
+            ga, g1h = ops.scale_rows(g1, s_attn, n), None
+        grads[5], grads[6] = ops.linear_param_grads(ga, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
+        dao = ops.linear_dgrad(ga, projw, a16=g1h)
         del g1h
         dqkvh = None
         l1x, l116 = xarg(ln1)
@@ -731,6 +746,20 @@ class AttnCoreFn(torch.autograd.Function):
             qkv, out, lse, cinv, policy = ctx.saved_tensors
             dqkv = ops.attn_policy_bwd(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
         return (dqkv, None, None, None, None, None) + (None,) * ctx.nextra
+
+
+class DropPathFn(torch.autograd.Function):
+    """x [B, ...] * s[b] with s the drawn 0 / (1 / keep) vector (deit.py:69-77 with the draw as an input); the backward is the same scaling."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        ctx.save_for_backward(s)
+        return ops.drop_path_fwd(x.contiguous(), s)
+
+    @staticmethod
+    def backward(ctx, g):
+        (s,) = ctx.saved_tensors
+        return ops.drop_path_fwd(g.contiguous(), s), None
 
 
 class PerturbedTopKFn(torch.autograd.Function):

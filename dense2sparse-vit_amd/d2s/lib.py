@@ -87,6 +87,13 @@ _SIGS = {
     "d2s_block_wgrad_workspace_bytes": (Z, [I, I, I, I, I]),
     "d2s_block_fwd_f32": (I, [P, P, I, I, I, I, I, F, F, P, P, P, I, I, P, Z]),
     "d2s_block_bwd_f32": (I, [P, P, P, P, P, I, I, I, I, I, F, P, P, P, I, P, Z, P, Z, P]),
+    "d2s_drop_path_scales": (I, [P, P, I, I, ctypes.c_ulonglong]),
+    "d2s_gemm_f32_rowscale": (I, [I, P, L, P, L, P, L, I, I, I, P, P, L, P, I, I, P, P, P, P, Z]),
+    "d2s_scale_rows": (I, [P, P, P, L, I, I]),
+    "d2s_drop_path_fwd": (I, [P, P, P, I, L]),
+    "d2s_block_bwd_dp_scratch_floats": (L, [I, I, I, I, I]),
+    "d2s_block_fwd_f32_dp": (I, [P, P, P, P, I, I, I, I, I, F, F, P, P, P, I, I, P, Z]),
+    "d2s_block_bwd_f32_dp": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, I, P, Z, P, Z, P]),
     "d2s_adamw_chunk_elems": (I, None),
     "d2s_adamw_step": (I, [P, P, P, P, P, I, F, F, F, I, F, P]),
     "d2s_adamw_step_ema": (I, [P, P, P, P, P, I, F, F, F, I, F, P, P, F]),

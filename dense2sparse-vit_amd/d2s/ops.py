@@ -12,6 +12,7 @@ from . import lib
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2, 3, 4
 EPI_MUL_GELU_GRAD, EPI_MUL_RELU_MASK, EPI_BIAS_ROWADD, EPI_ACCUM = 5, 6, 7, 8
 EPI_BIAS_GELU_Z16, EPI_MUL_GELU_GRAD_Z16 = 9, 10      # d2s_gemm_f32_bf16io only: the saved GELU pre-activation in bf16 (chosen by gemm() from the tensor's dtype)
+EPI_BIAS_RESID_ROWSCALE = 11                          # d2s_gemm_f32_rowscale only: rowscale[m / rows_per_group] * (acc + bias) + aux (stochastic depth)
 NT, NN, TN = 0, 1, 2
 
 _ws = {}
@@ -154,7 +155,7 @@ class Bf16Weights:
 
 
 def gemm(layout, A, lda, B, ldb, C, ldc, M, N, K, epi=EPI_NONE, bias=None, aux=None, ldaux=0, aux_out=None, aux_rows=0,
-         remap_rows=0, remap_skip=0, accumulate=False, a16=None, c16=None, b16=None):
+         remap_rows=0, remap_skip=0, accumulate=False, a16=None, c16=None, b16=None, rowscale=None, rows_per_group=0):
     mode = get_gemm_mode()
     qk = (layout, M, N, K, mode)
     need = _WS_NEED.get(qk)
@@ -162,6 +163,14 @@ def gemm(layout, A, lda, B, ldb, C, ldc, M, N, K, epi=EPI_NONE, bias=None, aux=N
         need = _WS_NEED[qk] = lib.query("d2s_gemm_f32_workspace_bytes", layout, M, N, K, mode)
     dev = C.device if C is not None else c16.device
     ws = workspace(need, dev) if need else None
+    if epi == EPI_BIAS_RESID_ROWSCALE:      # stochastic depth: its own entry point, every arithmetic mode (bf16 side channels in mode 2 only)
+        assert rowscale is not None and rows_per_group > 0 and aux is not None and not accumulate and remap_rows == 0 and aux_rows == 0
+        assert rowscale.dtype == torch.float32 and rowscale.is_contiguous() and rowscale.numel() * rows_per_group >= M
+        assert (a16 is None and c16 is None and b16 is None) or mode == GEMM_BF16
+        lib.call("d2s_gemm_f32_rowscale", layout, lib.ptr(A), lda, lib.ptr(B), ldb, lib.ptr(C), ldc, M, N, K, lib.ptr(bias), lib.ptr(aux), ldaux,
+                 lib.ptr(rowscale), int(rows_per_group), mode, lib.ptr(a16), lib.ptr(b16), lib.ptr(c16), lib.ptr(ws), ws.numel() if ws is not None else 0)
+        return C
+    assert rowscale is None, "a row scale needs EPI_BIAS_RESID_ROWSCALE"
     z16 = (aux_out if epi == EPI_BIAS_GELU else aux if epi == EPI_MUL_GELU_GRAD else None)
     if z16 is not None and z16.dtype == torch.bfloat16:      # bf16 data path: the GELU pre-activation is kept in bf16 (as under autocast)
         assert a16 is not None or c16 is not None or b16 is not None, "a bf16 pre-activation exists on the bf16 data path only"
@@ -180,8 +189,9 @@ def gemm(layout, A, lda, B, ldb, C, ldc, M, N, K, epi=EPI_NONE, bias=None, aux=N
     return C
 
 
-def linear_fwd(x, W, bias=None, epi=None, aux=None, aux_out=None, out=None, a16=None, c16=None, want_f32=True):
+def linear_fwd(x, W, bias=None, epi=None, aux=None, aux_out=None, out=None, a16=None, c16=None, want_f32=True, rowscale=None, rows_per_group=0):
     """y[M,N] = epi(x[M,K] @ W[N,K]^T + bias).  nn.Linear forward (F.linear).
+    rowscale [ceil(M / rows_per_group)] with epi=EPI_BIAS_RESID (stochastic depth): y = rowscale[m // rows_per_group] * (x W^T + bias) + aux.
     bf16 mode only: a16 = bf16 copy of x (x itself may then be None), c16 = bf16 [M, N] buffer that receives a copy of y;
     want_f32=False (needs c16) skips the fp32 result and returns None."""
     _f32(W)
@@ -194,7 +204,11 @@ def linear_fwd(x, W, bias=None, epi=None, aux=None, aux_out=None, out=None, a16=
     if epi is None:
         epi = EPI_BIAS if bias is not None else EPI_NONE
     b16 = bf16_weight(W) if get_gemm_mode() == GEMM_BF16 else None
-    return gemm(NT, x, K, W, K, out, N, M, N, K, epi, bias, aux, N if aux is not None else 0, aux_out, a16=a16, c16=c16, b16=b16)
+    if rowscale is not None:
+        assert epi in (EPI_BIAS_RESID, EPI_BIAS_RESID_ROWSCALE) and aux_out is None
+        epi = EPI_BIAS_RESID_ROWSCALE
+    return gemm(NT, x, K, W, K, out, N, M, N, K, epi, bias, aux, N if aux is not None else 0, aux_out, a16=a16, c16=c16, b16=b16,
+                rowscale=rowscale, rows_per_group=rows_per_group)
 
 
 # ---- k-contiguous copies W^T of Linear weights for the input-gradient GEMM ----
@@ -740,7 +754,8 @@ def _block_sizes(B, n, D, H, hidden, mode):
     if ent is None:
         ent = _BLOCK_SIZES[key] = (lib.query("d2s_block_saved_floats", B, n, D, H, hidden, 1), lib.query("d2s_block_saved_floats", B, n, D, H, hidden, 0),
                                    lib.query("d2s_block_bwd_scratch_floats", B, n, D, H, hidden), lib.query("d2s_block_workspace_bytes", B, n, D, hidden, mode),
-                                   lib.query("d2s_block_wgrad_workspace_bytes", B, n, D, hidden, mode))
+                                   lib.query("d2s_block_wgrad_workspace_bytes", B, n, D, hidden, mode),
+                                   lib.query("d2s_block_bwd_dp_scratch_floats", B, n, D, H, hidden))
     return ent
 
 
@@ -749,25 +764,38 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
-def block_fwd(x, params, B, n, D, H, hidden, eps, scale, want_cls, train):
-    """-> (y [B,n,D], cls_row [B,H,n] or None, slab): slab holds what block_bwd needs when train, forward-only scratch otherwise."""
+def _dp_row(s, B):
+    if s is not None:
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() == B and s.is_cuda, "a drop-path row is [B] fp32 on the device"
+    return s
+
+
+def block_fwd(x, params, B, n, D, H, hidden, eps, scale, want_cls, train, s_attn=None, s_mlp=None):
+    """-> (y [B,n,D], cls_row [B,H,n] or None, slab): slab holds what block_bwd needs when train, forward-only scratch otherwise.
+    s_attn / s_mlp: [B] rows of the drop_path_scales table (stochastic depth), None = branch not dropped."""
     mode = get_gemm_mode()
     sz = _block_sizes(B, n, D, H, hidden, mode)
     slab = torch.empty((sz[0] if train else sz[1],), dtype=torch.float32, device=x.device)
     y = torch.empty((B, n, D), dtype=torch.float32, device=x.device)
     cls_row = torch.empty((B, H, n), dtype=torch.float32, device=x.device) if want_cls else None
     ws = workspace(sz[3], x.device)
-    lib.call("d2s_block_fwd_f32", lib.ptr(x), _ptr_array(params), B, n, D, H, hidden, float(eps), float(scale), lib.ptr(y), lib.ptr(cls_row),
-             lib.ptr(slab), int(train), mode, lib.ptr(ws), ws.numel())
+    if s_attn is None and s_mlp is None:
+        lib.call("d2s_block_fwd_f32", lib.ptr(x), _ptr_array(params), B, n, D, H, hidden, float(eps), float(scale), lib.ptr(y), lib.ptr(cls_row),
+                 lib.ptr(slab), int(train), mode, lib.ptr(ws), ws.numel())
+    else:
+        lib.call("d2s_block_fwd_f32_dp", lib.ptr(x), _ptr_array(params), lib.ptr(_dp_row(s_attn, B)), lib.ptr(_dp_row(s_mlp, B)), B, n, D, H, hidden,
+                 float(eps), float(scale), lib.ptr(y), lib.ptr(cls_row), lib.ptr(slab), int(train), mode, lib.ptr(ws), ws.numel())
     return y, cls_row, slab
 
 
-def block_bwd(gy, x, slab, params, B, n, D, H, hidden, scale, want_dx, dparams):
-    """dparams: 12 gradient buffers (None = not wanted; LayerNorm weight / bias come as a pair).  -> dx [B,n,D] or None"""
+def block_bwd(gy, x, slab, params, B, n, D, H, hidden, scale, want_dx, dparams, s_attn=None, s_mlp=None):
+    """dparams: 12 gradient buffers (None = not wanted; LayerNorm weight / bias come as a pair).  -> dx [B,n,D] or None
+    s_attn / s_mlp: the rows the forward ran with."""
     mode = get_gemm_mode()
     sz = _block_sizes(B, n, D, H, hidden, mode)
     dev = gy.device
-    scratch = torch.empty((sz[2],), dtype=torch.float32, device=dev)
+    dp = s_attn is not None or s_mlp is not None
+    scratch = torch.empty((sz[5] if dp else sz[2],), dtype=torch.float32, device=dev)
     dx = torch.empty((B, n, D), dtype=torch.float32, device=dev) if want_dx else None
     # input gradients through the cached k-contiguous W^T copies (exact mode, arena weights, enough rows: linear_dgrad's rule)
     wt = [None] * 4
@@ -778,9 +806,13 @@ def block_bwd(gy, x, slab, params, B, n, D, H, hidden, scale, want_dx, dparams):
     side = _WGRAD["stream"] if (_WGRAD["on"] and any(dparams[i] is not None for i in (2, 3, 4, 5, 8, 9, 10, 11))) else None
     ws_side = workspace_on(side, sz[4], dev) if side is not None else None
     ws = workspace(sz[3] if side is not None else max(sz[3], sz[4]), dev)      # in line, the weight gradients use the main scratch too
-    lib.call("d2s_block_bwd_f32", lib.ptr(gy), lib.ptr(x), lib.ptr(slab), _ptr_array(params), _ptr_array(wt), B, n, D, H, hidden, float(scale),
-             lib.ptr(dx), _ptr_array(dparams), lib.ptr(scratch), mode, lib.ptr(ws), ws.numel(), lib.ptr(ws_side),
-             ws_side.numel() if ws_side is not None else 0, side.cuda_stream if side is not None else None)
+    tail = (lib.ptr(dx), _ptr_array(dparams), lib.ptr(scratch), mode, lib.ptr(ws), ws.numel(), lib.ptr(ws_side),
+            ws_side.numel() if ws_side is not None else 0, side.cuda_stream if side is not None else None)
+    if dp:
+        lib.call("d2s_block_bwd_f32_dp", lib.ptr(gy), lib.ptr(x), lib.ptr(slab), _ptr_array(params), _ptr_array(wt), lib.ptr(_dp_row(s_attn, B)),
+                 lib.ptr(_dp_row(s_mlp, B)), B, n, D, H, hidden, float(scale), *tail)
+    else:
+        lib.call("d2s_block_bwd_f32", lib.ptr(gy), lib.ptr(x), lib.ptr(slab), _ptr_array(params), _ptr_array(wt), B, n, D, H, hidden, float(scale), *tail)
     if side is not None:       # autograd may free these on the main stream while the side stream still reads / writes them
         for t in (gy, slab, scratch):
             t.record_stream(side)
@@ -789,6 +821,41 @@ def block_bwd(gy, x, slab, params, B, n, D, H, hidden, scale, want_dx, dparams):
                 t.record_stream(side)
         _WGRAD["used"] = True
     return dx
+
+
+# ---- stochastic depth (csrc/droppath.hip) ----
+def drop_path_scales(rates, B, seed, out=None):
+    """[R, B] table of 0 / (1 / keep) from rates [R] (fp32, device) and a 64-bit seed: row 2i = block i's attention branch, 2i + 1 its MLP branch."""
+    _f32(rates)
+    R = rates.numel()
+    if out is None:
+        out = torch.empty((R, B), dtype=torch.float32, device=rates.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (R, B)
+    lib.call("d2s_drop_path_scales", lib.ptr(rates), lib.ptr(out), R, B, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return out
+
+
+def scale_rows(g, rowscale, rows_per_group, out=None):
+    """out[m] = rowscale[m // rows_per_group] * g[m] for g [M, D]."""
+    _f32(g)
+    _f32(rowscale)
+    M, D = g.shape
+    assert rowscale.numel() * rows_per_group >= M
+    if out is None:
+        out = torch.empty_like(g)
+    lib.call("d2s_scale_rows", lib.ptr(g), lib.ptr(rowscale), lib.ptr(out), M, D, int(rows_per_group))
+    return out
+
+
+def drop_path_fwd(x, s):
+    """x [B, ...] * s[b] (DropPath.forward with the draws given; also its backward)."""
+    _f32(x)
+    _f32(s)
+    B = x.shape[0]
+    assert s.numel() == B
+    out = torch.empty_like(x)
+    lib.call("d2s_drop_path_fwd", lib.ptr(x), lib.ptr(s), lib.ptr(out), B, x.numel() // B)
+    return out
 
 
 KL_LOGIT_TARGET, KL_PROB_TARGET, CE_LABEL, MSE_TARGET, SOFT_CE = 0, 1, 2, 3, 4

@@ -52,6 +52,8 @@ def check_supported(args):
         print("Attention: --random-drop has no effect on the forward pass at this commit of the reference (attribute only)")
     if args.mask_loss_type not in ("kl_div", "mse"):
         bad.append(f"--mask-loss-type {args.mask_loss_type} (kl_div and mse are on the path; bce is broken in the reference)")
+    if not 0.0 <= getattr(args, "drop_path", 0.0) < 1.0:
+        bad.append(f"--drop-path {args.drop_path} (0 <= rate < 1)")
     if args.use_dp:
         bad.append("--use-dp (one process per GPU only: --use-ddp under torch.distributed.run)")
     folder = getattr(args, "data_source", "synthetic") == "folder"
@@ -104,6 +106,7 @@ def build_models(args):
                                                    random_drop=args.random_drop, small_predictor=args.small_predictor,
                                                    predictor_loss_type=args.mask_loss_type, predictor_bn=args.predictor_bn,
                                                    patch_score_threshold=args.patch_score_threshold,
+                                                   drop_path_rate=getattr(args, "drop_path", 0.0),
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)

@@ -128,6 +128,8 @@ def parse_args(argv=None):
     p.add_argument('--remode', type=str, default='pixel')
     p.add_argument('--recount', type=int, default=1)
     p.add_argument('--resplit', action='store_true', default=False)
+    p.add_argument('--drop-path', type=float, default=0.0, metavar='RATE',
+                   help="stochastic depth rate of the student's last block (DeiT's flag; block i drops with linspace(0, RATE, depth)[i])")
     p.add_argument('--mixup', type=float, default=0.8)
     p.add_argument('--cutmix', type=float, default=1.0)
     p.add_argument('--cutmix-minmax', type=float, nargs='+', default=None)

@@ -2,7 +2,7 @@
 every model file; only the dense-to-sparse path and the T2T path are provided here)."""
 from .dynamic_vit import *  # noqa: F401,F403
 from .dynamic_vit import (VisionTransformerDiffPruning, VisionTransformerTeacher, PredictorLG, Attention, Block, Mlp, PatchEmbed,  # noqa: F401
-                          BatchNormLayer, batch_index_select, resize_pos_embed, checkpoint_filter_fn)
+                          BatchNormLayer, DropPath, batch_index_select, resize_pos_embed, checkpoint_filter_fn)
 from .peturbed_topk import PerturbedTopK, PerturbedTopKFunction  # noqa: F401
 from .token_performer import Token_performer  # noqa: F401
 from .token_transformer import Token_transformer  # noqa: F401

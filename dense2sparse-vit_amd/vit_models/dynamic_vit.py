@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from d2s import functional as DF
-from .peturbed_topk import PerturbedTopK
+from .peturbed_topk import PerturbedTopK, draw_seed
 
 
 def to_2tuple(x):
@@ -63,6 +63,107 @@ def _scores(predictor, x):
         raise RuntimeError("the score predictor was built with topk_selection=False: the reference's PredictorLG.forward returns None on that "
                            "path (vit_models/dynamic_vit.py:537), so the pruning stages cannot run - pass --topk-selection / topk_selection=True")
     return out
+
+class DropPath(nn.Module):
+    """Stochastic depth per sample (timm's DropPath as restated in vit_models/deit.py:69-89): identity in eval or at rate 0; in training
+    x[b] * floor(keep + u[b]) / keep.  The draw is made on the device from a seed taken from torch's default CPU generator (draw_seed).
+    Inside a Block the scaling is fused into the proj / fc2 GEMM epilogues (the model hands the block its rows of one per-step table);
+    this forward serves stand-alone use."""
+
+    def __init__(self, drop_prob=None):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def draw(self, B, device, seed=None):
+        """-> s [B]: 0 or 1 / keep"""
+        from d2s import ops
+        rates = torch.full((1,), float(self.drop_prob), dtype=torch.float32, device=device)
+        return ops.drop_path_scales(rates, B, draw_seed() if seed is None else seed)[0]
+
+    def forward(self, x):
+        if not self.drop_prob or not self.training:
+            return x
+        return DF.DropPathFn.apply(x, self.draw(x.shape[0], x.device))
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob}"
+
+
+def drop_path_rates(drop_path_rate, depth):
+    """dpr of the reference's trunks (:694): linspace(0, rate, depth) as Python floats"""
+    return [x.item() for x in torch.linspace(0, drop_path_rate, depth)]
+
+
+class _DropPathTable:
+    """The per-step table of a model's stochastic-depth draws: [2 * depth, B] fp32 scales (row 2i: block i's attention branch, 2i + 1:
+    its MLP branch) in ONE persistent buffer per batch size, filled by one launch at the start of a training forward.  Not a registered
+    buffer: the state-dict keys are those of a model without stochastic depth."""
+
+    def __init__(self, rates):
+        self.rates = [float(r) for r in rates for _ in (0, 1)]
+        self.active = any(r > 0. for r in self.rates)
+        self._dev = {}      # (device, B) -> (rates tensor, table)
+
+    def buffers(self, B, device):
+        key = (str(device), B)
+        ent = self._dev.get(key)
+        if ent is None:
+            if len(self._dev) >= 4:      # batch sizes come and go (a shorter last batch, evaluation): keep a handful of buffers, not a history
+                self._dev.clear()
+            ent = self._dev[key] = (torch.tensor(self.rates, dtype=torch.float32, device=device),
+                                    torch.empty((len(self.rates), B), dtype=torch.float32, device=device))
+        return ent
+
+    def fill(self, B, device, masks=None, seed=None):
+        """-> table [2 * depth, B].  masks: injected 0/1 draws [2 * depth, B] (tests, fixtures) used instead of the generator."""
+        from d2s import ops
+        rates, table = self.buffers(B, device)
+        if masks is not None:
+            assert tuple(masks.shape) == tuple(table.shape), f"drop_path_masks must be [2 * depth, B] = {tuple(table.shape)}"
+            table.copy_(masks.to(device=device, dtype=torch.float32) / (1.0 - rates)[:, None])
+        else:
+            ops.drop_path_scales(rates, B, draw_seed() if seed is None else seed, out=table)
+        return table
+
+    def rows(self, table, i):
+        """(s_attn, s_mlp) of block i; None where the block's rate is 0 (the block then issues its plain launches)"""
+        if table is None or self.rates[2 * i] == 0.:
+            return None
+        return table[2 * i], table[2 * i + 1]
+
+
+class _DropPathModel:
+    """What a model with stochastic depth shares (mixed into _ViTBase and T2T_ViT): the rate, the per-block rates and the table."""
+
+    def _init_drop_path(self, drop_path_rate, depth):
+        """-> dpr, the per-block rates for the Block constructors"""
+        assert 0. <= drop_path_rate < 1., "drop_path_rate is a probability below 1"
+        self.drop_path_rate = float(drop_path_rate)
+        dpr = drop_path_rates(drop_path_rate, depth)      # :694 stochastic depth decay rule
+        self._drop_path = _DropPathTable(dpr)
+        # injected draws (tests, fixtures): a 0/1 tensor [2 * depth, B] used instead of the generator until set back to None
+        self.drop_path_masks = None
+        return dpr
+
+    def _drop_path_table(self, B, device):
+        """The table of this forward's stochastic-depth draws, or None (eval, no gradient wanted, rate 0).  Each forward gets its OWN
+        copy of the persistent buffer (12 KB at depth 12, B 128): the rows are kept for the backward, and a second training forward
+        before the first one's backward (gradient accumulation, two forwards under one loss) refills the buffer."""
+        t = self._drop_path
+        if not (self.training and t.active and torch.is_grad_enabled()):
+            return None
+        return t.fill(B, device, masks=self.drop_path_masks).clone()
+
+
+def block_drop_path_rows(block, x, rows):
+    """The trailing BlockFn inputs of a block's stochastic depth: (policy slot, s_attn, s_mlp) or () - in eval, without gradients and at
+    rate 0.  Without rows from a model's table (stand-alone use) the block makes its own two draws."""
+    if not (block.training and isinstance(block.drop_path, DropPath) and torch.is_grad_enabled()):
+        return None
+    if rows is None:
+        rows = (block.drop_path.draw(x.shape[0], x.device), block.drop_path.draw(x.shape[0], x.device))
+    return tuple(rows)
+
 
 class Mlp(nn.Module):
     """:159-175."""
@@ -114,11 +215,11 @@ class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
-        assert drop_path == 0., "DropPath is identity at rate 0 (:249); stochastic depth is not on the hot path"
+        assert 0. <= drop_path < 1., "drop_path is a probability below 1"
         assert qkv_bias, "qkv_bias=True everywhere on the path"
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()      # :249
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
 
@@ -127,9 +228,14 @@ class Block(nn.Module):
         return (self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
                 self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias)
 
-    def forward(self, x, policy=None, return_cls_attn=False):
+    def forward(self, x, policy=None, return_cls_attn=False, drop_path_rows=None):
+        """drop_path_rows: (s_attn, s_mlp), this block's rows [B] of the model's stochastic-depth table; without them a block in training
+        mode with a rate above 0 makes its own two draws (stand-alone use)."""
         a = self.attn
         extra = () if policy is None else (DF.as_policy(policy, x.shape[0], x.shape[1]),)     # :263-283 with policy -> fused policy softmax
+        rows = block_drop_path_rows(self, x, drop_path_rows)
+        if rows is not None:
+            extra = (extra[0] if extra else None,) + rows
         y, cls_row = DF.run(DF.BlockFn, x, *self._params(), a.num_heads, self.norm1.eps, bool(return_cls_attn), a.scale, *extra)
         return (y, cls_row) if return_cls_attn else y
 
@@ -265,12 +371,13 @@ class PredictorLG(nn.Module):
         return self.forward_tokens(torch.cat([pad, x], dim=1))
 
 
-class _ViTBase(nn.Module):
+class _ViTBase(_DropPathModel, nn.Module):
     def _build_trunk(self, img_size, patch_size, in_chans, num_classes, embed_dim, depth, num_heads, mlp_ratio, qkv_bias, qk_scale,
                      representation_size, drop_rate, attn_drop_rate, drop_path_rate, hybrid_backbone, norm_layer):
         assert hybrid_backbone is None, "HybridEmbed is not on the hot path"
         assert representation_size is None, "pre_logits representation layer is unused by the reference's factories"
-        assert drop_rate == 0. and attn_drop_rate == 0. and drop_path_rate == 0., "dropout / drop-path are 0 on the path"
+        assert drop_rate == 0. and attn_drop_rate == 0., "dropout is 0 on the path"
+        dpr = self._init_drop_path(drop_path_rate, depth)
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
         norm_layer = norm_layer or partial(nn.LayerNorm, eps=1e-6)
@@ -281,7 +388,7 @@ class _ViTBase(nn.Module):
         self.pos_drop = nn.Dropout(p=drop_rate)
         self.blocks = nn.ModuleList([
             Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop_rate,
-                  attn_drop=attn_drop_rate, drop_path=0., norm_layer=norm_layer) for _ in range(depth)])
+                  attn_drop=attn_drop_rate, drop_path=dpr[i], norm_layer=norm_layer) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.pre_logits = nn.Identity()
         self.head = nn.Linear(self.num_features, num_classes) if num_classes > 0 else nn.Identity()
@@ -385,6 +492,7 @@ class VisionTransformerDiffPruning(_ViTBase):
     def forward(self, x, stacked_cls_attn_weights=None):
         if self.patch_score_threshold is not None:
             return self._forward_threshold(x)
+        dp = self._drop_path_table(x.shape[0], x.device)
         x = self._embed(x)                                                  # :816-824
         self.num_kept_tokens, self.cls_attns, self.pred_logits = [], [], []
         self.kept_token_indices, self.dropped_token_indices = [], []
@@ -406,7 +514,7 @@ class VisionTransformerDiffPruning(_ViTBase):
                 self.pred_logits.append(pred_logits)
                 x = DF.GatherFn.apply(x, kept)                               # :907-912 / :954-960
                 p_count += 1
-            x, cls_attn = blk(x, return_cls_attn=True)                       # :924 / :985
+            x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
             self.cls_attns.append(cls_attn[:, :, 1:])
         logits, features = self._head(x)                                      # :993-1006
         if self.training:
@@ -430,6 +538,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         after it], [pred_logits], [keep mask [B,N]])."""
         from d2s import ops
         thr = float(self.patch_score_threshold)
+        dp = self._drop_path_table(x.shape[0], x.device)
         x = self._embed(x)
         B, n, D = x.shape
         N = n - 1
@@ -450,7 +559,7 @@ class VisionTransformerDiffPruning(_ViTBase):
                     self.kept_token_indices.append(policy[:, 1:])
                     self.dropped_token_indices.append(1.0 - policy[:, 1:])
                     p_count += 1
-                x = blk(x, policy=policy)                                                          # :894 / :983
+                x = blk(x, policy=policy, drop_path_rows=self._drop_path.rows(dp, i))             # :894 / :983
             logits, features = self._head(x)
             return logits, features, self.pred_logits, self.kept_token_indices
         if len(self.pruning_loc) > 1:

@@ -5,6 +5,15 @@ import torch.nn as nn
 from d2s import functional as DF
 
 
+def draw_seed():
+    """A 64-bit stream seed from torch's default CPU generator (two 31-bit draws, no device sync) mixed with the data-parallel rank:
+    torch.manual_seed / a restored RNG state reproduce it, ranks seeded alike still differ."""
+    import torch.distributed as dist
+    draw = torch.randint(0, 2 ** 31 - 1, (2,))
+    rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
+    return ((int(draw[0]) << 31) | int(draw[1])) ^ (0x9E3779B97F4A7C15 * (rank + 1) & 0xFFFFFFFFFFFFFFFF)
+
+
 class PerturbedTopKFunction:
     """apply(x, k, num_samples, sigma, noise=None) -> indicators [b, k, d]  (peturbed_topk.py:18-69; backward :72-80).
     The reference draws the noise from torch's global RNG on the CPU and copies it to the device (:29); here it is an explicit input so
@@ -20,10 +29,7 @@ class PerturbedTopKFunction:
         b, d = x.shape
         if noise is None:
             if seed is None:
-                import torch.distributed as dist
-                draw = torch.randint(0, 2 ** 31 - 1, (2,))                   # two 31-bit words from the default CPU generator (no device sync)
-                rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
-                seed = ((int(draw[0]) << 31) | int(draw[1])) ^ (0x9E3779B97F4A7C15 * (rank + 1) & 0xFFFFFFFFFFFFFFFF)
+                seed = draw_seed()
             noise = ops.normal_noise((b, num_samples, d), seed, x.device)
         return DF.PerturbedTopKFn.apply(x, noise, int(k), float(sigma))
 

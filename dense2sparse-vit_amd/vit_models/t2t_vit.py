@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from d2s import functional as DF
 from d2s import functional_t2t as TF
-from .dynamic_vit import PredictorLG, trunc_normal_
+from .dynamic_vit import PredictorLG, trunc_normal_, _DropPathModel
 from .token_performer import Token_performer
 from .token_transformer import Token_transformer
 from .transformer_block import Block, get_sinusoid_encoding
@@ -59,14 +59,15 @@ class T2T_module(nn.Module):
         return DF.LinearFn.apply(x.reshape(B * L, F_), self.project.weight, self.project.bias, None).reshape(B, L, -1)
 
 
-class T2T_ViT(nn.Module):
+class T2T_ViT(_DropPathModel, nn.Module):
     """:106-179."""
 
     def __init__(self, img_size=224, tokens_type='performer', in_chans=3, num_classes=1000, embed_dim=768, depth=12, num_heads=12,
                  mlp_ratio=4., qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
                  norm_layer=nn.LayerNorm, token_dim=64):
         super().__init__()
-        assert drop_rate == 0. and attn_drop_rate == 0. and drop_path_rate == 0.
+        assert drop_rate == 0. and attn_drop_rate == 0.
+        dpr = self._init_drop_path(drop_path_rate, depth)      # t2t_vit.py:122 (the token stages stay at 0)
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
         self.tokens_to_token = T2T_module(img_size=img_size, tokens_type=tokens_type, in_chans=in_chans, embed_dim=embed_dim,
@@ -76,7 +77,7 @@ class T2T_ViT(nn.Module):
         self.pos_embed = nn.Parameter(data=get_sinusoid_encoding(n_position=num_patches + 1, d_hid=embed_dim), requires_grad=False)
         self.pos_drop = nn.Identity()
         self.blocks = nn.ModuleList([Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
-                                           norm_layer=norm_layer) for _ in range(depth)])
+                                           drop_path=dpr[i], norm_layer=norm_layer) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         trunc_normal_(self.cls_token, std=.02)
@@ -104,10 +105,11 @@ class T2T_ViT(nn.Module):
         return DF.AddClsPosFn.apply(t, self.cls_token, self.pos_embed)
 
     def forward_features(self, x):
+        dp = self._drop_path_table(x.shape[0], x.device)
         x = self._tokens(x)
         block_heads = []
-        for blk in self.blocks:
-            x = blk(x)
+        for i, blk in enumerate(self.blocks):
+            x = blk(x, drop_path_rows=self._drop_path.rows(dp, i))
             block_heads.append(TF.LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps))
         return block_heads[-1][:, 0], block_heads
 
@@ -146,6 +148,7 @@ class T2T_ViT_DiffPruning(T2T_ViT):
         self.grad_ready_hook = None
 
     def forward(self, x):
+        dp = self._drop_path_table(x.shape[0], x.device)
         x = self._tokens(x)
         self.cls_attns, self.pred_logits, self.kept_token_indices, self.dropped_token_indices = [], [], [], []
         p = 0
@@ -160,7 +163,7 @@ class T2T_ViT_DiffPruning(T2T_ViT):
                 self.pred_logits.append(pred_logits)
                 x = DF.GatherFn.apply(x, kept)
                 p += 1
-            x, cls_row = blk(x, return_cls_attn=True)
+            x, cls_row = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))
             self.cls_attns.append(cls_row[:, :, 1:])
         logits, features = DF.run(DF.HeadFn, x, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.norm.eps)
         if self.training:

@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from d2s import functional as DF
+from .dynamic_vit import DropPath, block_drop_path_rows
 
 
 class Mlp(nn.Module):
@@ -48,18 +49,21 @@ class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
-        assert drop_path == 0. and drop == 0. and qk_scale is None
+        assert 0. <= drop_path < 1. and drop == 0. and qk_scale is None
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()      # transformer_block.py:66
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
 
-    def forward(self, x, return_cls_attn=False):
+    def forward(self, x, return_cls_attn=False, drop_path_rows=None):
+        """drop_path_rows: as vit_models.dynamic_vit.Block.forward"""
         a, m = self.attn, self.mlp
+        rows = block_drop_path_rows(self, x, drop_path_rows)
+        extra = () if rows is None else (None,) + rows
         y, cls_row = DF.run(DF.BlockFn, x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
                                       self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                      a.num_heads, self.norm1.eps, bool(return_cls_attn), a.scale)
+                                      a.num_heads, self.norm1.eps, bool(return_cls_attn), a.scale, *extra)
         return (y, cls_row) if return_cls_attn else y
 
 

@@ -300,6 +300,33 @@ int d2s_augment_images(const unsigned char* pix, long pix_bytes, const int* desc
 /* out: [B, C] fp32 soft labels, timm's mixup_target (partner of sample i: B-1-i). */
 int d2s_augment_labels(const int* desc, int B, int C, float on, float off, float* out, d2s_stream_t stream);
 
+/* ---- stochastic depth (DropPath, vit_models/deit.py:69-77; dynamic_vit.py:249, 263-269), training only ------------------------------
+ * One table per step: table [R][B] fp32 from rates [R] (device, 0 <= rate < 1) and a 64-bit seed, R = 2 * depth; row 2i = block i's
+ * attention branch, row 2i + 1 its MLP branch.  Entry = floor(keep + u) / keep with keep = 1 - rate: 0 or 1 / keep; u is Philox4x32-10
+ * keyed by the seed at counter (sample, row), so the table is a function of (seed, rates, row, sample) alone.  A rate-0 row is 1.0f. */
+int d2s_drop_path_scales(const float* rates, float* table, int R, int B, unsigned long long seed, d2s_stream_t stream);
+/* The forward applies a table row inside the residual GEMM: C = rowscale[m / rows_per_group] * (A B^T + bias[n]) + aux[m][n] (epilogue kind
+ * 11, this entry only; NT / NN layouts, every mode; a row with scale 0 is a bit copy of aux).  a_bf16 / b_bf16 / c_bf16: as in
+ * d2s_gemm_f32_bf16io, mode 2 only, NULL otherwise.  Workspace: d2s_gemm_f32_workspace_bytes. */
+int d2s_gemm_f32_rowscale(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
+                          const float* bias, const float* aux, long ldaux, const float* rowscale, int rows_per_group, int mode,
+                          const void* a_bf16, const void* b_bf16, void* c_bf16, void* workspace, size_t workspace_bytes, d2s_stream_t stream);
+/* The backward scales the gradient that enters a branch: out [M][D] = rowscale[m / rows_per_group] * g [M][D] (out may alias g). */
+int d2s_scale_rows(const float* g, const float* rowscale, float* out, long M, int D, int rows_per_group, d2s_stream_t stream);
+/* DropPath.forward with the draws given, x [B, inner]: out[b][:] = s[b] * x[b][:]; its backward is the same call on the gradient. */
+int d2s_drop_path_fwd(const float* x, const float* s, float* out, int B, long inner, d2s_stream_t stream);
+/* d2s_block_fwd_f32 / d2s_block_bwd_f32 with two table rows (s_attn, s_mlp: [B] device floats, either may be NULL): x1 = x + s_attn[b] *
+ * proj(..), y = x1 + s_mlp[b] * fc2(..).  With both NULL they ARE the plain entries (which call these).  The backward needs
+ * d2s_block_bwd_dp_scratch_floats floats of scratch when a row is given (two scaled-gradient buffers more). */
+long d2s_block_bwd_dp_scratch_floats(int B, int n, int D, int H, int hidden);
+int d2s_block_fwd_f32_dp(const float* x, const float* const* params, const float* s_attn, const float* s_mlp, int B, int n, int D, int H,
+                         int hidden, float eps, float scale, float* y, float* cls_row, float* saved, int train, int mode, void* workspace,
+                         size_t workspace_bytes, d2s_stream_t stream);
+int d2s_block_bwd_f32_dp(const float* gy, const float* x, const float* saved, const float* const* params, const float* const* paramsT,
+                         const float* s_attn, const float* s_mlp, int B, int n, int D, int H, int hidden, float scale, float* dx,
+                         float* const* dparams, float* scratch, int mode, void* workspace, size_t workspace_bytes, void* wgrad_workspace,
+                         size_t wgrad_workspace_bytes, d2s_stream_t wgrad_stream, d2s_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
