@@ -500,6 +500,13 @@ class TrainStep:
                 raise lib.D2SError("TrainStep(graph=True) with drop_path_rate > 0 is not supported: a replayed step would reuse the "
                                    "stochastic-depth masks it was captured with; run the step eagerly (graph=False)")
             self.graph = False
+        if bool(getattr(student, "diff_topk", False)):
+            # same reason: the perturbation noise comes from a seed drawn on the host inside the model's forward (one draw per step), and
+            # sigma changes per epoch as a launch argument: a replayed step would repeat the noise and the sigma it was captured with
+            if self.graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with diff_topk is not supported: a replayed step would reuse the perturbation "
+                                   "noise and the sigma it was captured with; run the step eagerly (graph=False)")
+            self.graph = False
         self.graph_auto_max_rows = int(os.environ.get("D2S_STEP_GRAPH_AUTO_ROWS", "16384"))
         self._graphs = {}                   # key -> entry (see _graph_step)
         self._capture_stream = None
@@ -567,6 +574,8 @@ class TrainStep:
             "patch_score_threshold": None if thr is None else float(thr),
             "gemm_mode": int(ops.get_gemm_mode()),
             "drop_path_rate": float(getattr(s, "drop_path_rate", 0.0)),
+            "diff_topk": bool(getattr(s, "diff_topk", False)),
+            "topk_num_samples": int(getattr(s, "topk_num_samples", 500)) if getattr(s, "diff_topk", False) else 0,
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -600,6 +609,8 @@ class TrainStep:
                                "through --student-checkpoint)")
         theirs, ours = dict(sd["config"]), self.config()
         theirs.setdefault("drop_path_rate", 0.0)       # checkpoints written before stochastic depth existed were trained without it
+        theirs.setdefault("diff_topk", False)          # ... and before the perturbed top-k mode existed: hard selection
+        theirs.setdefault("topk_num_samples", 0)
         for k in ours:
             if k not in theirs or theirs[k] != ours[k]:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")

@@ -778,3 +778,42 @@ class PerturbedTopKFn(torch.autograd.Function):
         x, noise = ctx.saved_tensors
         k, sigma = ctx.meta
         return ops.perturbed_topk_bwd(x, noise, g.contiguous(), k, sigma), None, None, None
+
+
+@mode_recorded
+class SoftGatherFn(torch.autograd.Function):
+    """The soft token gather of the perturbed top-k training mode (dynamic_vit.py:896-900, stated there in comments):
+    y[:, 0] = x[:, 0], y[:, 1:] = ind @ x[:, 1:] with ind [B, k, N] the PerturbedTopKFn indicators.  Returns (dx, dind).
+    Selection stays fp32 in every GEMM arithmetic mode: the three products always run on the exact-fp32 MFMA and the output is the
+    fp32 residual stream without a bf16 shadow (the mode is recorded like the neighbours', nothing here depends on it)."""
+
+    @staticmethod
+    def forward(ctx, x, ind):
+        x, ind = x.contiguous(), ind.contiguous()
+        ctx.save_for_backward(x, ind)
+        return ops.soft_gather_fwd(x, ind)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, ind = ctx.saved_tensors
+        g = g.contiguous()
+        dx = ops.soft_gather_bwd_x(g, ind, x.shape[1]) if ctx.needs_input_grad[0] else None
+        dind = ops.soft_gather_bwd_ind(g, x) if ctx.needs_input_grad[1] else None
+        return dx, dind
+
+
+class KeepProbsFn(torch.autograd.Function):
+    """keep_probs = softmax(scores) (dynamic_vit.py:551) as a differentiable value.  The predictor Functions return their probabilities
+    marked non-differentiable (the hard selection needs no gradient); the perturbed top-k mode repeats the same launch on the same
+    scores - the same bits - and this backward carries d2s_perturbed_topk_bwd's gradient into the predictor's scores."""
+
+    @staticmethod
+    def forward(ctx, scores):
+        probs = ops.softmax_rows(scores.contiguous())
+        ctx.save_for_backward(probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, g):
+        (probs,) = ctx.saved_tensors
+        return ops.softmax_rows_bwd(probs, g.contiguous())

@@ -81,6 +81,10 @@ _SIGS = {
     "d2s_perturbed_topk_workspace_bytes": (Z, [I, I, I]),
     "d2s_perturbed_topk_fwd": (I, [P, P, P, I, I, I, I, F, P, Z]),
     "d2s_perturbed_topk_bwd": (I, [P, P, P, P, I, I, I, I, F]),
+    "d2s_soft_gather_fwd": (I, [P, P, P, I, I, I, I]),
+    "d2s_soft_gather_bwd_x": (I, [P, P, P, I, I, I, I]),
+    "d2s_soft_gather_bwd_ind": (I, [P, P, P, I, I, I, I]),
+    "d2s_softmax_rows_bwd": (I, [P, P, P, I, I]),
     "d2s_block_saved_floats": (L, [I, I, I, I, I, I]),
     "d2s_block_bwd_scratch_floats": (L, [I, I, I, I, I]),
     "d2s_block_workspace_bytes": (Z, [I, I, I, I, I]),

@@ -1027,6 +1027,51 @@ def perturbed_topk_bwd(x, noise, g, k, sigma):
     return gx
 
 
+def soft_gather_fwd(x, ind):
+    """x [B,n,D], ind [B,k,n-1] -> y [B,k+1,D]: y[:,0] = x[:,0], y[:,1:] = ind @ x[:,1:] (dynamic_vit.py:896-900); always exact fp32"""
+    _f32(x)
+    _f32(ind)
+    B, n, D = x.shape
+    k = ind.shape[1]
+    assert ind.shape == (B, k, n - 1), f"indicators must be [B, k, n - 1] = [{B}, k, {n - 1}]"
+    y = torch.empty((B, k + 1, D), dtype=torch.float32, device=x.device)
+    lib.call("d2s_soft_gather_fwd", lib.ptr(x), lib.ptr(ind), lib.ptr(y), B, n, k, D)
+    return y
+
+
+def soft_gather_bwd_x(g, ind, n):
+    """g [B,k+1,D], ind [B,k,n-1] -> dx [B,n,D]: dx[:,0] = g[:,0], dx[:,1:] = ind^T @ g[:,1:]"""
+    _f32(g)
+    _f32(ind)
+    B, k1, D = g.shape
+    assert ind.shape == (B, k1 - 1, n - 1)
+    dx = torch.empty((B, n, D), dtype=torch.float32, device=g.device)
+    lib.call("d2s_soft_gather_bwd_x", lib.ptr(g), lib.ptr(ind), lib.ptr(dx), B, n, k1 - 1, D)
+    return dx
+
+
+def soft_gather_bwd_ind(g, x):
+    """g [B,k+1,D], x [B,n,D] -> dind [B,k,n-1] = g[:,1:] @ x[:,1:]^T"""
+    _f32(g)
+    _f32(x)
+    B, k1, D = g.shape
+    n = x.shape[1]
+    assert x.shape == (B, n, D)
+    dind = torch.empty((B, k1 - 1, n - 1), dtype=torch.float32, device=g.device)
+    lib.call("d2s_soft_gather_bwd_ind", lib.ptr(g), lib.ptr(x), lib.ptr(dind), B, n, k1 - 1, D)
+    return dind
+
+
+def softmax_rows_bwd(probs, gprobs):
+    _f32(probs)
+    _f32(gprobs)
+    R, T = probs.shape
+    assert gprobs.shape == probs.shape
+    out = torch.empty_like(probs)
+    lib.call("d2s_softmax_rows_bwd", lib.ptr(probs), lib.ptr(gprobs), lib.ptr(out), R, T)
+    return out
+
+
 def adamw_step(params, grads, exp_avg, exp_avg_sq, desc, n_chunks, beta1, beta2, eps, step, grad_scale=1.0, chunk_steps=None):
     """chunk_steps: int32 [n_chunks] per-tensor update counters (torch.optim.AdamW's state['step']), advanced in place."""
     assert chunk_steps is None or (chunk_steps.dtype == torch.int32 and chunk_steps.numel() == n_chunks)

@@ -54,6 +54,13 @@ def check_supported(args):
         bad.append(f"--mask-loss-type {args.mask_loss_type} (kl_div and mse are on the path; bce is broken in the reference)")
     if not 0.0 <= getattr(args, "drop_path", 0.0) < 1.0:
         bad.append(f"--drop-path {args.drop_path} (0 <= rate < 1)")
+    if getattr(args, "diff_topk", False):
+        if not args.topk_selection:
+            bad.append("--diff-topk without --topk-selection (the perturbed top-k acts on the score predictor's keep probabilities)")
+        if args.patch_score_threshold is not None:
+            bad.append("--diff-topk with --patch-score-threshold (the soft gather applies to the fixed-ratio path only)")
+        if getattr(args, "topk_samples", 500) < 1:
+            bad.append(f"--topk-samples {args.topk_samples} (at least 1)")
     if args.use_dp:
         bad.append("--use-dp (one process per GPU only: --use-ddp under torch.distributed.run)")
     folder = getattr(args, "data_source", "synthetic") == "folder"
@@ -107,6 +114,8 @@ def build_models(args):
                                                    predictor_loss_type=args.mask_loss_type, predictor_bn=args.predictor_bn,
                                                    patch_score_threshold=args.patch_score_threshold,
                                                    drop_path_rate=getattr(args, "drop_path", 0.0),
+                                                   diff_topk=getattr(args, "diff_topk", False),
+                                                   topk_num_samples=getattr(args, "topk_samples", 500),
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
@@ -239,8 +248,10 @@ def main(argv=None):
                                        warming_up_step=args.warmup_steps, base_multi=0.1)                  # :300-301
         else:
             optim.set_epoch(epoch)
-        if args.topk_selection and hasattr(args, "current_sigma"):
+        if args.topk_selection:
+            args.current_sigma = utils.current_sigma(args, epoch)       # the fused step's schedule does not touch args
             student.current_sigma = args.current_sigma
+            print(f"### current_sigma = {args.current_sigma:.6f}" + (" (perturbed top-k soft gather)" if getattr(args, "diff_topk", False) else ""))
         if folder:
             train_loader, val_loader = folder_loaders(args, samples, split, epoch, rank, world)
             n_images = len(train_loader.set.order)

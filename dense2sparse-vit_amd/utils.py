@@ -28,10 +28,15 @@ def get_param_groups(model, args):
             {'params': early_exit, 'weight_decay': args.weight_decay, 'name': 'early_exit'}]
 
 
+def current_sigma(args, step):
+    """The perturbation scale of epoch `step` (utils.py:95-96 of the reference): linear from --initial-sigma to 0 at step == epochs"""
+    return max(0, (1 - step / args.epochs) * args.initial_sigma)
+
+
 def adjust_learning_rate(param_groups, args, step, model, warming_up_step=2, warmup_predictor=False, base_multi=0.1):
     """utils.py:93-147 for torch.optim param groups (d2s.engine.adjust_learning_rate is the same schedule for FusedAdamW)."""
     if getattr(args, "topk_selection", False):
-        args.current_sigma = max(0, (1 - step / args.epochs) * args.initial_sigma)
+        args.current_sigma = current_sigma(args, step)
     cos_lr = (math.cos(step / args.epochs * math.pi) + 1) * 0.5
     cos_lr = args.min_lr + cos_lr * (args.lr - args.min_lr)
     for n, p in model.named_parameters():
@@ -156,6 +161,10 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
+    p.add_argument('--diff-topk', action='store_true', default=False,
+                   help='with --topk-selection: train through the perturbed top-k soft gather (sigma decays from --initial-sigma to 0 over '
+                        'the epochs); evaluation and the trained model keep the hard top-k')
+    p.add_argument('--topk-samples', type=int, default=500, metavar='N', help="noise samples of --diff-topk (the reference's PerturbedTopK default)")
     return p.parse_args(argv)
 
 

@@ -64,6 +64,12 @@ def _scores(predictor, x):
                            "path (vit_models/dynamic_vit.py:537), so the pruning stages cannot run - pass --topk-selection / topk_selection=True")
     return out
 
+DIFF_TOPK_THRESHOLD_ERROR = ("diff_topk (perturbed top-k soft gather) applies to the fixed-ratio path only: it cannot be combined with "
+                             "patch_score_threshold")
+DIFF_TOPK_OVERRIDE_ERROR = ("diff_topk cannot replay a recorded selection in training: kept_token_override fixes the ids, the soft gather "
+                            "draws its own; set kept_token_override = None or call eval()")
+
+
 class DropPath(nn.Module):
     """Stochastic depth per sample (timm's DropPath as restated in vit_models/deit.py:69-89): identity in eval or at rate 0; in training
     x[b] * floor(keep + u[b]) / keep.  The draw is made on the device from a seed taken from torch's default CPU generator (draw_seed).
@@ -431,8 +437,12 @@ class VisionTransformerDiffPruning(_ViTBase):
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., hybrid_backbone=None, norm_layer=None,
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
-                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, init_n=14 * 14):
+                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
         super().__init__()
+        if diff_topk and patch_score_threshold is not None:
+            raise ValueError(DIFF_TOPK_THRESHOLD_ERROR)
+        if diff_topk and not topk_selection:
+            raise ValueError("diff_topk needs topk_selection=True: the perturbed top-k acts on the score predictor's keep probabilities")
         self._build_trunk(img_size, patch_size, in_chans, num_classes, embed_dim, depth, num_heads, mlp_ratio, qkv_bias, qk_scale,
                           representation_size, drop_rate, attn_drop_rate, drop_path_rate, hybrid_backbone, norm_layer)
         if early_exit:      # :752-758: the head is created (state-dict keys, 'early_exit' parameter group) but no forward path of the
@@ -463,6 +473,19 @@ class VisionTransformerDiffPruning(_ViTBase):
         # replay of a recorded selection (analysis / tests): a list of int64 [B, k_i] kept-id tensors, one per stage, used INSTEAD of the
         # top-k of this forward's scores (which are still computed and returned); None = normal operation
         self.kept_token_override = None
+        # differentiable token selection (the "dense to sparse" scheme the reference states at :896-900 and never connects): in a training
+        # forward every stage's kept-token gather becomes PerturbedTopK(keep_probs; k, topk_num_samples, current_sigma) @ tokens
+        self.diff_topk = bool(diff_topk)
+        self.topk_num_samples = int(topk_num_samples)       # peturbed_topk.py:6
+        if self.topk_num_samples < 1:
+            raise ValueError("topk_num_samples must be at least 1")
+        # injected perturbation noise (tests, fixtures): a list of [B, topk_num_samples, N_i] tensors, one per stage, used instead of the
+        # device stream until set back to None
+        self.topk_noise = None
+        # inspection (tests): with keep_topk_indicators set, the last soft forward's indicators [B, k_i, N_i] per stage stay referenced here
+        # (detached) until the next forward; off by default so that nothing outlives the step
+        self.keep_topk_indicators = False
+        self.topk_indicators = []
         self.unpruned = False
         self.distill = distill
         self.pruning_loc, self.token_ratio = pruning_loc, token_ratio
@@ -493,6 +516,9 @@ class VisionTransformerDiffPruning(_ViTBase):
         if self.patch_score_threshold is not None:
             return self._forward_threshold(x)
         dp = self._drop_path_table(x.shape[0], x.device)
+        soft = self._soft_selection()
+        soft_seed = draw_seed() if (soft and self.topk_noise is None) else None     # one draw per training forward, mixed with the stage index
+        self.topk_indicators = []
         x = self._embed(x)                                                  # :816-824
         self.num_kept_tokens, self.cls_attns, self.pred_logits = [], [], []
         self.kept_token_indices, self.dropped_token_indices = [], []
@@ -512,7 +538,10 @@ class VisionTransformerDiffPruning(_ViTBase):
                 self.kept_token_indices.append(kept)
                 self.dropped_token_indices.append(dropped)
                 self.pred_logits.append(pred_logits)
-                x = DF.GatherFn.apply(x, kept)                               # :907-912 / :954-960
+                if soft:                                                     # :896-900
+                    x = self._soft_gather(x, pred_logits, num_keep_node, p_count, soft_seed)
+                else:
+                    x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
             x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
             self.cls_attns.append(cls_attn[:, :, 1:])
@@ -520,6 +549,33 @@ class VisionTransformerDiffPruning(_ViTBase):
         if self.training:
             return logits, features, self.pred_logits, self.kept_token_indices   # :1013
         return logits, self.cls_attns, self.pred_logits, self.kept_token_indices  # :1015
+
+    def _soft_selection(self):
+        """Does this forward use the soft gather?  Only a training forward that keeps a graph does: eval(), torch.no_grad() and every
+        forward-only branch keep the hard gather (the pruned inference model is what this training produces), and so does
+        sigma <= 0, where the perturbed top-k IS the hard top-k and its gradient (1 / sigma) is undefined."""
+        if not (self.diff_topk and self.training and torch.is_grad_enabled()):
+            return False
+        if self.kept_token_override is not None:
+            raise RuntimeError(DIFF_TOPK_OVERRIDE_ERROR)
+        return float(self.current_sigma) > 0.
+
+    def _soft_gather(self, x, scores, k, stage, seed):
+        """x [B, n, D] -> [B, k + 1, D]: CLS passes through, row 1 + i = sum_j ind[b, i, j] x[b, 1 + j] with ind the perturbed top-k
+        indicators of the keep probabilities.  Row i of ind is the i-th selected id in ascending order - the order of `kept`."""
+        from d2s import ops
+        B, n, _ = x.shape
+        probs = DF.KeepProbsFn.apply(scores)                                 # :551, the bits of the predictor's own keep_probs
+        if self.topk_noise is not None:
+            noise = self.topk_noise[stage].to(device=x.device, dtype=torch.float32).contiguous()
+            assert tuple(noise.shape) == (B, self.topk_num_samples, n - 1), \
+                f"topk_noise[{stage}] must be [B, topk_num_samples, N] = {(B, self.topk_num_samples, n - 1)}"
+        else:
+            noise = ops.normal_noise((B, self.topk_num_samples, n - 1), (seed + 0x9E3779B97F4A7C15 * (stage + 1)) & 0xFFFFFFFFFFFFFFFF, x.device)
+        ind = DF.PerturbedTopKFn.apply(probs, noise, int(k), float(self.current_sigma))
+        if self.keep_topk_indicators:
+            self.topk_indicators.append(ind.detach())
+        return DF.SoftGatherFn.apply(x, ind)
 
     def _forward_threshold(self, x):
         """Dynamic keep ratio (patch_score_threshold is set).

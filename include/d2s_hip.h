@@ -177,6 +177,21 @@ int d2s_performer_attn_bwd(const float* kqv, const float* w, const float* y, con
                            float* dD, float* dqp, float* dkp, float* dA, float* dksum, int B, int T, float eps, void* workspace,
                            size_t workspace_bytes, d2s_stream_t stream);
 
+/* ---- soft token gather of the perturbed top-k training mode ------------------------------------------------------ */
+/* vit_models/dynamic_vit.py:896-900 states the product in comments only (`spatial_x = pred_score @ spatial_x  # shape: (B, K, D)`,
+ * `x = torch.cat((cls_x, spatial_x), dim=1)`): x [B,n,D], ind [B,k,n-1] (d2s_perturbed_topk_fwd's indicators) ->
+ * y [B,k+1,D] with y[b,0] = x[b,0] and y[b,1+i] = sum_j ind[b,i,j] * x[b,1+j].  Exact fp32 MFMA, one launch, batch on a grid axis,
+ * deterministic; a one-hot ind gives d2s_gather_pack_fwd's bits */
+int d2s_soft_gather_fwd(const float* x, const float* ind, float* y, int B, int n, int k, int D, d2s_stream_t stream);
+/* its backward w.r.t. x (:896-900 transposed): g [B,k+1,D] -> dx [B,n,D], dx[b,0] = g[b,0], dx[b,1+j] = sum_i ind[b,i,j] * g[b,1+i];
+ * every row of dx is written once (no memset needed) */
+int d2s_soft_gather_bwd_x(const float* g, const float* ind, float* dx, int B, int n, int k, int D, d2s_stream_t stream);
+/* its backward w.r.t. the indicators (:896-900): dind[b,i,j] = sum_d g[b,1+i,d] * x[b,1+j,d] -> [B,k,n-1], the grad_out of
+ * d2s_perturbed_topk_bwd */
+int d2s_soft_gather_bwd_ind(const float* g, const float* x, float* dind, int B, int n, int k, int D, d2s_stream_t stream);
+/* backward of d2s_softmax_rows (F.softmax, vit_models/dynamic_vit.py:551): grad_scores = probs * (grad_probs - sum(grad_probs * probs)) */
+int d2s_softmax_rows_bwd(const float* probs, const float* grad_probs, float* grad_scores, int rows, int T, d2s_stream_t stream);
+
 /* ---- perturbed top-k (vit_models/peturbed_topk.py:16-80), noise injected ------------------------------------------ */
 /* peturbed_topk.py:29 draws torch.normal on the host; this fills out[0..n) with standard normals of the counter-based stream `seed`
  * (Philox4x32-10 + Box-Muller; element i does not depend on the launch shape) so that production needs no host RNG / H2D copy */

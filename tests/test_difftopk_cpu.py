@@ -1,0 +1,182 @@
+"""Differentiable token selection (perturbed top-k soft gather), the parts that need no GPU: the fixture's condition, the restatement in
+tests/difftopk_ref.py against the reference's own run, the command line, the constructor's refusals and the checkpoint config keys."""
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import cases
+from tests import difftopk_ref as R
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MICRO = dict(img_size=64, patch_size=16, embed_dim=128, depth=4, num_heads=2, mlp_ratio=4.0, qkv_bias=True, num_classes=10)
+MARGIN_MIN = 2e-5
+
+
+@pytest.mark.parametrize("tag", ["m1", "m2"])
+def test_fixture_margin_condition(tag):
+    """The generator's condition, read back from the file and recomputed from the stored probabilities and noise: the gap between the
+    k-th and (k + 1)-th largest perturbed value is at least 2e-5 everywhere (30 x what the predictor-logit tolerance, atol 1e-5, can
+    move a probability of ~0.06), so the integer sample counts do not depend on fp32 rounding order."""
+    g = cases.load_golden("difftopk_micro")
+    assert float(g[f"{tag}_margin"]) >= MARGIN_MIN
+    case, noises, sigma = R.fixture_case(g, tag)
+    assert sigma == 0.05 and int(g[f"{tag}_num_samples"]) == 16 and case["batch"] == 4
+    worst = float("inf")
+    for i, nz in enumerate(noises):
+        k = g[f"{tag}_kept_{i}"].shape[1]
+        worst = min(worst, R.margin(torch.from_numpy(g[f"{tag}_probs_{i}"]), nz, k, sigma))
+        assert nz.shape == (4, 16, g[f"{tag}_probs_{i}"].shape[1])
+    assert worst >= MARGIN_MIN
+    assert worst == pytest.approx(float(g[f"{tag}_margin"]), rel=1e-6)
+
+
+@pytest.mark.parametrize("tag", ["m1", "m2"])
+def test_restatement_reproduces_the_reference_composition(tag):
+    """tests/difftopk_ref.py with the fixture's noise injected, in the reference's own arithmetic (float32 on the CPU), against what the
+    reference's live PredictorLG, PerturbedTopKFunction and Blocks produced composed as dynamic_vit.py:896-900 states
+    (tools/gen_difftopk_fixture.py): indicators and kept ids exactly; probabilities, logits, features, predictor logits, the probe loss
+    and the gradients to the tolerances tests/test_oracle_golden.py applies to the same quantities of a model case (1e-5 / 1e-6, probabilities
+    atol 1e-8, gradient norms 2e-4 (atol 5e-8), leading elements 2e-3 (atol 1e-7))."""
+    g = cases.load_golden("difftopk_micro")
+    out = R.run_fixture_case(g, tag, dtype=torch.float32)
+    stages = int(g[f"{tag}_stages"])
+    assert stages == len(out["kept"]) == (1 if tag == "m1" else 2)
+    for i in range(stages):
+        np.testing.assert_array_equal(out["ind"][i].numpy(), g[f"{tag}_ind_{i}"])
+        np.testing.assert_array_equal(out["kept"][i].numpy(), g[f"{tag}_kept_{i}"])
+        np.testing.assert_allclose(out["probs"][i].numpy(), g[f"{tag}_probs_{i}"], rtol=1e-5, atol=1e-8)
+        np.testing.assert_allclose(out["pred_logits"][i].numpy(), g[f"{tag}_pred_logits_{i}"], rtol=1e-5, atol=1e-6)
+        gx = out["grad_x"][i]
+        np.testing.assert_allclose(float(gx.double().norm()), float(g[f"{tag}_grad_x_norm_{i}"]), rtol=2e-4, atol=5e-8)
+        np.testing.assert_allclose(gx[:, :, :8].numpy(), g[f"{tag}_grad_x_slice_{i}"], rtol=2e-3, atol=1e-7)
+        # row i of the indicators is the i-th selected id in ascending order: every row sums to 1, and so far from sigma = 0 it is soft
+        np.testing.assert_allclose(g[f"{tag}_ind_{i}"].sum(axis=-1), 1.0, rtol=0, atol=1e-6)
+        assert float(g[f"{tag}_ind_{i}"].max()) <= 1.0 and (g[f"{tag}_ind_{i}"] * 16 == np.round(g[f"{tag}_ind_{i}"] * 16)).all()
+    np.testing.assert_allclose(out["logits"].numpy(), g[f"{tag}_logits"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(out["features"].numpy(), g[f"{tag}_features"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(float(out["loss"]), float(g[f"{tag}_probe_loss"]), rtol=1e-5)
+    seen = 0
+    for n, ref_norm, ref_head in zip([str(s) for s in g[f"{tag}_grad_names"]], g[f"{tag}_grad_norms"], g[f"{tag}_grad_heads"]):
+        gf = out["grads"][n].flatten()
+        np.testing.assert_allclose(float(gf.double().norm()), ref_norm, rtol=2e-4, atol=5e-8, err_msg=n)
+        m = min(8, gf.numel())
+        np.testing.assert_allclose(gf[:m].numpy(), ref_head[:m], rtol=2e-3, atol=1e-7, err_msg=n)
+        seen += 1
+    assert seen == 24 * stages      # every predictor tensor of every stage gets a gradient from the backbone outputs alone
+
+
+def test_restatement_at_tiny_sigma_is_the_hard_gather():
+    """x + sigma * noise rounds to x at sigma = 1e-12: one-hot indicators, and the soft gather equals the oracle's gather"""
+    import oracle.d2s_oracle as O
+    g = cases.load_golden("difftopk_micro")
+    case, noises, _ = R.fixture_case(g, "m2")
+    cfg = case["cfg"]
+    from d2s import synth
+    sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in cases.make_weights(case)[0].items()}
+    x = torch.from_numpy(synth.images(case["batch"], 3, cfg["img_size"], seed=case["seed"]))
+    sdg = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    (lo, fe, _, kept), aux = R.student_forward(sdg, x, cfg, noises, 1e-12)
+    (olo, ofe, _, okept), _ = O.student_forward(sd, x, cfg, training=True)
+    for a, b, ind in zip(kept, okept, aux["ind"]):
+        np.testing.assert_array_equal(a.numpy(), b.numpy())
+        onehot = torch.nn.functional.one_hot(a, ind.shape[-1]).float()
+        np.testing.assert_array_equal(ind.detach().numpy(), onehot.numpy())
+    np.testing.assert_allclose(lo.detach().numpy(), olo.numpy(), rtol=1e-5, atol=1e-6)
+
+
+def test_cli_accepts_the_new_flags():
+    import mask_predictor
+    import utils
+    a = utils.parse_args([])
+    assert a.diff_topk is False and a.topk_samples == 500
+    a = utils.parse_args(["--topk-selection", "--diff-topk", "--topk-samples", "64"])
+    assert a.diff_topk is True and a.topk_samples == 64 and a.topk_selection is True
+    mask_predictor.check_supported(a)
+    assert utils.current_sigma(types.SimpleNamespace(epochs=10, initial_sigma=0.05), 0) == 0.05
+    assert utils.current_sigma(types.SimpleNamespace(epochs=10, initial_sigma=0.05), 10) == 0
+
+
+@pytest.mark.parametrize("extra, needle", [
+    (["--diff-topk"], "--topk-selection"),
+    (["--topk-selection", "--diff-topk", "--patch-score-threshold", "0.5"], "--patch-score-threshold"),
+    (["--topk-selection", "--diff-topk", "--topk-samples", "0"], "--topk-samples"),
+])
+def test_check_supported_rejects(extra, needle):
+    import mask_predictor
+    import utils
+    with pytest.raises(SystemExit, match=needle):
+        mask_predictor.check_supported(utils.parse_args(extra))
+
+
+def _student(**kw):
+    import vit_models
+    return vit_models.VisionTransformerDiffPruning(pruning_loc=[1], token_ratio=[0.05], distill=True, topk_selection=True,
+                                                   predictor_loss_type="kl_div", **MICRO, **kw)
+
+
+def test_constructor_defaults_and_refusals():
+    import inspect
+    import vit_models
+    names = list(inspect.signature(vit_models.VisionTransformerDiffPruning.__init__).parameters)
+    assert names[-3:] == ["init_n", "diff_topk", "topk_num_samples"]      # trailing: positional callers of the reference's signature are unaffected
+    off, on = _student(), _student(diff_topk=True, topk_num_samples=16)
+    assert off.diff_topk is False and off.topk_num_samples == 500 and on.diff_topk is True and on.topk_num_samples == 16
+    assert on.topk_noise is None
+    assert list(off.state_dict()) == list(on.state_dict())
+    with pytest.raises(ValueError, match="patch_score_threshold"):
+        _student(diff_topk=True, patch_score_threshold=0.5)
+    with pytest.raises(ValueError, match="topk_num_samples"):
+        _student(diff_topk=True, topk_num_samples=0)
+    assert on.keep_topk_indicators is False and on.topk_indicators == []
+    with pytest.raises(ValueError, match="topk_selection"):
+        vit_models.VisionTransformerDiffPruning(pruning_loc=[1], token_ratio=[0.05], diff_topk=True, **MICRO)
+    on.train()
+    on.kept_token_override = [torch.zeros(1, 9, dtype=torch.int64)]
+    with pytest.raises(RuntimeError, match="kept_token_override"):
+        on._soft_selection()
+    on.eval()
+    assert on._soft_selection() is False
+    on.train()
+    on.kept_token_override = None
+    assert on._soft_selection() is True
+    on.current_sigma = 0
+    assert on._soft_selection() is False          # sigma <= 0: the hard gather
+    with torch.no_grad():
+        on.current_sigma = 0.05
+        assert on._soft_selection() is False
+    small = vit_models.dynamic_vit_small_patch16_224_student([3], [0.5], topk_selection=True, diff_topk=True, topk_num_samples=8)
+    assert small.diff_topk and small.topk_num_samples == 8      # the factories forward **kwargs
+
+
+def test_config_round_trips_the_new_keys():
+    from d2s.engine import TrainStep
+    args = types.SimpleNamespace(mask_loss_type="kl_div")
+    cfgs = [TrainStep.config(types.SimpleNamespace(student=s, args=args)) for s in (_student(), _student(diff_topk=True, topk_num_samples=16))]
+    assert cfgs[0]["diff_topk"] is False and cfgs[0]["topk_num_samples"] == 0
+    assert cfgs[1]["diff_topk"] is True and cfgs[1]["topk_num_samples"] == 16
+    for c in cfgs:
+        assert json.loads(json.dumps(c)) == c
+    assert {k for k in cfgs[0] if cfgs[0][k] != cfgs[1][k]} == {"diff_topk", "topk_num_samples"}
+
+
+def test_library_binding_declares_the_new_entries():
+    from d2s import lib
+    for name in ("d2s_soft_gather_fwd", "d2s_soft_gather_bwd_x", "d2s_soft_gather_bwd_ind", "d2s_softmax_rows_bwd"):
+        assert name in lib.exported_symbols()
+        assert name in open(os.path.join(REPO, "include", "d2s_hip.h")).read()
+    assert "dynamic_vit.py:896-900" in open(os.path.join(REPO, "include", "d2s_hip.h")).read()
+
+
+def test_product_still_never_imports_oracle():
+    pkg = os.path.join(REPO, "dense2sparse-vit_amd")
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(root, f)).read()
+                assert "oracle" not in src.replace("# oracle", ""), f"{f} references the oracle"
+    src = open(os.path.join(REPO, "tools", "gen_difftopk_fixture.py")).read()
+    assert "sys.dont_write_bytecode = True" in src

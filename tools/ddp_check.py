@@ -6,6 +6,14 @@ averaged gradients and the same updated parameters as one process with the conca
 
 Backend: RCCL ("nccl") when every rank has its own GPU, otherwise gloo on GPU tensors (rehearsal on a 1-GPU box: all ranks
 share cuda:0).  Exit code 0 = pass.
+
+D2S_DDP_DIFF_TOPK=1 runs the same check with the differentiable token selection on (diff_topk=True, 16 noise samples, sigma 0.05): one
+noise tensor [B, 16, N_i] per stage is shared, every rank injects its own images' slice (student.topk_noise) and the single process the
+whole tensor, so both sides perturb the same probabilities with the same numbers.  Epoch 0 is then the case in which the stage outputs
+require a gradient although the backbone is frozen: the grad_ready hooks fire against the predictor-only live set.  The indicators are
+integer sample counts: the comparison presupposes that no perturbed value sits within fp32 rounding of its selection boundary, so the
+smallest gap between the k-th and (k + 1)-th largest perturbed value of the single-process run is printed and must be at least 2e-5 (the
+condition of tests/golden/difftopk_micro.npz); a run that misses it exits with code 3 - a property of the noise seed, not a mismatch.
 """
 import os
 import sys
@@ -23,13 +31,40 @@ import torch.distributed as dist
 from tests import cases
 
 
+DIFF_TOPK = os.environ.get("D2S_DDP_DIFF_TOPK") == "1"
+NOISE_SAMPLES, NOISE_SEED, MARGIN_MIN = 16, 41, 2e-5
+
+
+def stage_noise(case, B):
+    """one shared standard-normal tensor [B, NOISE_SAMPLES, N_i] per stage"""
+    from d2s import synth
+    cfg = case["cfg"]
+    n, out = cfg["n_patches"], []
+    for i, r in enumerate(cfg["token_ratio"]):
+        out.append(torch.from_numpy(synth.normal(f"ddp_check/noise/{i}", (B, NOISE_SAMPLES, n), std=1.0, seed=NOISE_SEED)))
+        n = int(cfg["init_n"] * r)
+    return out
+
+
+def selection_margin(student, noises):
+    """smallest gap between the k-th and (k + 1)-th largest perturbed keep probability of the student's last forward"""
+    worst = float("inf")
+    for scores, kept, nz in zip(student.pred_logits, student.kept_token_indices, noises):
+        k = kept.shape[1]
+        pert = torch.sort(torch.softmax(scores.detach(), dim=-1)[:, None, :] + nz.to(scores.device) * float(student.current_sigma),
+                          dim=-1, descending=True)[0]
+        worst = min(worst, float((pert[..., k - 1] - pert[..., k]).min()))
+    return worst
+
+
 def build(case, dev):
     import vit_models
     cfg = case["cfg"]
+    extra = dict(diff_topk=True, topk_num_samples=NOISE_SAMPLES) if DIFF_TOPK else {}
     common = dict(img_size=cfg["img_size"], patch_size=cfg["patch"], embed_dim=cfg["dim"], depth=cfg["depth"],
                   num_heads=cfg["heads"], mlp_ratio=cfg["mlp_ratio"], qkv_bias=True, num_classes=cfg["num_classes"])
     s = vit_models.VisionTransformerDiffPruning(pruning_loc=list(cfg["pruning_loc"]), token_ratio=list(cfg["token_ratio"]),
-                                                distill=True, topk_selection=True, predictor_loss_type="kl_div", **common)
+                                                distill=True, topk_selection=True, predictor_loss_type="kl_div", **common, **extra)
     t = vit_models.VisionTransformerTeacher(**common)
     sd_s, sd_t = cases.make_weights(case)
     s.load_state_dict({k: torch.from_numpy(v) for k, v in sd_s.items()})
@@ -65,7 +100,12 @@ def main():
     if rank == 0:
         s1, t1, args1 = build(case, dev)
         ref = TrainStep(s1, t1, args1, distributed=False, warmup_steps=1)
-    ok = True
+    noises = stage_noise(case, B) if DIFF_TOPK else None
+    if DIFF_TOPK:
+        s.topk_noise = [nz[rank * per:(rank + 1) * per] for nz in noises]
+        if rank == 0:
+            s1.topk_noise = noises
+    ok, margin_ok = True, True
     for epoch in (0, 1):
         ts.set_epoch(epoch)
         live = list(ts.reducer.live)
@@ -85,10 +125,16 @@ def main():
             print(f"[ddp_check] world={world} backend={'nccl' if own_gpu else 'gloo'} epoch {epoch} live {len(sel)}/{ts.arena.total} "
                   f"rel grad diff {gd:.3e}  max param diff {pd:.3e}")
             ok = ok and gd < 1e-4 and pd < 2 * 2 * 5e-4 * 1.01
-    flag = torch.tensor([1 if ok else 0])
-    dist.broadcast(flag.to(dev) if own_gpu else flag, src=0)
+            if DIFF_TOPK:
+                margin = selection_margin(s1, noises)
+                print(f"[ddp_check] diff_topk epoch {epoch}: selection margin of the single-process run {margin:.3e} (needs >= {MARGIN_MIN:.0e})")
+                margin_ok = margin_ok and margin >= MARGIN_MIN
+    flag = torch.tensor([(1 if ok else 0) + (0 if margin_ok else 2)])
+    flag = flag.to(dev) if own_gpu else flag
+    dist.broadcast(flag, src=0)
     dist.destroy_process_group()
-    sys.exit(0 if ok else 1)
+    code = int(flag.item())
+    sys.exit(3 if code & 2 else (0 if code & 1 else 1))
 
 
 if __name__ == "__main__":
