@@ -239,11 +239,15 @@ struct ChunkDesc { float lr, wd; int active; int pad; };
 // against 28 + 12 for a separate pass.  A chunk that is not active (frozen tensor, or one that is in no parameter group) is not
 // updated, but its average still moves towards its parameters: such a workgroup reads p and ema and writes ema only.  Padding is
 // zero in both arenas and stays zero.  EMA = false is the body of the plain kernel: `ema` is never touched there.
-template <bool EMA>
+//
+// CLIP form (global-norm clipping, csrc/gradaccum.hip): the gradient scale is fl(grad_scale * coef_dev[0]) with the clipping coefficient
+// read from device memory, once per thread - the host never sees the norm.  CLIP = false never touches `coef_dev`.
+template <bool EMA, bool CLIP = false>
 __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, const ChunkDesc* __restrict__ desc, float b1, float b2, float eps,
                                             float bc1, float bc2_sqrt, float grad_scale, int* __restrict__ chunk_steps,
-                                            float* __restrict__ ema, float ema_decay, float ema_rest) {
+                                            float* __restrict__ ema, float ema_decay, float ema_rest,
+                                            const float* __restrict__ coef_dev = nullptr) {
     const ChunkDesc d = desc[blockIdx.x];
     if (!d.active) {
         if constexpr (EMA) {
@@ -277,6 +281,7 @@ __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* 
     f32x4 mv = *reinterpret_cast<f32x4*>(m + base);
     f32x4 vv = *reinterpret_cast<f32x4*>(v + base);
     const float step = d.lr / bc1;
+    if constexpr (CLIP) grad_scale = grad_scale * coef_dev[0];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float gj = gv[j] * grad_scale;
@@ -309,6 +314,15 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
                                                         int* __restrict__ chunk_steps, float* __restrict__ ema, float ema_decay,
                                                         float ema_rest) {
     adamw_chunk<true>(p, g, m, v, desc, b1, b2, eps, bc1, bc2_sqrt, grad_scale, chunk_steps, ema, ema_decay, ema_rest);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, const ChunkDesc* __restrict__ desc, float b1, float b2,
+                                                         float eps, float bc1, float bc2_sqrt, float grad_scale,
+                                                         int* __restrict__ chunk_steps, float* __restrict__ ema, float ema_decay,
+                                                         float ema_rest, const float* __restrict__ coef_dev) {
+    adamw_chunk<EMA, true>(p, g, m, v, desc, b1, b2, eps, bc1, bc2_sqrt, grad_scale, chunk_steps, ema, ema_decay, ema_rest, coef_dev);
 }
 
 }  // namespace
@@ -401,6 +415,26 @@ int d2s_adamw_step_ema(float* params, const float* grads, float* exp_avg, float*
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(n_chunks), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq,
                        static_cast<const ChunkDesc*>(desc), beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, chunk_steps, ema,
                        ema_decay, (float)(1.0 - (double)ema_decay));
+    return d2s_check_launch();
+}
+
+// d2s_adamw_step (ema null) or d2s_adamw_step_ema (ema given) with the gradient scale fl(grad_scale * coef_dev[0]): coef_dev is the
+// clipping coefficient d2s_grad_clip_coef left in device memory.  Everything else is the same body.
+int d2s_adamw_step_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* desc, int n_chunks, float beta1,
+                        float beta2, float eps, int step, float grad_scale, int* chunk_steps, float* ema, float ema_decay,
+                        const float* coef_dev, hipStream_t stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !desc || n_chunks <= 0 || (!chunk_steps && step < 1) || !coef_dev) return D2S_ERR_ARG;
+    if (ema && (ema == params || !(ema_decay >= 0.f && ema_decay < 1.f))) return D2S_ERR_ARG;
+    const double bc1 = chunk_steps ? 1.0 : 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = chunk_steps ? 1.0 : 1.0 - pow((double)beta2, (double)step);
+    const ChunkDesc* d = static_cast<const ChunkDesc*>(desc);
+    if (ema)
+        hipLaunchKernelGGL(adamw_clip_kernel<true>, dim3(n_chunks), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, d, beta1, beta2,
+                           eps, (float)bc1, (float)sqrt(bc2), grad_scale, chunk_steps, ema, ema_decay, (float)(1.0 - (double)ema_decay),
+                           coef_dev);
+    else
+        hipLaunchKernelGGL(adamw_clip_kernel<false>, dim3(n_chunks), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, d, beta1, beta2,
+                           eps, (float)bc1, (float)sqrt(bc2), grad_scale, chunk_steps, static_cast<float*>(nullptr), 0.f, 0.f, coef_dev);
     return d2s_check_launch();
 }
 

@@ -171,18 +171,30 @@ class FusedAdamW:
     def mark_dirty(self):
         self._dirty = True
 
-    def step(self, grad_scale=1.0):
+    def desc(self):
+        """The per-chunk {lr, wd, active} table on the device, rebuilt when learning rates or the frozen set changed."""
+        if self._dirty:
+            self._build_desc()
+        return self._desc
+
+    def step(self, grad_scale=1.0, clip_coef=None):
+        """clip_coef: None, or a one-float device tensor - the gradient scale is then fl(grad_scale * clip_coef[0]), formed on the device
+        (d2s_adamw_step_clip); without it d2s_adamw_step / d2s_adamw_step_ema are launched with the host scale."""
         if self._dirty:
             self._build_desc()
         self.steps += 1
         a = self.arena
-        if self.ema is None:
+        if self.ema is not None and not self._ema_primed:
+            self.ema.copy_(a.params)
+            self._ema_primed = True
+        if clip_coef is not None:
+            ops.adamw_step_clip(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
+                                self.eps, self.steps, clip_coef, ema=self.ema, ema_decay=self.ema_decay or 0.0, grad_scale=grad_scale,
+                                chunk_steps=self.chunk_steps)
+        elif self.ema is None:
             ops.adamw_step(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
                            self.eps, self.steps, grad_scale, chunk_steps=self.chunk_steps)
         else:
-            if not self._ema_primed:
-                self.ema.copy_(a.params)
-                self._ema_primed = True
             ops.adamw_step_ema(a.params, a.grads, self.exp_avg, self.exp_avg_sq, self._desc, a.n_chunks, self.betas[0], self.betas[1],
                                self.eps, self.steps, self.ema, self.ema_decay, grad_scale, chunk_steps=self.chunk_steps)
         ops.bump_weights_epoch()        # the kernel wrote the parameters through raw pointers: cached W^T copies are stale
@@ -462,12 +474,27 @@ class TrainStep:
     GRAPH_WARM_STEPS = 2        # eager steps of a given shape before it is captured (lazy one-time work happens there)
 
     def __init__(self, student, teacher, args, lr=5e-4, min_lr=1e-5, weight_decay=0.05, epochs=25, warmup_steps=0,
-                 distributed=False, bucket_mb=None, collective=None, graph=None):
-        """graph: capture the step into a hipGraph and replay it (None: D2S_STEP_GRAPH = 0 | 1 | auto, default 0; see _use_graph).
+                 distributed=False, bucket_mb=None, collective=None, graph=None, accum_steps=1, clip_grad=None):
+        """accum_steps = A: an optimiser step is computed from a window of A calls.  Every call runs forward, losses and backward on its own
+        batch; the first A - 1 add their gradient to a second arena and return, the last one combines (fp32, arrival order), exchanges,
+        clips and updates with the scale 1 / (A * world).  flush() closes a shorter window.  clip_grad = M: the gradient the optimiser sees
+        is clipped to the global L2 norm M (torch.nn.utils.clip_grad_norm_ over the parameters it updates); norm and coefficient stay on the
+        device (last_clip).  With A = 1 and no clipping the step is launch for launch what it is without these keywords.
+        graph: capture the step into a hipGraph and replay it (None: D2S_STEP_GRAPH = 0 | 1 | auto, default 0; see _use_graph).
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
         from losses import MaskLoss, BackboneLoss
+        if int(accum_steps) != accum_steps or accum_steps < 1:
+            raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
+        if clip_grad is not None and not float(clip_grad) > 0.0:
+            raise lib.D2SError(f"clip_grad {clip_grad!r}: expected a norm > 0 (None = no clipping)")
+        self.accum_steps, self.clip_grad = int(accum_steps), None if clip_grad is None else float(clip_grad)
+        self._pending = 0                   # micro-steps of the open window whose gradients have not reached the optimiser yet
+        self._acc = None                    # accumulation arena, partial sums of squares: allocated on first use
+        self._partials = None
+        self.last_clip = None               # device floats {pre-clip norm, coefficient} of the last clipped optimiser step
+        self._norm_sum, self._norm_steps = None, 0
         self.student, self.teacher, self.args = student, teacher, args
         self.teacher.eval()
         for p in self.teacher.parameters():
@@ -507,6 +534,20 @@ class TrainStep:
                 raise lib.D2SError("TrainStep(graph=True) with diff_topk is not supported: a replayed step would reuse the perturbation "
                                    "noise and the sigma it was captured with; run the step eagerly (graph=False)")
             self.graph = False
+        if self.accum_steps > 1:
+            # a captured step overwrites the gradient arena on every replay, and which launches follow the backward (accumulate, or
+            # combine + exchange + update) changes from call to call within a window
+            if self.graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with accum_steps > 1 is not supported: accumulation inside a captured step is "
+                                   "not built; run the step eagerly (graph=False)")
+            self.graph = False
+            if self.reducer is not None:
+                self.reducer.paused = True      # no exchange from inside backward: finish() sends the combined gradient, once per window
+        if self.clip_grad is not None:
+            if self.graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with clip_grad is not supported: the clipped update after a replayed step is "
+                                   "not covered by a test; run the step eagerly (graph=False)")
+            self.graph = False
         self.graph_auto_max_rows = int(os.environ.get("D2S_STEP_GRAPH_AUTO_ROWS", "16384"))
         self._graphs = {}                   # key -> entry (see _graph_step)
         self._capture_stream = None
@@ -517,7 +558,13 @@ class TrainStep:
         self.last_step_captured = False     # diagnostic: did the last call replay a graph
         self.set_epoch(0)
 
+    def _no_open_window(self, what):
+        if self._pending:
+            raise lib.D2SError(f"{what} with {self._pending} of {self.accum_steps} micro-steps of an accumulation window pending: "
+                               "call flush() first (a window never crosses an epoch or a checkpoint)")
+
     def set_epoch(self, epoch):
+        self._no_open_window("set_epoch")
         self.epoch = epoch
         self.args.step = epoch
         out = adjust_learning_rate(self.opt, self.student, epoch, self.epochs, self.lr, self.min_lr, self.warmup_steps, self.frozen)
@@ -583,6 +630,7 @@ class TrainStep:
         nested dict of CPU tensors, numbers, strings and lists (torch.load(..., weights_only=True) reads it back).  Keys are the
         student's parameter names and every tensor has its parameter's own shape - the arena layout stays an implementation detail.
         epoch: the last finished one (default: the epoch set_epoch was last called with)."""
+        self._no_open_window("state_dict")
         dev = self.arena.params.device
         sd = {
             "model": self._model_state(self.arena.params),
@@ -604,6 +652,7 @@ class TrainStep:
         the first mismatch and leaves this step as it was); the tensors are then copied INTO the arenas this step already owns, the
         per-tensor AdamW counters rebuilt, EMA weights and RNG states restored, and everything that remembers the old weights (captured
         step graphs, a teacher pass issued ahead, cached W^T / bf16 copies) dropped.  The caller continues with set_epoch(sd["epoch"] + 1)."""
+        self._no_open_window("load_state_dict")
         if not isinstance(sd, dict) or not isinstance(sd.get("config"), dict) or "model" not in sd or "optimizer" not in sd:
             raise lib.D2SError("not a training checkpoint: 'config', 'model' and 'optimizer' are expected (a weights-only file goes "
                                "through --student-checkpoint)")
@@ -784,10 +833,78 @@ class TrainStep:
     def _eager_step(self, images, labels, next_images=None):
         self.last_step_captured = False
         loss, info = self._forward_backward(images, labels, accumulate=True, next_images=next_images)
-        scale = self.reducer.finish() if self.reducer is not None else 1.0
-        self.opt.step(grad_scale=scale)
         info["loss"] = loss.detach()
+        if self.accum_steps == 1 and self.clip_grad is None:
+            scale = self.reducer.finish() if self.reducer is not None else 1.0
+            self.opt.step(grad_scale=scale)
+            info["stepped"] = True
+            return info
+        self._pending += 1
+        if self._pending < self.accum_steps:
+            a = self.arena
+            if self._acc is None:
+                self._acc = torch.zeros_like(a.grads)
+            ops.grad_accumulate(self._acc, a.grads, self.opt.desc(), a.n_chunks, 0 if self._pending == 1 else 1)
+            info["stepped"] = False
+            return info
+        self._apply_window(combine=2)
+        info["stepped"] = True
+        if self.clip_grad is not None:
+            info["grad_norm"] = self.last_clip[0].clone()      # last_clip is overwritten by the next clipped step: infos may be kept
         return info
+
+    def flush(self):
+        """Apply a window that is still open (an epoch that ended inside it) with c = the number of micro-steps seen; nothing pending:
+        nothing happens.  -> whether an optimiser step was taken."""
+        if not self._pending:
+            return False
+        cur = torch.cuda.current_stream()
+        side = self._capture_stream if self._step_on_side else None
+        if side is not None:                    # where the calls of this window were issued (_place_beside_process_group)
+            side.wait_stream(cur)
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            self._apply_window(combine=0)
+        if side is not None:
+            cur.wait_stream(side)
+        return True
+
+    def _apply_window(self, combine):
+        """The optimiser step of a window of c = self._pending micro-steps.  combine = 2: the last gradient is still alone in the gradient
+        arena (g = fl(acc + g)); 0: every gradient is in the accumulation arena already (flush: g = acc).  Then exchange, norm, update."""
+        a, c = self.arena, self._pending
+        desc = self.opt.desc()
+        if c > 1:
+            if combine == 2:
+                ops.grad_accumulate(self._acc, a.grads, desc, a.n_chunks, 2)
+            else:
+                ops.grad_accumulate(a.grads, self._acc, desc, a.n_chunks, 0)
+        world = 1
+        if self.reducer is not None:
+            self.reducer.finish()
+            world = self.reducer.world
+        scale = 1.0 / (c * world)
+        if self.clip_grad is None:
+            self.opt.step(grad_scale=scale)
+        else:
+            if self.last_clip is None:
+                self.last_clip = torch.zeros(2, dtype=torch.float32, device=a.grads.device)
+                self._partials = torch.zeros(a.n_chunks, dtype=torch.float32, device=a.grads.device)
+                self._norm_sum = torch.zeros((), dtype=torch.float32, device=a.grads.device)
+            ops.grad_clip_coef(a.grads, desc, a.n_chunks, scale, self.clip_grad, self._partials, self.last_clip)
+            self.opt.step(grad_scale=scale, clip_coef=self.last_clip[1:])
+            self._norm_sum.add_(self.last_clip[0])
+            self._norm_steps += 1
+        self._pending = 0
+
+    def grad_norm_mean(self, reset=True):
+        """Mean pre-clip gradient norm over the clipped optimiser steps since the last reset (one device read), or None."""
+        if not self._norm_steps:
+            return None
+        mean = float(self._norm_sum) / self._norm_steps
+        if reset:
+            self._norm_sum.zero_()
+            self._norm_steps = 0
+        return mean
 
     def _forward_backward(self, images, labels, accumulate, next_images=None):
         self.opt.refresh_transposed_weights()
@@ -865,6 +982,7 @@ class TrainStep:
             with torch.cuda.graph(g, stream=self._capture_stream):
                 loss, info = self._forward_backward(ent["images"], ent["labels"], accumulate=False)
                 info["loss"] = loss.detach()
+                info["stepped"] = True
         finally:
             if self.reducer is not None:
                 self.reducer.paused = False

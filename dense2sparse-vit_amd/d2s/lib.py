@@ -101,6 +101,9 @@ _SIGS = {
     "d2s_adamw_chunk_elems": (I, None),
     "d2s_adamw_step": (I, [P, P, P, P, P, I, F, F, F, I, F, P]),
     "d2s_adamw_step_ema": (I, [P, P, P, P, P, I, F, F, F, I, F, P, P, F]),
+    "d2s_adamw_step_clip": (I, [P, P, P, P, P, I, F, F, F, I, F, P, P, F, P]),
+    "d2s_grad_accumulate": (I, [P, P, P, I, I]),
+    "d2s_grad_clip_coef": (I, [P, P, I, F, F, P, P]),
     "d2s_augment_desc_ints": (I, None),
     "d2s_augment_images": (I, [P, L, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P]),
     "d2s_augment_labels": (I, [P, I, I, F, F, P]),

@@ -1088,6 +1088,34 @@ def adamw_step_ema(params, grads, exp_avg, exp_avg_sq, desc, n_chunks, beta1, be
              float(beta1), float(beta2), float(eps), int(step), float(grad_scale), lib.ptr(chunk_steps), lib.ptr(ema), float(ema_decay))
 
 
+def adamw_step_clip(params, grads, exp_avg, exp_avg_sq, desc, n_chunks, beta1, beta2, eps, step, coef, ema=None, ema_decay=0.0,
+                    grad_scale=1.0, chunk_steps=None):
+    """adamw_step (ema None) or adamw_step_ema with the gradient scale fl(grad_scale * coef[0]); coef: device float (grad_clip_coef)."""
+    assert chunk_steps is None or (chunk_steps.dtype == torch.int32 and chunk_steps.numel() == n_chunks)
+    assert coef.dtype == torch.float32 and coef.numel() >= 1
+    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == params.numel() and ema.data_ptr() != params.data_ptr())
+    lib.call("d2s_adamw_step_clip", lib.ptr(params), lib.ptr(grads), lib.ptr(exp_avg), lib.ptr(exp_avg_sq), lib.ptr(desc), n_chunks,
+             float(beta1), float(beta2), float(eps), int(step), float(grad_scale), lib.ptr(chunk_steps), lib.ptr(ema), float(ema_decay),
+             lib.ptr(coef))
+
+
+def grad_accumulate(acc, g, desc, n_chunks, mode):
+    """Active chunks only.  mode 0: acc = g; 1: acc = fl(acc + g); 2: g = fl(acc + g)."""
+    _f32(acc)
+    _f32(g)
+    chunk = lib.query("d2s_adamw_chunk_elems")
+    assert acc.numel() == g.numel() == n_chunks * chunk and acc.is_contiguous() and g.is_contiguous()
+    lib.call("d2s_grad_accumulate", lib.ptr(acc), lib.ptr(g), lib.ptr(desc), n_chunks, int(mode))
+
+
+def grad_clip_coef(g, desc, n_chunks, scale, max_norm, partials, out):
+    """out[0] = scale * ||g||_2 over the active chunks, out[1] = min(1, max_norm / (out[0] + 1e-6)); partials: n_chunks floats of scratch."""
+    _f32(g)
+    assert g.numel() == n_chunks * lib.query("d2s_adamw_chunk_elems") and g.is_contiguous()
+    assert partials.dtype == torch.float32 and partials.numel() >= n_chunks and out.dtype == torch.float32 and out.numel() >= 2
+    lib.call("d2s_grad_clip_coef", lib.ptr(g), lib.ptr(desc), n_chunks, float(scale), float(max_norm), lib.ptr(partials), lib.ptr(out))
+
+
 # ---- gradient-arena routing: the slice of a flat gradient arena that the gradient of a parameter is written into.  The record lives
 # ON the Parameter object (not in a table keyed by its address), so it dies with the parameter, an arena is freed as soon as its model
 # and TrainStep are, and a recycled device address can never alias a stale entry. ----

@@ -14,6 +14,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --output-dir runs/a --model-ema      (runs/a/last.pt after every epoch, best.pt)
     python dense2sparse-vit_amd/mask_predictor.py ... --output-dir runs/a --resume runs/a/last.pt
     python dense2sparse-vit_amd/mask_predictor.py ... --eval-only --resume runs/a/best.pt
+    python dense2sparse-vit_amd/mask_predictor.py ... --batch-size 64 --accum-steps 8 --clip-grad 1.0     (512 images per optimiser step)
 """
 import os
 import sys
@@ -61,6 +62,10 @@ def check_supported(args):
             bad.append("--diff-topk with --patch-score-threshold (the soft gather applies to the fixed-ratio path only)")
         if getattr(args, "topk_samples", 500) < 1:
             bad.append(f"--topk-samples {args.topk_samples} (at least 1)")
+    if getattr(args, "accum_steps", 1) < 1:
+        bad.append(f"--accum-steps {args.accum_steps} (at least 1)")
+    if getattr(args, "clip_grad", None) is not None and not args.clip_grad > 0:
+        bad.append(f"--clip-grad {args.clip_grad} (a norm > 0)")
     if args.use_dp:
         bad.append("--use-dp (one process per GPU only: --use-ddp under torch.distributed.run)")
     folder = getattr(args, "data_source", "synthetic") == "folder"
@@ -194,7 +199,7 @@ def main(argv=None):
         optim = torch.optim.AdamW(utils.get_param_groups(student, args), lr=args.lr, weight_decay=args.weight_decay)   # :213,229-230
     else:
         optim = TrainStep(student, teacher, args, lr=args.lr, min_lr=args.min_lr, weight_decay=args.weight_decay, epochs=args.epochs,
-                          warmup_steps=args.warmup_steps, distributed=distributed)
+                          warmup_steps=args.warmup_steps, distributed=distributed, accum_steps=args.accum_steps, clip_grad=args.clip_grad)
         if distributed:
             dist.broadcast(optim.arena.params, src=0)
     start_epoch, best_acc = 0, 0.0
@@ -237,6 +242,10 @@ def main(argv=None):
             print("eval only: " + ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
         return metrics["val_acc"]
     print(f"Start training for {args.epochs} epochs, with batch size of {args.batch_size}")
+    if args.accum_steps > 1 or args.clip_grad is not None:
+        print(f"Optimiser step: {args.accum_steps} batch(es) x {args.batch_size} images x {world} rank(s) = "
+              f"{args.accum_steps * args.batch_size * world} images"
+              + (f", gradient clipped to norm {args.clip_grad}" if args.clip_grad is not None else ""))
     since = time.time()
     first_save = True
     for epoch in range(start_epoch, args.epochs):

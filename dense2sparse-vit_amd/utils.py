@@ -165,6 +165,12 @@ def parse_args(argv=None):
                    help='with --topk-selection: train through the perturbed top-k soft gather (sigma decays from --initial-sigma to 0 over '
                         'the epochs); evaluation and the trained model keep the hard top-k')
     p.add_argument('--topk-samples', type=int, default=500, metavar='N', help="noise samples of --diff-topk (the reference's PerturbedTopK default)")
+    p.add_argument('--accum-steps', type=int, default=1, metavar='N',
+                   help='one optimiser step per N batches (gradient = mean over the N; effective batch = N x --batch-size x ranks), '
+                        'accumulated inside the fused arena step')
+    p.add_argument('--clip-grad', type=float, default=None, metavar='NORM',
+                   help="clip the gradient to this global L2 norm before the update (DeiT's flag; default: no clipping); the norm never "
+                        "leaves the device, its epoch mean is reported as train_grad_norm")
     return p.parse_args(argv)
 
 

@@ -303,6 +303,23 @@ int d2s_adamw_step(float* params, const float* grads, float* exp_avg, float* exp
 int d2s_adamw_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* chunk_desc, int n_chunks,
                        float beta1, float beta2, float eps, int step, float grad_scale, int* chunk_steps, float* ema, float ema_decay,
                        d2s_stream_t stream);
+/* Either of the two with the gradient scale taken partly from device memory: every element sees fl(grad * fl(grad_scale * coef_dev[0])),
+ * coef_dev being the clipping coefficient d2s_grad_clip_coef wrote (no host round trip).  ema == NULL: the update of d2s_adamw_step
+ * (ema_decay ignored); otherwise that of d2s_adamw_step_ema. */
+int d2s_adamw_step_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* chunk_desc, int n_chunks,
+                        float beta1, float beta2, float eps, int step, float grad_scale, int* chunk_steps, float* ema, float ema_decay,
+                        const float* coef_dev, d2s_stream_t stream);
+
+/* ---- gradient accumulation and global-norm clipping over the gradient arena (timm / DeiT --clip-grad; no line of the reference) ------
+ * acc and g: arenas of n_chunks * d2s_adamw_chunk_elems() floats; chunk_desc as for d2s_adamw_step.  Chunks that are not active are
+ * neither read nor written.  mode 0: acc = g; 1: acc = fl(acc + g); 2: g = fl(acc + g) - the sum of a window of gradients in arrival
+ * order lands in the gradient arena, where the exchange and the optimiser read it. */
+int d2s_grad_accumulate(float* acc, float* g, const void* chunk_desc, int n_chunks, int mode, d2s_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_ (L2) over the active chunks of g, for the gradient scale * g: out[0] = total_norm = scale * sqrt(sum g^2),
+ * out[1] = coef = min(1, max_norm / (total_norm + 1e-6)), both left in device memory.  partials: n_chunks floats of scratch (per-chunk
+ * sums of squares, fp32 tree of depth 10; their fold is ordered and in double).  Deterministic: no atomics.  scale, max_norm > 0. */
+int d2s_grad_clip_coef(const float* g, const void* chunk_desc, int n_chunks, float scale, float max_norm, float* partials, float* out,
+                       d2s_stream_t stream);
 
 /* ---- input pipeline: crop + resize (bit-exact with Pillow), flip, Normalize, RandomErasing, Mixup / CutMix (build_data_sets.py:8-34,
  * train.py:29-31; d2s/data.py packs the batch) ------------------------------------------------------------------------------------ */

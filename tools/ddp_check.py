@@ -14,6 +14,11 @@ require a gradient although the backbone is frozen: the grad_ready hooks fire ag
 integer sample counts: the comparison presupposes that no perturbed value sits within fp32 rounding of its selection boundary, so the
 smallest gap between the k-th and (k + 1)-th largest perturbed value of the single-process run is printed and must be at least 2e-5 (the
 condition of tests/golden/difftopk_micro.npz); a run that misses it exits with code 3 - a property of the noise seed, not a mismatch.
+
+D2S_DDP_ACCUM=A (default 1) makes every optimiser step a window of A micro-batches (TrainStep accum_steps=A): each rank is given its
+slice of every micro-batch, the single process the whole micro-batches in the same order; the comparison is made after the call that
+steps, on the combined gradient.  D2S_DDP_CLIP=M adds clip_grad=M on both sides, prints the two pre-clip norms
+and requires them to agree to 1e-4 relative, the gradient criterion.
 """
 import os
 import sys
@@ -33,6 +38,8 @@ from tests import cases
 
 DIFF_TOPK = os.environ.get("D2S_DDP_DIFF_TOPK") == "1"
 NOISE_SAMPLES, NOISE_SEED, MARGIN_MIN = 16, 41, 2e-5
+ACCUM = int(os.environ.get("D2S_DDP_ACCUM", "1"))
+CLIP = float(os.environ["D2S_DDP_CLIP"]) if os.environ.get("D2S_DDP_CLIP") else None
 
 
 def stage_noise(case, B):
@@ -90,16 +97,17 @@ def main():
     case = dict(cases.MODEL_CASES["micro2"])
     per = 2
     B = per * world
-    x = torch.from_numpy(synth.images(B, 3, case["cfg"]["img_size"], seed=77))
-    y = torch.from_numpy(synth.labels(B, case["cfg"]["num_classes"], seed=77))
+    xs = [torch.from_numpy(synth.images(B, 3, case["cfg"]["img_size"], seed=77 + 100 * i)) for i in range(ACCUM)]
+    ys = [torch.from_numpy(synth.labels(B, case["cfg"]["num_classes"], seed=77 + 100 * i)) for i in range(ACCUM)]
+    window = dict(accum_steps=ACCUM, clip_grad=CLIP) if (ACCUM > 1 or CLIP is not None) else {}
     # tiny bucket so that several all-reduces are launched from inside backward (exercises the hook path); warmup_steps=1: epoch 0
     # trains the predictors only (live gradient set = their slices, exchanged by finish()), epoch 1 everything (hooks + buckets)
     s, t, args = build(case, dev)
-    ts = TrainStep(s, t, args, distributed=True, bucket_mb=0.25, warmup_steps=1)
+    ts = TrainStep(s, t, args, distributed=True, bucket_mb=0.25, warmup_steps=1, **window)
     ref = None
     if rank == 0:
         s1, t1, args1 = build(case, dev)
-        ref = TrainStep(s1, t1, args1, distributed=False, warmup_steps=1)
+        ref = TrainStep(s1, t1, args1, distributed=False, warmup_steps=1, **window)
     noises = stage_noise(case, B) if DIFF_TOPK else None
     if DIFF_TOPK:
         s.topk_noise = [nz[rank * per:(rank + 1) * per] for nz in noises]
@@ -111,13 +119,16 @@ def main():
         live = list(ts.reducer.live)
         if epoch == 0:
             assert ts.reducer.live_elems() < ts.arena.total // 2, "warm-up epoch must only exchange the predictor slices"
-        info = ts(x[rank * per:(rank + 1) * per].to(dev), y[rank * per:(rank + 1) * per].to(dev))
+        for x, y in zip(xs, ys):
+            info = ts(x[rank * per:(rank + 1) * per].to(dev), y[rank * per:(rank + 1) * per].to(dev))
+        assert info.get("stepped", True), "the last call of the window must have stepped"
         torch.cuda.synchronize()
         grads = ts.arena.grads.clone() / world
         params = ts.arena.params.clone()
         if rank == 0:
             ref.set_epoch(epoch)
-            ref(x.to(dev), y.to(dev))
+            for x, y in zip(xs, ys):
+                ref(x.to(dev), y.to(dev))
             torch.cuda.synchronize()
             sel = torch.cat([torch.arange(a, b) for a, b in live]).to(dev)       # the gradients the optimiser reads
             gd = float((grads[sel] - ref.arena.grads[sel]).norm() / ref.arena.grads[sel].norm())
@@ -125,6 +136,14 @@ def main():
             print(f"[ddp_check] world={world} backend={'nccl' if own_gpu else 'gloo'} epoch {epoch} live {len(sel)}/{ts.arena.total} "
                   f"rel grad diff {gd:.3e}  max param diff {pd:.3e}")
             ok = ok and gd < 1e-4 and pd < 2 * 2 * 5e-4 * 1.01
+            if CLIP is not None:
+                # the norm is taken from the exchanged sum: one taken before the exchange, or scaled by the wrong 1 / (c * world),
+                # differs in the first digit, the summation orders of the two sides differ by rounding only
+                nd = abs(float(ts.last_clip[0]) - float(ref.last_clip[0])) / float(ref.last_clip[0])
+                ok = ok and nd < 1e-4
+                print(f"[ddp_check] rel pre-clip norm diff {nd:.3e}")
+                print(f"[ddp_check] accum {ACCUM} clip {CLIP}: pre-clip norm {float(ts.last_clip[0]):.6e} (coef {float(ts.last_clip[1]):.6f}), "
+                      f"single process {float(ref.last_clip[0]):.6e} (coef {float(ref.last_clip[1]):.6f})")
             if DIFF_TOPK:
                 margin = selection_margin(s1, noises)
                 print(f"[ddp_check] diff_topk epoch {epoch}: selection margin of the single-process run {margin:.3e} (needs >= {MARGIN_MIN:.0e})")
