@@ -155,9 +155,9 @@ __device__ float keyed_normal(unsigned long long seed, int sample, int c, int y,
     return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
 }
 
-// One sample's value at output (y, x) for the 3 channels: vertical resample of the scratch, flip, ToTensor + Normalize, erasing.
-__device__ __forceinline__ void sample_pixel(const int* __restrict__ d, const uint8_t* __restrict__ inter, const int* kv, int kmax,
-                                             int ymin, int cnt, int sample, int S, int y, int x, unsigned long long seed, float v[3]) {
+// One sample's uint8 pixel at output (y, x): vertical resample of the scratch, flip.
+__device__ __forceinline__ void vresample_pixel(const int* __restrict__ d, const uint8_t* __restrict__ inter, const int* kv, int ymin, int cnt,
+                                                int S, int x, int u[3]) {
     const int xc = d[A_FLIP] ? S - 1 - x : x;
     const int yn = d[A_YN];
     const uint8_t* base = inter + ((long)d[A_ROWOFF] * S + xc) * 3;
@@ -172,8 +172,15 @@ __device__ __forceinline__ void sample_pixel(const int* __restrict__ d, const ui
         a1 += (int)q[1] * w;
         a2 += (int)q[2] * w;
     }
+    u[0] = clip8(a0);
+    u[1] = clip8(a1);
+    u[2] = clip8(a2);
+}
+
+// ToTensor + Normalize and erasing of one sample's uint8 pixel at output (y, x).
+__device__ __forceinline__ void finish_pixel(const int* __restrict__ d, const int u[3], int sample, int y, int x, unsigned long long seed,
+                                             float v[3]) {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    const int u[3] = {clip8(a0), clip8(a1), clip8(a2)};
 #pragma unroll
     for (int c = 0; c < 3; ++c) v[c] = ((float)u[c] / 255.f - mean[c]) / stdv[c];
     const int mode = d[A_EMODE], n = d[A_ECOUNT];
@@ -189,6 +196,14 @@ __device__ __forceinline__ void sample_pixel(const int* __restrict__ d, const ui
                 v[c] = mode == 1 ? 0.f : (mode == 2 ? keyed_normal(seed, sample, c, 0xFFFF - hit, 0xFFFF) : keyed_normal(seed, sample, c, y, x));
         }
     }
+}
+
+// One sample's value at output (y, x) for the 3 channels: the two steps above, fused.
+__device__ __forceinline__ void sample_pixel(const int* __restrict__ d, const uint8_t* __restrict__ inter, const int* kv, int kmax,
+                                             int ymin, int cnt, int sample, int S, int y, int x, unsigned long long seed, float v[3]) {
+    int u[3];
+    vresample_pixel(d, inter, kv, ymin, cnt, S, x, u);
+    finish_pixel(d, u, sample, y, x, seed, v);
 }
 
 __device__ __forceinline__ void mix_out(const int* __restrict__ d, const float vi[3], const float vj[3], int y, int x, float o[3]) {
@@ -253,6 +268,69 @@ __global__ __launch_bounds__(256) void augment_vpass_kernel(const uint8_t* __res
     }
 }
 
+// ---- the same in two passes around the op kernel of csrc/randaug.hip (RandAugment / ColorJitter work on the uint8 image) ------------------
+// pass 2a: vertical resample + flip into uint8 [B, S, S, 3].  grid (ceil(S / VROWS), B); LDS: VROWS * kmax coefficients, ymin, counts.
+__global__ __launch_bounds__(256) void augment_vpass_u8_kernel(const uint8_t* __restrict__ inter, const int* __restrict__ desc, int S, int kmax,
+                                                               uint8_t* __restrict__ img) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int i = blockIdx.y;
+    const int y0 = blockIdx.x * VROWS;
+    const int ny = min(VROWS, S - y0);
+    const int* d = desc + (long)i * DESC;
+    int* kk = reinterpret_cast<int*>(lds);                    // [VROWS][kmax]
+    int* kmin = kk + VROWS * kmax;
+    int* kcnt = kmin + VROWS;
+    for (int r = threadIdx.x; r < ny; r += blockDim.x) {
+        int cnt;
+        kmin[r] = pillow_coeffs(d[A_FILTER], d[A_CH], d[A_GH], d[A_WY] + y0 + r, kk + r * kmax, cnt);
+        kcnt[r] = cnt;
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < ny * S; p += blockDim.x) {
+        const int r = p / S, x = p - r * S;
+        int u[3];
+        vresample_pixel(d, inter, kk + r * kmax, kmin[r], kcnt[r], S, x, u);
+        uint8_t* o = img + (((long)i * S + y0 + r) * S + x) * 3;
+        o[0] = (uint8_t)u[0];
+        o[1] = (uint8_t)u[1];
+        o[2] = (uint8_t)u[2];
+    }
+}
+
+// pass 2b: ToTensor + Normalize, erasing and the mix for the pair (i, B-1-i) from uint8 [B, S, S, 3].  grid (ceil(S / VROWS), ceil(B / 2)).
+__global__ __launch_bounds__(256) void augment_finish_kernel(const uint8_t* __restrict__ img, const int* __restrict__ desc, int B, int S,
+                                                             unsigned long long seed, float* __restrict__ out) {
+    const int i = blockIdx.y, j = B - 1 - i;
+    const int y0 = blockIdx.x * VROWS;
+    const int ny = min(VROWS, S - y0);
+    const int* di = desc + (long)i * DESC;
+    const int* dj = desc + (long)j * DESC;
+    const long plane = (long)S * S;
+    for (int p = threadIdx.x; p < ny * S; p += blockDim.x) {
+        const int r = p / S, x = p - r * S, y = y0 + r;
+        const long pos = (long)y * S + x;
+        const uint8_t* qi = img + ((long)i * plane + pos) * 3;
+        const uint8_t* qj = img + ((long)j * plane + pos) * 3;
+        const int ui[3] = {qi[0], qi[1], qi[2]}, uj[3] = {qj[0], qj[1], qj[2]};
+        float vi[3], vj[3], o[3];
+        finish_pixel(di, ui, i, y, x, seed, vi);
+        if (j != i) {
+            finish_pixel(dj, uj, j, y, x, seed, vj);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vj[c] = vi[c];
+        }
+        mix_out(di, vi, vj, y, x, o);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[((long)i * 3 + c) * plane + pos] = o[c];
+        if (j != i) {
+            mix_out(dj, vj, vi, y, x, o);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[((long)j * 3 + c) * plane + pos] = o[c];
+        }
+    }
+}
+
 // ---- soft labels (timm mixup_target): label[i] = one_hot(t_i) * laba_i + one_hot(t_{B-1-i}) * labb_i, one_hot in {off, on} -----------
 __global__ __launch_bounds__(256) void augment_labels_kernel(const int* __restrict__ desc, int B, int C, float on, float off,
                                                              float* __restrict__ out) {
@@ -269,6 +347,9 @@ __global__ __launch_bounds__(256) void augment_labels_kernel(const int* __restri
 }  // namespace
 
 extern "C" {
+
+size_t d2s_randaug_scratch_bytes(int B, int S);                                  // csrc/randaug.hip
+int d2s_randaug_apply(const uint8_t* in, const int* table, int B, int S, uint8_t* scratch, uint8_t* out, hipStream_t stream);
 
 int d2s_augment_desc_ints(void) { return DESC; }
 
@@ -298,6 +379,37 @@ int d2s_augment_images(const uint8_t* pix, long pix_bytes, const int* desc, int 
     if (rc) return rc;
     hipLaunchKernelGGL(augment_vpass_kernel, dim3((unsigned)((S + VROWS - 1) / VROWS), (unsigned)((B + 1) / 2)), dim3(256), vlds, stream,
                        inter, desc, B, S, kmax_v, seed, out);
+    return d2s_check_launch();
+}
+
+size_t d2s_augment_ops_scratch_bytes(int B, int S) { return 3 * d2s_randaug_scratch_bytes(B, S); }
+
+/* d2s_augment_images with an op table (csrc/randaug.hip) applied to the uint8 image between the flip and ToTensor: the fused second pass
+ * becomes vertical pass + flip -> uint8, the op kernel, Normalize + erase + mix.  images: d2s_augment_ops_scratch_bytes(B, S) bytes of
+ * scratch (three uint8 [B, S, S, 3] images), 16-byte aligned.  With an empty list for every image the output equals d2s_augment_images'. */
+int d2s_augment_images_ops(const uint8_t* pix, long pix_bytes, const int* desc, const int* table, int B, int S, int max_rows, int kmax_h,
+                           int kmax_v, int rowbytes, unsigned long long seed, uint8_t* inter, uint8_t* images, float* out,
+                           hipStream_t stream) {
+    if (!pix || !desc || !table || !inter || !images || !out || B <= 0 || S <= 0 || S > 4096 || max_rows <= 0 || kmax_h <= 0 || kmax_v <= 0 ||
+        rowbytes < 32 || (rowbytes & 15) || (pix_bytes & 15) || pix_bytes <= 0)
+        return D2S_ERR_ARG;
+    const int rows = hpass_rows(S, kmax_h, rowbytes);
+    const size_t vlds = (size_t)VROWS * (kmax_v + 2) * 4;
+    if (rows == 0 || vlds > (size_t)LDS_MAX) return D2S_ERR_ARG;
+    const size_t one = d2s_randaug_scratch_bytes(B, S);
+    const size_t hlds = hpass_lds(S, kmax_h, rows, rowbytes);
+    hipLaunchKernelGGL(augment_hpass_kernel, dim3((unsigned)((max_rows + rows - 1) / rows), (unsigned)B), dim3(256), hlds, stream, pix,
+                       pix_bytes >> 4, desc, S, kmax_h, rows, rowbytes, inter);
+    int rc = d2s_check_launch();
+    if (rc) return rc;
+    const unsigned bands = (unsigned)((S + VROWS - 1) / VROWS);
+    hipLaunchKernelGGL(augment_vpass_u8_kernel, dim3(bands, (unsigned)B), dim3(256), vlds, stream, inter, desc, S, kmax_v, images);
+    rc = d2s_check_launch();
+    if (rc) return rc;
+    rc = d2s_randaug_apply(images, table, B, S, images + one, images + 2 * one, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(augment_finish_kernel, dim3(bands, (unsigned)((B + 1) / 2)), dim3(256), 0, stream, images + 2 * one, desc, B, S, seed,
+                       out);
     return d2s_check_launch();
 }
 

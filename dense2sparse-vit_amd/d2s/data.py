@@ -5,7 +5,8 @@ per-pixel work on the GPU (csrc/augment.hip) and only JPEG decode on the host.
                  list matched case-insensitively, decoded with Pillow open(...).convert('RGB') in DataLoader workers
     split        mask_predictor.py:236-240: np.random.seed(42); shuffle(range(N)); the first 20 % is the validation set
     train        timm create_transform(is_training=True): RandomResizedCropAndInterpolation(224, scale (0.08, 1), ratio (3/4, 4/3)),
-                 RandomHorizontalFlip(0.5), ToTensor, Normalize(ImageNet mean / std), RandomErasing(reprob, remode, recount)
+                 RandomHorizontalFlip(0.5), RandAugment (--aa rand-...) or else ColorJitter (--color-jitter), ToTensor,
+                 Normalize(ImageNet mean / std), RandomErasing(reprob, remode, recount)
     val          Resize(256) (bilinear), CenterCrop(224), ToTensor, Normalize
     mix          timm Mixup (train.py:29-31) with its soft labels (mixup_target)
 
@@ -35,6 +36,14 @@ BILINEAR, BICUBIC = 0, 1
 FILTERS = {"bilinear": BILINEAR, "bicubic": BICUBIC}
 ERASE_MODES = {"const": 1, "rand": 2, "pixel": 3}      # timm: anything that is not 'rand' or 'pixel' erases with zeros
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+# RandAugment / ColorJitter op table (csrc/randaug.hip): [B, RA_MAX_OPS, RA_OP_INTS] int32, an image's list ends at the first code 0
+RA_MAX_OPS, RA_OP_INTS = 8, 16
+(OP_NONE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT, OP_POSTERIZE, OP_SOLARIZE, OP_SOLARIZE_ADD, OP_AFFINE, OP_COLOR, OP_CONTRAST,
+ OP_BRIGHTNESS, OP_SHARPNESS) = range(12)
+E_CODE, E_RESAMPLE, E_IARG, E_FARG, E_MATRIX = range(5)       # E_FARG: a float32's bits; E_MATRIX: six float64 (ints 4..15)
+# timm's _RAND_INCREASING_TRANSFORMS, in its order
+RAND_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "PosterizeIncreasing", "SolarizeIncreasing", "SolarizeAdd", "ColorIncreasing",
+            "ContrastIncreasing", "BrightnessIncreasing", "SharpnessIncreasing", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
 
 
 # ---- listing, split, shards -----------------------------------------------------------------------------------------------------------
@@ -148,26 +157,169 @@ def erase_params(rng, prob, max_count, S, min_area=0.02, max_area=1 / 3, min_asp
     return boxes
 
 
+# ---- RandAugment / ColorJitter (timm 0.4.12's auto_augment.py and torchvision's ColorJitter on PIL images, restated) ---------------------
+def parse_auto_augment(text):
+    """timm's rand_augment_transform config string `rand-mM[-mstdS][-nN][-pP][-mmaxX]-inc1` -> dict(m, mstd, n, p, mmax), or None when
+    off ('', 'none', None).  Only the "increasing" op set with uniform choice is built: another policy family, inc0 (or no inc key) and
+    the weighted choice `w` raise ValueError."""
+    if text is None or text.strip().lower() in ("", "none"):
+        return None
+    parts = text.strip().lower().split("-")
+    if parts[0] != "rand":
+        raise ValueError(f"auto-augment policy '{text}': only RandAugment ('rand-m9-mstd0.5-inc1') is built")
+    cfg, inc = dict(m=10.0, mstd=0.0, n=2, p=0.5, mmax=10.0), None
+    for part in parts[1:]:
+        for key in ("mstd", "mmax", "inc", "m", "n", "p", "w"):            # longer keys first
+            if part.startswith(key):
+                val = part[len(key):]
+                break
+        else:
+            raise ValueError(f"auto-augment policy '{text}': unknown key in '{part}'")
+        try:
+            num = float(val)
+        except ValueError:
+            raise ValueError(f"auto-augment policy '{text}': '{part}' has no number") from None
+        if key == "w":
+            raise ValueError(f"auto-augment policy '{text}': weighted op choice ('w') is not built")
+        if key == "inc":
+            inc = bool(int(num))
+        elif key == "n":
+            cfg["n"] = int(num)
+        else:
+            cfg[key] = num
+    if not inc:
+        raise ValueError(f"auto-augment policy '{text}': only the increasing op set ('inc1') is built")
+    if not 0 <= cfg["n"] <= RA_MAX_OPS:
+        raise ValueError(f"auto-augment policy '{text}': n outside 0..{RA_MAX_OPS} (ops per image in the op table)")
+    if not (0 <= cfg["p"] <= 1 and cfg["m"] >= 0 and cfg["mstd"] >= 0 and cfg["mmax"] >= 0):
+        raise ValueError(f"auto-augment policy '{text}': p outside [0, 1] or a negative magnitude")
+    return cfg
+
+
+def rotate_matrix(angle, W, H):
+    """PIL/Image.py::rotate (no expand, default centre): the six AFFINE coefficients, in double as the Python computes them; None when
+    Pillow copies the image (angle % 360 == 0).  RandAugment's angles stay within +-30 degrees, so the transpose paths never apply."""
+    angle = angle % 360.0
+    if angle == 0:
+        return None
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = W / 2, H / 2
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def _op(code, resample=0, iarg=0, farg=0.0, matrix=None):
+    """One op of the table: (code, resample, int argument, float argument, six doubles)."""
+    return (code, resample, int(iarg), float(np.float32(farg)), tuple(float(v) for v in matrix) if matrix is not None else (0.0,) * 6)
+
+
+def randaug_op(name, t, neg, S, resample):
+    """timm's level_fn of the increasing op `name` at t = level / 10 with the coin flip `neg` -> the table op, or None for an identity."""
+    sgn = -1.0 if neg else 1.0
+    if name == "AutoContrast":
+        return _op(OP_AUTOCONTRAST)
+    if name == "Equalize":
+        return _op(OP_EQUALIZE)
+    if name == "Invert":
+        return _op(OP_INVERT)
+    if name == "Rotate":
+        m = rotate_matrix(sgn * (30.0 * t), S, S)
+        return None if m is None else _op(OP_AFFINE, resample, matrix=m)
+    if name == "ShearX":
+        return _op(OP_AFFINE, resample, matrix=(1, sgn * (0.3 * t), 0, 0, 1, 0))
+    if name == "ShearY":
+        return _op(OP_AFFINE, resample, matrix=(1, 0, 0, sgn * (0.3 * t), 1, 0))
+    if name == "TranslateXRel":
+        return _op(OP_AFFINE, resample, matrix=(1, 0, sgn * (0.45 * t) * S, 0, 1, 0))
+    if name == "TranslateYRel":
+        return _op(OP_AFFINE, resample, matrix=(1, 0, 0, 0, 1, sgn * (0.45 * t) * S))
+    if name == "PosterizeIncreasing":
+        bits = 4 - int(4 * t)
+        return None if bits >= 8 else _op(OP_POSTERIZE, iarg=bits)
+    if name == "SolarizeIncreasing":
+        return _op(OP_SOLARIZE, iarg=256 - int(256 * t))
+    if name == "SolarizeAdd":
+        return _op(OP_SOLARIZE_ADD, iarg=min(128, int(110 * t)))
+    code = {"ColorIncreasing": OP_COLOR, "ContrastIncreasing": OP_CONTRAST, "BrightnessIncreasing": OP_BRIGHTNESS,
+            "SharpnessIncreasing": OP_SHARPNESS}[name]
+    return _op(code, farg=max(0.1, 1.0 + sgn * (0.9 * t)))
+
+
+def randaug_ops(rng, cfg, S, interpolation):
+    """One image's RandAugment: n ops chosen uniformly with replacement; each is the identity with probability 1 - p, otherwise drawn at
+    level clip(gauss(m, mstd), 0, mmax) with its coin flip, and with BILINEAR or BICUBIC drawn per application when the run's
+    interpolation is 'random'."""
+    names = [RAND_OPS[int(k)] for k in rng.integers(0, len(RAND_OPS), cfg["n"])]
+    ops = []
+    for name in names:
+        if not rng.random() < cfg["p"]:
+            continue
+        m = float(rng.normal(cfg["m"], cfg["mstd"])) if cfg["mstd"] > 0 else float(cfg["m"])
+        m = min(max(m, 0.0), float(cfg["mmax"]))
+        neg = bool(rng.random() < 0.5)
+        resample = FILTERS.get(interpolation)
+        if resample is None:
+            resample = int(rng.integers(0, 2))
+        op = randaug_op(name, m / 10.0, neg, S, resample)
+        if op is not None:
+            ops.append(op)
+    return ops
+
+
+def jitter_ops(rng, j):
+    """ColorJitter(j, j, j): brightness, contrast and saturation factors uniform in [max(0, 1 - j), 1 + j], applied in a random order
+    (ImageEnhance.Brightness / Contrast / Color).  No hue."""
+    lo, hi = max(0.0, 1.0 - j), 1.0 + j
+    f = [float(rng.uniform(lo, hi)) for _ in range(3)]
+    codes = (OP_BRIGHTNESS, OP_CONTRAST, OP_COLOR)
+    return [_op(codes[int(k)], farg=f[int(k)]) for k in rng.permutation(3)]
+
+
+def pack_ops(op_lists):
+    """Per-image op lists -> the int32 table [B, RA_MAX_OPS, RA_OP_INTS] of csrc/randaug.hip."""
+    table = np.zeros((len(op_lists), RA_MAX_OPS, RA_OP_INTS), np.int32)
+    for b, ops in enumerate(op_lists):
+        if len(ops) > RA_MAX_OPS:
+            raise ValueError(f"at most {RA_MAX_OPS} ops per image")
+        for k, (code, resample, iarg, farg, matrix) in enumerate(ops):
+            assert OP_NONE < code <= OP_SHARPNESS and resample in (BILINEAR, BICUBIC) and 0 <= iarg <= 256, (code, resample, iarg)
+            table[b, k, :E_MATRIX] = (code, resample, iarg, int(np.float32(farg).view(np.int32)))
+            table[b, k, E_MATRIX:E_MATRIX + 12] = np.asarray(matrix, np.float64).view(np.int32)
+    return table
+
+
 @dataclass
 class AugmentOptions:
-    """The training transform's flags (utils.parse_args: --train-interpolation, --reprob, --remode, --recount)."""
+    """The training transform's flags (utils.parse_args: --train-interpolation, --reprob, --remode, --recount, --aa, --color-jitter)."""
     interpolation: str = "bicubic"          # bilinear | bicubic | random (one of the two per image)
     reprob: float = 0.25
     remode: str = "pixel"
     recount: int = 1
     hflip: float = 0.5
+    auto_augment: str = ""                  # '' / 'none': off; else timm's 'rand-m9-mstd0.5-inc1' form (parse_auto_augment)
+    color_jitter: float = 0.0               # used only when auto_augment is off, as in timm's transforms_imagenet_train
 
 
 def train_params(rng, H, W, opts, S):
-    """One image's RandomResizedCropAndInterpolation + RandomHorizontalFlip + RandomErasing parameters."""
+    """One image's RandomResizedCropAndInterpolation + RandomHorizontalFlip + RandomErasing parameters and, when the options ask for
+    them, its RandAugment or ColorJitter ops (drawn last: with both off the draws are those of the transform without them)."""
     i, j, h, w = rrc_params(rng, H, W)
     interp = opts.interpolation
     if interp == "random":
         interp = ("bilinear", "bicubic")[int(rng.integers(0, 2))]
     flip = bool(rng.random() < opts.hflip)
     boxes = erase_params(rng, opts.reprob, opts.recount, S)
-    return dict(crop=(i, j, h, w), grid=(S, S), win=(0, 0), filt=FILTERS[interp], flip=flip,
-                emode=ERASE_MODES.get(opts.remode.lower(), 1) if boxes else 0, boxes=boxes)
+    p = dict(crop=(i, j, h, w), grid=(S, S), win=(0, 0), filt=FILTERS[interp], flip=flip,
+             emode=ERASE_MODES.get(opts.remode.lower(), 1) if boxes else 0, boxes=boxes)
+    ra = parse_auto_augment(opts.auto_augment)
+    if ra is not None:
+        p["ops"] = randaug_ops(rng, ra, S, opts.interpolation)
+    elif opts.color_jitter > 0:
+        p["ops"] = jitter_ops(rng, opts.color_jitter)
+    return p
 
 
 def val_params(H, W, S=224, resize=256):
@@ -327,7 +479,8 @@ def resample_taps(in_size, out_size, filt):
 # ---- packing ------------------------------------------------------------------------------------------------------------------------------
 def pack_batch(images, labels, params, S=224, mix=None, seed=0):
     """images: uint8 HWC RGB arrays; params: per-image dicts of train_params / val_params; mix: None or mix_params' tuple.
-    -> dict(pix=uint8 [n * 16], desc=int32 [B, DESC_INTS], labels=int64 [B], meta=dict of the host maxima and the erase seed, mixed=bool)."""
+    -> dict(pix=uint8 [n * 16], desc=int32 [B, DESC_INTS], labels=int64 [B], meta=dict of the host maxima and the erase seed, mixed=bool)
+    and, when any image's params carry an "ops" list (RandAugment / ColorJitter), ops=int32 [B, RA_MAX_OPS, RA_OP_INTS]."""
     B = len(images)
     desc = np.zeros((B, DESC_INTS), np.int32)
     sizes = [int(im.size) for im in images]
@@ -372,8 +525,11 @@ def pack_batch(images, labels, params, S=224, mix=None, seed=0):
     else:
         desc[:, A_PIXA], desc[:, A_LABA] = fl(np.full(B, one)), fl(np.full(B, one))
     meta = dict(total_rows=row_off, max_rows=max_rows, kmax_h=kmax_h, kmax_v=kmax_v, rowbytes=rowbytes, seed=int(seed), size=S)
-    return dict(pix=torch.from_numpy(pix), desc=torch.from_numpy(desc), labels=torch.as_tensor(np.asarray(labels, np.int64)),
-                meta=meta, mixed=mix is not None)
+    hb = dict(pix=torch.from_numpy(pix), desc=torch.from_numpy(desc), labels=torch.as_tensor(np.asarray(labels, np.int64)),
+              meta=meta, mixed=mix is not None)
+    if any("ops" in p for p in params):
+        hb["ops"] = torch.from_numpy(pack_ops([p.get("ops", []) for p in params]))
+    return hb
 
 
 def decode(path):
@@ -457,7 +613,7 @@ class FolderLoader:
 
     def _upload(self, hb, stream=None):
         with torch.cuda.stream(stream):          # None: the current stream
-            dev = {k: hb[k].to(self.device, non_blocking=True) for k in ("pix", "desc", "labels")}
+            dev = {k: hb[k].to(self.device, non_blocking=True) for k in ("pix", "desc", "labels", "ops") if k in hb}
             ev = torch.cuda.Event()
             ev.record()
         return dev, ev, hb
@@ -469,7 +625,7 @@ class FolderLoader:
         main.wait_event(ev)
         for t in dev.values():
             t.record_stream(main)
-        images = ops.augment_images(dev["pix"], dev["desc"], hb["meta"], self.S)
+        images = ops.augment_images(dev["pix"], dev["desc"], hb["meta"], self.S, dev.get("ops"))
         labels = ops.augment_labels(dev["desc"], self.mix.num_classes, self.mix.smoothing) if hb["mixed"] else dev["labels"]
         return images, labels
 

@@ -107,6 +107,12 @@ _SIGS = {
     "d2s_augment_desc_ints": (I, None),
     "d2s_augment_images": (I, [P, L, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P]),
     "d2s_augment_labels": (I, [P, I, I, F, F, P]),
+    "d2s_randaug_max_ops": (I, None),
+    "d2s_randaug_op_ints": (I, None),
+    "d2s_randaug_scratch_bytes": (Z, [I, I]),
+    "d2s_randaug_apply": (I, [P, P, I, I, P, P]),
+    "d2s_augment_ops_scratch_bytes": (Z, [I, I]),
+    "d2s_augment_images_ops": (I, [P, L, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P, P]),
 }
 
 _lib = None

@@ -1191,12 +1191,21 @@ class gemm_mode:
 
 # ---- input pipeline (csrc/augment.hip; d2s/data.py packs the batch) ------------------------------------------------------------------
 AUG_DESC_INTS = 64        # == d2s_augment_desc_ints(), checked by augment_images
+RA_MAX_OPS, RA_OP_INTS = 8, 16      # == d2s_randaug_max_ops(), d2s_randaug_op_ints(): the op table is [B, RA_MAX_OPS, RA_OP_INTS] int32
 
 
-def augment_images(pix, desc, meta, size):
+def _check_op_table(table, B):
+    if lib.query("d2s_randaug_max_ops") != RA_MAX_OPS or lib.query("d2s_randaug_op_ints") != RA_OP_INTS:
+        raise lib.D2SError("op table layout of the library and of d2s.ops disagree")
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.shape == (B, RA_MAX_OPS, RA_OP_INTS), table.shape
+
+
+def augment_images(pix, desc, meta, size, op_table=None):
     """Crop + resize (Pillow-exact) + flip + Normalize + RandomErasing + Mixup / CutMix of a packed batch, on the current stream.
     pix: uint8 device buffer (a multiple of 16 bytes), desc: [B, AUG_DESC_INTS] int32 device descriptors, meta: the host maxima written
-    by d2s.data.pack_batch.  Returns fp32 [B, 3, size, size].  The scratch and the output are allocated on the current stream."""
+    by d2s.data.pack_batch.  op_table: None, or the [B, RA_MAX_OPS, RA_OP_INTS] int32 device table of RandAugment / ColorJitter ops
+    (d2s.data.pack_ops), applied to the uint8 image between the flip and ToTensor.  Returns fp32 [B, 3, size, size].  The scratch and
+    the output are allocated on the current stream."""
     if lib.query("d2s_augment_desc_ints") != AUG_DESC_INTS:
         raise lib.D2SError("augment descriptor layout of the library and of d2s.ops disagree")
     assert pix.dtype == torch.uint8 and pix.is_contiguous() and desc.dtype == torch.int32 and desc.is_contiguous()
@@ -1204,12 +1213,32 @@ def augment_images(pix, desc, meta, size):
     assert desc.shape == (B, AUG_DESC_INTS), desc.shape
     inter = torch.empty(max(int(meta["total_rows"]) * size * 3, 16), dtype=torch.uint8, device=pix.device)
     out = torch.empty((B, 3, size, size), dtype=torch.float32, device=pix.device)
-    rc = lib._fn("d2s_augment_images")(lib.ptr(pix), pix.numel(), lib.ptr(desc), B, int(size), int(meta["max_rows"]), int(meta["kmax_h"]),
-                                        int(meta["kmax_v"]), int(meta["rowbytes"]), int(meta["seed"]) & 0xFFFFFFFFFFFFFFFF,
-                                        lib.ptr(inter), lib.ptr(out), lib.stream())
+    args = (B, int(size), int(meta["max_rows"]), int(meta["kmax_h"]), int(meta["kmax_v"]), int(meta["rowbytes"]),
+            int(meta["seed"]) & 0xFFFFFFFFFFFFFFFF, lib.ptr(inter))
+    if op_table is None:
+        name = "d2s_augment_images"
+        rc = lib._fn(name)(lib.ptr(pix), pix.numel(), lib.ptr(desc), *args, lib.ptr(out), lib.stream())
+    else:
+        name = "d2s_augment_images_ops"
+        _check_op_table(op_table, B)
+        images = torch.empty(lib.query("d2s_augment_ops_scratch_bytes", B, int(size)), dtype=torch.uint8, device=pix.device)
+        rc = lib._fn(name)(lib.ptr(pix), pix.numel(), lib.ptr(desc), lib.ptr(op_table), *args, lib.ptr(images), lib.ptr(out), lib.stream())
     if rc != 0:
-        raise lib.D2SError(f"d2s_augment_images failed with code {rc} (a crop more than ~40x the output size does not fit the "
-                           "coefficient tables)" if rc == -1 else f"d2s_augment_images failed with code {rc}")
+        raise lib.D2SError(f"{name} failed with code {rc} (a crop more than ~40x the output size does not fit the "
+                           "coefficient tables)" if rc == -1 else f"{name} failed with code {rc}")
+    return out
+
+
+def randaug_apply(images, op_table):
+    """RandAugment / ColorJitter ops on uint8 [B, S, S, 3] device images, bit-exact with Pillow (csrc/randaug.hip): image b's list
+    op_table[b] (d2s.data.pack_ops) applied in order.  Returns a new uint8 [B, S, S, 3]; the input is not written."""
+    assert images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3, images.shape
+    B, S = images.shape[0], images.shape[1]
+    assert images.shape[2] == S, images.shape
+    _check_op_table(op_table, B)
+    scratch = torch.empty(lib.query("d2s_randaug_scratch_bytes", B, S), dtype=torch.uint8, device=images.device)
+    out = torch.empty_like(images)
+    lib.call("d2s_randaug_apply", lib.ptr(images), lib.ptr(op_table), B, S, lib.ptr(scratch), lib.ptr(out))
     return out
 
 

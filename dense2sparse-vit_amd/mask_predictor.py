@@ -83,6 +83,13 @@ def check_supported(args):
             bad.append("--recount above 8 (erase boxes per image)")
         if not 0 <= args.num_workers <= 16:
             bad.append("--num-workers outside 0..16")
+        try:
+            from d2s import data
+            data.parse_auto_augment(args.aa)
+        except ValueError as e:
+            bad.append(f"--aa: {e}")
+        if args.color_jitter < 0:
+            bad.append(f"--color-jitter {args.color_jitter} (a single non-negative strength)")
     if args.resume and args.torch_optim:
         bad.append("--resume with --torch-optim (a checkpoint restores the fused step's arenas; that recipe has none)")
     if args.model_ema and args.torch_optim:
@@ -101,9 +108,6 @@ def check_supported(args):
     if args.predictor_bn and args.use_ddp:
         print("Attention: --predictor-bn keeps per-rank batch statistics (not synchronised), exactly like the reference")
     if folder:
-        if (args.aa and args.aa.lower() != "none") or args.color_jitter > 0:
-            print("Attention: --aa / --color-jitter: RandAugment and ColorJitter are not built; the training transform is "
-                  "RandomResizedCrop + flip + Normalize + RandomErasing (+ Mixup/CutMix)")
         return
     if args.mixup > 0 or args.cutmix > 0 or args.cutmix_minmax is not None:
         print("Attention: mixup/cutmix are not used (synthetic batches)")
@@ -135,7 +139,8 @@ def folder_loaders(args, samples, split, epoch, rank, world):
     if args.mixup > 0 or args.cutmix > 0 or args.cutmix_minmax is not None:                                # :261-267
         mix = data.MixConfig(args.mixup, args.cutmix, tuple(args.cutmix_minmax) if args.cutmix_minmax else None, args.mixup_prob,
                              args.mixup_switch_prob, args.mixup_mode, args.smoothing, args.nb_classes)
-    opts = data.AugmentOptions(args.train_interpolation, args.reprob, args.remode, args.recount)
+    opts = data.AugmentOptions(args.train_interpolation, args.reprob, args.remode, args.recount, auto_augment=args.aa or "",
+                               color_jitter=args.color_jitter)
     common = dict(seed=42, epoch=epoch, rank=rank, num_workers=args.num_workers)
     train = data.FolderLoader(samples, data.shard(data.epoch_order(train_idx, 42, epoch), rank, world), args.batch_size, args.device,
                               train=True, opts=opts, mix=mix, **common)

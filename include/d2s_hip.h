@@ -332,6 +332,27 @@ int d2s_augment_images(const unsigned char* pix, long pix_bytes, const int* desc
 /* out: [B, C] fp32 soft labels, timm's mixup_target (partner of sample i: B-1-i). */
 int d2s_augment_labels(const int* desc, int B, int C, float on, float off, float* out, d2s_stream_t stream);
 
+/* ---- RandAugment / ColorJitter on uint8 images, bit-exact with Pillow (timm auto_augment.py "increasing" ops, ImageEnhance; the
+ * reference's utils.py:284 --aa, --color-jitter; csrc/randaug.hip) ----------------------------------------------------------------------
+ * table: [B, d2s_randaug_max_ops(), d2s_randaug_op_ints()] int32 (device, 8-byte aligned).  An entry is (code, resample, int argument,
+ * float argument as its bits, six doubles of an AFFINE matrix, padding); an image's list ends at the first entry with code 0.  Codes:
+ * 1 AutoContrast, 2 Equalize, 3 Invert, 4 Posterize (bits), 5 Solarize (threshold), 6 SolarizeAdd (addend, threshold 128), 7 Affine
+ * (matrix; resample 0 bilinear / 1 bicubic; fill (124, 116, 104)), 8 Color, 9 Contrast, 10 Brightness, 11 Sharpness (factor).  The host
+ * draws every random quantity (d2s/data.py).  No floating-point atomics: two runs give the same bytes. */
+int d2s_randaug_max_ops(void);
+int d2s_randaug_op_ints(void);
+size_t d2s_randaug_scratch_bytes(int B, int S);
+/* in, out: [B, S, S, 3] uint8, three distinct 16-byte aligned buffers with scratch (d2s_randaug_scratch_bytes).  out = the image's ops
+ * applied to in, in order; an empty list copies.  One workgroup per image. */
+int d2s_randaug_apply(const unsigned char* in, const int* table, int B, int S, unsigned char* scratch, unsigned char* out,
+                      d2s_stream_t stream);
+/* d2s_augment_images with the op table applied between the flip and ToTensor (three passes instead of the fused second one).  images:
+ * d2s_augment_ops_scratch_bytes(B, S) bytes of scratch, 16-byte aligned.  Empty lists for every image: the bytes of d2s_augment_images. */
+size_t d2s_augment_ops_scratch_bytes(int B, int S);
+int d2s_augment_images_ops(const unsigned char* pix, long pix_bytes, const int* desc, const int* table, int B, int S, int max_rows,
+                           int kmax_h, int kmax_v, int rowbytes, unsigned long long seed, unsigned char* inter, unsigned char* images,
+                           float* out, d2s_stream_t stream);
+
 /* ---- stochastic depth (DropPath, vit_models/deit.py:69-77; dynamic_vit.py:249, 263-269), training only ------------------------------
  * One table per step: table [R][B] fp32 from rates [R] (device, 0 <= rate < 1) and a 64-bit seed, R = 2 * depth; row 2i = block i's
  * attention branch, row 2i + 1 its MLP branch.  Entry = floor(keep + u) / keep with keep = 1 - rate: 0 or 1 / keep; u is Philox4x32-10

@@ -1,11 +1,12 @@
 """Input-pipeline measurements (csrc/augment.hip, d2s/data.py) on one GPU:
 
   1. the augment kernels alone (crop-resize + flip + normalize + erase + Mixup, and the soft labels) at B = 128 on ImageNet-like
-     sources (about 500 x 375), timed with device events;
+     sources (about 500 x 375), timed with device events: without RandAugment / ColorJitter (the fused route), with the default
+     --aa rand-m9-mstd0.5-inc1 and with --color-jitter 0.4 alone (the three-pass route around csrc/randaug.hip), and the op kernel alone;
   2. the loader's host rate (JPEG decode + parameter sampling + packing) with 8 and 16 workers, on JPEGs generated into a temp dir;
   3. mask_predictor.py --data-source folder images/s next to --data-source synthetic (fresh child processes, same model and batch).
 
-    python tools/augment_bench.py [--batch 128] [--images 1280] [--arch deit_small] [--skip-train]
+    python tools/augment_bench.py [--batch 128] [--images 1280] [--arch deit_small] [--skip-train] [--kernels-only]
 """
 import argparse
 import json
@@ -31,33 +32,53 @@ def _imagenet_like(rng):
     return np.clip(base + rng.integers(-30, 31, (H, W, 3)), 0, 255).astype(np.uint8)
 
 
+def _timed(fn, iters, repeats=5):
+    """Median and spread (min, max) of `repeats` event-timed runs of `iters` calls, in ms per call."""
+    import torch
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / iters)
+    return dict(median=round(float(np.median(ms)), 4), min=round(min(ms), 4), max=round(max(ms), 4))
+
+
 def kernels(B, iters=200):
     import torch
     from d2s import data, ops
-    rng = np.random.default_rng(0)
-    images = [_imagenet_like(rng) for _ in range(B)]
-    opts = data.AugmentOptions("bicubic", 0.25, "pixel", 1)
-    params = [data.train_params(rng, im.shape[0], im.shape[1], opts, 224) for im in images]
-    mp = data.mix_params(rng, B, data.MixConfig(), 224)
-    hb = data.pack_batch(images, list(range(B)), params, 224, mp, seed=1)
-    pix, desc = hb["pix"].cuda(), hb["desc"].cuda()
-    for _ in range(10):
-        ops.augment_images(pix, desc, hb["meta"], 224)
-        ops.augment_labels(desc, 1000, 0.1)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        ops.augment_images(pix, desc, hb["meta"], 224)
-        ops.augment_labels(desc, 1000, 0.1)
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / iters
+    res = {}
+    for tag, aa, jitter in (("off", "", 0.0), ("randaug", "rand-m9-mstd0.5-inc1", 0.4), ("jitter", "", 0.4)):
+        rng = np.random.default_rng(0)
+        images = [_imagenet_like(rng) for _ in range(B)]
+        opts = data.AugmentOptions("bicubic", 0.25, "pixel", 1, auto_augment=aa, color_jitter=jitter)
+        params = [data.train_params(np.random.default_rng([0, k]), im.shape[0], im.shape[1], opts, 224) for k, im in enumerate(images)]
+        mp = data.mix_params(rng, B, data.MixConfig(), 224)
+        hb = data.pack_batch(images, list(range(B)), params, 224, mp, seed=1)
+        pix, desc = hb["pix"].cuda(), hb["desc"].cuda()
+        table = hb["ops"].cuda() if "ops" in hb else None
+
+        def step():
+            ops.augment_images(pix, desc, hb["meta"], 224, table)
+            ops.augment_labels(desc, 1000, 0.1)
+        res[f"ms_per_batch_{tag}"] = _timed(step, iters)
+        if table is not None:
+            u8 = torch.randint(0, 256, (B, 224, 224, 3), dtype=torch.uint8, device="cuda")
+            res[f"ms_op_kernel_{tag}"] = _timed(lambda: ops.randaug_apply(u8, table), iters)
+            res[f"ops_per_image_{tag}"] = round(float((hb["ops"][:, :, 0] != 0).sum()) / B, 2)
     src = int(sum(im.size for im in images))
     inter = int(hb["meta"]["total_rows"]) * 224 * 3
     out = B * 3 * 224 * 224 * 4
-    return dict(batch=B, ms_per_batch=round(ms, 4), src_mb=round(src / 1e6, 1), scratch_mb=round(inter / 1e6, 1),
-                out_mb=round(out / 1e6, 1), bytes_floor_us=round((src + 2 * inter + out + B * 4000) / 8.0e12 * 1e6, 1))        # at the 8 TB/s HBM peak
+    res.update(batch=B, ms_per_batch=res["ms_per_batch_off"]["median"], src_mb=round(src / 1e6, 1), scratch_mb=round(inter / 1e6, 1),
+               out_mb=round(out / 1e6, 1), u8_image_mb=round(B * 224 * 224 * 3 / 1e6, 1),
+               bytes_floor_us=round((src + 2 * inter + out + B * 4000) / 8.0e12 * 1e6, 1))        # at the 8 TB/s HBM peak (fused route)
+    return res
 
 
 def make_folder(root, n, rng):
@@ -104,9 +125,13 @@ def main():
     ap.add_argument("--images", type=int, default=1280)
     ap.add_argument("--arch", default="deit_small")
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--kernels-only", action="store_true", help="measurement 1 only")
     a = ap.parse_args()
     res = {"kernels": kernels(a.batch)}
     print(f"[augment] kernels: {res['kernels']}", flush=True)
+    if a.kernels_only:
+        print(json.dumps(res))
+        return
     with tempfile.TemporaryDirectory() as root:
         make_folder(root, a.images, np.random.default_rng(1))
         res["decode_img_s"] = {w: loader_rate(root, a.batch, w) for w in (8, 16)}
