@@ -377,15 +377,49 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     }
 }
 
+// the tile fetch of the DPOL instantiation: 32-bit element offsets from the (wave-uniform) panel bases - a head's panel spans n * ld < 2^32
+// elements (checked by the entry) - so that the loop-invariant per-thread addresses cost one register each, not two
+__device__ __forceinline__ void tile_load_u32(const float* __restrict__ base, unsigned ld, int row0, int nrows, int tid, f32x4 (&r)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int f = tid + i * 256, row = row0 + (f >> 4);
+        const unsigned off = (unsigned)row * ld + (unsigned)((f & 15) * 4);
+        r[i] = row < nrows ? *reinterpret_cast<const f32x4*>(base + off) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+__device__ __forceinline__ void dkv_fetch_next(const float* __restrict__ qb, const float* __restrict__ dob, const float* __restrict__ lse_b,
+                                               const float* __restrict__ dl_b, const float* __restrict__ ci_b, unsigned ld, unsigned ldo,
+                                               int t1, int n, int tid, f32x4 (&qr)[2], f32x4 (&dr)[2], float& lr, float& dlr, float& cir) {
+    tile_load_u32(qb, ld, t1 * 32, n, tid, qr);
+    tile_load_u32(dob, ldo, t1 * 32, n, tid, dr);
+    if (tid < 32) {
+        const unsigned qi = (unsigned)(t1 * 32 + tid);
+        lr = qi < (unsigned)n ? lse_b[qi] : INFINITY;
+        dlr = qi < (unsigned)n ? dl_b[qi] : 0.f;
+        cir = qi < (unsigned)n ? ci_b[qi] : 0.f;
+    }
+}
+__device__ __forceinline__ float* first_arg() { return nullptr; }
+__device__ __forceinline__ float* first_arg(float* a) { return a; }
+
 // ---------------------------------------------------------------------------------------------------------
 // backward, dK / dV: one wave per 32 keys, loops over query tiles (natural orientation S = Q K^T)
 // ---------------------------------------------------------------------------------------------------------
 // POLICY: P_ij = exp(S_ij - lse_i) mk_ij + cinv_i feeds dV (the eps/n term reaches every key, masked or not); dS as in the dQ kernel.
-template <bool POLICY>
+// DPOL (its one extra argument, float* dpol_part, is the variadic tail, so that the two existing instantiations keep their argument
+// lists and their instructions): the gradient of the policy itself, for the DynamicViT baseline whose predictor learns through the mask of this softmax only.  With
+// m_ij = p_j + (1 - p_j) [i == j]:  dL/dm_ij = exp(S_ij - lse_i) (dP_ij - delta_i) - the product below BEFORE the mask multiplies it - and
+// dpolicy[b, j] = sum_h sum_{i != j} dL/dm_ij.  The lane owns key j and walks every query, so its column sum needs no atomics: 16 rows per
+// tile in register order, tiles in ascending order, then the two half-waves (rows 4 half + ...) are added once.  Each wave of a workgroup
+// owns 32 keys of its own, so nothing is reduced across waves.  A masked key (p_j = 0) has dS = 0 but a non-zero column sum (that is the
+// straight-through estimator's signal) and the policy is real-valued here: nothing is skipped and 0/1 is not assumed.
+// dpol_part [B, H, n]: per-head partials, folded over h in ascending order by attn_dpol_fold_kernel.
+template <bool POLICY, bool DPOL = false, typename... DpolPart>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            float* __restrict__ dqkv, int n, int H, float scale,
-                                                           const float* __restrict__ policy, const float* __restrict__ cinv) {
+                                                           const float* __restrict__ policy, const float* __restrict__ cinv,
+                                                           DpolPart... dpol_part_) {
     __shared__ __attribute__((aligned(16))) float Qs[32 * PITCH];
     __shared__ __attribute__((aligned(16))) float Ds[32 * PITCH];
     __shared__ float lse_s[32], dl_s[32], ci_s[32];
@@ -414,6 +448,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     const int ntiles = (n + 31) / 32;
     f32x4 qr[2], dr[2];
     float lr = 0.f, dlr = 0.f, cir = 0.f;
+    float dpol_acc = 0.f;
     const float* ci_b = POLICY ? cinv + ((long)b * H + h) * n : nullptr;
     const float pol_key = (POLICY && k0 + l31 < n) ? policy[(long)b * n + k0 + l31] : 0.f;   // this lane's key
     tile_load(qb, ld, 0, n, tid, qr);
@@ -425,7 +460,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
         tile_store(Ds, tid, dr);
         if (tid < 32) { lse_s[tid] = lr; dl_s[tid] = dlr; if (POLICY) ci_s[tid] = cir; }
         __syncthreads();
-        if (t + 1 < ntiles) {
+        // the next tile's rows travel through registers while this tile is multiplied; DPOL has no registers to spare for that (one more
+        // accumulator at 2 waves per SIMD) and fetches them after the products instead (dkv_fetch_next), the CU's other workgroup covering the wait
+        if (!DPOL && t + 1 < ntiles) {
             tile_load(qb, ld, (t + 1) * 32, n, tid, qr);
             tile_load(dob, ldo, (t + 1) * 32, n, tid, dr);
             if (tid < 32) {
@@ -435,6 +472,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
                 if (POLICY) cir = qi < n ? ci_b[qi] : 0.f;
             }
         }
+        if (DPOL && !active && t + 1 < ntiles) dkv_fetch_next(qb, dob, lse_b, dl_b, ci_b, (unsigned)ld, (unsigned)ldo, t + 1, n, tid, qr, dr, lr, dlr, cir);
         if (!active) continue;
         f32x16 s, dp;
 #pragma unroll
@@ -445,6 +483,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
         for (int r = 0; r < 16; ++r) {
             const int qi = mfma32_row(r, half);
             float p = __expf(s[r] - lse_s[qi]);  // rows beyond n carry lse = +inf -> p = 0
+            if (DPOL) {      // w = dL/dm_ij; rows beyond n carry p = 0
+                const bool diag = t * 32 + qi == k0 + l31;
+                const float g = dp[r] - dl_s[qi];
+                dpol_acc += diag ? 0.f : p * g;
+                p *= diag ? 1.f : pol_key;
+                s[r] = p + ci_s[qi];
+                dp[r] = p * g;                             // the bits of the plain POLICY instantiation
+                continue;
+            }
             if (POLICY) p *= (t * 32 + qi == k0 + l31) ? 1.f : pol_key;
             s[r] = POLICY ? p + ci_s[qi] : p;
             dp[r] = p * (dp[r] - dl_s[qi]);
@@ -452,22 +499,44 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
         const int qgroups = min(4, (n - t * 32 + 7) >> 3);          // query rows of this tile that exist
         mma_reg_lds(s, Ds, l31, half, dv, qgroups);     // dV[key][d] += sum_query P[query][key] dO[query][d]
         mma_reg_lds(dp, Qs, l31, half, dk, qgroups);    // dK[key][d] += sum_query dS[query][key] Q[query][d]
+        if (DPOL && t + 1 < ntiles) dkv_fetch_next(qb, dob, lse_b, dl_b, ci_b, (unsigned)ld, (unsigned)ldo, t + 1, n, tid, qr, dr, lr, dlr, cir);
     }
     if (!active) return;
+    // DPOL: the epilogue's lane coordinates are derived afresh from an opaque copy of the thread id, so that the loop does not carry them
+    int l31e = l31, halfe = half, k0e = k0;
+    if (DPOL) {
+        int t2 = (int)threadIdx.x;
+        asm volatile("" : "+v"(t2));
+        l31e = t2 & 31; halfe = (t2 >> 5) & 1; k0e = bx * 128 + (t2 >> 6) * 32;
+        float* dpol_part = first_arg(dpol_part_...);
+        dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
+        if (halfe == 0 && k0e + l31e < n) dpol_part[((long)b * H + h) * n + k0e + l31e] = dpol_acc;
+    }
     float* dkb = dqkv + (long)b * n * ld + (long)H * DH + h * DH;
     float* dvb = dkb + (long)H * DH;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int ki = k0 + mfma32_row(r, half);
+        const int ki = k0e + mfma32_row(r, halfe);
         if (ki < n) {
             float* pk = dkb + (long)ki * ld;
             float* pv = dvb + (long)ki * ld;
-            pk[l31] = dk[0][r] * scale;
-            pk[32 + l31] = dk[1][r] * scale;
-            pv[l31] = dv[0][r];
-            pv[32 + l31] = dv[1][r];
+            pk[l31e] = dk[0][r] * scale;
+            pk[32 + l31e] = dk[1][r] * scale;
+            pv[l31e] = dv[0][r];
+            pv[32 + l31e] = dv[1][r];
         }
     }
+}
+
+// dpolicy[b, j] = sum_h part[b, h, j], h ascending; column 0 (the CLS key, constant 1 in every policy) gets 0
+__global__ __launch_bounds__(256) void attn_dpol_fold_kernel(const float* __restrict__ part, float* __restrict__ dpolicy, int B, int n, int H) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * n) return;
+    const long b = i / n, j = i - b * n;
+    float s = 0.f;
+    if (j > 0)
+        for (int h = 0; h < H; ++h) s += part[(b * H + h) * n + j];
+    dpolicy[i] = s;
 }
 
 }  // namespace
@@ -545,6 +614,23 @@ int d2s_attn_policy_bwd_f32(const float* qkv, const float* policy, const float* 
     dim3 grid((n + 127) / 128, B * H), block(256);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy, cinv);
+    return d2s_check_launch();
+}
+
+// d2s_attn_policy_bwd_f32 plus the gradient of the policy: dpolicy [B, n] is fully written (column 0 = 0), dpol_ws: [B, H, n] floats of
+// scratch.  dqkv is bit for bit what d2s_attn_policy_bwd_f32 writes; no atomics, so two launches are bit-identical.
+int d2s_attn_policy_bwd_dpol_f32(const float* qkv, const float* policy, const float* out, const float* dout, const float* lse,
+                                 const float* cinv, float* dqkv, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H,
+                                 float scale, hipStream_t stream) {
+    if (!qkv || !policy || !out || !dout || !lse || !cinv || !dqkv || !delta_ws || !dpolicy || !dpol_ws || B <= 0 || n <= 0 || H <= 0)
+        return D2S_ERR_ARG;
+    if ((long)n * 3 * H * 64 >= (1L << 32)) return D2S_ERR_ARG;      // tile_load_u32: one image's qkv panel must fit 32-bit element offsets
+    const long rows = (long)B * n;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true, float*>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy, cinv, dpol_ws);
+    hipLaunchKernelGGL(attn_dpol_fold_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, dpol_ws, dpolicy, B, n, H);
     return d2s_check_launch();
 }
 

@@ -484,7 +484,7 @@ class TrainStep:
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
-        from losses import MaskLoss, BackboneLoss
+        from losses import MaskLoss, BackboneLoss, DynamicViTLoss
         if int(accum_steps) != accum_steps or accum_steps < 1:
             raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
         if clip_grad is not None and not float(clip_grad) > 0.0:
@@ -503,8 +503,17 @@ class TrainStep:
         self.arena = ParamArena(student, order)
         self.block_offset = {i: self.arena.offsets[starts[i]] for i in starts}
         self.opt = FusedAdamW(self.arena, lr=lr, weight_decay=weight_decay)
-        self.mask_loss_fn = MaskLoss(args, "train")
-        self.backbone_loss_fn = BackboneLoss(args)
+        # the DynamicViT baseline (vit_models/default_dynamic_vit.py) returns (logits, features, decision, [decision per stage]) and is
+        # trained with its own objective, the full one in every epoch; the freeze / learning-rate schedule is the d2s one
+        self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
+        if self.baseline:
+            if not getattr(student, "distill", False):
+                raise lib.D2SError("TrainStep with the DynamicViT baseline needs distill=True: the objective reads the student's features")
+            self.dynamicvit_loss_fn = DynamicViTLoss(args)
+            self.mask_loss_fn = self.backbone_loss_fn = None
+        else:
+            self.mask_loss_fn = MaskLoss(args, "train")
+            self.backbone_loss_fn = BackboneLoss(args)
         self.metrics = {}
         self.lr, self.min_lr, self.epochs, self.warmup_steps = lr, min_lr, epochs, warmup_steps
         self.reducer = GradReducer(self.arena, bucket_mb=bucket_mb, collective=collective) if distributed else None
@@ -533,6 +542,12 @@ class TrainStep:
             if self.graph is True:
                 raise lib.D2SError("TrainStep(graph=True) with diff_topk is not supported: a replayed step would reuse the perturbation "
                                    "noise and the sigma it was captured with; run the step eagerly (graph=False)")
+            self.graph = False
+        if self.baseline:
+            # same reason: the Gumbel noise of every stage comes from a seed drawn on the host inside the model's forward (one draw per step)
+            if self.graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with the DynamicViT baseline is not supported: a replayed step would reuse the "
+                                   "Gumbel noise it was captured with; run the step eagerly (graph=False)")
             self.graph = False
         if self.accum_steps > 1:
             # a captured step overwrites the gradient arena on every replay, and which launches follow the backward (accumulate, or
@@ -721,8 +736,8 @@ class TrainStep:
             side, main = self._teacher_stream, torch.cuda.current_stream()
             ready = main.record_event() if next_images is not None else None
             if ahead is not None:                       # issued during the previous step (_teacher_ahead)
-                logits_t, token_t, cls_attn = ahead["out"]
-                logits_s, token_s, pred_logits, kept = self.student(images)
+                out_t = ahead["out"]
+                out_s = self.student(images)
                 main.wait_event(ahead["done"])
             else:
                 with shared_patch_columns():
@@ -731,10 +746,10 @@ class TrainStep:
                         prime_patch_columns(images, pe.patch_size[0])       # one im2col for both, built before the fork
                     side.wait_stream(main)
                     with torch.cuda.stream(side), torch.no_grad():
-                        logits_t, token_t, cls_attn = self.teacher(images)
-                    logits_s, token_s, pred_logits, kept = self.student(images)
+                        out_t = self.teacher(images)
+                    out_s = self.student(images)
                     main.wait_stream(side)
-            for t in (logits_t, token_t, cls_attn):      # produced on the side stream, consumed (and later freed) on the main one
+            for t in out_t:                              # produced on the side stream, consumed (and later freed) on the main one
                 t.record_stream(main)
             if next_images is not None:
                 self._teacher_ahead(next_images, ready)
@@ -742,13 +757,28 @@ class TrainStep:
             from .functional import shared_patch_columns
             with shared_patch_columns():       # teacher and student embed the same images: one im2col pass for both
                 with torch.no_grad():
-                    logits_t, token_t, cls_attn = self.teacher(images)
-                logits_s, token_s, pred_logits, kept = self.student(images)
+                    out_t = self.teacher(images)
+                out_s = self.student(images)
+        if self.baseline:
+            return self._baseline_losses(out_s, out_t, labels, accumulate)
+        logits_t, token_t, cls_attn = out_t
+        logits_s, token_s, pred_logits, kept = out_s
         mask_loss = self.mask_loss_fn(pred_logits, cls_attn, kept, self.metrics, accumulate=accumulate)
         backbone_loss = self.backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept, labels, self.metrics, accumulate=accumulate)
         loss = mask_loss if self.epoch < self.warmup_steps else backbone_loss + mask_loss     # train.py:50-53
         return loss, dict(mask_loss=mask_loss, backbone_loss=backbone_loss, kept=kept, logits_s=logits_s, token_s=token_s,
                           pred_logits=pred_logits, logits_t=logits_t, token_t=token_t, cls_attn=cls_attn)
+
+    def _baseline_losses(self, out_s, out_t, labels, accumulate):
+        """DynamicViTLoss on the baseline's outputs.  The teacher is this file's dense one ((logits, tokens)) or a d2s teacher, whose third
+        output is not used.  'mask_loss' reports the weighted ratio term - the part only the predictors see - and 'backbone_loss' the rest."""
+        logits_s, token_s, decision, stages = out_s
+        logits_t, token_t = out_t[0], out_t[1]
+        fn = self.dynamicvit_loss_fn
+        loss = fn(logits_s, token_s, decision, stages, logits_t, token_t, labels, self.metrics, accumulate=accumulate)
+        ratio = fn.ratio_weight * fn.last[2]
+        return loss, dict(mask_loss=ratio, backbone_loss=fn.last[0] - ratio, kept=stages, logits_s=logits_s, token_s=token_s,
+                          pred_logits=stages, logits_t=logits_t, token_t=token_t, cls_attn=None)
 
     def __call__(self, images, labels, next_images=None):
         """next_images: the batch of the FOLLOWING call, if the caller already has it (a prefetching loader does).  The frozen teacher's

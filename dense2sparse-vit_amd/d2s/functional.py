@@ -357,7 +357,7 @@ class BlockFn(torch.autograd.Function):
         grads[5], grads[6] = ops.linear_param_grads(ga, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
         dao = ops.linear_dgrad(ga, projw, a16=g1h)
         del g1h
-        dqkvh = None
+        dqkvh = dpolicy = None
         l1x, l116 = xarg(ln1)
         dqkv_bf16_only = False
         if policy is None:
@@ -365,6 +365,8 @@ class BlockFn(torch.autograd.Function):
                 dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev)
                 dqkv_bf16_only = l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
             dqkv = ops.attn_bwd(qkv, ao, dao, lse, B, n, heads, scale, dqkv16=dqkvh, want_f32=not dqkv_bf16_only)
+        elif ctx.needs_input_grad[17]:      # a policy that wants its gradient (DynamicViT baseline); constant masks keep their launches
+            dqkv, dpolicy = ops.attn_policy_bwd_dpol(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale)
         else:
             dqkv = ops.attn_policy_bwd(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale)
         grads[3], grads[4] = ops.linear_param_grads(dqkv, l1x, qkvw, qkvb, wants[3], wants[4], x16=l116, dy16=dqkvh if dqkv_bf16_only else None)
@@ -382,7 +384,7 @@ class BlockFn(torch.autograd.Function):
             if gxh is not None:
                 ops.shadow_put(gx, gxh)
         grads[0] = gx
-        return tuple(grads) + (None, None, None, None) + (None,) * ctx.nextra
+        return tuple(grads) + (None, None, None, None) + ((dpolicy,) + (None,) * (ctx.nextra - 1) if ctx.nextra else ())
 
 
 @mode_recorded
@@ -744,6 +746,9 @@ class AttnCoreFn(torch.autograd.Function):
             dqkv = ops.attn_bwd(qkv, out, g.contiguous(), lse, B, n, H, scale)
         else:
             qkv, out, lse, cinv, policy = ctx.saved_tensors
+            if ctx.needs_input_grad[6]:      # the policy itself is learnt through (DynamicViT baseline): one more column sum in the dK/dV pass
+                dqkv, dpol = ops.attn_policy_bwd_dpol(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
+                return (dqkv, None, None, None, None, None, dpol) + (None,) * (ctx.nextra - 1)
             dqkv = ops.attn_policy_bwd(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
         return (dqkv, None, None, None, None, None) + (None,) * ctx.nextra
 

@@ -72,6 +72,7 @@ _SIGS = {
     "d2s_compose_ids": (I, [P, I, P, I, P, I]),
     "d2s_attn_policy_fwd_f32": (I, [P, P, P, P, P, P, I, I, I, F, F]),
     "d2s_attn_policy_bwd_f32": (I, [P, P, P, P, P, P, P, P, I, I, I, F]),
+    "d2s_attn_policy_bwd_dpol_f32": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_varlen_fwd_f32": (I, [P, P, P, P, I, I, I, I, F]),
     "d2s_sum_scalar": (I, [P, L, F, P]),
     "d2s_scale_by_scalar": (I, [P, P, F, P, L]),
@@ -113,6 +114,14 @@ _SIGS = {
     "d2s_randaug_apply": (I, [P, P, I, I, P, P]),
     "d2s_augment_ops_scratch_bytes": (Z, [I, I]),
     "d2s_augment_images_ops": (I, [P, L, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P, P]),
+    "d2s_gumbel_noise": (I, [P, L, ctypes.c_ulonglong]),
+    "d2s_gumbel_from_bits": (I, [P, P, L]),
+    "d2s_gumbel_keep_fwd": (I, [P, P, P, P, P, P, P, L]),
+    "d2s_gumbel_keep_bwd": (I, [P, P, P, P, P, P, L]),
+    "d2s_policy_pool_fwd": (I, [P, P, P, P, P, I, I, I]),
+    "d2s_policy_pool_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I]),
+    "d2s_ratio_rows_fwd": (I, [P, F, P, P, I, I]),
+    "d2s_ratio_rows_bwd": (I, [P, P, F, P, I, I]),
 }
 
 _lib = None

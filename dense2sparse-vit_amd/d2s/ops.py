@@ -969,6 +969,17 @@ def attn_policy_bwd(qkv, policy, out, dout, lse, cinv, B, n, H, scale):
     return dqkv
 
 
+def attn_policy_bwd_dpol(qkv, policy, out, dout, lse, cinv, B, n, H, scale):
+    """attn_policy_bwd plus the gradient of the policy (DynamicViT baseline).  -> (dqkv, dpolicy [B, n], column 0 = 0)"""
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    part = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    dpolicy = torch.empty((B, n), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_policy_bwd_dpol_f32", lib.ptr(qkv), lib.ptr(policy), lib.ptr(out), lib.ptr(dout), lib.ptr(lse), lib.ptr(cinv),
+             lib.ptr(dqkv), lib.ptr(delta), lib.ptr(dpolicy), lib.ptr(part), B, n, H, float(scale))
+    return dqkv, dpolicy
+
+
 def attn_varlen_fwd(qkv, cu, B, total, max_n, H, scale, want_cls=False):
     out = torch.empty((total, H * 64), dtype=torch.float32, device=qkv.device)
     cls_row = torch.empty((H, total), dtype=torch.float32, device=qkv.device) if want_cls else None
@@ -1007,6 +1018,78 @@ def normal_noise(shape, seed, device):
     out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
     lib.call("d2s_normal_noise", lib.ptr(out), out.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF)
     return out
+
+
+# ---- DynamicViT baseline (vit_models/default_dynamic_vit.py) ----
+def gumbel_noise(shape, seed, device):
+    """Gumbel(0, 1) tensor from the library's counter-based stream `seed` (the noise of F.gumbel_softmax)."""
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    lib.call("d2s_gumbel_noise", lib.ptr(out), out.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return out
+
+
+def gumbel_from_bits(bits):
+    """bits: int32 tensor holding 32-bit draws -> the Gumbel numbers gumbel_noise makes of them (the conversion alone)"""
+    assert bits.dtype == torch.int32 and bits.is_contiguous()
+    out = torch.empty(bits.shape, dtype=torch.float32, device=bits.device)
+    lib.call("d2s_gumbel_from_bits", lib.ptr(bits), lib.ptr(out), bits.numel())
+    return out
+
+
+def gumbel_keep_fwd(z, g, prev):
+    """z, g [M, 2], prev [M] -> (logp [M, 2], y0, hard, decision [M])"""
+    _f32(z), _f32(g), _f32(prev)
+    M = z.shape[0]
+    logp = torch.empty_like(z)
+    y0, hard, dec = (torch.empty((M,), dtype=torch.float32, device=z.device) for _ in range(3))
+    lib.call("d2s_gumbel_keep_fwd", lib.ptr(z), lib.ptr(g), lib.ptr(prev), lib.ptr(logp), lib.ptr(y0), lib.ptr(hard), lib.ptr(dec), M)
+    return logp, y0, hard, dec
+
+
+def gumbel_keep_bwd(gd, prev, y0, hard):
+    """-> (dz [M, 2] w.r.t. the raw logits, dprev [M])"""
+    M = gd.numel()
+    dz = torch.empty((M, 2), dtype=torch.float32, device=gd.device)
+    dprev = torch.empty((M,), dtype=torch.float32, device=gd.device)
+    lib.call("d2s_gumbel_keep_bwd", lib.ptr(_f32(gd)), lib.ptr(prev), lib.ptr(y0), lib.ptr(hard), lib.ptr(dz), lib.ptr(dprev), M)
+    return dz, dprev
+
+
+def policy_pool_fwd(x, p, B, N, C):
+    """x [B*N, C], p [B, N] -> (out [B*N, C], psum [B], glob [B, C/2])"""
+    _f32(x), _f32(p)
+    out = torch.empty_like(x)
+    psum = torch.empty((B,), dtype=torch.float32, device=x.device)
+    glob = torch.empty((B, C // 2), dtype=torch.float32, device=x.device)
+    lib.call("d2s_policy_pool_fwd", lib.ptr(x), lib.ptr(p), lib.ptr(out), lib.ptr(psum), lib.ptr(glob), B, N, C)
+    return out, psum, glob
+
+
+def policy_pool_bwd(gout, x, p, psum, glob, B, N, C):
+    """-> (dx [B*N, C], dp [B, N])"""
+    dx = torch.empty_like(x)
+    dp = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    ws = torch.empty((B, C // 2), dtype=torch.float32, device=x.device)
+    lib.call("d2s_policy_pool_bwd", lib.ptr(_f32(gout)), lib.ptr(x), lib.ptr(p), lib.ptr(psum), lib.ptr(glob), lib.ptr(dx), lib.ptr(dp),
+             lib.ptr(ws), B, N, C)
+    return dx, dp
+
+
+def ratio_rows_fwd(d, rho):
+    """d [B, N] keep decisions -> (loss_row [B] = (mean_j d - rho)^2, diff [B] = mean_j d - rho)"""
+    B, N = d.shape
+    loss_row = torch.empty((B,), dtype=torch.float32, device=d.device)
+    diff = torch.empty((B,), dtype=torch.float32, device=d.device)
+    lib.call("d2s_ratio_rows_fwd", lib.ptr(_f32(d)), float(rho), lib.ptr(loss_row), lib.ptr(diff), B, N)
+    return loss_row, diff
+
+
+def ratio_rows_bwd(diff, g, scale, N):
+    """-> grad [B, N] = g * scale * 2 diff[b] / N (g: 0-d device tensor)"""
+    B = diff.numel()
+    grad = torch.empty((B, N), dtype=torch.float32, device=diff.device)
+    lib.call("d2s_ratio_rows_bwd", lib.ptr(diff), lib.ptr(_f32(g)), float(scale), lib.ptr(grad), B, N)
+    return grad
 
 
 def perturbed_topk_fwd(x, noise, k, sigma):

@@ -15,12 +15,21 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
+    baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # DynamicViT baseline: eval returns logits alone
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():
         for val_inputs, val_labels in val_data_loader:
             val_inputs = val_inputs.to(args.device, non_blocking=True)
             val_labels = val_labels.to(args.device, non_blocking=True)
+            if baseline:      # no mask loss (the predictor has no teacher target) and no second pass: the model has no unpruned switch
+                logits = model(val_inputs)
+                loss = DF.RowLossFn.apply(logits, ops.CE_LABEL, None, None, val_labels.contiguous(), logits.shape[0])
+                correct = float((torch.argmax(logits, dim=1) == val_labels).sum()) / val_labels.shape[0]
+                running_loss += float(loss)
+                running_acc += correct
+                n += 1
+                continue
             cls_attn_weights = teacher_model.forward_cls_attention(val_inputs)          # :33
             outputs = model(val_inputs)                                                 # :35
             model.unpruned = True
@@ -44,7 +53,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
          metrics["val_max_keep_ratio"]) = keep_ratio_summary(keep_ratio_batches)
     metrics["val_loss"] = running_loss / n
     metrics["val_acc"] = running_acc / n
-    metrics["unpruned_acc"] = running_unpruned_acc / n
+    if not baseline:
+        metrics["unpruned_acc"] = running_unpruned_acc / n
     args.epoch_acc = metrics["val_acc"]
     print(f'val loss: {metrics["val_loss"]:.4f}, acc: {metrics["val_acc"]:.4f}')
     return metrics

@@ -141,3 +141,58 @@ class BackboneLoss(torch.nn.Module):
         metrics["train_token_kl_loss"] = self.running_token_dist_loss / self.count      # sic: swapped in the reference
         metrics["train_cls_kl_loss"] = self.running_token_kl_loss / self.count          # (losses.py:238-239)
         self.count += 1
+
+
+class DynamicViTLoss(torch.nn.Module):
+    """The objective of the DynamicViT baseline (vit_models/default_dynamic_vit.py).  The reference ships no loss for this model - its
+    --ratio-weight / --dist-weight / --cls-weight flags are read nowhere (mask_predictor.py:150-151) - so this is the DynamicViT paper's
+    objective, and its parity with the reference is unpinned:
+
+        L = cls_weight * CE(logits, y)                                   (soft-target CE under mixup, as BackboneLoss)
+          + ratio_weight / S * sum_s mean_b (mean_j d_s[b, j] - rho_s)^2
+          + dist_weight * KL(log_softmax(logits_s) || log_softmax(logits_t), batchmean, log_target)
+          + dist_weight * sum(mask * mean_c (f_s - f_t)^2) / sum(mask)   (mask = the final decision, detached)
+
+    Everything stays on the device: the running means are 0-d tensors, `float(v)` reads them."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.soft_targets = getattr(args, "mixup", 0.) > 0.
+        self.keep_ratios = [float(r) for r in args.keep_ratios]
+        self.cls_weight = float(getattr(args, "cls_weight", 1.0))
+        self.ratio_weight = float(getattr(args, "ratio_weight", 2.0))
+        self.dist_weight = float(getattr(args, "dist_weight", 0.5))
+        self.count = 1
+        self.running = [0, 0, 0, 0, 0]
+
+    def forward(self, logits_s, token_s, mask, out_pred_prob, logits_t, token_t, train_labels, metrics, accumulate=True):
+        """logits_s [B, classes], token_s / token_t [B, N, D], mask [B, N] (the final decision), out_pred_prob: one [B, N] decision per stage."""
+        from d2s.functional_dynamicvit import RatioLossFn
+        B = logits_s.shape[0]
+        S = len(out_pred_prob)
+        if S != len(self.keep_ratios):
+            raise ValueError(f"{S} pruning stages, {len(self.keep_ratios)} keep ratios")
+        if self.soft_targets:
+            cls_loss = DF.RowLossFn.apply(logits_s, ops.SOFT_CE, train_labels.float().contiguous(), None, None, B)
+        else:
+            cls_loss = DF.RowLossFn.apply(logits_s, ops.CE_LABEL, None, None, train_labels.contiguous(), B)
+        ratio_loss = 0
+        for d, rho in zip(out_pred_prob, self.keep_ratios):
+            ratio_loss = ratio_loss + RatioLossFn.apply(d, rho, B * S)
+        cls_kl_loss = DF.RowLossFn.apply(logits_s, ops.KL_LOGIT_TARGET, logits_t.detach(), None, None, B)
+        # w = mask / sum(mask): the weighted sum of the rows' squared differences, over D, is the mean over the kept tokens
+        w = ops.mask_row_weights(mask.detach().contiguous())
+        token_loss = DF.RowLossFn.apply(token_s, ops.MSE_TARGET, token_t.detach(), None, None, token_s.shape[-1], w)
+        loss = self.cls_weight * cls_loss + self.ratio_weight * ratio_loss + self.dist_weight * cls_kl_loss + self.dist_weight * token_loss
+        self.last = (loss.detach(), cls_loss.detach(), ratio_loss.detach(), cls_kl_loss.detach(), token_loss.detach())
+        self.last_terms = self.last[1:]
+        if accumulate:
+            self.accumulate(metrics, self.last)
+        return loss
+
+    def accumulate(self, metrics, last):
+        """Advance the running means by one batch."""
+        self.running = [r + v for r, v in zip(self.running, last)]
+        for key, r in zip(("train_dynamicvit_loss", "train_cls_loss", "train_ratio_loss", "train_cls_kl_loss", "train_token_mse_loss"), self.running):
+            metrics[key] = r / self.count
+        self.count += 1

@@ -15,6 +15,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --output-dir runs/a --resume runs/a/last.pt
     python dense2sparse-vit_amd/mask_predictor.py ... --eval-only --resume runs/a/best.pt
     python dense2sparse-vit_amd/mask_predictor.py ... --batch-size 64 --accum-steps 8 --clip-grad 1.0     (512 images per optimiser step)
+    python dense2sparse-vit_amd/mask_predictor.py --method dynamicvit --arch deit_small --pruning-locs 3 6 9 --keep-ratios 0.7 0.49 0.343
 """
 import os
 import sys
@@ -35,11 +36,18 @@ _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": 
              "deit_base": "dynamic_vit_base_patch16_224_student"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
+# --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
+_NOT_WITH_DYNAMICVIT = (("topk_selection", "--topk-selection"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"),
+                        ("small_predictor", "--small-predictor"), ("predictor_bn", "--predictor-bn"))
 
 
 def check_supported(args):
     """Flags whose code path is outside the accelerated hot path fail here, loudly, instead of silently training something else."""
     bad = []
+    if getattr(args, "method", "d2s") == "dynamicvit":
+        for attr, flag in _NOT_WITH_DYNAMICVIT:
+            if getattr(args, attr, None) not in (None, False):
+                bad.append(f"--method dynamicvit with {flag} (the baseline keeps tokens by its own Gumbel decision and predictor)")
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
@@ -117,6 +125,12 @@ def check_supported(args):
 def build_models(args):
     """mask_predictor.py:170-202 (the arch switch), with local checkpoints instead of URL downloads."""
     arch = args.arch if args.arch in _STUDENTS else "deit_small"
+    if getattr(args, "method", "d2s") == "dynamicvit":
+        student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
+                                                                    drop_path_rate=getattr(args, "drop_path", 0.0),
+                                                                    checkpoint_path=args.student_checkpoint)
+        teacher = getattr(vit_models, "default_" + _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
+        return student.to(args.device), teacher.to(args.device)
     student = getattr(vit_models, _STUDENTS[arch])(args.pruning_locs, args.keep_ratios, topk_selection=args.topk_selection,
                                                    early_exit=args.early_exit, mean_heads=args.mean_heads,
                                                    random_drop=args.random_drop, small_predictor=args.small_predictor,

@@ -10,7 +10,7 @@ the mean over the window, clipped to the global L2 norm M.  A TrainStep carries 
 step) and is flushed at the end of the epoch; for a torch optimizer the same window is spelled out here with torch."""
 import torch
 
-from losses import MaskLoss, BackboneLoss
+from losses import MaskLoss, BackboneLoss, DynamicViTLoss
 
 
 def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mixup_fn=None):
@@ -22,12 +22,19 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
     model.train()
     teacher_model.eval()
     fast = isinstance(optimizer, TrainStep)
+    baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer
         step.metrics = metrics
-        step.mask_loss_fn, step.backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)   # fresh running means per epoch (:14-15)
+        if baseline:
+            step.dynamicvit_loss_fn = DynamicViTLoss(args)
+        else:
+            step.mask_loss_fn, step.backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)   # fresh running means per epoch (:14-15)
     else:
-        mask_loss_fn, backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)
+        if baseline:
+            dynamicvit_loss_fn = DynamicViTLoss(args)
+        else:
+            mask_loss_fn, backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)
         accum, clip = max(1, int(getattr(args, "accum_steps", 1) or 1)), getattr(args, "clip_grad", None)
         pending, norm_sum, norm_steps = 0, 0.0, 0
 
@@ -56,12 +63,19 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
             info = step(train_inputs, train_labels)
             mask_loss, train_loss = info["mask_loss"], info["loss"]
         else:
-            with torch.no_grad():
-                logits_t, token_t, cls_attn_weights = teacher_model(train_inputs)                    # :40
-            logits_s, token_s, pred_logits, kept_token_idx = model(train_inputs)                     # :43
-            mask_loss = mask_loss_fn(pred_logits, cls_attn_weights, kept_token_idx, metrics)          # :46
-            backbone_loss = backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept_token_idx, train_labels, metrics)   # :48
-            train_loss = mask_loss if args.step < args.warmup_steps else backbone_loss + mask_loss   # :50-53
+            if baseline:
+                with torch.no_grad():
+                    logits_t, token_t = teacher_model(train_inputs)[:2]
+                logits_s, token_s, decision, stage_decisions = model(train_inputs)
+                train_loss = dynamicvit_loss_fn(logits_s, token_s, decision, stage_decisions, logits_t, token_t, train_labels, metrics)
+                mask_loss = dynamicvit_loss_fn.ratio_weight * dynamicvit_loss_fn.last[2]
+            else:
+                with torch.no_grad():
+                    logits_t, token_t, cls_attn_weights = teacher_model(train_inputs)                    # :40
+                logits_s, token_s, pred_logits, kept_token_idx = model(train_inputs)                     # :43
+                mask_loss = mask_loss_fn(pred_logits, cls_attn_weights, kept_token_idx, metrics)          # :46
+                backbone_loss = backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept_token_idx, train_labels, metrics)   # :48
+                train_loss = mask_loss if args.step < args.warmup_steps else backbone_loss + mask_loss   # :50-53
             if pending == 0:
                 optimizer.zero_grad()
             train_loss.backward()

@@ -9,3 +9,7 @@ from .token_transformer import Token_transformer  # noqa: F401
 from .transformer_block import get_sinusoid_encoding  # noqa: F401
 from .t2t_vit import (T2T_ViT, T2T_module, T2t_vit_14, T2t_vit_t_14, T2T_ViT_DiffPruning, T2T_ViT_Teacher,  # noqa: F401
                       t2t_vit_14_student, t2t_vit_14_teacher)
+from .default_dynamic_vit import (DefaultVisionTransformerDiffPruning, DefaultVisionTransformerTeacher,  # noqa: F401
+                                  default_dynamic_vit_tiny_patch16_224_student, default_dynamic_vit_small_patch16_224_student,
+                                  default_dynamic_vit_base_patch16_224_student, default_dynamic_vit_tiny_patch16_224_teacher,
+                                  default_dynamic_vit_small_patch16_224_teacher, default_dynamic_vit_base_patch16_224_teacher)

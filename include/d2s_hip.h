@@ -248,6 +248,12 @@ int d2s_attn_policy_fwd_f32(const float* qkv, const float* policy, float* out, f
                             int H, float scale, float eps, d2s_stream_t stream);
 int d2s_attn_policy_bwd_f32(const float* qkv, const float* policy, const float* out, const float* dout, const float* lse,
                             const float* cinv, float* dqkv, float* delta_ws, int B, int n, int H, float scale, d2s_stream_t stream);
+/* d2s_attn_policy_bwd_f32 plus the gradient of the (real-valued) policy, for the DynamicViT baseline (vit_models/default_dynamic_vit.py:
+ * 185-199, 454-458): dpolicy [B,n] = sum_h sum_{i != j} exp(S_ij - lse_i) (dP_ij - delta_i), column 0 = 0.  dpol_ws: [B,H,n] floats of
+ * scratch.  dqkv is bit for bit that of d2s_attn_policy_bwd_f32; no atomics. */
+int d2s_attn_policy_bwd_dpol_f32(const float* qkv, const float* policy, const float* out, const float* dout, const float* lse,
+                                 const float* cinv, float* dqkv, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H,
+                                 float scale, d2s_stream_t stream);
 /* ragged packed attention forward (inference): qkv [total,3,H,64], image b = rows cu[b]..cu[b+1]; cls_row (optional) [H,total] */
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, d2s_stream_t stream);
@@ -379,6 +385,28 @@ int d2s_block_bwd_f32_dp(const float* gy, const float* x, const float* saved, co
                          const float* s_attn, const float* s_mlp, int B, int n, int D, int H, int hidden, float scale, float* dx,
                          float* const* dparams, float* scratch, int mode, void* workspace, size_t workspace_bytes, void* wgrad_workspace,
                          size_t wgrad_workspace_bytes, d2s_stream_t wgrad_stream, d2s_stream_t stream);
+
+
+/* ---- DynamicViT baseline (vit_models/default_dynamic_vit.py): decision and predictor kernels ------------------------------------ */
+/* out[0..n) = Gumbel(0,1) = -log(-log(u)) numbers of the counter-based stream `seed` (the noise of F.gumbel_softmax, :454) */
+int d2s_gumbel_noise(float* out, long n, unsigned long long seed, d2s_stream_t stream);
+/* the conversion d2s_gumbel_noise applies to each 32-bit draw, alone: out[i] from bits[i]; finite for every input (u in [2^-24, 1 - 2^-24]) */
+int d2s_gumbel_from_bits(const unsigned* bits, float* out, long n, d2s_stream_t stream);
+/* z, g [M,2], prev [M] -> logp = log_softmax(z) [M,2], y0 = softmax(logp + g)_0, hard = (logp_0 + g_0 >= logp_1 + g_1), decision = hard * prev */
+int d2s_gumbel_keep_fwd(const float* z, const float* g, const float* prev, float* logp, float* y0, float* hard, float* decision, long M,
+                        d2s_stream_t stream);
+/* straight-through backward: dz [M,2] (w.r.t. the raw logits z) = (+-) gd * prev * y0 (1 - y0), dprev = gd * hard */
+int d2s_gumbel_keep_bwd(const float* gd, const float* prev, const float* y0, const float* hard, float* dz, float* dprev, long M,
+                        d2s_stream_t stream);
+/* PredictorLG's policy-weighted pooling (:327-329): x [B,N,C], p [B,N] -> out [B,N,C] (lower half copied, upper half = sum_j x p / sum p);
+ * psum [B], glob [B,C/2] are kept for the backward, which returns dx [B,N,C] and dp [B,N]; gsum_ws: [B,C/2] floats of scratch */
+int d2s_policy_pool_fwd(const float* x, const float* p, float* out, float* psum, float* glob, int B, int N, int C, d2s_stream_t stream);
+int d2s_policy_pool_bwd(const float* gout, const float* x, const float* p, const float* psum, const float* glob, float* dx, float* dp,
+                        float* gsum_ws, int B, int N, int C, d2s_stream_t stream);
+/* ratio term of the DynamicViT objective: d [B,N] keep decisions -> loss_row [B] = (mean_j d - rho)^2, diff [B] = mean_j d - rho */
+int d2s_ratio_rows_fwd(const float* d, float rho, float* loss_row, float* diff, int B, int N, d2s_stream_t stream);
+/* its backward: grad [B,N] = g[0] * scale * 2 diff[b] / N, g a device scalar */
+int d2s_ratio_rows_bwd(const float* diff, const float* g, float scale, float* grad, int B, int N, d2s_stream_t stream);
 
 #ifdef __cplusplus
 }
