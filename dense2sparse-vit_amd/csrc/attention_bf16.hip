@@ -9,6 +9,21 @@
 // The 32x32x16 MFMA wants 8 CONSECUTIVE reduction indices per lane half; the accumulator hands a lane keys {0-3, 8-11} (half 0) /
 // {4-7, 12-15} (half 1) of each 16-key block.  A reduction may be walked in any order, so V^T is stored in LDS with its keys permuted
 // to that order (pos(key)) and both operands agree.
+//
+// POLICY (the 32-key-tile forward, dQ and dK/dV; the 64-key-tile forward has no policy form): Attention.softmax_with_policy
+// (vit_models/dynamic_vit.py:195-214) fused into the same passes, the math of the fp32 POLICY kernels (attention_f32.hip) in this file's
+// orientation:  mk_ij = (i == j) ? 1 : policy[b, j] (real-valued, 0/1 is not assumed; column 0 is the CLS key);
+//     e_ij = 2^(s log2 e - m log2 e) mk_ij with the running maximum m over ALL real keys, masked ones included; l_i = sum_j e_ij; the bf16 P
+//     that the MFMA multiplies is the masked e;  O_i = (acc_i + (eps/n) vsum) * 1 / (l_i + eps), vsum[d] = the column sum over the n keys of
+//     the bf16-rounded V, folded out of the V tiles on their way to LDS (per thread in ascending key order, then 32 partials in ascending
+//     order: no atomics);  lse_i = m_i + log(l_i + eps), cinv_i = (eps/n) / (l_i + eps);  CLS row (e_0j mk_0j + eps/n) / (l_0 + eps).
+//     With an all-ones policy and eps = 0 every factor is 1 and every addend 0: the bits of the plain kernel.
+//   backward:  P~_ij = exp(S_ij - lse_i);  dS_ij = P~_ij mk_ij (dP_ij - delta_i);  dV uses P~_ij mk_ij + cinv_i;
+//     DPOL: dpolicy[b, j] = sum_h sum_{i != j} P~_ij (dP_ij - delta_i) - the key-owning lane walks the queries in ascending tile order into
+//     [B, H, n] partials, an ordered fold over the heads follows, column 0 = 0; a masked key keeps its non-zero dpolicy, nothing is skipped.
+//     As in the fp32 kernels the O(eps) gradient through the row maximum (which the reference's autograd carries because it does not
+//     detach the max) is left out: it is <= eps = 1e-6 relative.
+// The policy arguments are a variadic tail of each kernel, so the mask-free instantiations keep their argument lists and instructions.
 #include "d2s_common.h"
 #include <cstdlib>
 
@@ -41,12 +56,32 @@ __device__ __forceinline__ void load8(const __bf16* __restrict__ p, f32x4 (&r)[2
     for (int j = 0; j < 4; ++j) { r[0][j] = (float)v[j]; r[1][j] = (float)v[4 + j]; }
 }
 
-template <typename QT>
+// the variadic tails of the POLICY instantiations
+struct AttnPolFwd { const float* policy; float* cinv; float eps; };
+struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
+template <typename T>
+__device__ __forceinline__ T tail_arg(T a) { return a; }
+// mk of the 16 keys a lane holds in accumulator order (registers 4g .. 4g+3 = tile rows 8g + 4 half + 0..3) from the tile's policy in LDS.
+// A wave's 32 queries start at a multiple of 32, so the diagonal i == j lies in one key tile only (diag_tile, wave-uniform), at row l31.
+__device__ __forceinline__ void tile_policy(const float* __restrict__ pol_s, int half, int l31, bool diag_tile, f32x4 (&pg)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pg[g] = *reinterpret_cast<const f32x4*>(&pol_s[8 * g + 4 * half]);
+    if (diag_tile) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (mfma32_row(r, half) == l31) pg[r >> 2][r & 3] = 1.f;
+    }
+}
+
+template <typename QT, bool POLICY = false, typename... Pol>
 __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restrict__ qkv, float* __restrict__ out,
                                                                __bf16* __restrict__ out16, float* __restrict__ lse, float* __restrict__ cls_row, int n, int H,
-                                                               float scale) {
+                                                               float scale, Pol... pol_) {
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];      // [key][d]
     __shared__ __attribute__((aligned(16))) __bf16 Vt[DH * VP];      // [d][pos(key)]
+    __shared__ __attribute__((aligned(16))) float pol_s[POLICY ? 32 : 1];            // the tile's policy
+    __shared__ __attribute__((aligned(16))) float vred[POLICY ? 32 * DH : 1];        // [staging key row][d] partial column sums of V
+    __shared__ float vsum_s[POLICY ? DH : 1];                                        // (eps/n) * column sums of V
     extern __shared__ __attribute__((aligned(16))) float cls_s[];    // [n] raw scaled scores of query 0 (block 0 only)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     int bx, by;
@@ -59,6 +94,15 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const int q0 = bx * 128 + wave * 32;
     const bool active = q0 < n;
     const bool want_cls = cls_row != nullptr && bx == 0 && wave == 0;
+    const float* polb = nullptr;
+    float* cinv = nullptr;
+    float eps = 0.f;
+    if constexpr (POLICY) {
+        const AttnPolFwd pa = tail_arg(pol_...);
+        polb = pa.policy + (long)b * n;
+        cinv = pa.cinv;
+        eps = pa.eps;
+    }
 
     // B operand of S^T = K Q^T: this lane's query, d = 16 kk + 8 half + j, scaled, as bf16 (scale = 2^-3 for 64-wide heads: the product
     // is exact, so fp32 and bf16 qkv inputs round to the same operand).  The softmax is evaluated as 2^(s log2 e - m log2 e): one FMA and
@@ -88,10 +132,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const int skey = tid >> 3, sd8 = (tid & 7) * 8;
     const int ntiles = (n + 31) / 32;
     f32x4 kr[2], vr[2];
+    float pr = 0.f;                              // POLICY: policy of key t * 32 + (tid & 31)
+    f32x4 vacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // POLICY: this thread's 8 columns of V summed over its key rows
     auto fetch = [&](int t) {
         const long row = min(t * 32 + skey, n - 1);
         load8(kb + row * ld + sd8, kr);
         load8(vb + row * ld + sd8, vr);
+        if constexpr (POLICY) { const int kj = t * 32 + (tid & 31); const float p0 = polb[min(kj, n - 1)]; pr = kj < n ? p0 : 0.f; }
     };
     fetch(0);
     for (int t = 0; t < ntiles; ++t) {
@@ -106,6 +153,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
             for (int j = 0; j < 4; ++j) {
                 Vt[(sd8 + j) * VP + pos] = (__bf16)vr[0][j];
                 Vt[(sd8 + 4 + j) * VP + pos] = (__bf16)vr[1][j];
+            }
+            if (POLICY) {
+                if (tid < 32) pol_s[tid] = pr;
+                if (t * 32 + skey < n) {         // rows past the sequence are clamped copies of the last key: not summed
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { vacc[0][j] += (float)(__bf16)vr[0][j]; vacc[1][j] += (float)(__bf16)vr[1][j]; }
+                }
             }
         }
         __syncthreads();
@@ -140,9 +194,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
         const float m_new = fmaxf(m_run, mt);
         const float m2 = m_new * L2E;
         float rs = 0.f;
+        f32x4 pg[4];
+        if (POLICY) tile_policy(pol_s, half, l31, kv0 == q0, pg);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -m2));
+            if (POLICY) s[r] *= pg[r >> 2][r & 3];      // keys past the sequence: e = 0 already
             rs += s[r];
         }
         rs += __shfl_xor(rs, 32, 64);
@@ -170,9 +227,23 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
                 o[dt] = mfma_bf16(vf, pf[kk], o[dt]);      // o[dt][r] = O^T[d = 32 dt + row(r, half)][query = l31]
             }
     }
+    float c = 0.f;
+    if constexpr (POLICY) {      // fold the 32 staging rows' partial column sums -> vsum_s[64] = (eps/n) * sum_key V[key][d]
+        c = eps / (float)n;
+        *reinterpret_cast<f32x4*>(&vred[skey * DH + sd8]) = vacc[0];
+        *reinterpret_cast<f32x4*>(&vred[skey * DH + sd8 + 4]) = vacc[1];
+        __syncthreads();
+        if (tid < DH) {
+            float tsum = 0.f;
+#pragma unroll
+            for (int g = 0; g < 32; ++g) tsum += vred[g * DH + tid];
+            vsum_s[tid] = tsum * c;
+        }
+        __syncthreads();
+    }
     if (!active) return;
     const bool qok = q0 + l31 < n;
-    const float inv_l = 1.0f / l_run;
+    const float inv_l = 1.0f / (POLICY ? l_run + eps : l_run);
     if (qok) {
         const long po = ((long)b * n + q0 + l31) * H * DH + h * DH;
 #pragma unroll
@@ -181,7 +252,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
             for (int g = 0; g < 4; ++g) {      // registers 4g .. 4g+3 hold d = 32 dt + 8 g + 4 half + 0..3
                 f32x4 v;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = o[dt][4 * g + j] * inv_l;
+                for (int j = 0; j < 4; ++j) v[j] = POLICY ? (o[dt][4 * g + j] + vsum_s[32 * dt + 8 * g + 4 * half + j]) * inv_l : o[dt][4 * g + j] * inv_l;
                 if (out) *reinterpret_cast<f32x4*>(out + po + 32 * dt + 8 * g + 4 * half) = v;
                 if (out16) {      // bf16 copy for the projection GEMM of the bf16 mode (its a_bf16)
                     typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
@@ -191,12 +262,19 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
                     *reinterpret_cast<bf16x4_t*>(out16 + po + 32 * dt + 8 * g + 4 * half) = hv;
                 }
             }
-        if (half == 0) lse[((long)b * H + h) * n + q0 + l31] = m_run + logf(l_run);
+        if (half == 0) {
+            lse[((long)b * H + h) * n + q0 + l31] = m_run + logf(POLICY ? l_run + eps : l_run);
+            if (POLICY) cinv[((long)b * H + h) * n + q0 + l31] = c * inv_l;
+        }
     }
     if (want_cls) {
         const float m0 = __shfl(m_run, 0, 64), il0 = __shfl(inv_l, 0, 64);
         float* cr = cls_row + ((long)b * H + h) * n;
-        for (int j = lane; j < n; j += 64) cr[j] = expf(cls_s[j] - m0) * il0;
+        for (int j = lane; j < n; j += 64) {
+            float e = expf(cls_s[j] - m0);
+            if (POLICY) e = e * (j == 0 ? 1.f : polb[j]) + c;
+            cr[j] = e * il0;
+        }
     }
 }
 
@@ -465,13 +543,15 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[2], float* __restric
 }
 
 // ---- backward, dQ: a lane owns one query; loop over key tiles (S^T, dP^T, dS^T lane-local, dQ^T = K^T dS^T) ------------------------
-template <typename QT>
+template <typename QT, bool POLICY = false, typename... Pol>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                  float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale) {
+                                                                  float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
+                                                                  Pol... pol_) {
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Vs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Kt[DH * VP];
+    __shared__ __attribute__((aligned(16))) float pol_s[POLICY ? 32 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     int bx, by;
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
@@ -494,6 +574,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
     for (int r = 0; r < 16; ++r) { dq[0][r] = 0.f; dq[1][r] = 0.f; }
     const int ntiles = (n + 31) / 32;
     f32x4 kr[2], vr[2];
+    const float* polb = nullptr;
+    float pr = 0.f;                              // POLICY: policy of the staged tile's key tid & 31
+    auto fetch_pol = [&](int row0) {
+        const int kj = row0 + (tid & 31);
+        const float p0 = polb[min(kj, n - 1)];
+        pr = kj < n ? p0 : 0.f;
+    };
+    if constexpr (POLICY) {
+        polb = tail_arg(pol_...) + (long)b * n;
+        fetch_pol(0);
+    }
     stage_rows(kb, ld, 0, n, tid, kr);
     stage_rows(vb, ld, 0, n, tid, vr);
     for (int t = 0; t < ntiles; ++t) {
@@ -501,14 +592,32 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
         put_rows(Ks, tid, kr, 1.0f);
         put_rows(Vs, tid, vr, 1.0f);
         put_rows_t(Kt, tid, kr);
+        if (POLICY && tid < 32) pol_s[tid] = pr;
         __syncthreads();
         const int tn = min(t + 1, ntiles - 1) * 32;
         stage_rows(kb, ld, tn, n, tid, kr);
         stage_rows(vb, ld, tn, n, tid, vr);
+        if (POLICY) fetch_pol(tn);
         if (!active) continue;
         f32x16 s = mma_rows(Ks, qf, l31, half);        // scaled scores^T [key][query]
         const f32x16 dp = mma_rows(Vs, dof, l31, half);  // dP^T[key][query] = sum_d V[key][d] dO[query][d]
         const int kv0 = t * 32;
+        if constexpr (POLICY) {                        // dS^T = P~^T mk (dP^T - delta)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 pg = *reinterpret_cast<const f32x4*>(&pol_s[8 * g + 4 * half]);
+                if (kv0 == q0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (8 * g + 4 * half + j == l31) pg[j] = 1.f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r = 4 * g + j;
+                    s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_i)) * pg[j] * (dp[r] - dl_i);
+                }
+            }
+        } else
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_i)) * (dp[r] - dl_i);      // dS^T = P^T (dP^T - delta)
         if (kv0 + 32 > n) {          // keys past the sequence exist in the last tile only (wave-uniform)
@@ -524,15 +633,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
 }
 
 // ---- backward, dK / dV: a lane owns one key; loop over query tiles ------------------------------------------------------------------
-template <typename QT>
+template <typename QT, bool POLICY = false, bool DPOL = false, typename... Pol>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                   float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale) {
+                                                                   float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
+                                                                   Pol... pol_) {
     __shared__ __attribute__((aligned(16))) __bf16 Qs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Ds[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Qt[DH * VP];
     __shared__ __attribute__((aligned(16))) __bf16 Dt[DH * VP];
     __shared__ float lse_s[32], dl_s[32];
+    __shared__ float ci_s[POLICY ? 32 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     int bx, by;
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
@@ -556,6 +667,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
     const int ntiles = (n + 31) / 32;
     f32x4 qr[2], dr[2];
     float lr, dlr;
+    const float* ci_b = nullptr;
+    float* dpol_part = nullptr;
+    float pol_key = 0.f, cir = 0.f, dpol_acc = 0.f;      // POLICY: this lane's key's policy, the staged query's cinv; DPOL: the column sum
+    if constexpr (POLICY) {
+        const AttnPolBwd pa = tail_arg(pol_...);
+        ci_b = pa.cinv + ((long)b * H + h) * n;
+        dpol_part = pa.dpol_part;
+        pol_key = kok ? pa.policy[(long)b * n + k0 + l31] : 0.f;
+    }
     auto fetch = [&](int row0) {
         stage_rows(qb, ld, row0, n, tid, qr);
         stage_rows(dob, ldo, row0, n, tid, dr);
@@ -563,6 +683,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
         const float l0 = lse_b[qc], d0 = dl_b[qc];
         lr = qi < n ? l0 * L2E : INFINITY;      // queries past the sequence: p = 2^(s log2 e - inf) = 0
         dlr = qi < n ? d0 : 0.f;
+        if constexpr (POLICY) { const float c0 = ci_b[qc]; cir = qi < n ? c0 : 0.f; }
     };
     fetch(0);
     for (int t = 0; t < ntiles; ++t) {
@@ -571,12 +692,25 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
         put_rows(Ds, tid, dr, 1.0f);
         put_rows_t(Qt, tid, qr);
         put_rows_t(Dt, tid, dr);
-        if (tid < 32) { lse_s[tid] = lr; dl_s[tid] = dlr; }
+        if (tid < 32) { lse_s[tid] = lr; dl_s[tid] = dlr; if (POLICY) ci_s[tid] = cir; }
         __syncthreads();
         fetch(min(t + 1, ntiles - 1) * 32);
         if (!active) continue;
         f32x16 s = mma_rows(Qs, kf, l31, half);          // S[query = row(r, half)][key = l31], scaled
         f32x16 dp = mma_rows(Ds, vf, l31, half);         // dP[query][key] = sum_d dO[query][d] V[key][d]
+        if constexpr (POLICY) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qi = mfma32_row(r, half);
+                const bool diag = t * 32 == k0 && qi == l31;      // a wave's 32 keys start at a multiple of 32: one query tile holds the diagonal
+                float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_s[qi]));      // P~; queries past the sequence: 0
+                const float g = dp[r] - dl_s[qi];
+                if (DPOL) dpol_acc += diag ? 0.f : p * g;      // dL/dmk_ij, before the mask multiplies it
+                p *= diag ? 1.f : pol_key;
+                s[r] = p + ci_s[qi];                           // dV sees the eps/n term of every key, masked or not
+                dp[r] = p * g;
+            }
+        } else
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int qi = mfma32_row(r, half);
@@ -590,11 +724,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
         mma_t(Dt, pf, l31, half, dv);                    // dV^T[d][key] += sum_query dO[query][d] P[query][key]
         mma_t(Qt, dsf, l31, half, dk);                   // dK^T[d][key] += sum_query Q[query][d] dS[query][key]
     }
+    if (DPOL && active) {
+        dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
+        if (half == 0 && kok) dpol_part[((long)b * H + h) * n + k0 + l31] = dpol_acc;
+    }
     if (active && kok) {
         const long row = ((long)b * n + k0 + l31) * ld + h * DH;
         store_t(dk, dqkv, dqkv16, row + (long)H * DH, half, scale);
         store_t(dv, dqkv, dqkv16, row + 2L * H * DH, half, 1.0f);
     }
+}
+
+// dpolicy[b, j] = sum_h part[b, h, j], h ascending; column 0 (the CLS key, constant 1 in every policy) gets 0
+__global__ __launch_bounds__(256) void attn_dpol_fold_bf16_kernel(const float* __restrict__ part, float* __restrict__ dpolicy, int B, int n, int H) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * n) return;
+    const long b = i / n, j = i - b * n;
+    float s = 0.f;
+    if (j > 0)
+        for (int h = 0; h < H; ++h) s += part[(b * H + h) * n + j];
+    dpolicy[i] = s;
 }
 
 }  // namespace
@@ -620,6 +769,26 @@ static int attn_bwd_bf16_impl(const QT* qkv, const float* out, const float* dout
     hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<QT>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale);
     return d2s_check_launch();
 }
+
+// Backward of d2s_attn_policy_fwd_bf16: delta, dQ, dK/dV (with the policy's column sums when dpolicy is asked for) and the fold over heads.
+template <typename QT>
+static int attn_policy_bwd_bf16_impl(const QT* qkv, const float* policy, const float* out, const float* dout, const float* lse, const float* cinv,
+                                     float* dqkv, __bf16* dqkv16, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H, float scale,
+                                     hipStream_t stream) {
+    const int rc = d2s_attn_delta(out, dout, delta_ws, B, n, H, stream);
+    if (rc != D2S_OK) return rc;
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    const AttnPolBwd pa{policy, cinv, dpolicy ? dpol_ws : nullptr};
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, true, const float*>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, policy);
+    if (dpolicy) {
+        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, true, true, AttnPolBwd>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, pa);
+        hipLaunchKernelGGL(attn_dpol_fold_bf16_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, stream, dpol_ws, dpolicy, B, n, H);
+    } else {
+        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, true, false, AttnPolBwd>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, pa);
+    }
+    return d2s_check_launch();
+}
+
 extern "C" {
 
 // Same contract as d2s_attn_fwd_f32; Q, K, V rounded to bf16 for the two matrix products (bf16 arithmetic mode).
@@ -674,6 +843,40 @@ int d2s_attn_bwd_bf16_bf16out(const void* qkv, int qkv_is_bf16, const float* out
     if (qkv_is_bf16)
         return attn_bwd_bf16_impl<__bf16>(static_cast<const __bf16*>(qkv), out, dout, lse, dqkv, static_cast<__bf16*>(dqkv_bf16), delta_ws, B, n, H, scale, stream);
     return attn_bwd_bf16_impl<float>(static_cast<const float*>(qkv), out, dout, lse, dqkv, static_cast<__bf16*>(dqkv_bf16), delta_ws, B, n, H, scale, stream);
+}
+
+// Policy attention (d2s_attn_policy_fwd_f32's contract and outputs) on the bf16 matrix cores and the bf16 data path: qkv fp32 or bf16 as in
+// d2s_attn_fwd_bf16_bf16out, out (fp32) and / or out_bf16 written - at least one; the backward needs out.  Always the 32-key-tile kernel.
+// With an all-ones policy and eps = 0 the outputs are the bits of d2s_attn_fwd_bf16_bf16out where that entry uses the same kernel.
+int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, float* out, void* out_bf16, float* lse, float* cinv,
+                             float* cls_row, int B, int n, int H, float scale, float eps, hipStream_t stream) {
+    if (!qkv || !policy || (!out && !out_bf16) || !lse || !cinv || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    const size_t sh = cls_row ? (size_t)n * sizeof(float) : 0;
+    const AttnPolFwd pa{policy, cinv, eps};
+    if (qkv_is_bf16)
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, true, AttnPolFwd>), grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, pa);
+    else
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, true, AttnPolFwd>), grid, block, sh, stream, static_cast<const float*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, pa);
+    return d2s_check_launch();
+}
+
+// Its backward (lse, cinv as that call wrote them; out its fp32 output): dqkv and / or dqkv_bf16 fully written - at least one.  dpolicy
+// (optional) [B, n]: the gradient of the policy, column 0 = 0; it needs dpol_ws, [B, H, n] floats of scratch.  dqkv does not depend on
+// whether dpolicy is asked for; no atomics, two launches are bit-identical.  The kernels address with 64-bit offsets: no panel limit.
+int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, const float* out, const float* dout, const float* lse,
+                             const float* cinv, float* dqkv, void* dqkv_bf16, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H,
+                             float scale, hipStream_t stream) {
+    if (!qkv || !policy || !out || !dout || !lse || !cinv || (!dqkv && !dqkv_bf16) || !delta_ws || (dpolicy && !dpol_ws) || B <= 0 || n <= 0 ||
+        H <= 0)
+        return D2S_ERR_ARG;
+    if (qkv_is_bf16)
+        return attn_policy_bwd_bf16_impl<__bf16>(static_cast<const __bf16*>(qkv), policy, out, dout, lse, cinv, dqkv, static_cast<__bf16*>(dqkv_bf16),
+                                                 delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
+    return attn_policy_bwd_bf16_impl<float>(static_cast<const float*>(qkv), policy, out, dout, lse, cinv, dqkv, static_cast<__bf16*>(dqkv_bf16),
+                                            delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
 }
 
 }  // extern "C"

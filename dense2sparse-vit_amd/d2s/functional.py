@@ -171,8 +171,8 @@ class BlockFn(torch.autograd.Function):
         hidden = fc1w.shape[0]
         # bf16 arithmetic mode: LayerNorm, the attention forward and the fc1 epilogue also emit the bf16 form of what the next GEMM
         # multiplies, and that GEMM reads it instead of converting its fp32 operand (no conversion passes on the forward path)
+        # (a policy block too: policy attention has its bf16 kernels, d2s_attn_policy_fwd_bf16 / _bwd_bf16)
         io = ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and x.is_cuda
-        io_attn = io and policy is None
         ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
         ctx.composite = False
         if policy is None and not io and ops.block_composite_ok(x, heads, hidden):
@@ -196,18 +196,14 @@ class BlockFn(torch.autograd.Function):
             # block at B=128), nothing saved; on the bf16 data path not even the fp32 form of the GEMM inputs
             if io:
                 _, _, _, ln1h = ops.layernorm_fwd_bf16(x, cmap, n1w, n1b, M, D, eps, stats=False, want_f32=False)
-                if io_attn:      # the bf16 attention kernel rounds q, k, v to bf16 anyway: the qkv GEMM writes only that form
-                    qkv = ops.bf16_buffer(M, 3 * D, x.device)
-                    ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
-                else:
-                    qkv = ops.linear_fwd(None, qkvw, qkvb, a16=ln1h)
+                # the bf16 attention kernels round q, k, v to bf16 anyway: the qkv GEMM writes only that form
+                qkv = ops.bf16_buffer(M, 3 * D, x.device)
+                ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
                 del ln1h
-                if io_attn:
+                if policy is None:
                     ao, _, cls_row, aoh = ops.attn_fwd_bf16io(qkv, B, n, heads, scale, want_cls, want_f32=False)
-                elif policy is None:
-                    (ao, _, cls_row), aoh = ops.attn_fwd(qkv, B, n, heads, scale, want_cls), None
                 else:
-                    (ao, _, _, cls_row), aoh = ops.attn_policy_fwd(qkv, policy, B, n, heads, scale, want_cls=want_cls), None
+                    ao, _, _, cls_row, aoh = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, heads, scale, want_cls=want_cls, want_f32=False)
                 del qkv
                 x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x.view(M, D), a16=aoh)
                 del ao, aoh
@@ -240,17 +236,17 @@ class BlockFn(torch.autograd.Function):
             ln1 = ln1h
         else:
             ln1, mean1, rstd1 = ops.layernorm_fwd(x, cmap, n1w, n1b, M, D, eps)
-        if io_attn:          # bf16 qkv only (see the forward-only branch); saved for the backward in that form
+        if io:               # bf16 qkv only (see the forward-only branch); saved for the backward in that form
             qkv = ops.bf16_buffer(M, 3 * D, x.device)
             ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
-        elif io:
-            qkv = ops.linear_fwd(None, qkvw, qkvb, a16=ln1h)
         else:
             qkv = ops.linear_fwd(ln1, qkvw, qkvb)
         del ln1h
         cinv = None
-        if io_attn:
+        if io and policy is None:
             ao, lse, cls_row, aoh = ops.attn_fwd_bf16io(qkv, B, n, heads, scale, want_cls)
+        elif io:    # softmax_with_policy on the bf16 matrix cores; the fp32 output stays for the backward's delta
+            ao, lse, cinv, cls_row, aoh = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, heads, scale, want_cls=want_cls)
         elif policy is None:
             ao, lse, cls_row = ops.attn_fwd(qkv, B, n, heads, scale, want_cls)
         else:   # dynamic keep ratio: softmax_with_policy fused into the attention pass (:195-214)
@@ -321,7 +317,6 @@ class BlockFn(torch.autograd.Function):
         # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
         io = ops.bf16_io() and z.shape[1] % 32 == 0 and D % 32 == 0 and gy.is_cuda
         policy, cinv = ctx.policy
-        io_attn = io and policy is None
         gyh = ops.shadow_take(gy) if io else None
         if gyh is not None:
             gyh = gyh.view(M, D)
@@ -360,11 +355,14 @@ class BlockFn(torch.autograd.Function):
         dqkvh = dpolicy = None
         l1x, l116 = xarg(ln1)
         dqkv_bf16_only = False
+        if io:
+            dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev)
+            dqkv_bf16_only = l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
         if policy is None:
-            if io_attn:
-                dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev)
-                dqkv_bf16_only = l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
             dqkv = ops.attn_bwd(qkv, ao, dao, lse, B, n, heads, scale, dqkv16=dqkvh, want_f32=not dqkv_bf16_only)
+        elif io:
+            dqkv, dpolicy = ops.attn_policy_bwd_bf16io(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale, dqkv16=dqkvh,
+                                                       want_f32=not dqkv_bf16_only, want_dpolicy=ctx.needs_input_grad[17])
         elif ctx.needs_input_grad[17]:      # a policy that wants its gradient (DynamicViT baseline); constant masks keep their launches
             dqkv, dpolicy = ops.attn_policy_bwd_dpol(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale)
         else:
@@ -730,7 +728,11 @@ class AttnCoreFn(torch.autograd.Function):
             out, lse, cls_row = ops.attn_fwd(qkv, B, n, H, scale, want_cls)
             ctx.save_for_backward(qkv, out, lse)
         else:
-            out, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, H, scale, want_cls=want_cls)
+            ctx.bf16 = ops.bf16_io() and qkv.is_cuda      # the arithmetic of BlockFn's policy block in the bf16 mode (fp32 tensors in and out)
+            if ctx.bf16:
+                out, lse, cinv, cls_row, _ = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, H, scale, want_cls=want_cls, want_bf16=False)
+            else:
+                out, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, H, scale, want_cls=want_cls)
             ctx.save_for_backward(qkv, out, lse, cinv, policy)
         ctx.dims = (B, n, H, scale)
         if cls_row is None:
@@ -746,6 +748,9 @@ class AttnCoreFn(torch.autograd.Function):
             dqkv = ops.attn_bwd(qkv, out, g.contiguous(), lse, B, n, H, scale)
         else:
             qkv, out, lse, cinv, policy = ctx.saved_tensors
+            if ctx.bf16:
+                dqkv, dpol = ops.attn_policy_bwd_bf16io(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale, want_dpolicy=ctx.needs_input_grad[6])
+                return (dqkv, None, None, None, None, None, dpol) + (None,) * (ctx.nextra - 1)
             if ctx.needs_input_grad[6]:      # the policy itself is learnt through (DynamicViT baseline): one more column sum in the dK/dV pass
                 dqkv, dpol = ops.attn_policy_bwd_dpol(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
                 return (dqkv, None, None, None, None, None, dpol) + (None,) * (ctx.nextra - 1)

@@ -73,6 +73,8 @@ _SIGS = {
     "d2s_attn_policy_fwd_f32": (I, [P, P, P, P, P, P, I, I, I, F, F]),
     "d2s_attn_policy_bwd_f32": (I, [P, P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_policy_bwd_dpol_f32": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, F]),
+    "d2s_attn_policy_fwd_bf16": (I, [P, I, P, P, P, P, P, P, I, I, I, F, F]),
+    "d2s_attn_policy_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_varlen_fwd_f32": (I, [P, P, P, P, I, I, I, I, F]),
     "d2s_sum_scalar": (I, [P, L, F, P]),
     "d2s_scale_by_scalar": (I, [P, P, F, P, L]),

@@ -980,6 +980,34 @@ def attn_policy_bwd_dpol(qkv, policy, out, dout, lse, cinv, B, n, H, scale):
     return dqkv, dpolicy
 
 
+def attn_policy_fwd_bf16io(qkv, policy, B, n, H, scale, eps=1e-6, want_cls=False, want_f32=True, want_bf16=True):
+    """Policy attention on the bf16 matrix cores (bf16 arithmetic mode): qkv fp32 or bf16 (the qkv GEMM's c16); the fp32 output (the
+    backward needs it), its bf16 copy for the projection GEMM, or both.  -> (out or None, lse, cinv, cls_row, out16 or None)"""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16) and (want_f32 or want_bf16)
+    out = torch.empty((B * n, H * 64), dtype=torch.float32, device=qkv.device) if want_f32 else None
+    out16 = bf16_buffer(B * n, H * 64, qkv.device) if want_bf16 else None
+    lse = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    cinv = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    cls_row = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if want_cls else None
+    lib.call("d2s_attn_policy_fwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(_f32(policy)), lib.ptr(out), lib.ptr(out16),
+             lib.ptr(lse), lib.ptr(cinv), lib.ptr(cls_row), B, n, H, float(scale), float(eps))
+    return out, lse, cinv, cls_row, out16
+
+
+def attn_policy_bwd_bf16io(qkv, policy, out, dout, lse, cinv, B, n, H, scale, dqkv16=None, want_f32=True, want_dpolicy=False):
+    """Backward of attn_policy_fwd_bf16io.  dqkv16: bf16 buffer shaped like qkv that receives a copy of dqkv; want_f32=False (needs dqkv16):
+    only that form is written.  -> (dqkv or None, dpolicy [B, n] with column 0 = 0, or None)"""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
+    assert dqkv16 is None or (dqkv16.dtype == torch.bfloat16 and dqkv16.is_contiguous() and dqkv16.numel() == qkv.numel())
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device) if (want_f32 or dqkv16 is None) else None
+    delta = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    part = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if want_dpolicy else None
+    dpolicy = torch.empty((B, n), dtype=torch.float32, device=qkv.device) if want_dpolicy else None
+    lib.call("d2s_attn_policy_bwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(_f32(policy)), lib.ptr(out), lib.ptr(dout),
+             lib.ptr(lse), lib.ptr(cinv), lib.ptr(dqkv), lib.ptr(dqkv16), lib.ptr(delta), lib.ptr(dpolicy), lib.ptr(part), B, n, H, float(scale))
+    return dqkv, dpolicy
+
+
 def attn_varlen_fwd(qkv, cu, B, total, max_n, H, scale, want_cls=False):
     out = torch.empty((total, H * 64), dtype=torch.float32, device=qkv.device)
     cls_row = torch.empty((H, total), dtype=torch.float32, device=qkv.device) if want_cls else None

@@ -254,6 +254,18 @@ int d2s_attn_policy_bwd_f32(const float* qkv, const float* policy, const float* 
 int d2s_attn_policy_bwd_dpol_f32(const float* qkv, const float* policy, const float* out, const float* dout, const float* lse,
                                  const float* cinv, float* dqkv, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H,
                                  float scale, d2s_stream_t stream);
+/* The same policy attention on the bf16 matrix cores and the bf16 data path (bf16 arithmetic mode): qkv fp32 or bf16 (qkv_is_bf16 != 0) as in
+ * d2s_attn_fwd_bf16_bf16out; out (fp32) and / or out_bf16 [B,n,H*64] written, at least one (a backward needs out: delta = dout . out).
+ * Always the 32-key-tile kernel; with an all-ones policy and eps = 0 the outputs are that kernel's plain bits.  n <= 8192. */
+int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, float* out /* nullable */, void* out_bf16 /* nullable */,
+                             float* lse, float* cinv, float* cls_row /* nullable */, int B, int n, int H, float scale, float eps,
+                             d2s_stream_t stream);
+/* ... and its backward: dqkv (fp32) and / or dqkv_bf16 written in the [B,n,3,H,64] layout, at least one.  dpolicy (nullable) [B,n]: the gradient
+ * of the real-valued policy as in d2s_attn_policy_bwd_dpol_f32, column 0 = 0; dpol_ws: [B,H,n] floats of scratch, required iff dpolicy.  dqkv
+ * does not depend on whether dpolicy is asked for; no atomics, two launches are bit-identical. */
+int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, const float* out, const float* dout, const float* lse,
+                             const float* cinv, float* dqkv /* nullable if dqkv_bf16 */, void* dqkv_bf16 /* nullable */, float* delta_ws,
+                             float* dpolicy /* nullable */, float* dpol_ws, int B, int n, int H, float scale, d2s_stream_t stream);
 /* ragged packed attention forward (inference): qkv [total,3,H,64], image b = rows cu[b]..cu[b+1]; cls_row (optional) [H,total] */
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, d2s_stream_t stream);

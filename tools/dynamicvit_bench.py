@@ -1,4 +1,5 @@
-"""Cost of the DynamicViT baseline step next to the d2s headline step: DeiT-S 224x224, batch 128, exact fp32 GEMMs.
+"""Cost of the DynamicViT baseline step next to the d2s headline step: DeiT-S 224x224, batch 128, exact fp32 GEMMs (or --gemm-mode bf16:
+the bf16 arithmetic mode, where the baseline's policy blocks attend through d2s_attn_policy_fwd_bf16 / _bwd_bf16).
 
 Two TrainStep objects in one process - the d2s student (pruning at block 3, keep 0.5, top-k selection) and the DynamicViT baseline
 (default_dynamic_vit_small_patch16_224_student, stages 3 / 6 / 9 at 0.7 / 0.49 / 0.343, dense training) - timed alternately in rounds of
@@ -9,7 +10,7 @@ Per-launch times of the attention backward's dK/dV kernel with and without the p
 `rocprofv3 --kernel-trace --stats -- python tools/dynamicvit_bench.py --rounds 1`: the baseline's blocks 0-2 launch the mask-free
 instantiation and blocks 3-11 the DPOL one, at the same (B, H, n) = (128, 6, 197).
 
-usage: python tools/dynamicvit_bench.py [--batch 128] [--steps 10] [--rounds 4]
+usage: python tools/dynamicvit_bench.py [--batch 128] [--steps 10] [--rounds 4] [--gemm-mode exact|split|bf16]
 """
 import argparse
 import json
@@ -31,9 +32,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--gemm-mode", choices=["exact", "split", "bf16"], default="exact")
     a = ap.parse_args()
     import vit_models
-    from d2s import synth
+    from d2s import ops, synth
+    ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[a.gemm_mode])
     from d2s.engine import TrainStep
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -64,7 +67,7 @@ def main():
             torch.cuda.synchronize()
             ms[k].append(e0.elapsed_time(e1) / a.steps)
     best = {k: min(v) for k, v in ms.items()}
-    print(json.dumps({"tool": "dynamicvit_bench", "batch": a.batch, "ms_per_step_d2s": [round(v, 3) for v in ms["d2s"]],
+    print(json.dumps({"tool": "dynamicvit_bench", "batch": a.batch, "gemm_mode": a.gemm_mode, "ms_per_step_d2s": [round(v, 3) for v in ms["d2s"]],
                       "ms_per_step_dynamicvit": [round(v, 3) for v in ms["dynamicvit"]],
                       "ratio_best": round(best["dynamicvit"] / best["d2s"], 3),
                       "images_per_s_dynamicvit": round(a.batch / best["dynamicvit"] * 1e3, 1)}))
