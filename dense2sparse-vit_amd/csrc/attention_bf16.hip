@@ -24,6 +24,13 @@
 //     As in the fp32 kernels the O(eps) gradient through the row maximum (which the reference's autograd carries because it does not
 //     detach the max) is left out: it is <= eps = 1e-6 relative.
 // The policy arguments are a variadic tail of each kernel, so the mask-free instantiations keep their argument lists and instructions.
+//
+// VARLEN (the 32-key-tile forward only; no policy, no backward): a ragged packed batch, inference with a dynamic keep ratio
+// (vit_models/dynamic_vit.py:935-949).  Image b owns rows cu[b] .. cu[b+1] of qkv [total, 3, H, 64], of out [total, H*64] and of its bf16
+// copy; n = cu[b+1] - cu[b] is per image and the kernel's n argument is the bound that sized the grid.  A block whose first query lies past
+// its image returns before any barrier (block-uniform).  The CLS softmax row goes to cls_row[h * total + cu[b] + j]; no log-sum-exp is
+// written (forward only).  The arguments are the same kind of variadic tail (AttnVarlen), the code sits under `if constexpr`.  With
+// cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same bits.
 #include "d2s_common.h"
 #include <cstdlib>
 
@@ -59,6 +66,10 @@ __device__ __forceinline__ void load8(const __bf16* __restrict__ p, f32x4 (&r)[2
 // the variadic tails of the POLICY instantiations
 struct AttnPolFwd { const float* policy; float* cinv; float eps; };
 struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
+// the variadic tail of the VARLEN instantiations
+struct AttnVarlen { const int* cu; int total; };
+template <typename... T> struct is_varlen_tail { static constexpr bool value = false; };
+template <> struct is_varlen_tail<AttnVarlen> { static constexpr bool value = true; };
 template <typename T>
 __device__ __forceinline__ T tail_arg(T a) { return a; }
 // mk of the 16 keys a lane holds in accumulator order (registers 4g .. 4g+3 = tile rows 8g + 4 half + 0..3) from the tile's policy in LDS.
@@ -88,7 +99,19 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH;
-    const QT* qb = qkv + (long)b * n * ld + h * DH;
+    constexpr bool VARLEN = is_varlen_tail<Pol...>::value;
+    static_assert(!(POLICY && VARLEN), "the ragged form has no policy");
+    long tok0 = (long)b * n;                       // first token row of the image
+    [[maybe_unused]] long cls0 = 0;                // VARLEN: start of the image's CLS softmax row inside cls_row [H, total]
+    if constexpr (VARLEN) {
+        const AttnVarlen va = tail_arg(pol_...);
+        const int row_base = va.cu[b];
+        n = va.cu[b + 1] - row_base;
+        if (bx * 128 >= n) return;                 // block-uniform, before any barrier: this image has no queries in this tile
+        tok0 = row_base;
+        cls0 = (long)h * va.total + row_base;
+    }
+    const QT* qb = qkv + tok0 * ld + h * DH;
     const QT* kb = qb + (long)H * DH;
     const QT* vb = kb + (long)H * DH;
     const int q0 = bx * 128 + wave * 32;
@@ -245,7 +268,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const bool qok = q0 + l31 < n;
     const float inv_l = 1.0f / (POLICY ? l_run + eps : l_run);
     if (qok) {
-        const long po = ((long)b * n + q0 + l31) * H * DH + h * DH;
+        const long po = (tok0 + q0 + l31) * H * DH + h * DH;
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -262,14 +285,16 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
                     *reinterpret_cast<bf16x4_t*>(out16 + po + 32 * dt + 8 * g + 4 * half) = hv;
                 }
             }
-        if (half == 0) {
-            lse[((long)b * H + h) * n + q0 + l31] = m_run + logf(POLICY ? l_run + eps : l_run);
-            if (POLICY) cinv[((long)b * H + h) * n + q0 + l31] = c * inv_l;
+        if constexpr (!VARLEN) {
+            if (half == 0) {
+                lse[((long)b * H + h) * n + q0 + l31] = m_run + logf(POLICY ? l_run + eps : l_run);
+                if (POLICY) cinv[((long)b * H + h) * n + q0 + l31] = c * inv_l;
+            }
         }
     }
     if (want_cls) {
         const float m0 = __shfl(m_run, 0, 64), il0 = __shfl(inv_l, 0, 64);
-        float* cr = cls_row + ((long)b * H + h) * n;
+        float* cr = cls_row + (VARLEN ? cls0 : ((long)b * H + h) * n);
         for (int j = lane; j < n; j += 64) {
             float e = expf(cls_s[j] - m0);
             if (POLICY) e = e * (j == 0 ? 1.f : polb[j]) + c;
@@ -860,6 +885,27 @@ int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
     else
         hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, true, AttnPolFwd>), grid, block, sh, stream, static_cast<const float*>(qkv), out,
                            static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, pa);
+    return d2s_check_launch();
+}
+
+// Ragged packed batch on the bf16 matrix cores and the bf16 data path (d2s_attn_varlen_fwd_f32's contract; inference with a dynamic keep
+// ratio): qkv [total,3,H,64] fp32 or bf16 as in d2s_attn_fwd_bf16_bf16out, image b = rows cu_seqlens[b] .. cu_seqlens[b+1]; out (fp32)
+// [total,H*64] and / or out_bf16 written - at least one; cls_row (optional) [H,total]: softmax row of each image's first (CLS) token.
+// max_n bounds the longest image (sizes the grid and the CLS row's LDS; any upper bound works).  Always the 32-key-tile kernel: one launch
+// serves images of different lengths.  Forward only, no log-sum-exp.  With equal lengths the outputs are the bits of
+// d2s_attn_fwd_bf16_bf16out where that entry uses the same kernel.
+int d2s_attn_varlen_fwd_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seqlens, float* out, void* out_bf16, float* cls_row, int B,
+                             int total, int max_n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || (!out && !out_bf16) || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
+    dim3 grid((max_n + 127) / 128, B * H), block(256);
+    const size_t sh = cls_row ? (size_t)max_n * sizeof(float) : 0;
+    const AttnVarlen va{cu_seqlens, total};
+    if (qkv_is_bf16)
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, false, AttnVarlen>), grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), static_cast<float*>(nullptr), cls_row, max_n, H, scale, va);
+    else
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, false, AttnVarlen>), grid, block, sh, stream, static_cast<const float*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), static_cast<float*>(nullptr), cls_row, max_n, H, scale, va);
     return d2s_check_launch();
 }
 

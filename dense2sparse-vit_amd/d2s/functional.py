@@ -565,6 +565,23 @@ def ragged_block_forward(xp, cu, B, max_n, params, heads, eps, scale, want_cls=F
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     total, D = xp.shape
     cmap = ops.contiguous_map(total, D)
+    hidden = fc1w.shape[0]
+    if ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and xp.is_cuda:
+        # bf16 data path, the launches of BlockFn's forward-only branch over the packed rows: the bf16 form of what each GEMM multiplies is
+        # the only form written, the residual stream stays fp32
+        _, _, _, ln1h = ops.layernorm_fwd_bf16(xp, cmap, n1w, n1b, total, D, eps, stats=False, want_f32=False)
+        qkv = ops.bf16_buffer(total, 3 * D, xp.device)
+        ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
+        del ln1h
+        ao, cls_rows, aoh = ops.attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, heads, scale, want_cls=want_cls, want_f32=False)
+        del qkv
+        x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=xp, a16=aoh)
+        del ao, aoh
+        _, _, _, ln2h = ops.layernorm_fwd_bf16(x1, cmap, n2w, n2b, total, D, eps, stats=False, want_f32=False)
+        hh = ops.bf16_buffer(total, hidden, xp.device)
+        ops.linear_fwd(None, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, a16=ln2h, c16=hh, want_f32=False)
+        del ln2h
+        return ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh), cls_rows
     ln1, _, _ = ops.layernorm_fwd(xp, cmap, n1w, n1b, total, D, eps, stats=False)
     qkv = ops.linear_fwd(ln1, qkvw, qkvb)
     ao, cls_rows = ops.attn_varlen_fwd(qkv, cu, B, total, max_n, heads, scale, want_cls=want_cls)

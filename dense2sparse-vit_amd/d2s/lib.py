@@ -76,6 +76,7 @@ _SIGS = {
     "d2s_attn_policy_fwd_bf16": (I, [P, I, P, P, P, P, P, P, I, I, I, F, F]),
     "d2s_attn_policy_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_varlen_fwd_f32": (I, [P, P, P, P, I, I, I, I, F]),
+    "d2s_attn_varlen_fwd_bf16": (I, [P, I, P, P, P, P, I, I, I, I, F]),
     "d2s_sum_scalar": (I, [P, L, F, P]),
     "d2s_scale_by_scalar": (I, [P, P, F, P, L]),
     "d2s_mask_agreement": (I, [P, P, I, I, I, P]),

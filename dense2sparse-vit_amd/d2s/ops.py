@@ -1015,6 +1015,18 @@ def attn_varlen_fwd(qkv, cu, B, total, max_n, H, scale, want_cls=False):
     return out, cls_row
 
 
+def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
+    """Ragged attention forward on the bf16 matrix cores (bf16 arithmetic mode): qkv [total, 3*H*64] fp32 or bf16 (the qkv GEMM's c16);
+    always writes the bf16 copy of its output for the projection GEMM.  -> (out or None, cls_row [H, total] or None, out16)"""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
+    out = torch.empty((total, H * 64), dtype=torch.float32, device=qkv.device) if want_f32 else None
+    out16 = bf16_buffer(total, H * 64, qkv.device)
+    cls_row = torch.empty((H, total), dtype=torch.float32, device=qkv.device) if want_cls else None
+    lib.call("d2s_attn_varlen_fwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(cu), lib.ptr(out), lib.ptr(out16),
+             lib.ptr(cls_row), B, total, max_n, H, float(scale))
+    return out, cls_row, out16
+
+
 def sum_scalar(v, scale=1.0):
     out = torch.empty((), dtype=torch.float32, device=v.device)
     lib.call("d2s_sum_scalar", lib.ptr(v), v.numel(), float(scale), lib.ptr(out))

@@ -269,6 +269,12 @@ int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
 /* ragged packed attention forward (inference): qkv [total,3,H,64], image b = rows cu[b]..cu[b+1]; cls_row (optional) [H,total] */
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, d2s_stream_t stream);
+/* The same ragged forward on the bf16 matrix cores and the bf16 data path (bf16 arithmetic mode): qkv fp32 or bf16 (qkv_is_bf16 != 0) as in
+ * d2s_attn_fwd_bf16_bf16out; out (fp32) [total,H*64] and / or out_bf16 written, at least one.  max_n: any upper bound on the longest image,
+ * <= 8192 (sizes the grid).  Always the 32-key-tile kernel; no log-sum-exp (forward only).  With equal lengths the outputs are the bits of
+ * d2s_attn_fwd_bf16_bf16out wherever that entry runs its 32-key-tile kernel. */
+int d2s_attn_varlen_fwd_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seqlens, float* out /* nullable */, void* out_bf16 /* nullable */,
+                             float* cls_row /* nullable */, int B, int total, int max_n, int H, float scale, d2s_stream_t stream);
 
 /* ---- BatchNorm1d over the token rows of [R, C] (the --predictor-bn variant: vit_models/dynamic_vit.py:350-367 BatchNormLayer) ------ */
 size_t d2s_batchnorm_workspace_bytes(long R, int C);
