@@ -633,6 +633,7 @@ class TrainStep:
             "small_predictor": bool(getattr(pred, "small_predictor", False)),
             "predictor_bn": bool(getattr(pred, "use_bn", False)),
             "mask_loss_type": str(getattr(self.args, "mask_loss_type", "")),
+            "fuse_dropped": bool(getattr(s, "fuse_dropped", False)),
             "patch_score_threshold": None if thr is None else float(thr),
             "gemm_mode": int(ops.get_gemm_mode()),
             "drop_path_rate": float(getattr(s, "drop_path_rate", 0.0)),
@@ -675,6 +676,7 @@ class TrainStep:
         theirs.setdefault("drop_path_rate", 0.0)       # checkpoints written before stochastic depth existed were trained without it
         theirs.setdefault("diff_topk", False)          # ... and before the perturbed top-k mode existed: hard selection
         theirs.setdefault("topk_num_samples", 0)
+        theirs.setdefault("fuse_dropped", False)       # ... and before token fusion existed: dropped tokens were discarded
         for k in ours:
             if k not in theirs or theirs[k] != ours[k]:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")

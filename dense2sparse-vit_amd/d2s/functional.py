@@ -506,12 +506,34 @@ class GatherFn(torch.autograd.Function):
         return ops.scatter_unpack(g.contiguous(), kept, ctx.n), None
 
 
-@mode_recorded
-class HeadFn(torch.autograd.Function):
-    """Final LayerNorm + classifier head on the CLS row.  Returns (logits [B,C], features = normed tokens[:, 1:])."""
+class GatherFuseFn(torch.autograd.Function):
+    """GatherFn plus one package token per stage (fuse_dropped): x [B,n,D] whose last t rows are the package
+    tokens of earlier stages, p [B,n-1-t] the stage's keep probabilities (KeepProbsFn), kept / dropped the ids of select_topk ->
+    [B,k+t+2,D] = [CLS | kept | the t package rows | sum_{j in dropped} (p_j / S) x_j].  Returns (dx, dp, None, None, None): the task
+    loss reaches the predictor through dp.  Like GatherFn it works on the fp32 residual stream in every GEMM arithmetic mode."""
 
     @staticmethod
-    def forward(ctx, x, nw, nb, hw, hb, eps):
+    def forward(ctx, x, p, kept, dropped, t):
+        x, p = x.contiguous(), p.contiguous()
+        y, S = ops.gather_fuse_fwd(x, p, kept, dropped, t)
+        ctx.save_for_backward(x, p, S, y, kept, dropped)
+        ctx.t = int(t)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, p, S, y, kept, dropped = ctx.saved_tensors
+        dx, dp = ops.gather_fuse_bwd(g.contiguous(), x, p, S, y, kept, dropped, ctx.t)
+        return dx if _need(ctx, 0) else None, dp if _need(ctx, 1) else None, None, None, None
+
+
+@mode_recorded
+class HeadFn(torch.autograd.Function):
+    """Final LayerNorm + classifier head on the CLS row.  Returns (logits [B,C], features = normed tokens[:, 1:n - tail]); tail: the
+    trailing package rows of a fuse_dropped student, which are normalised with the rest but are no token features."""
+
+    @staticmethod
+    def forward(ctx, x, nw, nb, hw, hb, eps, tail=0):
         B, n, D = x.shape
         M = B * n
         x = x.contiguous()
@@ -523,7 +545,8 @@ class HeadFn(torch.autograd.Function):
         if train:
             ctx.save_for_backward(x, nw, hw, mean, rstd, xn, nb, hb)
             ctx.dims = (B, n, D, C)
-        return logits, xn.view(B, n, D)[:, 1:]
+        ctx.tail = int(tail)
+        return logits, xn.view(B, n, D)[:, 1:n - int(tail)]
 
     @staticmethod
     def backward(ctx, glogits, gfeat):
@@ -532,9 +555,10 @@ class HeadFn(torch.autograd.Function):
         M = B * n
         dev = x.device
         gfull = torch.zeros((B, n, D), dtype=torch.float32, device=dev)
-        if gfeat is not None and n > 1:
+        nf = n - 1 - ctx.tail             # feature rows per image
+        if gfeat is not None and nf > 0:
             gfeat = gfeat.contiguous()
-            ops.copy_rows(gfeat, ops.contiguous_map(B * (n - 1), D), B * (n - 1), D, dst=gfull, dst_map=ops.skip_cls_map(n, D))
+            ops.copy_rows(gfeat, ops.contiguous_map(B * nf, D), B * nf, D, dst=gfull, dst_map=ops.skip_cls_map(n, D, ctx.tail))
         dhw = dhb = None
         if glogits is not None:
             glogits = glogits.contiguous()
@@ -547,7 +571,7 @@ class HeadFn(torch.autograd.Function):
         dnb = ops.grad_buffer(nb) if dnw is not None else None
         ops.layernorm_bwd(x, ops.contiguous_map(M, D), gfull.view(M, D), nw, mean, rstd, gx, None, dnw, dnb, M, D)
         return (gx.view(B, n, D) if _need(ctx, 0) else None, dnw if _need(ctx, 1) else None, dnb if _need(ctx, 2) else None,
-                dhw, dhb, None)
+                dhw, dhb, None, None)
 
 
 def as_policy(policy, B, n):

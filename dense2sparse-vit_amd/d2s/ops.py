@@ -524,9 +524,9 @@ def contiguous_map(rows, D):
     return (rows, 0, D, 0)
 
 
-def skip_cls_map(n, D):
-    """rows of x[:, 1:] inside a contiguous [B, n, D] buffer."""
-    return (n - 1, n * D, D, D)
+def skip_cls_map(n, D, tail=0):
+    """rows of x[:, 1:n - tail] inside a contiguous [B, n, D] buffer."""
+    return (n - 1 - tail, n * D, D, D)
 
 
 def layernorm_fwd(x, rowmap, w, b, rows, D, eps, stats=True):
@@ -622,6 +622,43 @@ def scatter_unpack(g, ids, n):
     dx = torch.empty((B, n, D), dtype=torch.float32, device=g.device)
     lib.call("d2s_scatter_unpack_bwd", lib.ptr(g), lib.ptr(ids), lib.ptr(dx), B, n, k1 - 1, D)
     return dx
+
+
+def _fuse_shapes(x, p, kept, dropped, t):
+    B, n, D = x.shape
+    T, k = n - 1 - int(t), kept.shape[1]
+    assert kept.dtype == torch.int64 and kept.is_contiguous() and dropped.dtype == torch.int64 and dropped.is_contiguous()
+    assert p.shape == (B, T) and kept.shape == (B, k) and dropped.shape == (B, T - k), \
+        f"x {tuple(x.shape)} with t = {t}: p must be [B, {T}], kept [B, k], dropped [B, {T} - k]"
+    return B, n, D, T, k
+
+
+def gather_fuse_fwd(x, p, kept, dropped, t):
+    """x [B,n,D] = [CLS | T scored | t package rows], p [B,T], kept [B,k], dropped [B,T-k] -> (y [B,k+t+2,D], S [B]): the kept-token
+    gather, the package rows copied, and the new package row sum_{j in dropped} (p_j / S) x[:, 1 + j] last"""
+    _f32(x)
+    _f32(p)
+    B, n, D, T, k = _fuse_shapes(x, p, kept, dropped, t)
+    y = torch.empty((B, k + int(t) + 2, D), dtype=torch.float32, device=x.device)
+    S = torch.empty((B,), dtype=torch.float32, device=x.device)
+    lib.call("d2s_gather_fuse_fwd", lib.ptr(x), lib.ptr(p), lib.ptr(kept) if k else None, lib.ptr(dropped) if T - k else None,
+             lib.ptr(y), lib.ptr(S), B, n, int(t), k, D)
+    return y, S
+
+
+def gather_fuse_bwd(g, x, p, S, y, kept, dropped, t):
+    """g [B,k+t+2,D] and what gather_fuse_fwd read and wrote -> (dx [B,n,D], dp [B,T]), every element written by the one launch"""
+    _f32(g)
+    _f32(x)
+    _f32(p)
+    _f32(y)
+    B, n, D, T, k = _fuse_shapes(x, p, kept, dropped, t)
+    assert g.shape == y.shape == (B, k + int(t) + 2, D) and S.shape == (B,)
+    dx = torch.empty((B, n, D), dtype=torch.float32, device=g.device)
+    dp = torch.empty((B, T), dtype=torch.float32, device=g.device)
+    lib.call("d2s_gather_fuse_bwd", lib.ptr(g), lib.ptr(x), lib.ptr(p), lib.ptr(S), lib.ptr(y), lib.ptr(kept) if k else None,
+             lib.ptr(dropped) if T - k else None, lib.ptr(dx), lib.ptr(dp), B, n, int(t), k, D)
+    return dx, dp
 
 
 def half_mean_concat(x, B, T, C, relu_mask_src=None):

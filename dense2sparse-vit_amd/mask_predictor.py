@@ -38,7 +38,7 @@ _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": 
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
 _NOT_WITH_DYNAMICVIT = (("topk_selection", "--topk-selection"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"),
-                        ("small_predictor", "--small-predictor"), ("predictor_bn", "--predictor-bn"))
+                        ("small_predictor", "--small-predictor"), ("predictor_bn", "--predictor-bn"), ("fuse_dropped", "--fuse-dropped"))
 
 
 def check_supported(args):
@@ -70,6 +70,13 @@ def check_supported(args):
             bad.append("--diff-topk with --patch-score-threshold (the soft gather applies to the fixed-ratio path only)")
         if getattr(args, "topk_samples", 500) < 1:
             bad.append(f"--topk-samples {args.topk_samples} (at least 1)")
+    if getattr(args, "fuse_dropped", False):
+        if not args.topk_selection:
+            bad.append("--fuse-dropped without --topk-selection (the package token is weighted by the score predictor's keep probabilities)")
+        if args.patch_score_threshold is not None:
+            bad.append("--fuse-dropped with --patch-score-threshold (no token is removed there: nothing to fuse)")
+        if getattr(args, "diff_topk", False):
+            bad.append("--fuse-dropped with --diff-topk (the soft gather has no dropped set)")
     if getattr(args, "accum_steps", 1) < 1:
         bad.append(f"--accum-steps {args.accum_steps} (at least 1)")
     if getattr(args, "clip_grad", None) is not None and not args.clip_grad > 0:
@@ -139,6 +146,7 @@ def build_models(args):
                                                    drop_path_rate=getattr(args, "drop_path", 0.0),
                                                    diff_topk=getattr(args, "diff_topk", False),
                                                    topk_num_samples=getattr(args, "topk_samples", 500),
+                                                   fuse_dropped=getattr(args, "fuse_dropped", False),
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)

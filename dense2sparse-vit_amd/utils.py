@@ -168,6 +168,9 @@ def parse_args(argv=None):
                    help='with --topk-selection: train through the perturbed top-k soft gather (sigma decays from --initial-sigma to 0 over '
                         'the epochs); evaluation and the trained model keep the hard top-k')
     p.add_argument('--topk-samples', type=int, default=500, metavar='N', help="noise samples of --diff-topk (the reference's PerturbedTopK default)")
+    p.add_argument('--fuse-dropped', action='store_true', default=False,
+                   help='with --topk-selection: every pruning stage fuses the tokens it drops, weighted by their keep probabilities, into one '
+                        'package token that later stages carry along (training and evaluation alike; no new parameters)')
     p.add_argument('--accum-steps', type=int, default=1, metavar='N',
                    help='one optimiser step per N batches (gradient = mean over the N; effective batch = N x --batch-size x ranks), '
                         'accumulated inside the fused arena step')

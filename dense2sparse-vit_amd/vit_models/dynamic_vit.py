@@ -68,6 +68,12 @@ DIFF_TOPK_THRESHOLD_ERROR = ("diff_topk (perturbed top-k soft gather) applies to
                              "patch_score_threshold")
 DIFF_TOPK_OVERRIDE_ERROR = ("diff_topk cannot replay a recorded selection in training: kept_token_override fixes the ids, the soft gather "
                             "draws its own; set kept_token_override = None or call eval()")
+FUSE_DROPPED_THRESHOLD_ERROR = ("fuse_dropped (one package token per pruning stage) applies to the fixed-ratio path only: with "
+                                "patch_score_threshold no token is removed, there is nothing to fuse")
+FUSE_DROPPED_TOPK_SELECTION_ERROR = ("fuse_dropped needs topk_selection=True: the package token is weighted by the score predictor's keep "
+                                     "probabilities")
+FUSE_DROPPED_DIFF_TOPK_ERROR = ("fuse_dropped cannot be combined with diff_topk: the perturbed top-k soft gather mixes every token into every "
+                                "kept row and has no dropped set")
 
 
 class DropPath(nn.Module):
@@ -425,8 +431,9 @@ class _ViTBase(_DropPathModel, nn.Module):
         return DF.run(DF.EmbedFn, x, self.patch_embed.proj.weight, self.patch_embed.proj.bias, self.cls_token, self.pos_embed,
                                 self.patch_embed.patch_size[0])
 
-    def _head(self, x):
-        return DF.run(DF.HeadFn, x, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.norm.eps)
+    def _head(self, x, tail=0):
+        """tail: trailing rows of x that are package tokens (fuse_dropped) - normalised with the rest, left out of the features"""
+        return DF.run(DF.HeadFn, x, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.norm.eps, tail)
 
 
 class VisionTransformerDiffPruning(_ViTBase):
@@ -437,8 +444,15 @@ class VisionTransformerDiffPruning(_ViTBase):
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., hybrid_backbone=None, norm_layer=None,
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
-                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
+                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, init_n=14 * 14, diff_topk=False,
+                 topk_num_samples=500):
         super().__init__()
+        if fuse_dropped and patch_score_threshold is not None:
+            raise ValueError(FUSE_DROPPED_THRESHOLD_ERROR)
+        if fuse_dropped and diff_topk:
+            raise ValueError(FUSE_DROPPED_DIFF_TOPK_ERROR)
+        if fuse_dropped and not topk_selection:
+            raise ValueError(FUSE_DROPPED_TOPK_SELECTION_ERROR)
         if diff_topk and patch_score_threshold is not None:
             raise ValueError(DIFF_TOPK_THRESHOLD_ERROR)
         if diff_topk and not topk_selection:
@@ -486,6 +500,10 @@ class VisionTransformerDiffPruning(_ViTBase):
         # (detached) until the next forward; off by default so that nothing outlives the step
         self.keep_topk_indicators = False
         self.topk_indicators = []
+        # token fusion (EViT's fused token / SPViT's package token, weighted by this selector's own keep probabilities): every stage
+        # appends sum_{j in dropped} (p_j / sum p) x_j as one extra row, which later stages carry along unscored;
+        # training and eval alike - the pruned inference model carries the package tokens too
+        self.fuse_dropped = bool(fuse_dropped)
         self.unpruned = False
         self.distill = distill
         self.pruning_loc, self.token_ratio = pruning_loc, token_ratio
@@ -528,24 +546,28 @@ class VisionTransformerDiffPruning(_ViTBase):
                 x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
             if i in self.pruning_loc:
                 num_keep_node = int(self.init_n * self.token_ratio[p_count])   # :852
-                pred_logits, pred_score = _scores(self.score_predictor[p_count], x)   # :855
+                carried = p_count if self.fuse_dropped else 0                 # trailing package rows of earlier stages: never scored
+                scored = x[:, :x.shape[1] - carried].contiguous() if carried else x
+                pred_logits, pred_score = _scores(self.score_predictor[p_count], scored)   # :855
                 kept, dropped = DF.select_topk(pred_score, num_keep_node)     # :858-862
                 if self.kept_token_override is not None:
                     kept = self.kept_token_override[p_count].to(device=x.device, dtype=torch.int64).contiguous()
                     assert kept.shape == (x.shape[0], num_keep_node), "override ids must be [B, int(init_n * ratio)]"
-                    keep_mask = DF.ops.patch_keep_mask(kept, x.shape[1] - 1)
+                    keep_mask = DF.ops.patch_keep_mask(kept, scored.shape[1] - 1)
                     dropped = torch.nonzero(keep_mask == 0)[:, 1].reshape(x.shape[0], -1)
                 self.kept_token_indices.append(kept)
                 self.dropped_token_indices.append(dropped)
                 self.pred_logits.append(pred_logits)
                 if soft:                                                     # :896-900
                     x = self._soft_gather(x, pred_logits, num_keep_node, p_count, soft_seed)
+                elif self.fuse_dropped:      # the bits of the predictor's own keep_probs, differentiable: the task loss reaches the scores
+                    x = DF.GatherFuseFn.apply(x, DF.KeepProbsFn.apply(pred_logits), kept, dropped.contiguous(), carried)
                 else:
                     x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
             x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
             self.cls_attns.append(cls_attn[:, :, 1:])
-        logits, features = self._head(x)                                      # :993-1006
+        logits, features = self._head(x, tail=p_count if self.fuse_dropped else 0)   # :993-1006
         if self.training:
             return logits, features, self.pred_logits, self.kept_token_indices   # :1013
         return logits, self.cls_attns, self.pred_logits, self.kept_token_indices  # :1015

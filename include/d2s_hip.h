@@ -148,6 +148,19 @@ int d2s_select_topk(const float* probs, int B, int T, int k, long long* kept, lo
 /* torch.gather(x, 1, [0, kept+1]), vit_models/dynamic_vit.py:907-912 (train) / :954-960 (eval), and its backward */
 int d2s_gather_pack_fwd(const float* x, const long long* ids, float* out, int B, int n, int k, int D, d2s_stream_t stream);
 int d2s_scatter_unpack_bwd(const float* g, const long long* ids, float* dx, int B, int n, int k, int D, d2s_stream_t stream);
+/* token fusion at a pruning stage (no counterpart in the reference): x [B,n,D] = [CLS | T scored tokens | t package
+ * tokens of earlier stages], p [B,T] the stage's keep probabilities, kept [B,k] / dropped [B,T-k] the ascending stage-relative ids of
+ * d2s_select_topk -> y [B,k+t+2,D] = [CLS | kept rows | the t package rows, copied | f], f = sum_{j in dropped} (p_j / S) x[b,1+j],
+ * S[b] = sum_{j in dropped} p_j (written for the backward; an empty dropped set or S = 0 gives f = 0).  One launch, 16-byte accesses,
+ * fixed-order sums, no atomics: bit-identical from run to run.  D: a multiple of 64 up to 1024, n <= 4096 (8 bytes of LDS per
+ * dropped token; an id outside [0, T) gets weight 0 and, in the backward, no row) */
+int d2s_gather_fuse_fwd(const float* x, const float* p, const long long* kept, const long long* dropped, float* y, float* S, int B, int n,
+                        int t, int k, int D, d2s_stream_t stream);
+/* its backward, one launch: g [B,k+t+2,D] and the forward's x, p, S, y (f is read from y's last row) -> dx [B,n,D], dp [B,T].  CLS, kept
+ * and package rows of dx are their rows of g, a dropped row j is (p_j / S) g_f and dp_j = (<x_j, g_f> - <f, g_f>) / S with g_f the last
+ * row of g; dp is 0 at kept ids.  Every element of dx and dp is written exactly once (no memset needed, no atomics) */
+int d2s_gather_fuse_bwd(const float* g, const float* x, const float* p, const float* S, const float* y, const long long* kept,
+                        const long long* dropped, float* dx, float* dp, int B, int n, int t, int k, int D, d2s_stream_t stream);
 /* split / token-mean / concat of the predictor, vit_models/dynamic_vit.py:540-544 (self-adjoint: also its backward) */
 int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, d2s_stream_t stream);
 
