@@ -283,6 +283,18 @@ def _check_names_shapes(what, want, got):
 CHECKPOINT_FORMAT = 1
 
 
+def checkpoint_config(config):
+    """A checkpoint's 'config' with the keys that later features added filled in as the checkpoint's run had them: off."""
+    theirs = dict(config)
+    theirs.setdefault("drop_path_rate", 0.0)       # checkpoints written before stochastic depth existed were trained without it
+    theirs.setdefault("diff_topk", False)          # ... and before the perturbed top-k mode existed: hard selection
+    theirs.setdefault("topk_num_samples", 0)
+    theirs.setdefault("fuse_dropped", False)       # ... and before token fusion existed: dropped tokens were discarded
+    theirs.setdefault("attn_selection", False)     # ... and before attention selection existed: the score predictor selected
+    theirs.setdefault("mean_heads", False)
+    return theirs
+
+
 def adjust_learning_rate(optimizer, model, step, epochs, lr, min_lr, warmup_steps, frozen=()):
     """utils.adjust_learning_rate (utils.py:93-147): cosine schedule, backbone frozen for the first `warmup_steps`
     epochs (requires_grad toggled exactly like the reference), backbone lr = min(0.01 lr, cos) afterwards."""
@@ -496,6 +508,15 @@ class TrainStep:
         self.last_clip = None               # device floats {pre-clip norm, coefficient} of the last clipped optimiser step
         self._norm_sum, self._norm_steps = None, 0
         self.student, self.teacher, self.args = student, teacher, args
+        # a student that selects by its own CLS attention never calls its score predictors: like the early-exit head
+        # they are created for the state-dict keys only, get no gradient, and the optimiser must not move them (no update, no weight decay)
+        self.attn_selection = bool(getattr(student, "attn_selection", False))
+        if self.attn_selection:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with an attention-selecting student: the warm-up epochs train the score "
+                                 "predictors only (train.py:50-53), and attention selection has none to train - pass warmup_steps=0")
+            for p in student.score_predictor.parameters():
+                p.requires_grad_(False)       # listed in self.frozen below: the epoch schedule leaves them alone, AdamW marks their chunks idle
         self.teacher.eval()
         for p in self.teacher.parameters():
             p.requires_grad_(False)
@@ -639,6 +660,8 @@ class TrainStep:
             "drop_path_rate": float(getattr(s, "drop_path_rate", 0.0)),
             "diff_topk": bool(getattr(s, "diff_topk", False)),
             "topk_num_samples": int(getattr(s, "topk_num_samples", 500)) if getattr(s, "diff_topk", False) else 0,
+            "attn_selection": bool(getattr(s, "attn_selection", False)),
+            "mean_heads": bool(getattr(s, "mean_heads", False)) if getattr(s, "attn_selection", False) else False,
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -672,11 +695,7 @@ class TrainStep:
         if not isinstance(sd, dict) or not isinstance(sd.get("config"), dict) or "model" not in sd or "optimizer" not in sd:
             raise lib.D2SError("not a training checkpoint: 'config', 'model' and 'optimizer' are expected (a weights-only file goes "
                                "through --student-checkpoint)")
-        theirs, ours = dict(sd["config"]), self.config()
-        theirs.setdefault("drop_path_rate", 0.0)       # checkpoints written before stochastic depth existed were trained without it
-        theirs.setdefault("diff_topk", False)          # ... and before the perturbed top-k mode existed: hard selection
-        theirs.setdefault("topk_num_samples", 0)
-        theirs.setdefault("fuse_dropped", False)       # ... and before token fusion existed: dropped tokens were discarded
+        theirs, ours = checkpoint_config(sd["config"]), self.config()
         for k in ours:
             if k not in theirs or theirs[k] != ours[k]:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")
@@ -765,7 +784,7 @@ class TrainStep:
             return self._baseline_losses(out_s, out_t, labels, accumulate)
         logits_t, token_t, cls_attn = out_t
         logits_s, token_s, pred_logits, kept = out_s
-        mask_loss = self.mask_loss_fn(pred_logits, cls_attn, kept, self.metrics, accumulate=accumulate)
+        mask_loss = self.mask_loss_fn(pred_logits, cls_attn, kept, self.metrics, accumulate=accumulate, attn_selection=self.attn_selection)
         backbone_loss = self.backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept, labels, self.metrics, accumulate=accumulate)
         loss = mask_loss if self.epoch < self.warmup_steps else backbone_loss + mask_loss     # train.py:50-53
         return loss, dict(mask_loss=mask_loss, backbone_loss=backbone_loss, kept=kept, logits_s=logits_s, token_s=token_s,

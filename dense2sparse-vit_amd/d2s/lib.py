@@ -41,6 +41,7 @@ _SIGS = {
     "d2s_scatter_unpack_bwd": (I, [P, P, P, I, I, I, I]),
     "d2s_gather_fuse_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I]),
     "d2s_gather_fuse_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I]),
+    "d2s_select_cls_attn": (I, [P, I, I, I, I, I, I, I, P, P, P]),
     "d2s_half_mean_concat": (I, [P, P, P, I, I, I]),
     "d2s_im2col_patch": (I, [P, P, I, I, I, I, I]),
     "d2s_fill_cls": (I, [P, P, P, I, I, I]),

@@ -606,6 +606,21 @@ def select_topk(probs, k):
     return kept, dropped
 
 
+def select_cls_attn(cls_row, lead, T, k, mean_heads=False):
+    """cls_row [B,H,n] (a block's CLS softmax row), tokens in columns lead .. lead + T - 1 -> (probs [B,T], kept [B,k], dropped [B,T-k]):
+    max (or mean) over heads, renormalised over the T tokens, and the hard top-k of those probabilities in select_topk's order - one
+    launch"""
+    _f32(cls_row)
+    B, H, n = cls_row.shape
+    T, k = int(T), int(k)
+    probs = torch.empty((B, T), dtype=torch.float32, device=cls_row.device)
+    kept = torch.empty((B, k), dtype=torch.int64, device=cls_row.device)
+    dropped = torch.empty((B, T - k), dtype=torch.int64, device=cls_row.device)
+    lib.call("d2s_select_cls_attn", lib.ptr(cls_row), B, H, n, int(lead), T, k, 1 if mean_heads else 0, lib.ptr(probs),
+             lib.ptr(kept) if k > 0 else None, lib.ptr(dropped) if T - k > 0 else None)
+    return probs, kept, dropped
+
+
 def gather_pack(x, ids):
     _f32(x)
     B, n, D = x.shape

@@ -47,13 +47,16 @@ class MaskLoss(torch.nn.Module):
             mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.KL_PROB_TARGET, target, None, None, B)
         return mask_loss
 
-    def forward(self, pred_logits, cls_attn_weights, kept_token_idx, metrics, accumulate=True):
+    def forward(self, pred_logits, cls_attn_weights, kept_token_idx, metrics, accumulate=True, attn_selection=False):
         """accumulate=False: only the loss of this batch is computed (its running mean / accuracies are NOT advanced); the caller hands
         `self.last` to accumulate() later - the split a captured (hipGraph) step needs: the kernels replay, the host-side running
-        statistics of losses.py:105-119 are advanced once per replay (d2s.engine.TrainStep)."""
+        statistics of losses.py:105-119 are advanced once per replay (d2s.engine.TrainStep).
+        attn_selection: the student selected by its own CLS attention - there is no predictor output to distil, so the
+        KL / MSE term is exactly 0 without a gradient, and mask_acc_i is the agreement of the stage's kept ids with the teacher target's
+        top-k (same recursion, same kernels; only where the student's ids come from differs)."""
         target = ops.teacher_target(cls_attn_weights.contiguous())             # losses.py:76-79
         B = target.shape[0]
-        mask_loss = 0
+        mask_loss = torch.zeros((), dtype=torch.float32, device=target.device) if attn_selection else 0
         mask_accs = [0 for _ in self.keep_ratios]
         if self.patch_score_threshold is not None:
             mask_loss = self._forward_threshold(pred_logits, target, kept_token_idx, mask_accs)
@@ -68,6 +71,14 @@ class MaskLoss(torch.nn.Module):
                 gt_vals = target
             T = gt_vals.shape[1]
             nk = int(T * ratio)                                                               # :132,154
+            if attn_selection:
+                with torch.no_grad():
+                    gt_ids, _ = ops.select_topk(gt_vals, nk)
+                    pm_ids = kept_token_idx[i].contiguous()
+                    if pm_ids.shape[1] != nk:      # init_n is not this model's token count (micro geometries): the same rule at the target's count
+                        pm_ids, _ = ops.select_topk(pred_logits[i].detach().contiguous(), nk)
+                    mask_accs[i] = ops.sum_scalar(ops.mask_agreement(pm_ids, gt_ids, T), 1.0 / float(B * T))
+                continue
             if self.loss_type == "mse":      # :61-73: 100 * mean squared difference between the raw scores and the target; no accuracy
                 mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.MSE_TARGET, target, None, None, B * T / 100.0)
                 continue

@@ -16,6 +16,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --eval-only --resume runs/a/best.pt
     python dense2sparse-vit_amd/mask_predictor.py ... --batch-size 64 --accum-steps 8 --clip-grad 1.0     (512 images per optimiser step)
     python dense2sparse-vit_amd/mask_predictor.py --method dynamicvit --arch deit_small --pruning-locs 3 6 9 --keep-ratios 0.7 0.49 0.343
+    python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --attn-selection [--mean-heads] [--fuse-dropped]     (select by the CLS attention)
 """
 import os
 import sys
@@ -77,6 +78,18 @@ def check_supported(args):
             bad.append("--fuse-dropped with --patch-score-threshold (no token is removed there: nothing to fuse)")
         if getattr(args, "diff_topk", False):
             bad.append("--fuse-dropped with --diff-topk (the soft gather has no dropped set)")
+    if getattr(args, "attn_selection", False):
+        if getattr(args, "method", "d2s") == "dynamicvit":
+            bad.append("--method dynamicvit with --attn-selection (the baseline keeps tokens by its own Gumbel decision and predictor)")
+        if not args.topk_selection:
+            bad.append("--attn-selection without --topk-selection (the CLS attention is ranked by the hard top-k of the fixed-ratio path; "
+                       "the reference's recipe sets both, mask_predictor.py:147-148)")
+        if args.patch_score_threshold is not None:
+            bad.append("--attn-selection with --patch-score-threshold (attention selection applies to the fixed-ratio path only)")
+        if getattr(args, "diff_topk", False):
+            bad.append("--attn-selection with --diff-topk (the perturbed top-k trains the score predictor, which attention selection never calls)")
+        if 0 in list(args.pruning_locs or []):
+            bad.append("--attn-selection with a pruning location of 0 (a stage is scored by the CLS attention of the block before it)")
     if getattr(args, "accum_steps", 1) < 1:
         bad.append(f"--accum-steps {args.accum_steps} (at least 1)")
     if getattr(args, "clip_grad", None) is not None and not args.clip_grad > 0:
@@ -120,6 +133,14 @@ def check_supported(args):
     if args.output_dir and args.torch_optim and not args.eval_only:
         print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
               "loads through --student-checkpoint, it cannot be resumed")
+    if getattr(args, "attn_selection", False):
+        print("Attention: --attn-selection selects tokens by the student's own CLS attention and never calls the score predictors, so the "
+              "predictor warm-up has no meaning (mask_predictor.py:300): --warmup-steps is set to 0"
+              + (" (--mean-heads: mean over heads instead of max)" if args.mean_heads else ""))
+        args.warmup_steps = 0
+    elif args.mean_heads:
+        print("Attention: --mean-heads has no effect without --attn-selection (it chooses how attention selection aggregates the heads, "
+              "losses.py:126)")
     if args.predictor_bn and args.use_ddp:
         print("Attention: --predictor-bn keeps per-rank batch statistics (not synchronised), exactly like the reference")
     if folder:
@@ -147,6 +168,7 @@ def build_models(args):
                                                    diff_topk=getattr(args, "diff_topk", False),
                                                    topk_num_samples=getattr(args, "topk_samples", 500),
                                                    fuse_dropped=getattr(args, "fuse_dropped", False),
+                                                   attn_selection=getattr(args, "attn_selection", False),
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)

@@ -73,7 +73,8 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
                 with torch.no_grad():
                     logits_t, token_t, cls_attn_weights = teacher_model(train_inputs)                    # :40
                 logits_s, token_s, pred_logits, kept_token_idx = model(train_inputs)                     # :43
-                mask_loss = mask_loss_fn(pred_logits, cls_attn_weights, kept_token_idx, metrics)          # :46
+                mask_loss = mask_loss_fn(pred_logits, cls_attn_weights, kept_token_idx, metrics,          # :46
+                                         attn_selection=bool(getattr(model, "attn_selection", False)))
                 backbone_loss = backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept_token_idx, train_labels, metrics)   # :48
                 train_loss = mask_loss if args.step < args.warmup_steps else backbone_loss + mask_loss   # :50-53
             if pending == 0:

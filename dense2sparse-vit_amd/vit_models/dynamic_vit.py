@@ -74,6 +74,13 @@ FUSE_DROPPED_TOPK_SELECTION_ERROR = ("fuse_dropped needs topk_selection=True: th
                                      "probabilities")
 FUSE_DROPPED_DIFF_TOPK_ERROR = ("fuse_dropped cannot be combined with diff_topk: the perturbed top-k soft gather mixes every token into every "
                                 "kept row and has no dropped set")
+ATTN_SELECTION_TOPK_SELECTION_ERROR = ("attn_selection needs topk_selection=True: the CLS attention is ranked by the hard top-k of the fixed-ratio "
+                                       "path (the reference's recipe sets both, mask_predictor.py:147-148)")
+ATTN_SELECTION_THRESHOLD_ERROR = ("attn_selection applies to the fixed-ratio path only: it cannot be combined with patch_score_threshold")
+ATTN_SELECTION_DIFF_TOPK_ERROR = ("attn_selection cannot be combined with diff_topk: the perturbed top-k trains the score predictor, which "
+                                  "attention selection never calls")
+ATTN_SELECTION_BLOCK0_ERROR = ("attn_selection cannot prune at block 0: a stage is scored by the CLS attention of the block before it, and "
+                               "there is no attention before block 0")
 
 
 class DropPath(nn.Module):
@@ -437,7 +444,13 @@ class _ViTBase(_DropPathModel, nn.Module):
 
 
 class VisionTransformerDiffPruning(_ViTBase):
-    """:642-1015 - the student.  Hard top-k by score (argsort path, :858-862), kept-token gather (:907-912)."""
+    """:642-1015 - the student.  Hard top-k by score (argsort path, :858-862), kept-token gather (:907-912).
+
+    attn_selection=True (the branch the reference names at :265 and never connects): the stage at block i ranks its
+    tokens by the CLS attention row that block i - 1 of the same forward returned - max over heads, or the mean with mean_heads=True,
+    renormalised over the stage's scored tokens - instead of by the score predictor.  `score_predictor` is still constructed (state-dict keys
+    and checkpoints are unchanged) and never called; `pred_logits` then holds each stage's attention PROBABILITIES [B, T], detached (not
+    logits: there is no predictor output), and no gradient reaches the attention row through the selection or the fused package token."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, qk_scale=None, representation_size=None,
@@ -457,6 +470,15 @@ class VisionTransformerDiffPruning(_ViTBase):
             raise ValueError(DIFF_TOPK_THRESHOLD_ERROR)
         if diff_topk and not topk_selection:
             raise ValueError("diff_topk needs topk_selection=True: the perturbed top-k acts on the score predictor's keep probabilities")
+        if attn_selection:
+            if not topk_selection:
+                raise ValueError(ATTN_SELECTION_TOPK_SELECTION_ERROR)
+            if patch_score_threshold is not None:
+                raise ValueError(ATTN_SELECTION_THRESHOLD_ERROR)
+            if diff_topk:
+                raise ValueError(ATTN_SELECTION_DIFF_TOPK_ERROR)
+            if 0 in list(pruning_loc or []):
+                raise ValueError(ATTN_SELECTION_BLOCK0_ERROR)
         self._build_trunk(img_size, patch_size, in_chans, num_classes, embed_dim, depth, num_heads, mlp_ratio, qkv_bias, qk_scale,
                           representation_size, drop_rate, attn_drop_rate, drop_path_rate, hybrid_backbone, norm_layer)
         if early_exit:      # :752-758: the head is created (state-dict keys, 'early_exit' parameter group) but no forward path of the
@@ -547,25 +569,33 @@ class VisionTransformerDiffPruning(_ViTBase):
             if i in self.pruning_loc:
                 num_keep_node = int(self.init_n * self.token_ratio[p_count])   # :852
                 carried = p_count if self.fuse_dropped else 0                 # trailing package rows of earlier stages: never scored
-                scored = x[:, :x.shape[1] - carried].contiguous() if carried else x
-                pred_logits, pred_score = _scores(self.score_predictor[p_count], scored)   # :855
-                kept, dropped = DF.select_topk(pred_score, num_keep_node)     # :858-862
+                n_scored = x.shape[1] - 1 - carried
+                if self.attn_selection:      # the CLS row block i - 1 just returned: reduce over heads, renormalise, rank - one launch
+                    pred_logits, kept, dropped = DF.ops.select_cls_attn(prev_cls_row.detach().contiguous(), 1, n_scored, num_keep_node,
+                                                                        self.mean_heads)
+                else:
+                    scored = x[:, :x.shape[1] - carried].contiguous() if carried else x
+                    pred_logits, pred_score = _scores(self.score_predictor[p_count], scored)   # :855
+                    kept, dropped = DF.select_topk(pred_score, num_keep_node)     # :858-862
                 if self.kept_token_override is not None:
                     kept = self.kept_token_override[p_count].to(device=x.device, dtype=torch.int64).contiguous()
                     assert kept.shape == (x.shape[0], num_keep_node), "override ids must be [B, int(init_n * ratio)]"
-                    keep_mask = DF.ops.patch_keep_mask(kept, scored.shape[1] - 1)
+                    keep_mask = DF.ops.patch_keep_mask(kept, n_scored)
                     dropped = torch.nonzero(keep_mask == 0)[:, 1].reshape(x.shape[0], -1)
                 self.kept_token_indices.append(kept)
                 self.dropped_token_indices.append(dropped)
                 self.pred_logits.append(pred_logits)
                 if soft:                                                     # :896-900
                     x = self._soft_gather(x, pred_logits, num_keep_node, p_count, soft_seed)
+                elif self.fuse_dropped and self.attn_selection:      # the package token weighted by the attention probabilities, as a constant
+                    x = DF.GatherFuseFn.apply(x, pred_logits, kept, dropped.contiguous(), carried)
                 elif self.fuse_dropped:      # the bits of the predictor's own keep_probs, differentiable: the task loss reaches the scores
                     x = DF.GatherFuseFn.apply(x, DF.KeepProbsFn.apply(pred_logits), kept, dropped.contiguous(), carried)
                 else:
                     x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
             x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
+            prev_cls_row = cls_attn
             self.cls_attns.append(cls_attn[:, :, 1:])
         logits, features = self._head(x, tail=p_count if self.fuse_dropped else 0)   # :993-1006
         if self.training:

@@ -161,6 +161,14 @@ int d2s_gather_fuse_fwd(const float* x, const float* p, const long long* kept, c
  * row of g; dp is 0 at kept ids.  Every element of dx and dp is written exactly once (no memset needed, no atomics) */
 int d2s_gather_fuse_bwd(const float* g, const float* x, const float* p, const float* S, const float* y, const long long* kept,
                         const long long* dropped, float* dx, float* dp, int B, int n, int t, int k, int D, d2s_stream_t stream);
+/* token selection by the student's own CLS attention (attn_selection; no wired counterpart in the reference):
+ * cls_row [B,H,n] as the attention forward entries write it; token t of image b is column lead + t, 0 <= t < T, lead + T <= n.
+ * w = max over heads (reduce 0) or (sum over h = 0..H-1) / H (reduce 1); probs [B,T] = w / sum_t w, always written; kept [B,k] /
+ * dropped [B,T-k] (dropped may be NULL): the hard top-k of the EMITTED probs in d2s_select_topk's order (value descending, equal values
+ * lowest index first, both lists ascending), so d2s_select_topk(probs, k) reproduces the ids bit for bit.  One launch, one workgroup per
+ * image, fixed-order sums, no atomics: bit-identical from run to run.  T <= 16384, 0 <= k <= T. */
+int d2s_select_cls_attn(const float* cls_row, int B, int H, int n, int lead, int T, int k, int reduce, float* probs, long long* kept,
+                        long long* dropped, d2s_stream_t stream);
 /* split / token-mean / concat of the predictor, vit_models/dynamic_vit.py:540-544 (self-adjoint: also its backward) */
 int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, d2s_stream_t stream);
 
