@@ -1,6 +1,13 @@
 """Autograd glue: one torch.autograd.Function per module of the hot path.  Forward and backward are explicit
 sequences of C-ABI calls (d2s.ops); torch only owns the tensors and the graph.  No torch arithmetic runs here.
 
+The transformer block's seven launches (LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm, fc1 + GELU, fc2 + residual) are
+written once, in block_forward_sequence.  Its three callers: BlockFn.forward without a backward to serve (the frozen teacher, eval),
+BlockFn.forward in training, and ragged_block_forward; in front of it BlockFn keeps the composite path (ops.block_fwd / block_bwd: one
+C-ABI call for the same launches on the fp32 data path).  Which attention entry runs is decided in attn_forward / attn_backward, for
+BlockFn and AttnCoreFn alike; xarg, cls_or_empty and layernorm_backward are the small shared pieces (the latter also serves the
+predictor and Tokens-to-Token Functions of the neighbouring modules).
+
 Reference lines (relative to /root/reference):
   EmbedFn      vit_models/dynamic_vit.py:300-306, 820-823
   BlockFn      vit_models/dynamic_vit.py:263-269 (Block), :216-236 (Attention), :169-175 (Mlp)
@@ -152,6 +159,116 @@ class EmbedFn(torch.autograd.Function):
         return None, dw, db, dcls, dpos, None
 
 
+def bf16_data_path(t, D, hidden):
+    """bf16 arithmetic mode with the bf16 data path on, for a block of these widths: every GEMM input exists in bf16 (section 7 of
+    DESIGN.md); the kernels need multiples of 32."""
+    return ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and t.is_cuda
+
+
+def xarg(t):
+    """A saved layer input is fp32, or bf16 only on the bf16 data path -> the (x, x16) pair the GEMM wrappers take."""
+    return (None, t) if t.dtype == torch.bfloat16 else (t, None)
+
+
+def cls_or_empty(cls_row, device):
+    """A Function returns a tensor in every slot: the placeholder for CLS rows that were not asked for."""
+    return torch.empty((0,), device=device) if cls_row is None else cls_row
+
+
+def layernorm_backward(x, rowmap, dy, w, b, mean, rstd, dx, rows, D, want_w, want_b, add_src=None, relu_mask=False, dx16=None):
+    """ops.layernorm_bwd into `dx`.  The kernel produces the weight and the bias gradient together: both buffers are made when either is
+    wanted.  -> (dx, dw if wanted else None, db if wanted else None)"""
+    dw = ops.grad_buffer(w) if (want_w or want_b) else None
+    db = ops.grad_buffer(b) if dw is not None else None
+    ops.layernorm_bwd(x, rowmap, dy, w, mean, rstd, dx, add_src, dw, db, rows, D, relu_mask=relu_mask, dx16=dx16)
+    return dx, (dw if want_w else None), (db if want_b else None)
+
+
+def attn_forward(qkv, B, n, H, scale, want_cls, policy, io, want_f32=True, want_bf16=True):
+    """The attention forward of a dense [B * n, 3 * H * 64] qkv: plain or softmax_with_policy (:195-214, fused), fp32 kernels or (io) the
+    bf16 matrix cores, which take qkv in fp32 or bf16 and also (or only: want_f32 / want_bf16) write the bf16 form of the output.
+    -> (out or None, lse, cinv or None, cls_row or None, out16 or None)"""
+    if policy is None:
+        if io:
+            out, lse, cls_row, out16 = ops.attn_fwd_bf16io(qkv, B, n, H, scale, want_cls, want_f32=want_f32)
+            return out, lse, None, cls_row, out16
+        out, lse, cls_row = ops.attn_fwd(qkv, B, n, H, scale, want_cls)
+        return out, lse, None, cls_row, None
+    if io:
+        return ops.attn_policy_fwd_bf16io(qkv, policy, B, n, H, scale, want_cls=want_cls, want_f32=want_f32, want_bf16=want_bf16)
+    out, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, H, scale, want_cls=want_cls)
+    return out, lse, cinv, cls_row, None
+
+
+def attn_backward(qkv, out, dout, lse, B, n, H, scale, policy, cinv, io, dqkv16=None, want_f32=True, want_dpolicy=False):
+    """Backward of attn_forward.  dqkv16 (bf16 kernels): bf16 buffer that receives a copy of dqkv, the only form written with
+    want_f32=False.  A constant mask keeps its launches; a policy that is learnt through (DynamicViT baseline) costs one more column sum
+    in the dK/dV pass.  -> (dqkv or None, dpolicy or None)"""
+    if policy is None:
+        return ops.attn_bwd(qkv, out, dout, lse, B, n, H, scale, dqkv16=dqkv16, want_f32=want_f32), None
+    if io:
+        return ops.attn_policy_bwd_bf16io(qkv, policy, out, dout, lse, cinv, B, n, H, scale, dqkv16=dqkv16, want_f32=want_f32,
+                                          want_dpolicy=want_dpolicy)
+    if want_dpolicy:
+        return ops.attn_policy_bwd_dpol(qkv, policy, out, dout, lse, cinv, B, n, H, scale)
+    return ops.attn_policy_bwd(qkv, policy, out, dout, lse, cinv, B, n, H, scale), None
+
+
+def _varlen_attn_forward(qkv, cu, B, max_n, H, scale, want_cls, io, want_f32):
+    """attn_forward's shape for a ragged packed batch (per image through cu_seqlens; forward only, no policy)"""
+    if io:
+        out, cls_rows, out16 = ops.attn_varlen_fwd_bf16io(qkv, cu, B, qkv.shape[0], max_n, H, scale, want_cls=want_cls, want_f32=want_f32)
+        return out, None, None, cls_rows, out16
+    out, cls_rows = ops.attn_varlen_fwd(qkv, cu, B, qkv.shape[0], max_n, H, scale, want_cls=want_cls)
+    return out, None, None, cls_rows, None
+
+
+def _norm_linear(x, cmap, nw, nb, w, b, eps, io, train, epi=None, aux_out=None):
+    """LayerNorm and the Linear that reads it, each written in the one form the data path keeps: fp32, or (io) bf16 only - the bf16
+    attention kernels and the next GEMM round their input to bf16 anyway.  Statistics only when training.
+    -> (LayerNorm output if train else None, Linear output, mean, rstd)"""
+    rows, D = x.shape
+    if io:
+        _, mean, rstd, ln = ops.layernorm_fwd_bf16(x, cmap, nw, nb, rows, D, eps, stats=train, want_f32=False)
+        y = ops.bf16_buffer(rows, w.shape[0], x.device)
+        ops.linear_fwd(None, w, b, epi=epi, aux_out=aux_out, a16=ln, c16=y, want_f32=False)
+    else:
+        ln, mean, rstd = ops.layernorm_fwd(x, cmap, nw, nb, rows, D, eps, stats=train)
+        y = ops.linear_fwd(ln, w, b, epi=epi, aux_out=aux_out)
+    return (ln if train else None), y, mean, rstd
+
+
+def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0):
+    """THE launch sequence of a pre-norm transformer block on [rows, D] tokens: LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm,
+    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward.
+    io: bf16 data path - every GEMM input exists in bf16 only, the residual stream stays fp32.
+    train: keep the LayerNorm statistics, the GELU pre-activation and every layer input for BlockFn.backward; otherwise (the frozen
+    teacher, eval) nothing is kept and each intermediate dies before the next allocation (the pre-activation alone is 155 MB per block at
+    B = 128), on the bf16 data path not even the fp32 form of the attention output is written.
+    attn(qkv, *attn_args, io, want_f32) is attn_forward or a function of its shape.  s_attn / s_mlp: stochastic-depth row scales of the
+    two branches, one per rows_per_group rows.
+    -> (y, cls_row or None, what BlockFn.backward unpacks after x (None unless train), cinv)"""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
+    rows, D = x.shape
+    cmap = ops.contiguous_map(rows, D)
+    ln1, qkv, mean1, rstd1 = _norm_linear(x, cmap, n1w, n1b, qkvw, qkvb, eps, io, train)
+    ao, lse, cinv, cls_row, aoh = attn(qkv, *attn_args, io, train)      # training keeps the fp32 output for the backward's delta
+    if not train:
+        del qkv, lse, cinv
+    x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x, a16=aoh, rowscale=s_attn, rows_per_group=rows_per_group)
+    if not train:
+        del ao, aoh
+    # GELU pre-activation for the backward: fp32, or bf16 on the bf16 data path (what autocast keeps: fc1's output is bf16 there)
+    z = torch.empty((rows, fc1w.shape[0]), dtype=torch.bfloat16 if io else torch.float32, device=x.device) if train else None
+    ln2, h, mean2, rstd2 = _norm_linear(x1, cmap, n2w, n2b, fc1w, fc1b, eps, io, train, ops.EPI_BIAS_GELU, z)
+    hx, h16 = xarg(h)
+    y = ops.linear_fwd(hx, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=h16, rowscale=s_mlp, rows_per_group=rows_per_group)
+    if not train:
+        return y, cls_row, None, None
+    return y, cls_row, (n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
+                        n1b, qkvb, projb, n2b, fc1b, fc2b, aoh), cinv      # aoh: bf16 form of ao (bf16 attention only), proj's weight gradient
+
+
 @mode_recorded
 class BlockFn(torch.autograd.Function):
     """One pre-norm transformer block on a packed [B, n, D] token tensor; also returns the CLS row of the softmax."""
@@ -159,123 +276,39 @@ class BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, heads, eps, want_cls, scale, *extra):
         policy = extra[0] if extra else None         # optional 18th input: keep policy [B, n] of the dynamic-keep-ratio path (or None)
+        train = wants_grad(ctx)
         # optional 19th and 20th input, stochastic depth: the block's two rows [B] of the ops.drop_path_scales table (attention branch, MLP
         # branch; either may be None), non-differentiable.  Only a forward that keeps something for a backward applies them.
-        s_attn, s_mlp = (extra[1], extra[2]) if len(extra) >= 3 else (None, None)
+        s_attn, s_mlp = (extra[1], extra[2]) if (train and len(extra) >= 3) else (None, None)
         ctx.nextra = len(extra)
         B, n, D = x.shape
-        M = B * n
         x = x.contiguous()
         scale = float(_DH) ** -0.5 if scale is None else float(scale)     # Attention.scale = qk_scale or head_dim ** -0.5 (:188)
-        cmap = ops.contiguous_map(M, D)
         hidden = fc1w.shape[0]
-        # bf16 arithmetic mode: LayerNorm, the attention forward and the fc1 epilogue also emit the bf16 form of what the next GEMM
-        # multiplies, and that GEMM reads it instead of converting its fp32 operand (no conversion passes on the forward path)
+        params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
+        # bf16 arithmetic mode: LayerNorm, the attention forward and the fc1 epilogue emit the bf16 form of what the next GEMM multiplies,
+        # and that GEMM reads it instead of converting an fp32 operand (no conversion passes on the forward path)
         # (a policy block too: policy attention has its bf16 kernels, d2s_attn_policy_fwd_bf16 / _bwd_bf16)
-        io = ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and x.is_cuda
+        io = bf16_data_path(x, D, hidden)
         ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
-        ctx.composite = False
-        if policy is None and not io and ops.block_composite_ok(x, heads, hidden):
+        ctx.composite = policy is None and not io and ops.block_composite_ok(x, heads, hidden)
+        if ctx.composite:
             # fp32 data path: the whole block is ONE C-ABI call (csrc/block.hip issues the same seven launches)
-            train = wants_grad(ctx)
-            params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b)
-            y, cls_row, slab = ops.block_fwd(x, params, B, n, D, heads, hidden, eps, scale, want_cls, train,
-                                             s_attn if train else None, s_mlp if train else None)
-            if train:
-                ctx.save_for_backward(x, slab, *params)
-                ctx.drop_path = (s_attn, s_mlp)
-                ctx.composite = True
-                ctx.dims = (B, n, D, heads, scale)
-                ctx.hidden = hidden
-            if cls_row is None:
-                cls_row = torch.empty((0,), device=x.device)
-            ctx.mark_non_differentiable(cls_row)
-            return y, cls_row
-        if not wants_grad(ctx):
-            # forward-only (the frozen teacher under no_grad, eval): no LayerNorm statistics, no GELU pre-activation copy (155 MB per
-            # block at B=128), nothing saved; on the bf16 data path not even the fp32 form of the GEMM inputs
-            if io:
-                _, _, _, ln1h = ops.layernorm_fwd_bf16(x, cmap, n1w, n1b, M, D, eps, stats=False, want_f32=False)
-                # the bf16 attention kernels round q, k, v to bf16 anyway: the qkv GEMM writes only that form
-                qkv = ops.bf16_buffer(M, 3 * D, x.device)
-                ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
-                del ln1h
-                if policy is None:
-                    ao, _, cls_row, aoh = ops.attn_fwd_bf16io(qkv, B, n, heads, scale, want_cls, want_f32=False)
-                else:
-                    ao, _, _, cls_row, aoh = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, heads, scale, want_cls=want_cls, want_f32=False)
-                del qkv
-                x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x.view(M, D), a16=aoh)
-                del ao, aoh
-                _, _, _, ln2h = ops.layernorm_fwd_bf16(x1, cmap, n2w, n2b, M, D, eps, stats=False, want_f32=False)
-                hh = ops.bf16_buffer(M, hidden, x.device)
-                ops.linear_fwd(None, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, a16=ln2h, c16=hh, want_f32=False)
-                del ln2h
-                y = ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh)
-                if cls_row is None:
-                    cls_row = torch.empty((0,), device=x.device)
-                return y.view(B, n, D), cls_row
-            ln1, _, _ = ops.layernorm_fwd(x, cmap, n1w, n1b, M, D, eps, stats=False)
-            qkv = ops.linear_fwd(ln1, qkvw, qkvb)
-            del ln1
-            if policy is None:
-                ao, _, cls_row = ops.attn_fwd(qkv, B, n, heads, scale, want_cls)
-            else:
-                ao, _, _, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, heads, scale, want_cls=want_cls)
-            del qkv
-            x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x.view(M, D))
-            ln2, _, _ = ops.layernorm_fwd(x1, cmap, n2w, n2b, M, D, eps, stats=False)
-            h = ops.linear_fwd(ln2, fc1w, fc1b, epi=ops.EPI_BIAS_GELU)
-            y = ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1)
-            if cls_row is None:
-                cls_row = torch.empty((0,), device=x.device)
-            return y.view(B, n, D), cls_row
-        ln1h = aoh = ln2h = hh = None
-        if io:      # the GEMMs read the bf16 forms and so do the weight gradients: LayerNorm outputs and the GELU activation are kept in bf16 only
-            _, mean1, rstd1, ln1h = ops.layernorm_fwd_bf16(x, cmap, n1w, n1b, M, D, eps, want_f32=False)
-            ln1 = ln1h
+            y, cls_row, slab = ops.block_fwd(x, params, B, n, D, heads, hidden, eps, scale, want_cls, train, s_attn, s_mlp)
+            saved = (slab,) + params
+            ctx.hidden = hidden
         else:
-            ln1, mean1, rstd1 = ops.layernorm_fwd(x, cmap, n1w, n1b, M, D, eps)
-        if io:               # bf16 qkv only (see the forward-only branch); saved for the backward in that form
-            qkv = ops.bf16_buffer(M, 3 * D, x.device)
-            ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
-        else:
-            qkv = ops.linear_fwd(ln1, qkvw, qkvb)
-        del ln1h
-        cinv = None
-        if io and policy is None:
-            ao, lse, cls_row, aoh = ops.attn_fwd_bf16io(qkv, B, n, heads, scale, want_cls)
-        elif io:    # softmax_with_policy on the bf16 matrix cores; the fp32 output stays for the backward's delta
-            ao, lse, cinv, cls_row, aoh = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, heads, scale, want_cls=want_cls)
-        elif policy is None:
-            ao, lse, cls_row = ops.attn_fwd(qkv, B, n, heads, scale, want_cls)
-        else:   # dynamic keep ratio: softmax_with_policy fused into the attention pass (:195-214)
-            ao, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, heads, scale, want_cls=want_cls)
-        x2d = x.view(M, D)
-        x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x2d, a16=aoh, rowscale=s_attn, rows_per_group=n)
-        # GELU pre-activation for the backward: fp32, or bf16 on the bf16 data path (what autocast keeps: fc1's output is bf16 there)
-        z = torch.empty((M, hidden), dtype=torch.bfloat16 if io else torch.float32, device=x.device)
-        if io:
-            _, mean2, rstd2, ln2h = ops.layernorm_fwd_bf16(x1, cmap, n2w, n2b, M, D, eps, want_f32=False)
-            ln2 = ln2h
-            hh = ops.bf16_buffer(M, hidden, x.device)
-            ops.linear_fwd(None, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, aux_out=z, a16=ln2h, c16=hh, want_f32=False)
-            h = hh
-            y = ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh, rowscale=s_mlp, rows_per_group=n)
-        else:
-            ln2, mean2, rstd2 = ops.layernorm_fwd(x1, cmap, n2w, n2b, M, D, eps)
-            h = ops.linear_fwd(ln2, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, aux_out=z)
-            y = ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, rowscale=s_mlp, rows_per_group=n)
-        del ln2h, hh
-        ctx.save_for_backward(x, n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
-                              n1b, qkvb, projb, n2b, fc1b, fc2b, aoh)      # aoh: bf16 form of ao (bf16 attention only), proj's weight gradient
-        ctx.policy = (policy, cinv)
-        ctx.drop_path = (s_attn, s_mlp)
-        ctx.dims = (B, n, D, heads, scale)
-        if cls_row is None:
-            cls_row = torch.empty((0,), device=x.device)
+            y, cls_row, saved, cinv = block_forward_sequence(x.view(B * n, D), params, eps, io, train, attn_forward,
+                                                             (B, n, heads, scale, want_cls, policy), s_attn, s_mlp, n)
+            y = y.view(B, n, D)
+            ctx.policy = (policy, cinv)
+        if train:
+            ctx.save_for_backward(x, *saved)
+            ctx.drop_path = (s_attn, s_mlp)
+            ctx.dims = (B, n, D, heads, scale)
+        cls_row = cls_or_empty(cls_row, x.device)
         ctx.mark_non_differentiable(cls_row)
-        return y.view(B, n, D), cls_row
+        return y, cls_row
 
     @staticmethod
     def _backward_composite(ctx, gy):
@@ -308,14 +341,10 @@ class BlockFn(torch.autograd.Function):
         wants = [_need(ctx, i) for i in range(13)]
         grads = [None] * 13
 
-        new = ops.grad_buffer
-
         # ---- MLP branch ----
-        def xarg(t):      # a saved layer input is fp32, or bf16 only on the bf16 data path
-            return (None, t) if t.dtype == torch.bfloat16 else (t, None)
         hx, h16 = xarg(h)
         # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
-        io = ops.bf16_io() and z.shape[1] % 32 == 0 and D % 32 == 0 and gy.is_cuda
+        io = bf16_data_path(gy, D, z.shape[1])
         policy, cinv = ctx.policy
         gyh = ops.shadow_take(gy) if io else None
         if gyh is not None:
@@ -339,12 +368,9 @@ class BlockFn(torch.autograd.Function):
         grads[9], grads[10] = ops.linear_param_grads(dz, l2x, fc1w, fc1b, wants[9], wants[10], x16=l216, dy16=dzh if dz_bf16_only else None)
         dln2 = ops.linear_dgrad(dz, fc1w, a16=dzh)
         del dzh
-        g1 = torch.empty((M, D), dtype=torch.float32, device=dev)
-        g1h = ops.bf16_buffer(M, D, dev) if (io and ctx.drop_path[0] is None) else None
-        dn2w = new(n2w) if (wants[7] or wants[8]) else None
-        dn2b = new(n2b) if dn2w is not None else None
-        ops.layernorm_bwd(x1, cmap, dln2, n2w, mean2, rstd2, g1, g_res, dn2w, dn2b, M, D, dx16=g1h)
-        grads[7], grads[8] = (dn2w if wants[7] else None), (dn2b if wants[8] else None)
+        g1h = ops.bf16_buffer(M, D, dev) if (io and s_attn is None) else None
+        g1, grads[7], grads[8] = layernorm_backward(x1, cmap, dln2, n2w, n2b, mean2, rstd2, torch.empty((M, D), dtype=torch.float32, device=dev),
+                                                    M, D, wants[7], wants[8], add_src=g_res, dx16=g1h)
         # ---- attention branch ----
         ga = g1
         if s_attn is not None:
@@ -352,32 +378,19 @@ class BlockFn(torch.autograd.Function):
         grads[5], grads[6] = ops.linear_param_grads(ga, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
         dao = ops.linear_dgrad(ga, projw, a16=g1h)
         del g1h
-        dqkvh = dpolicy = None
         l1x, l116 = xarg(ln1)
-        dqkv_bf16_only = False
-        if io:
-            dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev)
-            dqkv_bf16_only = l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
-        if policy is None:
-            dqkv = ops.attn_bwd(qkv, ao, dao, lse, B, n, heads, scale, dqkv16=dqkvh, want_f32=not dqkv_bf16_only)
-        elif io:
-            dqkv, dpolicy = ops.attn_policy_bwd_bf16io(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale, dqkv16=dqkvh,
-                                                       want_f32=not dqkv_bf16_only, want_dpolicy=ctx.needs_input_grad[17])
-        elif ctx.needs_input_grad[17]:      # a policy that wants its gradient (DynamicViT baseline); constant masks keep their launches
-            dqkv, dpolicy = ops.attn_policy_bwd_dpol(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale)
-        else:
-            dqkv = ops.attn_policy_bwd(qkv, policy, ao, dao, lse, cinv, B, n, heads, scale)
+        dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev) if io else None
+        dqkv_bf16_only = io and l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
+        dqkv, dpolicy = attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh, not dqkv_bf16_only,
+                                      policy is not None and ctx.needs_input_grad[17])
         grads[3], grads[4] = ops.linear_param_grads(dqkv, l1x, qkvw, qkvb, wants[3], wants[4], x16=l116, dy16=dqkvh if dqkv_bf16_only else None)
         gx = None
         if wants[0] or wants[1] or wants[2]:
             dln1 = ops.linear_dgrad(dqkv, qkvw, a16=dqkvh)
             del dqkvh
-            gx = torch.empty((M, D), dtype=torch.float32, device=dev)
             gxh = ops.bf16_buffer(M, D, dev) if (io and wants[0]) else None
-            dn1w = new(n1w) if (wants[1] or wants[2]) else None
-            dn1b = new(n1b) if dn1w is not None else None
-            ops.layernorm_bwd(x, cmap, dln1, n1w, mean1, rstd1, gx, g1, dn1w, dn1b, M, D, dx16=gxh)
-            grads[1], grads[2] = (dn1w if wants[1] else None), (dn1b if wants[2] else None)
+            gx, grads[1], grads[2] = layernorm_backward(x, cmap, dln1, n1w, n1b, mean1, rstd1, torch.empty((M, D), dtype=torch.float32, device=dev),
+                                                        M, D, wants[1], wants[2], add_src=g1, dx16=gxh)
             gx = gx.view(B, n, D) if wants[0] else None
             if gxh is not None:
                 ops.shadow_put(gx, gxh)
@@ -450,9 +463,6 @@ class PredictorFn(torch.autograd.Function):
         d = gscores.contiguous().view(M, 1)
         d16 = None                      # bf16 copy of d, written by the LayerNorm backward that produced it, when the next GEMMs run in bf16
         io = ops.bf16_io() and gscores.is_cuda
-
-        def xarg(t):                    # a saved layer input: fp32, or bf16 only (bf16 data path)
-            return (None, t) if t.dtype == torch.bfloat16 else (t, None)
         for j in reversed(range(nl)):
             cur, ln, mean, rstd = saved[5 + 4 * j: 9 + 4 * j]
             lw, lb, fw, fb = params[4 + 4 * j: 8 + 4 * j]
@@ -463,29 +473,22 @@ class PredictorFn(torch.autograd.Function):
             with ops.gemm_mode(ops.GEMM_EXACT if j >= nl - 2 else ops.get_gemm_mode()):      # same arithmetic as the forward of this layer
                 grads[base + 2], grads[base + 3] = ops.linear_param_grads(d, lnx, fw, fb, want[base + 2], want[base + 3], x16=ln16)
                 dln = ops.linear_dgrad(d, fw, a16=d16 if ln16 is not None else None)
-            dcur = torch.empty((M, width), dtype=torch.float32, device=dev)
-            # the layer below (j - 1) multiplies dcur in bf16 if it is a bf16-mode layer: its saved input is bf16 then
+            # the layer below (j - 1) multiplies d in bf16 if it is a bf16-mode layer: its saved input is bf16 then
             below_bf16 = io and j >= 1 and saved[5 + 4 * (j - 1) + 1].dtype == torch.bfloat16 and width % 32 == 0
             d16 = ops.bf16_buffer(M, width, dev) if below_bf16 else None
-            dlw = ops.grad_buffer(lw) if (want[base] or want[base + 1]) else None
-            dlb = ops.grad_buffer(lb) if dlw is not None else None
             # cur is the ReLU output of layer j-1 for j >= 1 -> fold that ReLU's backward in; for j == 0 cur is the
             # split/mean/concat output and the mask is applied by half_mean_concat below
-            ops.layernorm_bwd(cur, ops.contiguous_map(M, width), dln, lw, mean, rstd, dcur, None, dlw, dlb, M, width,
-                              relu_mask=(j >= 1), dx16=d16)
-            grads[base], grads[base + 1] = (dlw if want[base] else None), (dlb if want[base + 1] else None)
-            d = dcur
+            d, grads[base], grads[base + 1] = layernorm_backward(cur, ops.contiguous_map(M, width), dln, lw, lb, mean, rstd,
+                                                                 torch.empty((M, width), dtype=torch.float32, device=dev), M, width,
+                                                                 want[base], want[base + 1], relu_mask=(j >= 1), dx16=d16)
         dz1 = ops.half_mean_concat(d, B, T, C, relu_mask_src=a1)
         h0x, h016 = xarg(h0)
         grads[2], grads[3] = ops.linear_param_grads(dz1, h0x, params[2], params[3], want[2], want[3], x16=h016)
         gx = None
         if _need(ctx, 0) or want[0] or want[1]:
             dh0 = ops.linear_dgrad(dz1, params[2])
-            gx = torch.zeros((B, n, D), dtype=torch.float32, device=dev)
-            dlw = ops.grad_buffer(params[0]) if (want[0] or want[1]) else None
-            dlb = ops.grad_buffer(params[1]) if dlw is not None else None
-            ops.layernorm_bwd(x, ops.skip_cls_map(n, D), dh0, params[0], mean0, rstd0, gx, None, dlw, dlb, M, D)
-            grads[0], grads[1] = (dlw if want[0] else None), (dlb if want[1] else None)
+            gx, grads[0], grads[1] = layernorm_backward(x, ops.skip_cls_map(n, D), dh0, params[0], params[1], mean0, rstd0,
+                                                        torch.zeros((B, n, D), dtype=torch.float32, device=dev), M, D, want[0], want[1])
             if not _need(ctx, 0):
                 gx = None
         return (gx,) + tuple(grads)
@@ -566,12 +569,9 @@ class HeadFn(torch.autograd.Function):
             ops.copy_rows(cls_g, ops.contiguous_map(B, D), B, D, dst=gfull, dst_map=(1, n * D, D, 0))
             cls_rows = ops.copy_rows(xn, (1, n * D, D, 0), B, D) if _need(ctx, 3) else None
             dhw, dhb = ops.linear_param_grads(glogits, cls_rows, hw, hb, _need(ctx, 3), _need(ctx, 4))
-        gx = torch.empty((M, D), dtype=torch.float32, device=dev)
-        dnw = ops.grad_buffer(nw) if (_need(ctx, 1) or _need(ctx, 2)) else None
-        dnb = ops.grad_buffer(nb) if dnw is not None else None
-        ops.layernorm_bwd(x, ops.contiguous_map(M, D), gfull.view(M, D), nw, mean, rstd, gx, None, dnw, dnb, M, D)
-        return (gx.view(B, n, D) if _need(ctx, 0) else None, dnw if _need(ctx, 1) else None, dnb if _need(ctx, 2) else None,
-                dhw, dhb, None, None)
+        gx, dnw, dnb = layernorm_backward(x, ops.contiguous_map(M, D), gfull.view(M, D), nw, nb, mean, rstd,
+                                          torch.empty((M, D), dtype=torch.float32, device=dev), M, D, _need(ctx, 1), _need(ctx, 2))
+        return gx.view(B, n, D) if _need(ctx, 0) else None, dnw, dnb, dhw, dhb, None, None
 
 
 def as_policy(policy, B, n):
@@ -584,35 +584,11 @@ def as_policy(policy, B, n):
 
 def ragged_block_forward(xp, cu, B, max_n, params, heads, eps, scale, want_cls=False):
     """One transformer block on a ragged packed batch [total, D] (inference with a dynamic keep ratio, :935-949: every image keeps its
-    own number of tokens).  LayerNorm and the four GEMMs run over all packed rows at once, attention per image through cu_seqlens.
-    Forward only.  Returns (y [total, D], cls_rows [H, total] or None)."""
-    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
-    total, D = xp.shape
-    cmap = ops.contiguous_map(total, D)
-    hidden = fc1w.shape[0]
-    if ops.bf16_io() and D % 32 == 0 and hidden % 32 == 0 and xp.is_cuda:
-        # bf16 data path, the launches of BlockFn's forward-only branch over the packed rows: the bf16 form of what each GEMM multiplies is
-        # the only form written, the residual stream stays fp32
-        _, _, _, ln1h = ops.layernorm_fwd_bf16(xp, cmap, n1w, n1b, total, D, eps, stats=False, want_f32=False)
-        qkv = ops.bf16_buffer(total, 3 * D, xp.device)
-        ops.linear_fwd(None, qkvw, qkvb, a16=ln1h, c16=qkv, want_f32=False)
-        del ln1h
-        ao, cls_rows, aoh = ops.attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, heads, scale, want_cls=want_cls, want_f32=False)
-        del qkv
-        x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=xp, a16=aoh)
-        del ao, aoh
-        _, _, _, ln2h = ops.layernorm_fwd_bf16(x1, cmap, n2w, n2b, total, D, eps, stats=False, want_f32=False)
-        hh = ops.bf16_buffer(total, hidden, xp.device)
-        ops.linear_fwd(None, fc1w, fc1b, epi=ops.EPI_BIAS_GELU, a16=ln2h, c16=hh, want_f32=False)
-        del ln2h
-        return ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=hh), cls_rows
-    ln1, _, _ = ops.layernorm_fwd(xp, cmap, n1w, n1b, total, D, eps, stats=False)
-    qkv = ops.linear_fwd(ln1, qkvw, qkvb)
-    ao, cls_rows = ops.attn_varlen_fwd(qkv, cu, B, total, max_n, heads, scale, want_cls=want_cls)
-    x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=xp)
-    ln2, _, _ = ops.layernorm_fwd(x1, cmap, n2w, n2b, total, D, eps, stats=False)
-    h = ops.linear_fwd(ln2, fc1w, fc1b, epi=ops.EPI_BIAS_GELU)
-    return ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1), cls_rows
+    own number of tokens): block_forward_sequence, forward only, over all packed rows at once, with attention per image through
+    cu_seqlens.  Returns (y [total, D], cls_rows [H, total] or None)."""
+    io = bf16_data_path(xp, xp.shape[1], params[8].shape[0])
+    y, cls_rows, _, _ = block_forward_sequence(xp, params, eps, io, False, _varlen_attn_forward, (cu, B, max_n, heads, scale, want_cls))
+    return y, cls_rows
 
 
 def rows_map_3d(t):
@@ -765,38 +741,23 @@ class AttnCoreFn(torch.autograd.Function):
         qkv = qkv.contiguous()
         policy = extra[0] if extra else None
         ctx.nextra = len(extra)
-        if policy is None:
-            out, lse, cls_row = ops.attn_fwd(qkv, B, n, H, scale, want_cls)
-            ctx.save_for_backward(qkv, out, lse)
-        else:
-            ctx.bf16 = ops.bf16_io() and qkv.is_cuda      # the arithmetic of BlockFn's policy block in the bf16 mode (fp32 tensors in and out)
-            if ctx.bf16:
-                out, lse, cinv, cls_row, _ = ops.attn_policy_fwd_bf16io(qkv, policy, B, n, H, scale, want_cls=want_cls, want_bf16=False)
-            else:
-                out, lse, cinv, cls_row = ops.attn_policy_fwd(qkv, policy, B, n, H, scale, want_cls=want_cls)
-            ctx.save_for_backward(qkv, out, lse, cinv, policy)
+        # a policy takes the arithmetic of BlockFn's policy block in the bf16 mode (fp32 tensors in and out); plain attention stays fp32
+        ctx.bf16 = policy is not None and ops.bf16_io() and qkv.is_cuda
+        out, lse, cinv, cls_row, _ = attn_forward(qkv, B, n, H, scale, want_cls, policy, ctx.bf16, want_bf16=False)
+        ctx.save_for_backward(qkv, out, lse, *(() if policy is None else (cinv, policy)))
         ctx.dims = (B, n, H, scale)
-        if cls_row is None:
-            cls_row = torch.empty((0,), device=qkv.device)
+        cls_row = cls_or_empty(cls_row, qkv.device)
         ctx.mark_non_differentiable(cls_row)
         return out, cls_row
 
     @staticmethod
     def backward(ctx, g, _gc):
         B, n, H, scale = ctx.dims
-        if len(ctx.saved_tensors) == 3:
-            qkv, out, lse = ctx.saved_tensors
-            dqkv = ops.attn_bwd(qkv, out, g.contiguous(), lse, B, n, H, scale)
-        else:
-            qkv, out, lse, cinv, policy = ctx.saved_tensors
-            if ctx.bf16:
-                dqkv, dpol = ops.attn_policy_bwd_bf16io(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale, want_dpolicy=ctx.needs_input_grad[6])
-                return (dqkv, None, None, None, None, None, dpol) + (None,) * (ctx.nextra - 1)
-            if ctx.needs_input_grad[6]:      # the policy itself is learnt through (DynamicViT baseline): one more column sum in the dK/dV pass
-                dqkv, dpol = ops.attn_policy_bwd_dpol(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
-                return (dqkv, None, None, None, None, None, dpol) + (None,) * (ctx.nextra - 1)
-            dqkv = ops.attn_policy_bwd(qkv, policy, out, g.contiguous(), lse, cinv, B, n, H, scale)
-        return (dqkv, None, None, None, None, None) + (None,) * ctx.nextra
+        qkv, out, lse, *rest = ctx.saved_tensors
+        cinv, policy = rest or (None, None)
+        dqkv, dpol = attn_backward(qkv, out, g.contiguous(), lse, B, n, H, scale, policy, cinv, ctx.bf16,
+                                   want_dpolicy=policy is not None and ctx.needs_input_grad[6])
+        return (dqkv, None, None, None, None, None) + ((dpol,) + (None,) * (ctx.nextra - 1) if ctx.nextra else ())
 
 
 class DropPathFn(torch.autograd.Function):

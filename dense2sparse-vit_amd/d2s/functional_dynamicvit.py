@@ -4,7 +4,7 @@ the 2-way LogSoftmax is fused into the Gumbel keep kernel behind it.  LayerNorm 
 import torch
 
 from . import ops
-from .functional import mode_recorded, wants_grad
+from .functional import layernorm_backward, mode_recorded, wants_grad
 
 
 @mode_recorded
@@ -61,11 +61,8 @@ class DynPredictorFn(torch.autograd.Function):
         gx = None
         if ctx.needs_input_grad[0] or want[0] or want[1]:
             dh0 = ops.linear_dgrad(dz0, w0)
-            gx = torch.zeros((B, n, D), dtype=torch.float32, device=gz.device)
-            dlw = ops.grad_buffer(lnw) if (want[0] or want[1]) else None
-            dlb = ops.grad_buffer(lnb) if dlw is not None else None
-            ops.layernorm_bwd(x, ops.skip_cls_map(n, D), dh0, lnw, mean0, rstd0, gx, None, dlw, dlb, M, D)
-            g[0], g[1] = (dlw if want[0] else None), (dlb if want[1] else None)
+            gx, g[0], g[1] = layernorm_backward(x, ops.skip_cls_map(n, D), dh0, lnw, lnb, mean0, rstd0,
+                                                torch.zeros((B, n, D), dtype=torch.float32, device=gz.device), M, D, want[0], want[1])
             if not ctx.needs_input_grad[0]:
                 gx = None
         return (gx, dpol if ctx.needs_input_grad[1] else None) + tuple(g)

@@ -4,7 +4,7 @@ d2s.functional.PredictorFn with exact-erf GELU (pre-activations are saved, the G
 import torch
 
 from . import ops
-from .functional import mode_recorded
+from .functional import layernorm_backward, mode_recorded
 
 
 @mode_recorded
@@ -59,11 +59,9 @@ class SmallPredictorFn(torch.autograd.Function):
             width = cur.shape[1]
             grads[base + 2], grads[base + 3] = ops.linear_param_grads(d, ln, fw, fb, want[base + 2], want[base + 3])
             dln = ops.linear_dgrad(d, fw)
-            dcur = torch.empty((M, width), dtype=torch.float32, device=dev)
-            dlw = ops.grad_buffer(lw) if (want[base] or want[base + 1]) else None
-            dlb = ops.grad_buffer(lb) if dlw is not None else None
-            ops.layernorm_bwd(cur, ops.contiguous_map(M, width), dln, lw, mean, rstd, dcur, None, dlw, dlb, M, width)
-            grads[base], grads[base + 1] = (dlw if want[base] else None), (dlb if want[base + 1] else None)
+            dcur, grads[base], grads[base + 1] = layernorm_backward(cur, ops.contiguous_map(M, width), dln, lw, lb, mean, rstd,
+                                                                    torch.empty((M, width), dtype=torch.float32, device=dev), M, width,
+                                                                    want[base], want[base + 1])
             if j >= 1:      # cur = gelu(z_{j-1}): gradient w.r.t. the previous layer's pre-activation
                 d = ops.act_grad(dcur, saved[5 + 5 * (j - 1) + 4], "gelu")
             else:
@@ -73,11 +71,8 @@ class SmallPredictorFn(torch.autograd.Function):
         gx = None
         if ctx.needs_input_grad[0] or want[0] or want[1]:
             dh0 = ops.linear_dgrad(dz1, params[2])
-            gx = torch.zeros((B, n, D), dtype=torch.float32, device=dev)
-            dlw = ops.grad_buffer(params[0]) if (want[0] or want[1]) else None
-            dlb = ops.grad_buffer(params[1]) if dlw is not None else None
-            ops.layernorm_bwd(x, ops.skip_cls_map(n, D), dh0, params[0], mean0, rstd0, gx, None, dlw, dlb, M, D)
-            grads[0], grads[1] = (dlw if want[0] else None), (dlb if want[1] else None)
+            gx, grads[0], grads[1] = layernorm_backward(x, ops.skip_cls_map(n, D), dh0, params[0], params[1], mean0, rstd0,
+                                                        torch.zeros((B, n, D), dtype=torch.float32, device=dev), M, D, want[0], want[1])
             if not ctx.needs_input_grad[0]:
                 gx = None
         return (gx,) + tuple(grads)

@@ -10,7 +10,7 @@ Reference lines (relative to /root/reference/vit_models):
 import torch
 
 from . import ops
-from .functional import mode_recorded
+from .functional import layernorm_backward, mode_recorded
 
 
 def _need(ctx, i):
@@ -33,11 +33,9 @@ class LayerNormFn(torch.autograd.Function):
     def backward(ctx, g):
         x2, w, b, mean, rstd = ctx.saved_tensors
         M, D = x2.shape
-        dx = torch.empty_like(x2)
-        dw = ops.grad_buffer(w) if (_need(ctx, 1) or _need(ctx, 2)) else None
-        db = ops.grad_buffer(b) if dw is not None else None
-        ops.layernorm_bwd(x2, ops.contiguous_map(M, D), g.contiguous().view(M, D), w, mean, rstd, dx, None, dw, db, M, D)
-        return dx.view(ctx.shape), (dw if _need(ctx, 1) else None), (db if _need(ctx, 2) else None), None
+        dx, dw, db = layernorm_backward(x2, ops.contiguous_map(M, D), g.contiguous().view(M, D), w, b, mean, rstd, torch.empty_like(x2), M, D,
+                                        _need(ctx, 1), _need(ctx, 2))
+        return dx.view(ctx.shape), dw, db, None
 
 
 class UnfoldFn(torch.autograd.Function):
@@ -87,11 +85,8 @@ def _mlp_tail_bwd(gout, y, saved, n2w, n2b, f1w, f1b, f2w, f2b, want):
     dz = ops.linear_dgrad(gout, f2w, epi=ops.EPI_MUL_GELU_GRAD, aux=z)
     grads[2], grads[3] = ops.linear_param_grads(dz, h2, f1w, f1b, want[2], want[3])
     dh2 = ops.linear_dgrad(dz, f1w)
-    gy = torch.empty((M, E), dtype=torch.float32, device=gout.device)
-    dw = ops.grad_buffer(n2w) if (want[0] or want[1]) else None
-    db = ops.grad_buffer(n2b) if dw is not None else None
-    ops.layernorm_bwd(y, ops.contiguous_map(M, E), dh2, n2w, mean2, rstd2, gy, gout, dw, db, M, E)
-    grads[0], grads[1] = (dw if want[0] else None), (db if want[1] else None)
+    gy, grads[0], grads[1] = layernorm_backward(y, ops.contiguous_map(M, E), dh2, n2w, n2b, mean2, rstd2,
+                                                torch.empty((M, E), dtype=torch.float32, device=gout.device), M, E, want[0], want[1], add_src=gout)
     return gy, grads
 
 
@@ -133,12 +128,9 @@ class TokenPerformerFn(torch.autograd.Function):
         grads[3], grads[4] = ops.linear_param_grads(dkqv, h, kqvw, kqvb, want[3], want[4])
         if want[0] or want[1] or want[2]:
             dh = ops.linear_dgrad(dkqv, kqvw)
-            dx = torch.empty((M, dim), dtype=torch.float32, device=gout.device)
-            dw = ops.grad_buffer(n1w) if (want[1] or want[2]) else None
-            db = ops.grad_buffer(n1b) if dw is not None else None
-            ops.layernorm_bwd(x2, ops.contiguous_map(M, dim), dh, n1w, mean1, rstd1, dx, None, dw, db, M, dim)
+            dx, grads[1], grads[2] = layernorm_backward(x2, ops.contiguous_map(M, dim), dh, n1w, n1b, mean1, rstd1,
+                                                        torch.empty((M, dim), dtype=torch.float32, device=gout.device), M, dim, want[1], want[2])
             grads[0] = dx.view(B, T, dim) if want[0] else None
-            grads[1], grads[2] = (dw if want[1] else None), (db if want[2] else None)
         return tuple(grads)
 
 
@@ -182,10 +174,7 @@ class TokenTransformerFn(torch.autograd.Function):
         grads[3], grads[4] = ops.linear_param_grads(dqkv, h, qkvw, qkvb, want[3], want[4])
         if want[0] or want[1] or want[2]:
             dh = ops.linear_dgrad(dqkv, qkvw)
-            dx = torch.empty((M, dim), dtype=torch.float32, device=gout.device)
-            dw = ops.grad_buffer(n1w) if (want[1] or want[2]) else None
-            db = ops.grad_buffer(n1b) if dw is not None else None
-            ops.layernorm_bwd(x2, ops.contiguous_map(M, dim), dh, n1w, mean1, rstd1, dx, None, dw, db, M, dim)
+            dx, grads[1], grads[2] = layernorm_backward(x2, ops.contiguous_map(M, dim), dh, n1w, n1b, mean1, rstd1,
+                                                        torch.empty((M, dim), dtype=torch.float32, device=gout.device), M, dim, want[1], want[2])
             grads[0] = dx.view(B, T, dim) if want[0] else None
-            grads[1], grads[2] = (dw if want[1] else None), (db if want[2] else None)
         return tuple(grads)

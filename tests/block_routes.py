@@ -1,0 +1,180 @@
+"""What the transformer block's host code does, per configuration, through the public entry points only (DF.run(DF.BlockFn, ...),
+DF.ragged_block_forward, DF.AttnCoreFn.apply): the C-ABI entries it issues (forward, backward), the bytes it saves for the backward and
+its peak of allocated memory.  Shared by tools/gen_block_routes.py, which records tests/golden/block_routes.json, and
+tests/test_block_routes_gpu.py, which compares a fresh recording with it.
+
+Geometry: the block of tests/test_ragged_bf16_gpu.py (D 128, 2 heads, hidden 512), B = 2, n = 33 (one key tile plus a remainder);
+the ragged case packs the lengths (5, 33)."""
+import torch
+
+from tests.test_ragged_bf16_gpu import BLOCK_D, BLOCK_H, SCALE, _block_params, _cu, _t
+
+DEV = "cuda:0"
+B, N = 2, 33
+RAGGED_LENGTHS = (5, 33)
+EPS = 1e-6
+MODES = ("exact", "split", "bf16", "bf16_noio")          # bf16_noio: bf16 arithmetic with the bf16 data path switched off
+
+
+def configurations():
+    """[(name, dict)] in the order they are run"""
+    out = []
+    for mode in MODES:
+        for train in (False, True):
+            for policy in ("none", "const", "grad"):
+                for dp in (False, True):
+                    composites = (True, False) if (mode in ("exact", "split") and policy == "none") else (True,)
+                    for composite in composites:
+                        name = f"block/{mode}/{'train' if train else 'nograd'}/policy_{policy}/{'dp' if dp else 'nodp'}"
+                        out.append((name + ("" if composite else "/percall"),
+                                    dict(kind="block", mode=mode, train=train, policy=policy, dp=dp, composite=composite, grads="all")))
+    for mode in ("exact", "bf16"):          # the backward prunes its launches by what wants a gradient
+        for grads in ("x", "params"):
+            for composite in ((True, False) if mode == "exact" else (True,)):
+                out.append((f"block/{mode}/train/only_{grads}" + ("" if composite else "/percall"),
+                            dict(kind="block", mode=mode, train=True, policy="none", dp=False, composite=composite, grads=grads)))
+    for mode in MODES:
+        for want_cls in (True, False):
+            out.append((f"ragged/{mode}/{'cls' if want_cls else 'nocls'}", dict(kind="ragged", mode=mode, want_cls=want_cls)))
+    for mode in ("exact", "bf16"):
+        for policy in ("none", "const", "grad"):
+            out.append((f"attn/{mode}/policy_{policy}", dict(kind="attn", mode=mode, policy=policy)))
+    return out
+
+
+_HOST = {}
+
+
+def _synth(tag, shape):
+    """a fresh device tensor per call; the values are made once"""
+    from d2s import synth
+    if (tag, shape) not in _HOST:
+        _HOST[tag, shape] = _t(synth.normal(f"routes/{tag}", shape, seed=21))
+    return _HOST[tag, shape].to(DEV)
+
+
+def _params():
+    if "params" not in _HOST:
+        _HOST["params"] = _block_params()
+    return [t.to(DEV) for t in _HOST["params"]]
+
+
+def _policy(kind):
+    if kind == "none":
+        return None
+    p = torch.ones(B, N, device=DEV)
+    p[0, 3::4] = 0.0
+    p[1, 2::3] = 0.0
+    return p.requires_grad_(kind == "grad")
+
+
+def _make_call(cfg):
+    """-> (call, leaves): call() runs the forward and returns (outputs, the output to run the backward from or None); leaves: the named
+    tensors whose .grad the backward fills"""
+    from d2s import functional as DF
+    leaves = {}
+    if cfg["kind"] == "ragged":
+        p = _params()
+        total = sum(RAGGED_LENGTHS)
+        xp, cu = _synth("xr", (total, BLOCK_D)), _cu(RAGGED_LENGTHS).to(DEV)
+
+        def call():
+            with torch.no_grad():
+                y, cls_rows = DF.ragged_block_forward(xp, cu, len(RAGGED_LENGTHS), max(RAGGED_LENGTHS), p, BLOCK_H, EPS, SCALE,
+                                                      want_cls=cfg["want_cls"])
+            return dict(y=y, cls=cls_rows), None
+        return call, leaves
+    policy = _policy(cfg["policy"])
+    if policy is not None and policy.requires_grad:
+        leaves["dpolicy"] = policy
+    if cfg["kind"] == "attn":
+        qkv = _synth("qkv", (B * N, 3 * BLOCK_D)).requires_grad_(True)
+        leaves["dqkv"] = qkv
+        extra = () if policy is None else (policy,)
+
+        def call():
+            out, cls_row = DF.AttnCoreFn.apply(qkv, B, N, BLOCK_H, SCALE, True, *extra)
+            return dict(y=out, cls=cls_row), out
+        return call, leaves
+    x = _synth("x", (B, N, BLOCK_D)).requires_grad_(cfg["grads"] in ("all", "x"))
+    p = [t.requires_grad_(cfg["grads"] in ("all", "params")) for t in _params()]
+    leaves.update(dx=x, **{f"dp{i}": t for i, t in enumerate(p)})
+    rows = (torch.tensor([1.25, 0.0], device=DEV), torch.tensor([0.0, 1.25], device=DEV)) if cfg["dp"] else ()
+    extra = (policy,) + rows if (rows or policy is not None) else ()
+
+    def call():
+        if cfg["train"]:
+            y, cls_row = DF.run(DF.BlockFn, x, *p, BLOCK_H, EPS, True, None, *extra)
+            return dict(y=y, cls=cls_row), y
+        with torch.no_grad():
+            y, cls_row = DF.run(DF.BlockFn, x, *p, BLOCK_H, EPS, True, None, *extra)
+        return dict(y=y, cls=cls_row), None
+    return call, leaves
+
+
+def _run(call, leaves, gy, names):
+    saved = [0]
+
+    def pack(t):
+        saved[0] += t.numel() * t.element_size()
+        return t
+    for t in leaves.values():
+        t.grad = None
+    del names[:]
+    with torch.autograd.graph.saved_tensors_hooks(pack, lambda t: t):
+        outs, root = call()
+    fwd = [s for s in names if s != "d2s_convert_bf16"]          # a weight's bf16 form is made once, on its first use
+    del names[:]
+    if root is not None:
+        if root.grad_fn is None:
+            saved[0] = 0
+        else:
+            torch.autograd.backward([root], [gy])
+    else:
+        saved[0] = 0
+    bwd = [s for s in names if s != "d2s_convert_bf16"]
+    torch.cuda.synchronize()
+    outs.update({k: t.grad for k, t in leaves.items() if t.grad is not None})
+    return dict(forward=fwd, backward=bwd, saved_bytes=saved[0]), outs
+
+
+def record(cfg):
+    """One configuration: a warm-up call, then the measured one from an emptied allocator cache.
+    -> ({forward, backward, saved_bytes, peak_bytes}, {name: output or gradient tensor})"""
+    from d2s import lib, ops
+    mode = {"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT}.get(cfg["mode"], ops.GEMM_BF16)
+    switches = ops._BF16_IO, ops._BLOCK_COMPOSITE
+    names, real = [], lib.call
+
+    def spy(name, *args):
+        names.append(name)
+        return real(name, *args)
+    lib.call = spy
+    try:
+        ops._BF16_IO = cfg["mode"] != "bf16_noio"
+        ops._BLOCK_COMPOSITE = cfg.get("composite", True)
+        call, leaves = _make_call(cfg)
+        gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
+        with ops.gemm_mode(mode):
+            _run(call, leaves, gy, names)
+            for t in leaves.values():
+                t.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            route, outs = _run(call, leaves, gy, names)
+            route["peak_bytes"] = torch.cuda.max_memory_allocated() - base
+    finally:
+        lib.call = real
+        ops._BF16_IO, ops._BLOCK_COMPOSITE = switches
+    return route, outs
+
+
+def record_all():
+    """-> ({name: route}, {name: {tensor name: tensor}})"""
+    routes, tensors = {}, {}
+    for name, cfg in configurations():
+        routes[name], outs = record(cfg)
+        tensors[name] = {k: t.detach().cpu() for k, t in outs.items() if t is not None}
+    return routes, tensors
