@@ -69,6 +69,9 @@ _SIGS = {
     "d2s_gather_rows_i32": (I, [P, P, P, I, I]),
     "d2s_ragged_offsets": (I, [P, I, I, P]),
     "d2s_ragged_pack": (I, [P, P, P, P, P, I, I, I]),
+    "d2s_half_mean_concat_varlen": (I, [P, P, P, I, I]),
+    "d2s_ragged_select_threshold": (I, [P, P, P, F, I, P, P, P, P, I]),
+    "d2s_ragged_repack": (I, [P, P, P, P, P, P, P, I, I]),
     "d2s_mask_row_weights": (I, [P, L, P]),
     "d2s_dense_mask_agreement": (I, [P, P, I, I, P]),
     "d2s_patch_keep_mask": (I, [P, I, I, I, P]),

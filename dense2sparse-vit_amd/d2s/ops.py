@@ -972,6 +972,42 @@ def ragged_pack(x, mask, cu, total):
     return out, src
 
 
+# ---- ragged inference through every threshold stage: a stage after the first, on the packed batch (csrc/ragged.hip) ----
+def half_mean_concat_varlen(x, cu, B):
+    """x [total, C] packed, cu [B+1] -> [total, C]: the first half copied, the second half the mean over each image's non-CLS rows."""
+    _f32(x)
+    total, C = x.shape
+    out = torch.empty((total, C), dtype=torch.float32, device=x.device)
+    lib.call("d2s_half_mean_concat_varlen", lib.ptr(x), lib.ptr(cu), lib.ptr(out), int(B), C)
+    return out
+
+
+def ragged_select_threshold(scores, cu, row_src, threshold, N, B, want_probs=False):
+    """scores [total] packed (CLS entries ignored) -> (keep [total] float 0/1 with 1 at the CLS rows, counts [B] int32 kept non-CLS
+    rows, dense_mask [B, N] in original patch coordinates, probs [total] or None)."""
+    _f32(scores)
+    total = scores.numel()
+    dev = scores.device
+    keep = torch.empty((total,), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    dense = torch.empty((B, N), dtype=torch.float32, device=dev)
+    probs = torch.empty((total,), dtype=torch.float32, device=dev) if want_probs else None
+    lib.call("d2s_ragged_select_threshold", lib.ptr(scores), lib.ptr(cu), lib.ptr(row_src), float(threshold), int(N), lib.ptr(probs),
+             lib.ptr(keep), lib.ptr(counts), lib.ptr(dense), int(B))
+    return keep, counts, dense, probs
+
+
+def ragged_repack(x, keep, cu_old, cu_new, row_src_old, total_new, B):
+    """x [total, D] packed, keep [total] -> (packed [total_new, D], row_src [total_new] int32 = original token index of every row)."""
+    _f32(x), _f32(keep)
+    D = x.shape[1]
+    out = torch.empty((total_new, D), dtype=torch.float32, device=x.device)
+    src = torch.empty((total_new,), dtype=torch.int32, device=x.device)
+    lib.call("d2s_ragged_repack", lib.ptr(x), lib.ptr(keep), lib.ptr(cu_old), lib.ptr(cu_new), lib.ptr(row_src_old), lib.ptr(out),
+             lib.ptr(src), int(B), D)
+    return out, src
+
+
 def mask_row_weights(mask):
     m = _f32(mask).reshape(-1)
     w = torch.empty_like(m)

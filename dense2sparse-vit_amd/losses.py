@@ -11,6 +11,11 @@ Differences that are deliberate and documented:
     :216-218).  The fix built here keeps their intent: no token is removed in training, so every stage's KL runs over all N tokens
     against the un-gathered teacher target and its accuracy compares the two THRESHOLD masks (student scores vs teacher target under
     the same cumulative rule); the token distillation term is the mean over the tokens the last stage's mask keeps.
+  * dynamic keep ratio at validation with more than one stage (the ragged cascade): a stage after the first scores
+    only the tokens that survived, so its pred_logits is the packed [total] vector.  mask_acc_i is computed for every stage, from the
+    dense cumulative [B, N] masks against the teacher's threshold mask as above; the KL / MSE term is computed for a stage only when its
+    pred_logits is the dense [B, N] tensor.  A packed stage contributes NO loss term: neither the reference nor the training-mode fix
+    defines one (val_mask_loss of such a student is the first stage's term).
 """
 import torch
 
@@ -39,12 +44,15 @@ class MaskLoss(torch.nn.Module):
         with torch.no_grad():
             gt_mask, _ = ops.select_threshold(target, float(self.patch_score_threshold))
         for i in range(len(keep_masks)):
+            dense = pred_logits[i].dim() == 2       # a packed stage of the ragged cascade hands over [total] scores: no loss term is defined
             if self.loss_type == "mse":
-                mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.MSE_TARGET, target, None, None, B * T / 100.0)
+                if dense:
+                    mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.MSE_TARGET, target, None, None, B * T / 100.0)
                 continue
             with torch.no_grad():
                 mask_accs[i] = ops.sum_scalar(ops.dense_mask_agreement(keep_masks[i].contiguous(), gt_mask), 1.0 / float(B * T))
-            mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.KL_PROB_TARGET, target, None, None, B)
+            if dense:
+                mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.KL_PROB_TARGET, target, None, None, B)
         return mask_loss
 
     def forward(self, pred_logits, cls_attn_weights, kept_token_idx, metrics, accumulate=True, attn_selection=False):

@@ -17,6 +17,8 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --batch-size 64 --accum-steps 8 --clip-grad 1.0     (512 images per optimiser step)
     python dense2sparse-vit_amd/mask_predictor.py --method dynamicvit --arch deit_small --pruning-locs 3 6 9 --keep-ratios 0.7 0.49 0.343
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --attn-selection [--mean-heads] [--fuse-dropped]     (select by the CLS attention)
+    python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
+        --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
 """
 import os
 import sys
@@ -52,9 +54,16 @@ def check_supported(args):
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
-        if len(args.pruning_locs) > 1:
+        if len(args.pruning_locs) > 1 and not getattr(args, "ragged_cascade", False):
             bad.append("--patch-score-threshold with more than one pruning stage (ragged inference supports one stage: the reference's "
-                       "second stage cannot run, dynamic_vit.py:945-946)")
+                       "second stage cannot run, dynamic_vit.py:945-946); --ragged-cascade selects this build's definition of the later stages")
+        elif len(args.pruning_locs) > 1 and args.predictor_bn:
+            bad.append("--ragged-cascade with --predictor-bn and more than one pruning stage (a stage on a ragged packed batch needs the "
+                       "LayerNorm predictor)")
+        elif len(args.pruning_locs) > 1:
+            print("Attention: --ragged-cascade: at inference every threshold stage after the first scores and selects, per image, among the "
+                  "tokens that survived the stages before it and packs the batch again - this build's definition, the reference's second "
+                  "stage cannot run (dynamic_vit.py:945-946; DESIGN.md section 10); a packed stage adds no mask-loss term at validation")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:

@@ -171,6 +171,10 @@ def parse_args(argv=None):
     p.add_argument('--fuse-dropped', action='store_true', default=False,
                    help='with --topk-selection: every pruning stage fuses the tokens it drops, weighted by their keep probabilities, into one '
                         'package token that later stages carry along (training and evaluation alike; no new parameters)')
+    p.add_argument('--ragged-cascade', action='store_true', default=False,
+                   help='with --patch-score-threshold and several --pruning-locs: at inference every threshold stage after the first scores '
+                        'and selects, per image, among the tokens that survived, and packs the batch again (this build\'s definition: the '
+                        'reference\'s second stage cannot run)')
     p.add_argument('--accum-steps', type=int, default=1, metavar='N',
                    help='one optimiser step per N batches (gradient = mean over the N; effective batch = N x --batch-size x ranks), '
                         'accumulated inside the fused arena step')

@@ -505,7 +505,8 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.pred_logits = []
         self.patch_score_threshold = patch_score_threshold
         self.keep_ratios = None          # :886 / :941 - per-image kept fraction of the last thresholded stage (device tensor)
-        self.cu_seqlens = self.ragged_row_src = None     # ragged inference: packed-row offsets per image / source token of each row
+        self.cu_seqlens = self.ragged_row_src = None     # ragged inference: packed-row offsets per image / ORIGINAL token of each row (last stage)
+        self.cu_seqlens_per_stage, self.ragged_row_src_per_stage = [], []     # the same after every threshold stage
         # replay of a recorded selection (analysis / tests): a list of int64 [B, k_i] kept-id tensors, one per stage, used INSTEAD of the
         # top-k of this forward's scores (which are still computed and returned); None = normal operation
         self.kept_token_override = None
@@ -641,10 +642,18 @@ class VisionTransformerDiffPruning(_ViTBase):
 
         Inference (:935-949, with the reference's undefined `score` read as `pred_score`): the kept tokens of every image are packed
         into one ragged batch [total, D] (`cu_seqlens` [B+1] gives each image's rows) and the remaining blocks run on it - LayerNorm
-        and GEMMs over all packed rows, attention per image.  One pruning stage (the reference's second stage scatters an n_kept-long
-        mask into an N-long buffer and cannot run).  Returns (logits, [cls rows: dense [B,H,N] before the stage, packed [H,total]
-        after it], [pred_logits], [keep mask [B,N]])."""
+        and GEMMs over all packed rows, attention per image.  A stage after the first (the reference's scatters an n_kept-long mask into
+        an N-long buffer and cannot run; the build's definition) acts on the packed batch, per image: the score
+        predictor runs over the image's surviving non-CLS tokens (its global half is their mean, its softmax runs over them), the
+        threshold rule selects among them, the kept rows are packed again - what the remaining network gives on each image alone.
+        Unlike training, where a later stage scores all N tokens and replaces the mask, a token dropped here is gone.
+        Returns (logits, [cls rows: dense [B,H,N] before the first stage, packed [H,total_s] after stage s; a pruning block returns
+        none], [pred_logits: dense [B,N] for the first stage, packed [total_{s-1}] for a later one (the CLS rows' entries have no
+        meaning)], [cumulative keep mask [B,N] per stage, original patch coordinates]).  `cu_seqlens` / `ragged_row_src` (the ORIGINAL
+        token index of every packed row, 0 for CLS) are the last stage's, `cu_seqlens_per_stage` / `ragged_row_src_per_stage` hold
+        every stage's; `keep_ratios` = survivors of the last stage / N; `ragged_features` = the final LayerNorm of the last packed batch."""
         from d2s import ops
+        from d2s.functional_ragged import ragged_predictor_forward
         thr = float(self.patch_score_threshold)
         dp = self._drop_path_table(x.shape[0], x.device)
         x = self._embed(x)
@@ -653,6 +662,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.num_kept_tokens, self.cls_attns, self.pred_logits = [], [], []
         self.kept_token_indices, self.dropped_token_indices = [], []       # here: per-stage keep masks / their complements
         self.cu_seqlens = self.ragged_row_src = None
+        self.cu_seqlens_per_stage, self.ragged_row_src_per_stage = [], []
         p_count = 0
         if self.training:
             policy = torch.ones((B, n), dtype=torch.float32, device=x.device)       # :830,839
@@ -670,24 +680,35 @@ class VisionTransformerDiffPruning(_ViTBase):
                 x = blk(x, policy=policy, drop_path_rows=self._drop_path.rows(dp, i))             # :894 / :983
             logits, features = self._head(x)
             return logits, features, self.pred_logits, self.kept_token_indices
-        if len(self.pruning_loc) > 1:
-            raise NotImplementedError("ragged inference with a dynamic keep ratio supports one pruning stage: the reference's second "
-                                      "stage scatters an n_kept-long mask into an N-long buffer (dynamic_vit.py:945-946) and cannot run")
+        if len(self.pruning_loc) > 1 and any(p.use_bn for p in self.score_predictor):
+            raise NotImplementedError("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
+                                      "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
+                                      "predictor; one stage works with either")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("ragged inference is forward only: call it under torch.no_grad()")
         cu = None
         for i, blk in enumerate(self.blocks):
             if i in self.pruning_loc:
-                pred_logits, pred_score = _scores(self.score_predictor[p_count], x)
-                mask, counts = ops.select_threshold(pred_score.contiguous(), thr)                  # :936-938 (score := pred_score)
+                if cu is None:
+                    pred_logits, pred_score = _scores(self.score_predictor[p_count], x)
+                    mask, counts = ops.select_threshold(pred_score.contiguous(), thr)              # :936-938 (score := pred_score)
+                    cu = ops.ragged_offsets(counts, extra=1)
+                    total = int(cu[-1])      # the one device sync of a stage: the packed row count sizes every later launch
+                    x, self.ragged_row_src = ops.ragged_pack(x, mask, cu, total)                   # :947-948
+                else:       # a later stage acts on the packed batch: per image, over the tokens that survived
+                    pred_logits = ragged_predictor_forward(self.score_predictor[p_count], x, cu, B)          # packed [total]
+                    keep, counts, mask, _ = ops.ragged_select_threshold(pred_logits, cu, self.ragged_row_src, thr, N, B)
+                    cu_new = ops.ragged_offsets(counts, extra=1)
+                    total = int(cu_new[-1])
+                    x, self.ragged_row_src = ops.ragged_repack(x, keep, cu, cu_new, self.ragged_row_src, total, B)
+                    cu = cu_new
                 self.keep_ratios = counts.float() / N                                              # :941
                 self.pred_logits.append(pred_logits)
                 self.kept_token_indices.append(mask)
                 self.dropped_token_indices.append(1.0 - mask)
-                cu = ops.ragged_offsets(counts, extra=1)
-                total = int(cu[-1])          # the one device sync of the ragged path: the packed row count sizes every later launch
-                x, self.ragged_row_src = ops.ragged_pack(x, mask, cu, total)                       # :947-948
                 self.cu_seqlens = cu
+                self.cu_seqlens_per_stage.append(cu)
+                self.ragged_row_src_per_stage.append(self.ragged_row_src)
                 x = blk.forward_ragged(x, cu, B, n)                                                # :949 blk(x)
                 p_count += 1
             elif cu is None:

@@ -255,6 +255,22 @@ int d2s_ragged_offsets(const int* counts, int B, int extra, int* cu_seqlens, d2s
 /* x [B,n,D] (row 0 = CLS, always kept), mask [B,n-1] -> out [cu[B], D]; row_src [cu[B]] (optional) = source token of each row */
 int d2s_ragged_pack(const float* x, const float* mask, const int* cu_seqlens, float* out, int* row_src, int B, int n, int D,
                     d2s_stream_t stream);
+/* ---- ragged inference through every threshold stage (--ragged-cascade) -----------------------------------
+ * A stage after the first acts on the packed batch [total, D] with cu_seqlens [B+1]: image b owns rows cu[b] .. cu[b+1]-1, row cu[b]
+ * is its CLS token.  The reference's second stage cannot run (vit_models/dynamic_vit.py:945-946); PARITY UNPINNED.
+ * :540-544 per segment: out[r, :C/2] = x[r, :C/2]; out[r, C/2:] = mean of x[., C/2:] over the segment's non-CLS rows (0 when it has
+ * none); every row of the segment is written, the CLS row too.  x, out [total, C], C even. */
+int d2s_half_mean_concat_varlen(const float* x, const int* cu_seqlens, float* out, int B, int C, d2s_stream_t stream);
+/* softmax over each segment's non-CLS scores (the arithmetic of d2s_softmax_rows), then the rule of d2s_select_threshold over them.
+ * scores [total] (the CLS rows' entries are ignored), row_src [total] = original token index of every packed row (patch id + 1,
+ * 0 for CLS) -> probs [total] (may be NULL; 0 at the CLS rows), keep [total] 0/1 (1 at the CLS rows), counts [B] = kept non-CLS rows,
+ * dense_mask [B,N] = 1 at row_src[r] - 1 of every kept non-CLS row, 0 elsewhere (written in full).  N <= 8192 bounds a segment. */
+int d2s_ragged_select_threshold(const float* scores, const int* cu_seqlens, const int* row_src, float threshold, int N, float* probs,
+                                float* keep, int* counts, float* dense_mask, int B, d2s_stream_t stream);
+/* the CLS row and the rows with keep != 0 of every segment, in order -> out [cu_new[B], D] (cu_new from d2s_ragged_offsets(counts, B, 1));
+ * row_src_new [cu_new[B]] = row_src_old of every kept row.  D a multiple of 4. */
+int d2s_ragged_repack(const float* x, const float* keep, const int* cu_old, const int* cu_new, const int* row_src_old, float* out,
+                      int* row_src_new, int B, int D, d2s_stream_t stream);
 /* weights[r] = mask[r] / sum(mask): the token-distillation term over the kept tokens only (the build's fix for losses.py:216-218) */
 int d2s_mask_row_weights(const float* mask, long rows, float* weights, d2s_stream_t stream);
 /* agree[b] = number of positions where two dense 0/1 masks [B,T] agree (mask accuracy, losses.py:96 for threshold masks) */
