@@ -125,7 +125,10 @@ struct AttnFwdArgs {
     int n, H; float scale, eps; int total;
 };
 
-template <bool POLICY, bool VARLEN>
+// KEYW: per-key weights (token merging, tome.hip / DESIGN.md section 22: key j stands for key_w[b,j] patches).  softmax_j(S_ij + log w_j) is
+// computed as e_ij w_j / sum_j e_ij w_j with e_ij = exp(S_ij - max_j S_ij): the weight multiplies the exponential, the running maximum stays
+// the one over the raw scores (1 <= w <= n).  The weights travel in a.policy and are staged in pol_s; lse_i = m_i + log(sum_j e_ij w_j).
+template <bool POLICY, bool VARLEN, bool KEYW = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnFwdArgs a) {
     __shared__ __attribute__((aligned(16))) float Ks[32 * PITCH];
     __shared__ __attribute__((aligned(16))) float Vs[32 * PITCH];
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnFwdArgs a) {
     const float* qb = a.qkv + tok0 * ld + h * DH;
     const float* kb = qb + (long)H * DH;
     const float* vb = kb + (long)H * DH;
-    const float* polb = POLICY ? a.policy + (long)b * n : nullptr;
+    const float* polb = (POLICY || KEYW) ? a.policy + (long)b * n : nullptr;
     const float scale = a.scale;
     const int q0 = bx * 128 + wave * 32;
     const bool active = q0 < n;
@@ -168,11 +171,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnFwdArgs a) {
     float pr = 0.f;
     tile_load(kb, ld, 0, n, tid, kr);
     tile_load(vb, ld, 0, n, tid, vr);
-    if (POLICY && tid < 32) pr = tid < n ? polb[tid] : 0.f;
+    if ((POLICY || KEYW) && tid < 32) pr = tid < n ? polb[tid] : 0.f;
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();
         tile_store(Ks, tid, kr);
         tile_store(Vs, tid, vr);
+        if (KEYW && tid < 32) pol_s[tid] = pr;
         if (POLICY) {
             if (tid < 32) pol_s[tid] = pr;
             vacc += vr[0];      // column sums of V over every key (rows beyond n were loaded as zeros)
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnFwdArgs a) {
         if (t + 1 < ntiles) {
             tile_load(kb, ld, (t + 1) * 32, n, tid, kr);
             tile_load(vb, ld, (t + 1) * 32, n, tid, vr);
-            if (POLICY && tid < 32) { const int kj = (t + 1) * 32 + tid; pr = kj < n ? polb[kj] : 0.f; }
+            if ((POLICY || KEYW) && tid < 32) { const int kj = (t + 1) * 32 + tid; pr = kj < n ? polb[kj] : 0.f; }
         }
         if (!active) continue;
         f32x16 s;
@@ -217,6 +221,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnFwdArgs a) {
                 const int kr_ = mfma32_row(r, half);
                 s[r] *= (kv0 + kr_ == qi) ? 1.f : pol_s[kr_];
             }
+            if (KEYW) s[r] *= pol_s[mfma32_row(r, half)];
             rs += s[r];
         }
         rs += __shfl_xor(rs, 32, 64);
@@ -580,6 +585,17 @@ int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out,
     dim3 grid((max_n + 127) / 128, B * H), block(256);
     AttnFwdArgs a{qkv, out, nullptr, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total};
     hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, cls_row ? (size_t)max_n * sizeof(float) : 0, stream, a);
+    return d2s_check_launch();
+}
+
+// Attention whose keys carry weights (token merging at inference): key_w [B,n], key j of image b counts key_w[b,j]
+// times in every softmax row - out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij); lse [B,H,n] (nullable) = log of that denominator.
+// With every weight 1.0 the output is bit for bit d2s_attn_fwd_f32's.  Forward only.
+int d2s_attn_keyw_fwd_f32(const float* qkv, const float* key_w, float* out, float* lse, int B, int n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !key_w || !out || B <= 0 || n < 2 || H <= 0 || n > 8192) return D2S_ERR_ARG;      // a merged sequence keeps CLS and a token
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    AttnFwdArgs a{qkv, out, lse, nullptr, key_w, nullptr, nullptr, n, H, scale, 0.f, 0};
+    hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), grid, block, 0, stream, a);
     return d2s_check_launch();
 }
 

@@ -621,6 +621,43 @@ def select_cls_attn(cls_row, lead, T, k, mean_heads=False):
     return probs, kept, dropped
 
 
+def tome_clip_r(r, n):
+    """ToMe's effective merge count of a block with n tokens: at most half of the non-CLS tokens (set A without CLS)."""
+    return max(0, min(int(r), (int(n) - 1) // 2))
+
+
+def tome_match(qkv, B, n, H, r):
+    """Bipartite soft matching of token merging on the keys of a [B * n, 3 * H * 64] qkv, read in place.  r is the
+    effective count (tome_clip_r).  -> (node_max [B,T_a], node_idx [B,T_a], unm_idx [B,T_a-r], src_idx [B,r], dst_idx [B,r]), int32"""
+    _f32(qkv)
+    B, n, H, r = int(B), int(n), int(H), int(r)
+    Ta = (n + 1) // 2
+    i32 = dict(dtype=torch.int32, device=qkv.device)
+    node_max = torch.empty((B, Ta), dtype=torch.float32, device=qkv.device)
+    node_idx, unm = torch.empty((B, Ta), **i32), torch.empty((B, max(Ta - r, 0)), **i32)
+    src, dst = torch.empty((B, max(r, 0)), **i32), torch.empty((B, max(r, 0)), **i32)
+    lib.call("d2s_tome_match", lib.ptr(qkv), B, n, H, r, lib.ptr(node_max), lib.ptr(node_idx), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
+             lib.ptr(dst) if r > 0 else None)
+    return node_max, node_idx, unm, src, dst
+
+
+def tome_merge(x, size, unm, src, dst, B, n, D, r):
+    """x [B * n, D] (or [B, n, D]), size [B, n] or None (all ones), a plan of tome_match -> (x_out [B * (n - r), D], size_out [B, n - r])"""
+    _f32(x)
+    B, n, D, r = int(B), int(n), int(D), int(r)
+    for t in (unm, src, dst):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert tuple(unm.shape) == (B, (n + 1) // 2 - r) and tuple(src.shape) == (B, r) and tuple(dst.shape) == (B, r)
+    if size is not None:
+        _f32(size)
+        assert tuple(size.shape) == (B, n)
+    out = torch.empty((B * max(n - r, 0), D), dtype=torch.float32, device=x.device)
+    size_out = torch.empty((B, max(n - r, 0)), dtype=torch.float32, device=x.device)
+    lib.call("d2s_tome_merge", lib.ptr(x), lib.ptr(size), lib.ptr(unm), lib.ptr(src) if r > 0 else None, lib.ptr(dst) if r > 0 else None,
+             B, n, D, r, lib.ptr(out), lib.ptr(size_out))
+    return out, size_out
+
+
 def gather_pack(x, ids):
     _f32(x)
     B, n, D = x.shape
@@ -754,6 +791,19 @@ def attn_fwd(qkv, B, n, H, scale, want_cls=True):
     entry = "d2s_attn_fwd_bf16" if get_gemm_mode() == GEMM_BF16 else "d2s_attn_fwd_f32"
     lib.call(entry, lib.ptr(qkv), lib.ptr(out), lib.ptr(lse), lib.ptr(cls_row), B, n, H, float(scale))
     return out, lse, cls_row
+
+
+def attn_keyw_fwd(qkv, key_w, B, n, H, scale, want_lse=False):
+    """Attention whose key j counts key_w[b, j] times in every softmax row (token merging).  fp32 kernel only: the
+    bf16 arithmetic mode has no weighted attention and is refused.  -> (out [B * n, H * 64], lse [B,H,n] or None)"""
+    if get_gemm_mode() == GEMM_BF16:
+        raise lib.D2SError("key-weighted attention exists in fp32 only (gemm modes exact and split)")
+    _f32(key_w)
+    assert tuple(key_w.shape) == (B, n)
+    out = torch.empty((B * n, H * 64), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if want_lse else None
+    lib.call("d2s_attn_keyw_fwd_f32", lib.ptr(qkv), lib.ptr(key_w), lib.ptr(out), lib.ptr(lse), B, n, H, float(scale))
+    return out, lse
 
 
 def attn_fwd_bf16io(qkv, B, n, H, scale, want_cls=True, want_f32=True):

@@ -15,7 +15,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
-    baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # DynamicViT baseline: eval returns logits alone
+    # DynamicViT and Token Merging baselines: eval returns logits alone
+    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe")
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():

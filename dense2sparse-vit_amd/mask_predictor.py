@@ -19,6 +19,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --attn-selection [--mean-heads] [--fuse-dropped]     (select by the CLS attention)
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
         --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
+    python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --student-checkpoint deit_small.pth
 """
 import os
 import sys
@@ -37,6 +38,7 @@ from train import train_one_epoch                    # noqa: E402
 
 _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": "dynamic_vit_small_patch16_224_student",
              "deit_base": "dynamic_vit_base_patch16_224_student"}
+_TOME = {"deit_tiny": "tome_deit_tiny_patch16_224", "deit_small": "tome_deit_small_patch16_224", "deit_base": "tome_deit_base_patch16_224"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
@@ -51,6 +53,17 @@ def check_supported(args):
         for attr, flag in _NOT_WITH_DYNAMICVIT:
             if getattr(args, attr, None) not in (None, False):
                 bad.append(f"--method dynamicvit with {flag} (the baseline keeps tokens by its own Gumbel decision and predictor)")
+    tome_r = getattr(args, "tome_r", 0)
+    if tome_r < 0:
+        bad.append(f"--tome-r {tome_r} (0 or more tokens per block)")
+    if getattr(args, "method", "d2s") == "tome":
+        if not args.eval_only:
+            bad.append("--method tome without --eval-only (token merging is built for inference: training through a merge needs the merge's "
+                       "backward and key weights in both attention-backward kernels)")
+        if getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--method tome with --gemm-mode bf16 (the key-weighted attention is an fp32 kernel; exact and split run)")
+    elif tome_r > 0:
+        bad.append(f"--tome-r {tome_r} with --method {getattr(args, 'method', 'd2s')} (tokens are merged by --method tome only)")
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
@@ -183,6 +196,23 @@ def build_models(args):
     return student.to(args.device), teacher.to(args.device)
 
 
+def build_tome(args):
+    """--method tome: the dense DeiT trunk with token merging, weights from --student-checkpoint or the 'model' entry of a --resume file.  A
+    dense-to-sparse student's checkpoint carries score predictors this model has no use for: they are ignored (strict=False)."""
+    arch = args.arch if args.arch in _TOME else "deit_small"
+    model = getattr(vit_models, _TOME[arch])(args.tome_r)
+    path = args.student_checkpoint or args.resume
+    sd = vit_models.checkpoint_filter_fn(torch.load(path, map_location="cpu", weights_only=True), model)
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    if missing:
+        raise SystemExit(f"{path}: no weights for {len(missing)} tensors of the trunk, first {missing[0]}")
+    pred = [k for k in unexpected if 'predictor' in k]
+    print(f"--method tome: trunk weights from {path}; ignored {len(pred)} predictor tensors" +
+          (f" and {len(unexpected) - len(pred)} others, first {[k for k in unexpected if k not in pred][0]}" if len(unexpected) > len(pred) else "") +
+          " (token merging has no predictor)")
+    return model.to(args.device)
+
+
 def folder_loaders(args, samples, split, epoch, rank, world):
     """The reference's ImageFolder loaders (mask_predictor.py:234-259, ddp_training.py:15-20) on the GPU input pipeline (d2s.data): the
     training subset in a new order per epoch, one DistributedSampler-style shard per rank; Mixup when the reference enables it."""
@@ -223,6 +253,30 @@ def save_checkpoints(args, optim, student, epoch, best_acc, improved, first):
     return first
 
 
+def eval_tome(args, rank, world, distributed):
+    """--method tome --eval-only: no teacher pass, no TrainStep - the model, the validation loader, one evaluation."""
+    model = build_tome(args)
+    if args.data_source == "folder":
+        from d2s import data
+        samples, classes = data.image_folder(args.imgnet_val_dir)
+        if len(classes) > args.nb_classes:
+            raise SystemExit(f"{len(classes)} classes in {args.imgnet_val_dir}, the heads have {args.nb_classes}")
+        _, val_loader = folder_loaders(args, samples, data.split_indices(len(samples)), 0, rank, world)
+    else:
+        val_loader = utils.SyntheticLoader(args.val_steps, args.batch_size, 224, seed=777 + rank, device=args.device)
+    metrics = evaluate_performance(args, model, torch.nn.Identity(), val_loader)
+    if distributed:
+        import torch.distributed as dist
+        t = torch.tensor([metrics["val_acc"]], device=args.device)
+        dist.all_reduce(t)
+        metrics["val_acc"] = float(t / world)
+        dist.destroy_process_group()
+    if rank == 0:
+        print(f"eval only: --method tome --tome-r {args.tome_r}: tokens per block {model.tokens_per_block}, " +
+              ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
+    return metrics["val_acc"]
+
+
 def main(argv=None):
     args = utils.parse_args(argv)
     check_supported(args)
@@ -240,6 +294,8 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
+    if args.method == "tome":
+        return eval_tome(args, rank, world, distributed)
     student, teacher = build_models(args)
     if rank == 0:
         for key in sorted(vars(args), key=str.lower):

@@ -161,9 +161,12 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit'],
+    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
-                        "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective")
+                        "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
+                        "tome: the Token Merging baseline (--tome-r, --eval-only: no predictor, no training)")
+    p.add_argument('--tome-r', type=int, default=0, metavar='R',
+                   help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,
                    help='with --topk-selection: train through the perturbed top-k soft gather (sigma decays from --initial-sigma to 0 over '
                         'the epochs); evaluation and the trained model keep the hard top-k')

@@ -1,0 +1,72 @@
+"""Token Merging baseline (ToMe, Bolya et al. 2023; DESIGN.md section 22 - no counterpart in the reference): an off-the-shelf DeiT trunk
+whose every block merges r tokens into their most similar partner between its attention branch and its MLP.  No predictor, no training:
+the model has the teacher's parameters and state-dict keys and loads any DeiT checkpoint.  Inference only."""
+import torch
+
+from d2s import functional as DF
+from d2s import functional_tome as TF
+from .dynamic_vit import VisionTransformerTeacher, _GEOM, _load_local
+
+TOME_TRAINING_ERROR = ("token merging is built for inference only: training through a merge needs the merge's backward and key weights in "
+                       "both attention-backward kernels (call model.eval(), or construct with tome_r=0)")
+
+
+class VisionTransformerToMe(VisionTransformerTeacher):
+    """The dense ViT with token merging.  tome_r: tokens merged away per block, one int for every block or a list of `depth` ints; each
+    block clips its count to (n - 1) // 2 of the n tokens it sees.  prop_attn: weight every key by the patches it stands for
+    (proportional attention) once something has merged.  forward (eval mode) returns the logits; afterwards tokens_per_block[i] is the
+    number of tokens (CLS included) that leave block i, and tome_plans[i] the block's (unm_idx, src_idx, dst_idx) or None."""
+
+    def __init__(self, *args, tome_r=0, prop_attn=True, **kwargs):
+        super().__init__(*args, **kwargs)
+        depth = len(self.blocks)
+        rs = [int(tome_r)] * depth if isinstance(tome_r, int) else [int(v) for v in tome_r]
+        if len(rs) != depth or any(v < 0 for v in rs):
+            raise ValueError(f"tome_r: one non-negative int or a list of {depth} of them, got {tome_r!r}")
+        self.tome_r = rs
+        self.prop_attn = bool(prop_attn)
+        self.tokens_per_block = None
+        self.tome_plans = None
+
+    def forward(self, x, plans=None):
+        """plans: per block (unm_idx, src_idx, dst_idx) or None, to replay instead of matching."""
+        merging = any(v > 0 for v in self.tome_r)
+        if self.training:
+            if merging:
+                raise NotImplementedError(TOME_TRAINING_ERROR)
+            x = self._embed(x)                  # r = 0 everywhere: the dense, differentiable trunk
+            for blk in self.blocks:
+                x = blk(x)
+            self.tokens_per_block, self.tome_plans = [x.shape[1]] * len(self.blocks), [None] * len(self.blocks)
+            return self._head(x)[0]
+        with torch.no_grad():
+            x = self._embed(x)
+            B, n, D = x.shape
+            x = x.view(B * n, D)
+            size, counts, used = None, [], []
+            for i, blk in enumerate(self.blocks):
+                a = blk.attn
+                x, size, plan = TF.tome_block_forward(x, size, blk._params(), B, n, a.num_heads, blk.norm1.eps, a.scale, self.tome_r[i],
+                                                      self.prop_attn, None if plans is None else plans[i])
+                n = x.shape[0] // B
+                counts.append(n)
+                used.append(plan)
+            self.tokens_per_block, self.tome_plans = counts, used
+            return DF.run(DF.HeadFn, x.view(B, n, D), self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.norm.eps, 0)[0]
+
+
+def _tome(size, tome_r, checkpoint_path=None, **kwargs):
+    model = VisionTransformerToMe(patch_size=16, depth=12, mlp_ratio=4, qkv_bias=True, tome_r=tome_r, **_GEOM[size], **kwargs)
+    return _load_local(model, checkpoint_path, strict=True)
+
+
+def tome_deit_tiny_patch16_224(tome_r=0, checkpoint_path=None, **kwargs):
+    return _tome("tiny", tome_r, checkpoint_path, **kwargs)
+
+
+def tome_deit_small_patch16_224(tome_r=0, checkpoint_path=None, **kwargs):
+    return _tome("small", tome_r, checkpoint_path, **kwargs)
+
+
+def tome_deit_base_patch16_224(tome_r=0, checkpoint_path=None, **kwargs):
+    return _tome("base", tome_r, checkpoint_path, **kwargs)

@@ -169,6 +169,20 @@ int d2s_gather_fuse_bwd(const float* g, const float* x, const float* p, const fl
  * image, fixed-order sums, no atomics: bit-identical from run to run.  T <= 16384, 0 <= k <= T. */
 int d2s_select_cls_attn(const float* cls_row, int B, int H, int n, int lead, int T, int k, int reduce, float* probs, long long* kept,
                         long long* dropped, d2s_stream_t stream);
+/* Token Merging at inference (ToMe, Bolya et al. 2023; no counterpart in the reference).  qkv [B,n,3,H,64] as the qkv
+ * GEMM writes it; the metric of a token is the mean of its keys over the heads (h ascending) divided by its L2 norm (a zero row is not
+ * special-cased).  A = even token indices (CLS = A row 0), T_a = ceil(n/2); B = odd indices.  node_max [B,T_a] = best cosine score of
+ * each A row among the B rows, node_idx [B,T_a] the lowest B index attaining it (CLS: -inf / 0, never a source).  The r A rows with the
+ * largest node_max (d2s_select_topk's order: value descending, equal values lowest index first) are the sources:
+ * src_idx [B,r] ascending, dst_idx [B,r] = node_idx[src_idx], unm_idx [B,T_a-r] the other A rows ascending; all int32, set-relative.
+ * One workgroup per image, no atomics, no scratch, nothing read back.  2 <= n <= 896, 0 <= r <= (n-1)/2 (the caller clips r). */
+int d2s_tome_match(const float* qkv, int B, int n, int H, int r, float* node_max, int* node_idx, int* unm_idx, int* src_idx, int* dst_idx,
+                   d2s_stream_t stream);
+/* x [B,n,D], size [B,n] (patches per token; NULL = all ones), a plan of d2s_tome_match -> x_out [B,n-r,D]: the unmerged A rows in unm_idx
+ * order, then every B row; B row j with sources = (s_j x_j + sum s_src x_src) / (s_j + sum s_src), sources in ascending src_idx order
+ * after the row itself; rows nothing merges into are copied bit for bit.  size_out [B,n-r] = the denominators (exact).  D % 4 == 0. */
+int d2s_tome_merge(const float* x, const float* size, const int* unm_idx, const int* src_idx, const int* dst_idx, int B, int n, int D, int r,
+                   float* x_out, float* size_out, d2s_stream_t stream);
 /* split / token-mean / concat of the predictor, vit_models/dynamic_vit.py:540-544 (self-adjoint: also its backward) */
 int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, d2s_stream_t stream);
 
@@ -303,6 +317,10 @@ int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
 int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, const float* out, const float* dout, const float* lse,
                              const float* cinv, float* dqkv /* nullable if dqkv_bf16 */, void* dqkv_bf16 /* nullable */, float* delta_ws,
                              float* dpolicy /* nullable */, float* dpol_ws, int B, int n, int H, float scale, d2s_stream_t stream);
+/* attention whose keys carry weights (token merging): out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B,n] (>= 1);
+ * lse [B,H,n] (nullable) = log of the denominator.  All weights 1.0: bit for bit d2s_attn_fwd_f32.  Forward only, n >= 2. */
+int d2s_attn_keyw_fwd_f32(const float* qkv, const float* key_w, float* out, float* lse, int B, int n, int H, float scale,
+                          d2s_stream_t stream);
 /* ragged packed attention forward (inference): qkv [total,3,H,64], image b = rows cu[b]..cu[b+1]; cls_row (optional) [H,total] */
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, d2s_stream_t stream);
