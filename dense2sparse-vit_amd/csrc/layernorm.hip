@@ -489,6 +489,7 @@ inline int pick_nv(int D) {
     if (nvec <= 512) return 8;
     return 16;
 }
+constexpr int LN_SCALAR_BWD_MAX_D = 2048;      // 4 * 2 * D * 4 B of dynamic LDS <= 64 KB
 inline int bwd_blocks(long rows) {
     // one wave walks its rows one after the other (load -> two wave reductions -> store), so the kernel is latency-bound unless
     // several workgroups share a CU: up to 3 per CU (measured: 256 blocks 48.8 us, 768 blocks see DESIGN.md section 7)
@@ -571,6 +572,9 @@ static int layernorm_bwd_impl(const float* x, long rows_per_group, long group_st
     const size_t sh = (size_t)3 * 2 * D * sizeof(float);
     if (scalar) {
         if (dx16) return D2S_ERR_ARG;      // the bf16 copy exists for the vector kernels only (D % 4 == 0)
+        // the scalar kernel keeps [4 waves][dw | db][D] floats in LDS: 64 KB at D = 2048.  Wider rows on this path (no model has
+        // them: its one user is the T2T LayerNorm at D = 147) are refused here rather than left to the launch to reject.
+        if (D > LN_SCALAR_BWD_MAX_D) return D2S_ERR_ARG;
         hipLaunchKernelGGL(ln_bwd_scalar_kernel, grid, block, (size_t)4 * 2 * D * sizeof(float), stream, x, m, dy, w, mean, rstd, dx,
                            add_src, part, rows, D, rpb, relu_mask);
         if (dweight)

@@ -97,7 +97,10 @@ int d2s_layernorm_fwd_bf16out(const float* x, long rows_per_group, long group_st
                               const float* b, float* y, void* y_bf16, float* mean, float* rstd, long rows, int D, float eps,
                               d2s_stream_t stream);
 size_t d2s_layernorm_bwd_workspace_bytes(long rows, int D);
-/* dx[map(r)] = (add_src ? add_src[map(r)] : 0) + mask * dLN/dx; relu_mask folds a preceding ReLU's backward in. */
+/* dx[map(r)] = (add_src ? add_src[map(r)] : 0) + mask * dLN/dx; relu_mask folds a preceding ReLU's backward in.
+ * 1 <= D <= 4096.  Where D or the row map's strides / offset are not multiples of 4 the scalar kernels run; their backward supports
+ * D <= 2048 and refuses wider rows (D2S_ERR_ARG, nothing launched, dx untouched) - e.g. D = 4094; the forward has no such limit.
+ * dweight and dbias come together or not at all (dweight without dbias: D2S_ERR_ARG); without them no workspace is needed. */
 int d2s_layernorm_bwd(const float* x, long rows_per_group, long group_stride, long row_stride, long offset, const float* dy,
                       const float* w, const float* mean, const float* rstd, float* dx, const float* add_src, float* dweight,
                       float* dbias, int accumulate_wb, int relu_mask, long rows, int D, void* workspace,

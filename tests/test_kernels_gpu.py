@@ -107,6 +107,7 @@ def test_linear_wgrad_fused_bias_grad(ops, tokens, n_out, n_in):
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
+# every dispatch branch (scalar / pair / NV kernels, row-count regimes, flags, row maps, limits) against float64: tests/test_layernorm_gpu.py
 @pytest.mark.parametrize("rows,D,eps", [(197 * 2, 384, 1e-6), (99 * 3, 1536, 1e-5), (77, 96, 1e-5), (50, 192, 1e-6),
                                         (33, 48, 1e-5), (20, 3072, 1e-5), (10, 128, 1e-6), (9, 768, 1e-6)])
 def test_layernorm_fwd_bwd(ops, rows, D, eps):
