@@ -304,7 +304,10 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 // POLICY: dS_ij = exp(S_ij - lse_i) mk_ij (dP_ij - delta_i) with lse_i = m_i + log(l_i + eps); the eps/n term of P does not depend on
 // S.  (The O(eps) gradient through the row maximum, which the reference's autograd carries because it does not detach the max, is
 // left out: it is <= eps = 1e-6 relative.)
-template <bool POLICY>
+// KEYW (backward of attn_fwd_kernel<false, false, true>, training through token merging): P_ij = w_j exp(S_ij - lse_i) with lse_i = m_i +
+// log sum_j e_ij w_j as that forward wrote it; the weights travel in `policy`, are staged per key tile in pol_s as the forward does, and
+// multiply the exponential - every key, the diagonal included.  They are counts and get no gradient.
+template <bool POLICY, bool KEYW = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           float* __restrict__ dqkv, int n, int H, float scale,
@@ -338,20 +341,20 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     const int ntiles = (n + 31) / 32;
     f32x4 kr[2], vr[2];
     float pr = 0.f;
-    const float* polb = POLICY ? policy + (long)b * n : nullptr;
+    const float* polb = (POLICY || KEYW) ? policy + (long)b * n : nullptr;
     tile_load(kb, ld, 0, n, tid, kr);
     tile_load(vb, ld, 0, n, tid, vr);
-    if (POLICY && tid < 32) pr = tid < n ? polb[tid] : 0.f;
+    if ((POLICY || KEYW) && tid < 32) pr = tid < n ? polb[tid] : 0.f;
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();
         tile_store(Ks, tid, kr);
         tile_store(Vs, tid, vr);
-        if (POLICY && tid < 32) pol_s[tid] = pr;
+        if ((POLICY || KEYW) && tid < 32) pol_s[tid] = pr;
         __syncthreads();
         if (t + 1 < ntiles) {
             tile_load(kb, ld, (t + 1) * 32, n, tid, kr);
             tile_load(vb, ld, (t + 1) * 32, n, tid, vr);
-            if (POLICY && tid < 32) { const int kj = (t + 1) * 32 + tid; pr = kj < n ? polb[kj] : 0.f; }
+            if ((POLICY || KEYW) && tid < 32) { const int kj = (t + 1) * 32 + tid; pr = kj < n ? polb[kj] : 0.f; }
         }
         if (!active) continue;
         f32x16 s, dp;
@@ -365,6 +368,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
             const int kr_ = mfma32_row(r, half);
             float p = (kv0 + kr_ < n) ? __expf(s[r] - lse_i) : 0.f;
             if (POLICY) p *= (kv0 + kr_ == q0 + l31) ? 1.f : pol_s[kr_];
+            if (KEYW) p *= pol_s[kr_];
             s[r] = p * (dp[r] - dl_i);          // dS^T
         }
         mma_reg_lds(s, Ks, l31, half, dq, min(4, (n - kv0 + 7) >> 3));      // dQ[query][d] += sum_key dS^T[key][query] K[key][d]
@@ -406,6 +410,15 @@ __device__ __forceinline__ void dkv_fetch_next(const float* __restrict__ qb, con
 }
 __device__ __forceinline__ float* first_arg() { return nullptr; }
 __device__ __forceinline__ float* first_arg(float* a) { return a; }
+// the dK/dV kernel's tail of the key-weighted instantiation (below): a type of its own, so that <POLICY, DPOL> and the float* tail of DPOL
+// keep their spelling, their argument lists and their instructions
+struct KeyWeights { const float* w; };
+__device__ __forceinline__ float* first_arg(KeyWeights) { return nullptr; }
+__device__ __forceinline__ const float* key_weights() { return nullptr; }
+__device__ __forceinline__ const float* key_weights(float*) { return nullptr; }
+__device__ __forceinline__ const float* key_weights(KeyWeights k) { return k.w; }
+template <typename... T> struct has_key_weights { static constexpr bool value = false; };
+template <> struct has_key_weights<KeyWeights> { static constexpr bool value = true; };
 
 // ---------------------------------------------------------------------------------------------------------
 // backward, dK / dV: one wave per 32 keys, loops over query tiles (natural orientation S = Q K^T)
@@ -419,6 +432,8 @@ __device__ __forceinline__ float* first_arg(float* a) { return a; }
 // owns 32 keys of its own, so nothing is reduced across waves.  A masked key (p_j = 0) has dS = 0 but a non-zero column sum (that is the
 // straight-through estimator's signal) and the policy is real-valued here: nothing is skipped and 0/1 is not assumed.
 // dpol_part [B, H, n]: per-head partials, folded over h in ascending order by attn_dpol_fold_kernel.
+// KEYW (the tail is one KeyWeights, <false, false, KeyWeights>; backward of the key-weighted forward): P_ij = w_j exp(S_ij - lse_i).  The
+// lane owns key j, so w_j is one register loaded once (pol_key's slot) and multiplies p before it feeds dV and dS; no diagonal exception.
 template <bool POLICY, bool DPOL = false, typename... DpolPart>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
@@ -455,7 +470,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     float lr = 0.f, dlr = 0.f, cir = 0.f;
     float dpol_acc = 0.f;
     const float* ci_b = POLICY ? cinv + ((long)b * H + h) * n : nullptr;
-    const float pol_key = (POLICY && k0 + l31 < n) ? policy[(long)b * n + k0 + l31] : 0.f;   // this lane's key
+    constexpr bool KEYW = has_key_weights<DpolPart...>::value;
+    const float* polk = KEYW ? key_weights(dpol_part_...) : policy;
+    const float pol_key = ((POLICY || KEYW) && k0 + l31 < n) ? polk[(long)b * n + k0 + l31] : 0.f;   // this lane's key
     tile_load(qb, ld, 0, n, tid, qr);
     tile_load(dob, ldo, 0, n, tid, dr);
     if (tid < 32) { lr = tid < n ? lse_b[tid] : INFINITY; dlr = tid < n ? dl_b[tid] : 0.f; if (POLICY) cir = tid < n ? ci_b[tid] : 0.f; }
@@ -498,6 +515,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
                 continue;
             }
             if (POLICY) p *= (t * 32 + qi == k0 + l31) ? 1.f : pol_key;
+            if (KEYW) p *= pol_key;
             s[r] = POLICY ? p + ci_s[qi] : p;
             dp[r] = p * (dp[r] - dl_s[qi]);
         }
@@ -590,7 +608,7 @@ int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out,
 
 // Attention whose keys carry weights (token merging at inference): key_w [B,n], key j of image b counts key_w[b,j]
 // times in every softmax row - out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij); lse [B,H,n] (nullable) = log of that denominator.
-// With every weight 1.0 the output is bit for bit d2s_attn_fwd_f32's.  Forward only.
+// With every weight 1.0 the output is bit for bit d2s_attn_fwd_f32's.  Its backward is d2s_attn_keyw_bwd_f32.
 int d2s_attn_keyw_fwd_f32(const float* qkv, const float* key_w, float* out, float* lse, int B, int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !key_w || !out || B <= 0 || n < 2 || H <= 0 || n > 8192) return D2S_ERR_ARG;      // a merged sequence keeps CLS and a token
     dim3 grid((n + 127) / 128, B * H), block(256);
@@ -618,6 +636,21 @@ int d2s_attn_bwd_f32(const float* qkv, const float* out, const float* dout, cons
                        static_cast<const float*>(nullptr));
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
                        static_cast<const float*>(nullptr), static_cast<const float*>(nullptr));
+    return d2s_check_launch();
+}
+
+// Backward of d2s_attn_keyw_fwd_f32 (training through token merging): lse as that call wrote it, P_ij = w_j
+// exp(S_ij - lse_i), dV = P^T dO, dS = P * (dP - delta).  The weights are counts and get no gradient.  d2s_attn_bwd_f32's launches and
+// geometry, the forward entry's limits; dqkv is fully written, and with every weight 1.0 it is bit for bit d2s_attn_bwd_f32's.
+int d2s_attn_keyw_bwd_f32(const float* qkv, const float* key_w, const float* out, const float* dout, const float* lse, float* dqkv,
+                          float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !key_w || !out || !dout || !lse || !dqkv || !delta_ws || B <= 0 || n < 2 || H <= 0 || n > 8192) return D2S_ERR_ARG;
+    const long rows = (long)B * n;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, key_w);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, KeyWeights>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
+                       static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), KeyWeights{key_w});
     return d2s_check_launch();
 }
 

@@ -12,6 +12,10 @@
 //              (s_j x_j + sum s_src x_src) / (s_j + sum s_src), sources in ascending src_idx order after the row itself; size_out is the
 //              denominator.  A row without sources (unmerged A, untouched B) is copied bit for bit.
 //
+//   backward   (training through the merge; the plan and the sizes are constants, the match reads K under no gradient)  the merge is linear
+//              in x, so every INPUT row's gradient is one output row's, scaled: a merged row (a source, or a B row with sources) gets
+//              (size_t / size_out_row) dy_row, every other row its output row's gradient bit for bit.
+//
 // No atomics, no memset, no scratch, nothing read back by the host: deterministic and legal inside a captured step.
 #include "d2s_common.h"
 
@@ -190,6 +194,66 @@ __global__ __launch_bounds__(256) void tome_merge_kernel(const float* __restrict
     if (lane == 0) size_out[row] = den;
 }
 
+// position of `key` in the ascending list v[0..len) or -1; every lane of the wave searches for the same key and gets the same answer
+__device__ __forceinline__ int find_ascending(const int* __restrict__ v, int len, int key) {
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (v[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return (lo < len && v[lo] == key) ? lo : -1;
+}
+
+// backward of tome_merge_kernel: one wave per INPUT row, 16-byte accesses, every dx row written exactly once.  The row's case is
+// wave-uniform: a B row (odd token) scans dst_idx with ballots as the forward does, an A row (even token) looks itself up in src_idx and
+// then in unm_idx (both ascending: binary search).  An A row in neither list (not a plan) gets zeros; every index taken from the plan
+// is checked against the image before it is used.
+__global__ __launch_bounds__(256) void tome_merge_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ size,
+                                                             const float* __restrict__ size_out, const int* __restrict__ unm_idx,
+                                                             const int* __restrict__ src_idx, const int* __restrict__ dst_idx, long rows_in,
+                                                             int n, int D, int r, float* __restrict__ dx) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (row >= rows_in) return;           // wave-uniform
+    const int Ta = (n + 1) >> 1, Tb = n >> 1, no = n - r, na = Ta - r;
+    const long b = row / n;
+    const int t = (int)(row - b * n);
+    const int* srcs = src_idx + b * r;
+    const int* dsts = dst_idx + b * r;
+    int o = -1;                           // the output row this input row's gradient comes from (-1: none)
+    bool scaled = false;
+    if (t & 1) {
+        const int j = t >> 1;
+        o = na + j;
+        for (int p0 = 0; p0 < r; p0 += 64) {
+            const int p = p0 + lane;
+            if (__ballot(p < r && dsts[p] == j)) { scaled = true; break; }
+        }
+    } else {
+        const int i = t >> 1;
+        const int p = r > 0 ? find_ascending(srcs, r, i) : -1;
+        if (p >= 0) {
+            const int d = dsts[p];
+            if (d >= 0 && d < Tb) { o = na + d; scaled = true; }
+        } else {
+            o = find_ascending(unm_idx + b * na, na, i);      // a position in [0, na) or -1
+        }
+    }
+    const int D4 = D >> 2;
+    f32x4* xo = reinterpret_cast<f32x4*>(dx + row * D);
+    if (o < 0) {
+        for (int c = lane; c < D4; c += 64) xo[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const f32x4* g = reinterpret_cast<const f32x4*>(dy + (b * no + o) * (long)D);
+    if (!scaled) {
+        for (int c = lane; c < D4; c += 64) xo[c] = g[c];
+        return;
+    }
+    const float w = (size ? size[b * n + t] : 1.f) / size_out[b * no + o];
+    for (int c = lane; c < D4; c += 64) xo[c] = g[c] * w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -223,6 +287,20 @@ int d2s_tome_merge(const float* x, const float* size, const int* unm_idx, const 
     if ((rows + 3) / 4 > 0x7fffffffL) return D2S_ERR_ARG;
     hipLaunchKernelGGL(tome_merge_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, size, unm_idx, src_idx, dst_idx, rows, n,
                        D, r, x_out, size_out);
+    return d2s_check_launch();
+}
+
+// Backward of d2s_tome_merge in x: dy [B,n-r,D], size [B,n] or null (all ones), size_out [B,n-r] as the forward wrote it, the forward's
+// plan -> dx [B,n,D], every row written once (r = 0: the identity copy).  The sizes and the plan get no gradient.  d2s_tome_merge's limits.
+int d2s_tome_merge_bwd(const float* dy, const float* size, const float* size_out, const int* unm_idx, const int* src_idx, const int* dst_idx,
+                       int B, int n, int D, int r, float* dx, hipStream_t stream) {
+    if (!dy || !size_out || !unm_idx || !dx || B <= 0 || n < 2 || n > TOME_MAX_N || D <= 0 || (D & 3) || r < 0 || r > (n - 1) / 2 ||
+        (r > 0 && (!src_idx || !dst_idx)))
+        return D2S_ERR_ARG;
+    const long rows = (long)B * n;
+    if ((rows + 3) / 4 > 0x7fffffffL) return D2S_ERR_ARG;
+    hipLaunchKernelGGL(tome_merge_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dy, size, size_out, unm_idx, src_idx,
+                       dst_idx, rows, n, D, r, dx);
     return d2s_check_launch();
 }
 

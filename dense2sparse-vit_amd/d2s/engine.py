@@ -292,6 +292,9 @@ def checkpoint_config(config):
     theirs.setdefault("fuse_dropped", False)       # ... and before token fusion existed: dropped tokens were discarded
     theirs.setdefault("attn_selection", False)     # ... and before attention selection existed: the score predictor selected
     theirs.setdefault("mean_heads", False)
+    theirs.setdefault("tome_r", [])                # ... and before a Token Merging student could be trained: no such student
+    theirs.setdefault("prop_attn", False)
+    theirs.setdefault("train_merge", False)
     return theirs
 
 
@@ -496,7 +499,7 @@ class TrainStep:
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
-        from losses import MaskLoss, BackboneLoss, DynamicViTLoss
+        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss
         if int(accum_steps) != accum_steps or accum_steps < 1:
             raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
         if clip_grad is not None and not float(clip_grad) > 0.0:
@@ -517,9 +520,27 @@ class TrainStep:
                                  "predictors only (train.py:50-53), and attention selection has none to train - pass warmup_steps=0")
             for p in student.score_predictor.parameters():
                 p.requires_grad_(False)       # listed in self.frozen below: the epoch schedule leaves them alone, AdamW marks their chunks idle
-        self.teacher.eval()
-        for p in self.teacher.parameters():
-            p.requires_grad_(False)
+        # a Token Merging student (vit_models/tome.py) returns logits alone and is trained with its own objective;
+        # its teacher is optional (None: no teacher forward, no side stream).  Every refusal comes before anything touches the device.
+        self.tome = type(student).__name__ == "VisionTransformerToMe"
+        if self.tome:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with a Token Merging student: the warm-up epochs train the score predictors "
+                                 "only (train.py:50-53), and token merging has none - pass warmup_steps=0")
+            if graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with a Token Merging student is not supported: a captured merging step is not "
+                                   "built; run the step eagerly (graph=False)")
+            if any(v > 0 for v in student.tome_r) and not getattr(student, "train_merge", False):
+                raise lib.D2SError("TrainStep with a merging VisionTransformerToMe needs train_merge=True (training through the merge is opt-in)")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with a Token Merging student and drop_path_rate > 0: stochastic depth is not built for a merging block")
+            graph = False
+        elif teacher is None:
+            raise lib.D2SError("TrainStep without a teacher: only a Token Merging student trains without one")
+        if self.teacher is not None:
+            self.teacher.eval()
+            for p in self.teacher.parameters():
+                p.requires_grad_(False)
         order, starts = execution_order(student)
         self.arena = ParamArena(student, order)
         self.block_offset = {i: self.arena.offsets[starts[i]] for i in starts}
@@ -527,7 +548,11 @@ class TrainStep:
         # the DynamicViT baseline (vit_models/default_dynamic_vit.py) returns (logits, features, decision, [decision per stage]) and is
         # trained with its own objective, the full one in every epoch; the freeze / learning-rate schedule is the d2s one
         self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
-        if self.baseline:
+        self.tome_loss_fn = None
+        if self.tome:
+            self.tome_loss_fn = ToMeLoss(args)
+            self.mask_loss_fn = self.backbone_loss_fn = None
+        elif self.baseline:
             if not getattr(student, "distill", False):
                 raise lib.D2SError("TrainStep with the DynamicViT baseline needs distill=True: the objective reads the student's features")
             self.dynamicvit_loss_fn = DynamicViTLoss(args)
@@ -544,7 +569,7 @@ class TrainStep:
         import os
         # the frozen teacher's forward runs on a second HIP stream beside the student's forward (independent until the losses):
         # +2.6 % images/s, identical losses (profiles/r02_f_teacher_stream_ab.txt).  D2S_TEACHER_STREAM=0 serialises them.
-        two = os.environ.get("D2S_TEACHER_STREAM", "1") == "1" and self.arena.params.is_cuda
+        two = os.environ.get("D2S_TEACHER_STREAM", "1") == "1" and self.arena.params.is_cuda and self.teacher is not None
         # chosen, not just created: it must sit on another hardware queue than the stream the step is issued on (ops.concurrent_stream)
         self._teacher_stream = ops.concurrent_stream([torch.cuda.current_stream()], "teacher forward") if two else None
         if graph is None:
@@ -662,6 +687,9 @@ class TrainStep:
             "topk_num_samples": int(getattr(s, "topk_num_samples", 500)) if getattr(s, "diff_topk", False) else 0,
             "attn_selection": bool(getattr(s, "attn_selection", False)),
             "mean_heads": bool(getattr(s, "mean_heads", False)) if getattr(s, "attn_selection", False) else False,
+            "tome_r": [int(v) for v in getattr(s, "tome_r", [])],
+            "prop_attn": bool(getattr(s, "prop_attn", False)),
+            "train_merge": bool(getattr(s, "train_merge", False)),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -745,7 +773,19 @@ class TrainStep:
         images.record_stream(side)
         self._ahead = dict(key=self._batch_key(images), images=images, out=out, done=done)
 
+    def _tome_losses(self, logits_s, out_t, labels, accumulate):
+        """ToMeLoss on the merging student's logits; 'mask_loss' reports the weighted distillation term (0 without a teacher)."""
+        fn = self.tome_loss_fn
+        logits_t = None if out_t is None else out_t[0]
+        loss = fn(logits_s, logits_t, labels, self.metrics, accumulate=accumulate)
+        dist_term = fn.dist_weight * fn.last[2]
+        return loss, dict(mask_loss=dist_term, backbone_loss=fn.last[0] - dist_term, kept=None, logits_s=logits_s, token_s=None,
+                          pred_logits=None, logits_t=logits_t, token_t=None, cls_attn=None,
+                          tokens_per_block=list(self.student.tokens_per_block))
+
     def forward_losses(self, images, labels, accumulate=True, next_images=None):
+        if self.teacher is None:
+            return self._tome_losses(self.student(images), None, labels, accumulate)
         ahead, self._ahead = self._ahead, None
         if ahead is not None and (self._teacher_stream is None or ahead["key"] != self._batch_key(images)):
             ahead = None                                # a different batch arrived than the one announced: its teacher pass is dropped
@@ -780,6 +820,8 @@ class TrainStep:
                 with torch.no_grad():
                     out_t = self.teacher(images)
                 out_s = self.student(images)
+        if self.tome:
+            return self._tome_losses(out_s, out_t, labels, accumulate)
         if self.baseline:
             return self._baseline_losses(out_s, out_t, labels, accumulate)
         logits_t, token_t, cls_attn = out_t

@@ -44,6 +44,7 @@ _SIGS = {
     "d2s_select_cls_attn": (I, [P, I, I, I, I, I, I, I, P, P, P]),
     "d2s_tome_match": (I, [P, I, I, I, I, P, P, P, P, P]),
     "d2s_tome_merge": (I, [P, P, P, P, P, I, I, I, I, P, P]),
+    "d2s_tome_merge_bwd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
     "d2s_half_mean_concat": (I, [P, P, P, I, I, I]),
     "d2s_im2col_patch": (I, [P, P, I, I, I, I, I]),
     "d2s_fill_cls": (I, [P, P, P, I, I, I]),
@@ -84,6 +85,7 @@ _SIGS = {
     "d2s_attn_policy_fwd_bf16": (I, [P, I, P, P, P, P, P, P, I, I, I, F, F]),
     "d2s_attn_policy_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_keyw_fwd_f32": (I, [P, P, P, P, I, I, I, F]),
+    "d2s_attn_keyw_bwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, F]),
     "d2s_attn_varlen_fwd_f32": (I, [P, P, P, P, I, I, I, I, F]),
     "d2s_attn_varlen_fwd_bf16": (I, [P, I, P, P, P, P, I, I, I, I, F]),
     "d2s_sum_scalar": (I, [P, L, F, P]),

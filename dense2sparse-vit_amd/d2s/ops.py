@@ -658,6 +658,25 @@ def tome_merge(x, size, unm, src, dst, B, n, D, r):
     return out, size_out
 
 
+def tome_merge_bwd(dy, size, size_out, unm, src, dst, B, n, D, r):
+    """Backward of tome_merge in x: dy [B * (n - r), D], size [B, n] or None and the plan as the forward took them, size_out [B, n - r] as
+    it wrote them -> dx [B * n, D]"""
+    _f32(dy)
+    _f32(size_out)
+    B, n, D, r = int(B), int(n), int(D), int(r)
+    for t in (unm, src, dst):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert tuple(unm.shape) == (B, (n + 1) // 2 - r) and tuple(src.shape) == (B, r) and tuple(dst.shape) == (B, r)
+    assert dy.numel() == B * (n - r) * D and tuple(size_out.shape) == (B, n - r)
+    if size is not None:
+        _f32(size)
+        assert tuple(size.shape) == (B, n)
+    dx = torch.empty((B * n, D), dtype=torch.float32, device=dy.device)
+    lib.call("d2s_tome_merge_bwd", lib.ptr(dy), lib.ptr(size), lib.ptr(size_out), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
+             lib.ptr(dst) if r > 0 else None, B, n, D, r, lib.ptr(dx))
+    return dx
+
+
 def gather_pack(x, ids):
     _f32(x)
     B, n, D = x.shape
@@ -804,6 +823,19 @@ def attn_keyw_fwd(qkv, key_w, B, n, H, scale, want_lse=False):
     lse = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if want_lse else None
     lib.call("d2s_attn_keyw_fwd_f32", lib.ptr(qkv), lib.ptr(key_w), lib.ptr(out), lib.ptr(lse), B, n, H, float(scale))
     return out, lse
+
+
+def attn_keyw_bwd(qkv, key_w, out, dout, lse, B, n, H, scale):
+    """Backward of attn_keyw_fwd (out, lse as it returned them with want_lse=True) -> dqkv shaped like qkv; the weights get no gradient."""
+    if get_gemm_mode() == GEMM_BF16:
+        raise lib.D2SError("key-weighted attention exists in fp32 only (gemm modes exact and split)")
+    _f32(key_w)
+    assert tuple(key_w.shape) == (B, n) and qkv.dtype == torch.float32
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device)
+    delta = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_keyw_bwd_f32", lib.ptr(qkv), lib.ptr(key_w), lib.ptr(out), lib.ptr(dout), lib.ptr(lse), lib.ptr(dqkv), lib.ptr(delta),
+             B, n, H, float(scale))
+    return dqkv
 
 
 def attn_fwd_bf16io(qkv, B, n, H, scale, want_cls=True, want_f32=True):

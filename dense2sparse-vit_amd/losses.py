@@ -215,3 +215,47 @@ class DynamicViTLoss(torch.nn.Module):
         for key, r in zip(("train_dynamicvit_loss", "train_cls_loss", "train_ratio_loss", "train_cls_kl_loss", "train_token_mse_loss"), self.running):
             metrics[key] = r / self.count
         self.count += 1
+
+
+class ToMeLoss(torch.nn.Module):
+    """The objective of a Token Merging student that trains through its merges (the reference has no ToMe):
+
+        L = cls_weight * CE(logits, y)                                   (soft-target CE under mixup, as BackboneLoss)
+          + dist_weight * KL(log_softmax(logits_s) || log_softmax(logits_t), batchmean, log_target)
+
+    The second term only with a teacher and dist_weight != 0.  The running means are 0-d device tensors, `float(v)` reads them."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.soft_targets = getattr(args, "mixup", 0.) > 0.
+        self.cls_weight = float(getattr(args, "cls_weight", 1.0))
+        self.dist_weight = float(getattr(args, "dist_weight", 0.5))
+        self.count = 1
+        self.running = [0, 0, 0]
+
+    def forward(self, logits_s, logits_t, train_labels, metrics, accumulate=True):
+        """logits_s [B, classes]; logits_t the teacher's, or None"""
+        B = logits_s.shape[0]
+        if self.soft_targets:
+            cls_loss = DF.RowLossFn.apply(logits_s, ops.SOFT_CE, train_labels.float().contiguous(), None, None, B)
+        else:
+            cls_loss = DF.RowLossFn.apply(logits_s, ops.CE_LABEL, None, None, train_labels.contiguous(), B)
+        loss = self.cls_weight * cls_loss
+        if logits_t is not None and self.dist_weight != 0.0:
+            cls_kl_loss = DF.RowLossFn.apply(logits_s, ops.KL_LOGIT_TARGET, logits_t.detach(), None, None, B)
+            loss = loss + self.dist_weight * cls_kl_loss
+            kl = cls_kl_loss.detach()
+        else:
+            kl = torch.zeros((), dtype=torch.float32, device=logits_s.device)
+        self.last = (loss.detach(), cls_loss.detach(), kl)
+        self.last_terms = self.last[1:]
+        if accumulate:
+            self.accumulate(metrics, self.last)
+        return loss
+
+    def accumulate(self, metrics, last):
+        """Advance the running means by one batch."""
+        self.running = [r + v for r, v in zip(self.running, last)]
+        for key, r in zip(("train_tome_loss", "train_cls_loss", "train_cls_kl_loss"), self.running):
+            metrics[key] = r / self.count
+        self.count += 1

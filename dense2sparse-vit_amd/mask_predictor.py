@@ -20,6 +20,8 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
         --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --student-checkpoint deit_small.pth
+    python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --student-checkpoint deit_small.pth \
+        --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
 """
 import os
 import sys
@@ -56,8 +58,15 @@ def check_supported(args):
     tome_r = getattr(args, "tome_r", 0)
     if tome_r < 0:
         bad.append(f"--tome-r {tome_r} (0 or more tokens per block)")
+    tome_train = bool(getattr(args, "tome_train", False))
+    if tome_train and getattr(args, "method", "d2s") != "tome":
+        bad.append(f"--tome-train with --method {getattr(args, 'method', 'd2s')} (it trains the Token Merging baseline: --method tome)")
+    if tome_train and getattr(args, "drop_path", 0.0) > 0.0:
+        bad.append(f"--tome-train with --drop-path {args.drop_path} (stochastic depth is not built for a merging block)")
+    if tome_train and args.torch_optim:
+        bad.append("--tome-train with --torch-optim (a merging student trains through the fused step only)")
     if getattr(args, "method", "d2s") == "tome":
-        if not args.eval_only:
+        if not args.eval_only and not tome_train:
             bad.append("--method tome without --eval-only (token merging is built for inference: training through a merge needs the merge's "
                        "backward and key weights in both attention-backward kernels)")
         if getattr(args, "gemm_mode", "exact") == "bf16":
@@ -155,6 +164,10 @@ def check_supported(args):
     if args.output_dir and args.torch_optim and not args.eval_only:
         print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
               "loads through --student-checkpoint, it cannot be resumed")
+    if tome_train and args.warmup_steps > 0:
+        print("Attention: --tome-train trains a model without score predictors, so the predictor warm-up has no meaning "
+              "(mask_predictor.py:300): --warmup-steps is set to 0")
+        args.warmup_steps = 0
     if getattr(args, "attn_selection", False):
         print("Attention: --attn-selection selects tokens by the student's own CLS attention and never calls the score predictors, so the "
               "predictor warm-up has no meaning (mask_predictor.py:300): --warmup-steps is set to 0"
@@ -200,8 +213,11 @@ def build_tome(args):
     """--method tome: the dense DeiT trunk with token merging, weights from --student-checkpoint or the 'model' entry of a --resume file.  A
     dense-to-sparse student's checkpoint carries score predictors this model has no use for: they are ignored (strict=False)."""
     arch = args.arch if args.arch in _TOME else "deit_small"
-    model = getattr(vit_models, _TOME[arch])(args.tome_r)
+    model = getattr(vit_models, _TOME[arch])(args.tome_r, train_merge=bool(getattr(args, "tome_train", False)))
     path = args.student_checkpoint or args.resume
+    if path is None:
+        print("--method tome: no --student-checkpoint, the trunk starts from its random initialisation")
+        return model.to(args.device)
     sd = vit_models.checkpoint_filter_fn(torch.load(path, map_location="cpu", weights_only=True), model)
     missing, unexpected = model.load_state_dict(sd, strict=False)
     if missing:
@@ -294,9 +310,15 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
-    if args.method == "tome":
+    if args.method == "tome" and not args.tome_train:
         return eval_tome(args, rank, world, distributed)
-    student, teacher = build_models(args)
+    if args.method == "tome":
+        # --tome-train: the merging student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
+        student = build_tome(args)
+        arch = args.arch if args.arch in _TEACHERS else "deit_small"
+        teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device) if args.dist_weight != 0 else None
+    else:
+        student, teacher = build_models(args)
     if rank == 0:
         for key in sorted(vars(args), key=str.lower):
             print(f'{key}: {getattr(args, key)}')
@@ -304,15 +326,19 @@ def main(argv=None):
         print('Freezing whole student, except predictor network')
         for n, p in student.named_parameters():
             p.requires_grad = 'predictor' in n
-    teacher.eval()
-    for p in teacher.parameters():
-        p.requires_grad = False
+    step_teacher = teacher
+    if teacher is not None:
+        teacher.eval()
+        for p in teacher.parameters():
+            p.requires_grad = False
+    else:
+        teacher = torch.nn.Identity()        # what the evaluation of a logits-only model is handed (eval_tome does the same)
     if args.torch_optim:
         if distributed:
             raise SystemExit("--torch-optim is the single-process reference recipe; drop it for --use-ddp")
         optim = torch.optim.AdamW(utils.get_param_groups(student, args), lr=args.lr, weight_decay=args.weight_decay)   # :213,229-230
     else:
-        optim = TrainStep(student, teacher, args, lr=args.lr, min_lr=args.min_lr, weight_decay=args.weight_decay, epochs=args.epochs,
+        optim = TrainStep(student, step_teacher, args, lr=args.lr, min_lr=args.min_lr, weight_decay=args.weight_decay, epochs=args.epochs,
                           warmup_steps=args.warmup_steps, distributed=distributed, accum_steps=args.accum_steps, clip_grad=args.clip_grad)
         if distributed:
             dist.broadcast(optim.arena.params, src=0)
@@ -411,6 +437,8 @@ def main(argv=None):
                 first_save = save_checkpoints(args, optim, student, epoch, best_acc, improved, first_save)
             if distributed:
                 dist.barrier()
+        if rank == 0 and args.method == "tome":
+            print(f"--method tome --tome-r {args.tome_r} --tome-train: tokens per block {student.tokens_per_block}")
         if rank == 0:
             print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))

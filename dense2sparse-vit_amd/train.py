@@ -10,7 +10,7 @@ the mean over the window, clipped to the global L2 norm M.  A TrainStep carries 
 step) and is flushed at the end of the epoch; for a torch optimizer the same window is spelled out here with torch."""
 import torch
 
-from losses import MaskLoss, BackboneLoss, DynamicViTLoss
+from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss
 
 
 def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mixup_fn=None):
@@ -20,13 +20,18 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
     running_loss = 0.0
     metrics = {}
     model.train()
-    teacher_model.eval()
+    if teacher_model is not None:
+        teacher_model.eval()
     fast = isinstance(optimizer, TrainStep)
+    if type(model).__name__ == "VisionTransformerToMe" and not fast:
+        raise ValueError("a Token Merging student trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer
         step.metrics = metrics
-        if baseline:
+        if getattr(step, "tome", False):
+            step.tome_loss_fn = ToMeLoss(args)
+        elif baseline:
             step.dynamicvit_loss_fn = DynamicViTLoss(args)
         else:
             step.mask_loss_fn, step.backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)   # fresh running means per epoch (:14-15)

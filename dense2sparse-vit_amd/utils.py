@@ -164,7 +164,10 @@ def parse_args(argv=None):
     p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
-                        "tome: the Token Merging baseline (--tome-r, --eval-only: no predictor, no training)")
+                        "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges)")
+    p.add_argument('--tome-train', action='store_true', default=False,
+                   help='with --method tome: train through the merges (merge backward, key-weighted attention backward); the objective is '
+                        '--cls-weight * CE + --dist-weight * KL to the dense teacher (--dist-weight 0: no teacher)')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

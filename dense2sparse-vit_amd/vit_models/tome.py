@@ -1,6 +1,7 @@
 """Token Merging baseline (ToMe, Bolya et al. 2023; DESIGN.md section 22 - no counterpart in the reference): an off-the-shelf DeiT trunk
-whose every block merges r tokens into their most similar partner between its attention branch and its MLP.  No predictor, no training:
-the model has the teacher's parameters and state-dict keys and loads any DeiT checkpoint.  Inference only."""
+whose every block merges r tokens into their most similar partner between its attention branch and its MLP.  No predictor: the model has
+the teacher's parameters and state-dict keys and loads any DeiT checkpoint.  Off the shelf it is an inference model; train_merge=True opts
+into training through the merge (d2s.functional_tome.ToMeBlockFn), as the paper's fine-tuned numbers do."""
 import torch
 
 from d2s import functional as DF
@@ -15,9 +16,11 @@ class VisionTransformerToMe(VisionTransformerTeacher):
     """The dense ViT with token merging.  tome_r: tokens merged away per block, one int for every block or a list of `depth` ints; each
     block clips its count to (n - 1) // 2 of the n tokens it sees.  prop_attn: weight every key by the patches it stands for
     (proportional attention) once something has merged.  forward (eval mode) returns the logits; afterwards tokens_per_block[i] is the
-    number of tokens (CLS included) that leave block i, and tome_plans[i] the block's (unm_idx, src_idx, dst_idx) or None."""
+    number of tokens (CLS included) that leave block i, and tome_plans[i] the block's (unm_idx, src_idx, dst_idx) or None.
+    train_merge: let the training-mode forward merge too - every block runs through ToMeBlockFn, gradients flow through the merge (a
+    size-weighted average with a constant plan) and the key-weighted attention; off (the default), a merging model refuses to train."""
 
-    def __init__(self, *args, tome_r=0, prop_attn=True, **kwargs):
+    def __init__(self, *args, tome_r=0, prop_attn=True, train_merge=False, **kwargs):
         super().__init__(*args, **kwargs)
         depth = len(self.blocks)
         rs = [int(tome_r)] * depth if isinstance(tome_r, int) else [int(v) for v in tome_r]
@@ -25,12 +28,18 @@ class VisionTransformerToMe(VisionTransformerTeacher):
             raise ValueError(f"tome_r: one non-negative int or a list of {depth} of them, got {tome_r!r}")
         self.tome_r = rs
         self.prop_attn = bool(prop_attn)
+        self.train_merge = bool(train_merge)
+        if self.train_merge and float(getattr(self, "drop_path_rate", 0.0)) > 0.0:
+            raise ValueError("train_merge with drop_path_rate > 0: stochastic depth is not built for a merging block")
+        self.grad_ready_hook = None          # set by a data-parallel TrainStep: called with i when block i's input gradient exists
         self.tokens_per_block = None
         self.tome_plans = None
 
     def forward(self, x, plans=None):
         """plans: per block (unm_idx, src_idx, dst_idx) or None, to replay instead of matching."""
         merging = any(v > 0 for v in self.tome_r)
+        if self.training and self.train_merge:
+            return self._forward_train_merge(x, plans)
         if self.training:
             if merging:
                 raise NotImplementedError(TOME_TRAINING_ERROR)
@@ -53,6 +62,21 @@ class VisionTransformerToMe(VisionTransformerTeacher):
                 used.append(plan)
             self.tokens_per_block, self.tome_plans = counts, used
             return DF.run(DF.HeadFn, x.view(B, n, D), self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.norm.eps, 0)[0]
+
+    def _forward_train_merge(self, x, plans):
+        """The eval forward's launches with everything a backward needs kept: one ToMeBlockFn per block, matching on the fly or replaying."""
+        x = self._embed(x)
+        size, counts, used = None, [], []
+        for i, blk in enumerate(self.blocks):
+            if self.grad_ready_hook is not None and x.requires_grad:
+                x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
+            a = blk.attn
+            x, size, plan = TF.tome_block_train(x, size, blk._params(), a.num_heads, blk.norm1.eps, a.scale, self.tome_r[i], self.prop_attn,
+                                                None if plans is None else plans[i])
+            counts.append(x.shape[1])
+            used.append(plan)
+        self.tokens_per_block, self.tome_plans = counts, used
+        return self._head(x)[0]
 
 
 def _tome(size, tome_r, checkpoint_path=None, **kwargs):

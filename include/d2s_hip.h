@@ -186,6 +186,12 @@ int d2s_tome_match(const float* qkv, int B, int n, int H, int r, float* node_max
  * after the row itself; rows nothing merges into are copied bit for bit.  size_out [B,n-r] = the denominators (exact).  D % 4 == 0. */
 int d2s_tome_merge(const float* x, const float* size, const int* unm_idx, const int* src_idx, const int* dst_idx, int B, int n, int D, int r,
                    float* x_out, float* size_out, d2s_stream_t stream);
+/* ... and its backward in x (training through the merge): dy [B,n-r,D], size and the plan as the forward took them, size_out [B,n-r] as it
+ * wrote them -> dx [B,n,D], every row written once by its own wave: a merged row (a source, or a B row with sources) gets
+ * (size_t / size_out_row) * dy_row - one division per row, one multiply per element - every other row its output row's gradient bit for
+ * bit (r = 0: the identity), an A row in neither list zeros.  The sizes and the plan get no gradient.  d2s_tome_merge's limits. */
+int d2s_tome_merge_bwd(const float* dy, const float* size, const float* size_out, const int* unm_idx, const int* src_idx, const int* dst_idx,
+                       int B, int n, int D, int r, float* dx, d2s_stream_t stream);
 /* split / token-mean / concat of the predictor, vit_models/dynamic_vit.py:540-544 (self-adjoint: also its backward) */
 int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, d2s_stream_t stream);
 
@@ -321,9 +327,14 @@ int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
                              const float* cinv, float* dqkv /* nullable if dqkv_bf16 */, void* dqkv_bf16 /* nullable */, float* delta_ws,
                              float* dpolicy /* nullable */, float* dpol_ws, int B, int n, int H, float scale, d2s_stream_t stream);
 /* attention whose keys carry weights (token merging): out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B,n] (>= 1);
- * lse [B,H,n] (nullable) = log of the denominator.  All weights 1.0: bit for bit d2s_attn_fwd_f32.  Forward only, n >= 2. */
+ * lse [B,H,n] (nullable) = log of the denominator.  All weights 1.0: bit for bit d2s_attn_fwd_f32.  n >= 2. */
 int d2s_attn_keyw_fwd_f32(const float* qkv, const float* key_w, float* out, float* lse, int B, int n, int H, float scale,
                           d2s_stream_t stream);
+/* ... and its backward (out, lse as that call wrote them): P_ij = w_j exp(S_ij - lse_i), dV = P^T dO, dS = P * (dP - delta).  dqkv
+ * [B,n,3,H,64] is fully written; delta_ws: [B,H,n] floats of scratch.  The weights are counts and get no gradient.  All weights 1.0: bit
+ * for bit d2s_attn_bwd_f32.  2 <= n <= 8192. */
+int d2s_attn_keyw_bwd_f32(const float* qkv, const float* key_w, const float* out, const float* dout, const float* lse, float* dqkv,
+                          float* delta_ws, int B, int n, int H, float scale, d2s_stream_t stream);
 /* ragged packed attention forward (inference): qkv [total,3,H,64], image b = rows cu[b]..cu[b+1]; cls_row (optional) [H,total] */
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, d2s_stream_t stream);

@@ -4,13 +4,19 @@ weights in the same process.  Every configuration is warmed up at its own shapes
 (so that a neighbour's load on the machine hits them alike), each round is a window of --iters forwards between two device events, and
 the table reports the median images/s with the lowest and highest round.  GPU box only.
 
-  python tools/tome_bench.py [--rounds 5] [--iters 10] [--r 0 8 13 16]
+--train: the same table for training through the merges (--tome-train): ms per d2s.engine.TrainStep call (forward, ToMeLoss without a
+teacher - dist_weight 0 -, backward, fused AdamW) of a train_merge student, hard labels, same alternating rounds; read every row against
+the r = 0 row of the same run.
+
+  python tools/tome_bench.py [--rounds 5] [--iters 10] [--r 0 8 13 16] [--train]
   rocprofv3 --kernel-trace --stats -d DIR -o tome -- python tools/tome_bench.py --no-teacher --r 13 --rounds 1      (kernel shares)
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o tome -- python tools/tome_bench.py --train --r 13 --rounds 1     (... of a train step)
 """
 import argparse
 import os
 import statistics
 import sys
+import types
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "dense2sparse-vit_amd"))
@@ -23,6 +29,7 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--r", type=int, nargs="+", default=[0, 8, 13, 16])
 ap.add_argument("--no-teacher", action="store_true", help="leave the teacher forward out (a kernel trace of one merging configuration alone)")
+ap.add_argument("--train", action="store_true", help="time a TrainStep of a train_merge student (no teacher, dist_weight 0) instead of the eval forward")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     raise SystemExit("tools/tome_bench.py needs a GPU: nothing here is measured on the CPU")
@@ -34,6 +41,41 @@ torch.manual_seed(0)
 x = torch.randn(B, 3, 224, 224, device=dev)
 teacher = vit_models.dynamic_vit_small_patch16_224_teacher().to(dev).eval()
 weights = teacher.state_dict()
+if args.train:
+    from d2s.engine import TrainStep
+    y = torch.randint(0, 1000, (B,), device=dev)
+    steps = []
+    for r in args.r:
+        m = vit_models.tome_deit_small_patch16_224(r, train_merge=True)
+        m.load_state_dict(weights)
+        steps.append((f"tome r = {r}", TrainStep(m.to(dev), None, types.SimpleNamespace(mixup=0.0, cls_weight=1.0, dist_weight=0.0, step=0))))
+    del teacher
+
+    def train_window(step, iters):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            step(x, y)
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e) / iters
+
+    for _, step in steps:
+        train_window(step, 3)                             # warm-up at this configuration's own shapes
+    ms = {name: [] for name, _ in steps}
+    for _ in range(args.rounds):
+        for name, step in steps:
+            ms[name].append(train_window(step, args.iters))
+    print(f"DeiT-S 224, B = {B}, fp32 exact GEMMs, TrainStep (no teacher, dist_weight 0), {args.rounds} rounds x {args.iters} steps per "
+          "configuration, rounds alternating")
+    print(f"{'configuration':16s} {'ms/step':>9s} {'min':>8s} {'max':>8s} {'images/s (median)':>18s} {'min':>8s} {'max':>8s}   tokens leaving each block")
+    for name, step in steps:
+        t = sorted(ms[name])
+        rate = sorted(B / v * 1e3 for v in t)
+        print(f"{name:16s} {statistics.median(t):9.2f} {t[0]:8.2f} {t[-1]:8.2f} {statistics.median(rate):18.0f} {rate[0]:8.0f} {rate[-1]:8.0f}   "
+              f"{' '.join(map(str, step.student.tokens_per_block))}", flush=True)
+    sys.exit(0)
+
 configs = [] if args.no_teacher else [("teacher forward", teacher)]
 for r in args.r:
     m = vit_models.tome_deit_small_patch16_224(r)
