@@ -31,6 +31,13 @@
 // its image returns before any barrier (block-uniform).  The CLS softmax row goes to cls_row[h * total + cu[b] + j]; no log-sum-exp is
 // written (forward only).  The arguments are the same kind of variadic tail (AttnVarlen), the code sits under `if constexpr`.  With
 // cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same bits.
+//
+// KEYW (the 32-key-tile forward only; no policy, no ragged form, no backward): attention whose keys carry weights, token merging at
+// inference on the bf16 data path.  out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B, n] >= 1: the
+// tile's 32 weights travel through pol_s as a policy does, e_ij = 2^(s log2 e - m log2 e) * w_j (one more fp32 rounding) feeds both the
+// row sum and the bf16 P; no diagonal exception.  The running maximum stays the one over the raw scores (w >= 1 keeps e w >= e), so
+// lse_i = m_i + log(l_i) is the log of the weighted denominator, d2s_attn_keyw_fwd_f32's definition.  The arguments are a variadic tail
+// (AttnKeyW).  With unit weights the multiply is by 1.0: the bits of the plain kernel.
 #include "d2s_common.h"
 #include <cstdlib>
 
@@ -70,6 +77,10 @@ struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
 struct AttnVarlen { const int* cu; int total; };
 template <typename... T> struct is_varlen_tail { static constexpr bool value = false; };
 template <> struct is_varlen_tail<AttnVarlen> { static constexpr bool value = true; };
+// the variadic tail of the KEYW instantiations: the keys carry weights (token merging), w [B, n], >= 1
+struct AttnKeyW { const float* w; };
+template <typename... T> struct is_keyw_tail { static constexpr bool value = false; };
+template <> struct is_keyw_tail<AttnKeyW> { static constexpr bool value = true; };
 template <typename T>
 __device__ __forceinline__ T tail_arg(T a) { return a; }
 // mk of the 16 keys a lane holds in accumulator order (registers 4g .. 4g+3 = tile rows 8g + 4 half + 0..3) from the tile's policy in LDS.
@@ -90,7 +101,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
                                                                float scale, Pol... pol_) {
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];      // [key][d]
     __shared__ __attribute__((aligned(16))) __bf16 Vt[DH * VP];      // [d][pos(key)]
-    __shared__ __attribute__((aligned(16))) float pol_s[POLICY ? 32 : 1];            // the tile's policy
+    constexpr bool KEYW = is_keyw_tail<Pol...>::value;
+    __shared__ __attribute__((aligned(16))) float pol_s[(POLICY || KEYW) ? 32 : 1];  // the tile's policy (KEYW: its key weights)
     __shared__ __attribute__((aligned(16))) float vred[POLICY ? 32 * DH : 1];        // [staging key row][d] partial column sums of V
     __shared__ float vsum_s[POLICY ? DH : 1];                                        // (eps/n) * column sums of V
     extern __shared__ __attribute__((aligned(16))) float cls_s[];    // [n] raw scaled scores of query 0 (block 0 only)
@@ -101,6 +113,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const long ld = 3L * H * DH;
     constexpr bool VARLEN = is_varlen_tail<Pol...>::value;
     static_assert(!(POLICY && VARLEN), "the ragged form has no policy");
+    static_assert(!(KEYW && (POLICY || VARLEN)), "key weights combine with neither the policy nor the ragged form");
     long tok0 = (long)b * n;                       // first token row of the image
     [[maybe_unused]] long cls0 = 0;                // VARLEN: start of the image's CLS softmax row inside cls_row [H, total]
     if constexpr (VARLEN) {
@@ -125,6 +138,10 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
         polb = pa.policy + (long)b * n;
         cinv = pa.cinv;
         eps = pa.eps;
+    }
+    if constexpr (KEYW) {
+        const AttnKeyW ka = tail_arg(pol_...);
+        polb = ka.w + (long)b * n;
     }
 
     // B operand of S^T = K Q^T: this lane's query, d = 16 kk + 8 half + j, scaled, as bf16 (scale = 2^-3 for 64-wide heads: the product
@@ -155,13 +172,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const int skey = tid >> 3, sd8 = (tid & 7) * 8;
     const int ntiles = (n + 31) / 32;
     f32x4 kr[2], vr[2];
-    float pr = 0.f;                              // POLICY: policy of key t * 32 + (tid & 31)
+    float pr = 0.f;                              // POLICY: policy of key t * 32 + (tid & 31); KEYW: its weight
     f32x4 vacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // POLICY: this thread's 8 columns of V summed over its key rows
     auto fetch = [&](int t) {
         const long row = min(t * 32 + skey, n - 1);
         load8(kb + row * ld + sd8, kr);
         load8(vb + row * ld + sd8, vr);
-        if constexpr (POLICY) { const int kj = t * 32 + (tid & 31); const float p0 = polb[min(kj, n - 1)]; pr = kj < n ? p0 : 0.f; }
+        if constexpr (POLICY || KEYW) { const int kj = t * 32 + (tid & 31); const float p0 = polb[min(kj, n - 1)]; pr = kj < n ? p0 : 0.f; }
     };
     fetch(0);
     for (int t = 0; t < ntiles; ++t) {
@@ -176,6 +193,9 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
             for (int j = 0; j < 4; ++j) {
                 Vt[(sd8 + j) * VP + pos] = (__bf16)vr[0][j];
                 Vt[(sd8 + 4 + j) * VP + pos] = (__bf16)vr[1][j];
+            }
+            if constexpr (KEYW) {
+                if (tid < 32) pol_s[tid] = pr;
             }
             if (POLICY) {
                 if (tid < 32) pol_s[tid] = pr;
@@ -219,10 +239,15 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
         float rs = 0.f;
         f32x4 pg[4];
         if (POLICY) tile_policy(pol_s, half, l31, kv0 == q0, pg);
+        if constexpr (KEYW) {      // the 16 key weights in accumulator order; a key weighs the same for every query, its own included
+#pragma unroll
+            for (int g = 0; g < 4; ++g) pg[g] = *reinterpret_cast<const f32x4*>(&pol_s[8 * g + 4 * half]);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -m2));
             if (POLICY) s[r] *= pg[r >> 2][r & 3];      // keys past the sequence: e = 0 already
+            if constexpr (KEYW) s[r] *= pg[r >> 2][r & 3];      // w >= 1 (e w >= e): the running maximum stays the one over the raw scores
             rs += s[r];
         }
         rs += __shfl_xor(rs, 32, 64);
@@ -923,6 +948,24 @@ int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
                                                  delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
     return attn_policy_bwd_bf16_impl<float>(static_cast<const float*>(qkv), policy, out, dout, lse, cinv, dqkv, static_cast<__bf16*>(dqkv_bf16),
                                             delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
+}
+
+// Key-weighted attention (d2s_attn_keyw_fwd_f32's definition; token merging at inference) on the bf16 matrix cores and the bf16 data path:
+// qkv fp32 or bf16 as in d2s_attn_fwd_bf16_bf16out, key_w [B, n] fp32 (>= 1), out (fp32) and / or out_bf16 written - at least one; lse
+// [B, H, n] = log of the weighted denominator.  No CLS row.  Always the 32-key-tile kernel, d2s_attn_policy_fwd_bf16's grid.  With unit
+// weights the outputs are the bits of d2s_attn_fwd_bf16_bf16out where that entry uses the same kernel.  2 <= n <= 8192.
+int d2s_attn_keyw_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* key_w, float* out, void* out_bf16, float* lse, int B, int n, int H,
+                           float scale, hipStream_t stream) {
+    if (!qkv || !key_w || (!out && !out_bf16) || !lse || B <= 0 || n < 2 || n > 8192 || H <= 0) return D2S_ERR_ARG;
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    const AttnKeyW ka{key_w};
+    if (qkv_is_bf16)
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, false, AttnKeyW>), grid, block, 0, stream, static_cast<const __bf16*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), lse, static_cast<float*>(nullptr), n, H, scale, ka);
+    else
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, false, AttnKeyW>), grid, block, 0, stream, static_cast<const float*>(qkv), out,
+                           static_cast<__bf16*>(out_bf16), lse, static_cast<float*>(nullptr), n, H, scale, ka);
+    return d2s_check_launch();
 }
 
 }  // extern "C"

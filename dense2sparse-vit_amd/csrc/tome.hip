@@ -17,25 +17,43 @@
 //              (size_t / size_out_row) dy_row, every other row its output row's gradient bit for bit.
 //
 // No atomics, no memset, no scratch, nothing read back by the host: deterministic and legal inside a captured step.
+//
+// The match also reads a bf16 qkv (the qkv GEMM's c_bf16 on the bf16 data path): the kernel is a template on the element type, the bf16
+// load converts each value to fp32 (exact) and everything after the load is the same fp32 code in the same order, so
+// d2s_tome_match_bf16(q16) is d2s_tome_match(float(q16)) bit for bit.
 #include "d2s_common.h"
 
 namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int DH = 64;
 constexpr int MPITCH = 68;        // floats per staged B row: 16-B aligned, a wave's 64 row writes spread over 16 bank slots instead of one
 constexpr int TOME_MAX_N = 896;   // (448 * 68 + 3 * 448) floats = 124.3 KiB of dynamic LDS (attnsel.hip runs with 128 KiB)
 
 // normalised metric of one token, computed by ONE thread in a fixed order (so equal K rows give equal bits wherever they sit)
-__device__ __forceinline__ void metric_row(const float* __restrict__ krow, int H, float (&m)[DH]) {
+// (from a bf16 row: 8 values per 16-byte access, each widened to fp32 - exact - and added in the same order, h ascending, d in place)
+template <typename T>
+__device__ __forceinline__ void metric_row(const T* __restrict__ krow, int H, float (&m)[DH]) {
 #pragma unroll
     for (int d = 0; d < DH; ++d) m[d] = 0.f;
     for (int h = 0; h < H; ++h) {
-        const f32x4* p = reinterpret_cast<const f32x4*>(krow + h * DH);
+        if constexpr (sizeof(T) == 4) {
+            const f32x4* p = reinterpret_cast<const f32x4*>(krow + h * DH);
 #pragma unroll
-        for (int q = 0; q < DH / 4; ++q) {
-            const f32x4 v = p[q];
+            for (int q = 0; q < DH / 4; ++q) {
+                const f32x4 v = p[q];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) m[4 * q + j] += v[j];
+                for (int j = 0; j < 4; ++j) m[4 * q + j] += v[j];
+            }
+        } else {
+            const bf16x8* p = reinterpret_cast<const bf16x8*>(krow + h * DH);
+#pragma unroll
+            for (int q = 0; q < DH / 8; ++q) {
+                const bf16x8 v = p[q];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) m[8 * q + j] += (float)v[j];
+            }
         }
     }
     const float fh = (float)H;
@@ -50,7 +68,8 @@ __device__ __forceinline__ void metric_row(const float* __restrict__ krow, int H
     for (int d = 0; d < DH; ++d) m[d] = m[d] / nrm;
 }
 
-__global__ __launch_bounds__(256) void tome_match_kernel(const float* __restrict__ qkv, int n, int H, int r, float* __restrict__ node_max,
+template <typename T>
+__global__ __launch_bounds__(256) void tome_match_kernel(const T* __restrict__ qkv, int n, int H, int r, float* __restrict__ node_max,
                                                          int* __restrict__ node_idx, int* __restrict__ unm_idx, int* __restrict__ src_idx,
                                                          int* __restrict__ dst_idx) {
     extern __shared__ __attribute__((aligned(16))) float sh[];   // [T_b][MPITCH] metric of set B, [T_a] node_max, [T_a] node_idx, [T_a] source flags
@@ -62,7 +81,7 @@ __global__ __launch_bounds__(256) void tome_match_kernel(const float* __restrict
     int* flag = vidx + Ta;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long ld = 3L * H * DH;
-    const float* kb = qkv + (long)blockIdx.x * n * ld + (long)H * DH;     // K of token 0, head 0
+    const T* kb = qkv + (long)blockIdx.x * n * ld + (long)H * DH;     // K of token 0, head 0
     float a[DH];
     for (int j = tid; j < Tb; j += 256) {
         metric_row(kb + (long)(2 * j + 1) * ld, H, a);
@@ -268,12 +287,32 @@ int d2s_tome_match(const float* qkv, int B, int n, int H, int r, float* node_max
     const int Ta = (n + 1) / 2, Tb = n / 2;
     static bool attr_set = false;       // n = 577 stages 80 KiB, above the runtime's default per-kernel limit of dynamic LDS (64 KiB)
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tome_match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tome_match_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (TOME_MAX_N / 2) * (MPITCH + 3) * (int)sizeof(float));
         attr_set = true;
     }
-    hipLaunchKernelGGL(tome_match_kernel, dim3(B), dim3(256), ((size_t)Tb * MPITCH + 3 * (size_t)Ta) * sizeof(float), stream, qkv, n, H, r,
+    hipLaunchKernelGGL(tome_match_kernel<float>, dim3(B), dim3(256), ((size_t)Tb * MPITCH + 3 * (size_t)Ta) * sizeof(float), stream, qkv, n, H, r,
                        node_max, node_idx, unm_idx, src_idx, dst_idx);
+    return d2s_check_launch();
+}
+
+// The same match on a bf16 qkv [B,n,3,H,64] (the qkv GEMM's c_bf16 on the bf16 data path): d2s_tome_match on the widened tensor, bit for
+// bit in all five outputs.  Its limits and refusals.  The raised dynamic-LDS limit is a property of the kernel function: this
+// instantiation sets its own on its first call.
+int d2s_tome_match_bf16(const void* qkv_bf16, int B, int n, int H, int r, float* node_max, int* node_idx, int* unm_idx, int* src_idx,
+                        int* dst_idx, hipStream_t stream) {
+    if (!qkv_bf16 || !node_max || !node_idx || !unm_idx || B <= 0 || n < 2 || n > TOME_MAX_N || H <= 0 || r < 0 || r > (n - 1) / 2 ||
+        (r > 0 && (!src_idx || !dst_idx)))
+        return D2S_ERR_ARG;
+    const int Ta = (n + 1) / 2, Tb = n / 2;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tome_match_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (TOME_MAX_N / 2) * (MPITCH + 3) * (int)sizeof(float));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(tome_match_kernel<__bf16>, dim3(B), dim3(256), ((size_t)Tb * MPITCH + 3 * (size_t)Ta) * sizeof(float), stream,
+                       static_cast<const __bf16*>(qkv_bf16), n, H, r, node_max, node_idx, unm_idx, src_idx, dst_idx);
     return d2s_check_launch();
 }
 

@@ -8,8 +8,10 @@ The match reads the keys of the qkv GEMM's output in place; the merge acts on x1
 rows.  Attention is the plain kernel while every token still stands for one patch (size is None) and the key-weighted one afterwards
 (proportional attention).  The composite block call (ops.block_fwd) cannot serve here - the merge sits in the middle of the block - so the
 launches are issued one by one, the same kernels in the same order as functional.block_forward_sequence: with r = 0 and no sizes the
-result is bit for bit the dense block's.  The bf16 arithmetic mode is refused (the key-weighted attention is an fp32 kernel; the GEMM modes
-exact and split both run).
+result is bit for bit the dense block's.  The bf16 arithmetic mode is refused there (the key-weighted attention it calls is an fp32
+kernel; the GEMM modes exact and split both run); tome_block_forward_bf16 is the same block on the bf16 data path, inference only:
+LayerNorm and the GEMMs hand bf16 to each other, attention and the match read the bf16 qkv (ops.attn_keyw_fwd_bf16io,
+ops.tome_match_bf16), the residual stream and therefore the merge stay fp32.
 
 Training: the merge is a size-weighted average with a constant plan (the match reads K under no gradient, as the published
 bipartite_soft_matching does), so its backward is one scaled row copy per input row (ops.tome_merge_bwd); the attention backward takes
@@ -19,7 +21,7 @@ residual gradient lives on n - r rows, the attention half's on n.
 import torch
 
 from . import ops
-from .functional import layernorm_backward, mode_recorded, wants_grad
+from .functional import _norm_linear, bf16_data_path, layernorm_backward, mode_recorded, wants_grad
 from .lib import D2SError
 
 _BF16_REFUSAL = "token merging runs in the fp32 arithmetic modes (exact, split): the key-weighted attention has no bf16 kernel"
@@ -57,6 +59,37 @@ def tome_block_forward(x, size, params, B, n, heads, eps, scale, r, prop_attn=Tr
     h = ops.linear_fwd(ln, fc1w, fc1b, epi=ops.EPI_BIAS_GELU)
     del ln
     y = ops.linear_fwd(h, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1)
+    return y, size, plan
+
+
+def tome_block_forward_bf16(x, size, params, B, n, heads, eps, scale, r, prop_attn=True, plan=None):
+    """tome_block_forward on the bf16 data path (inference): the launches of functional.block_forward_sequence with io=True, train=False,
+    and the match and the merge between proj and the second LayerNorm.  Same arguments, same shape of a result.  With r = 0 and no sizes:
+    bit for bit the bf16 forward-only block."""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
+    rows, D = x.shape
+    assert rows == B * n
+    if not bf16_data_path(x, D, fc1w.shape[0]):
+        raise D2SError("tome_block_forward_bf16 needs the bf16 data path: the bf16 arithmetic mode (ops.gemm_mode(ops.GEMM_BF16)), "
+                       "D2S_BF16_IO not 0, D and hidden multiples of 32 and device tensors")
+    r = ops.tome_clip_r(r, n)
+    _, qkv, _, _ = _norm_linear(x, ops.contiguous_map(rows, D), n1w, n1b, qkvw, qkvb, eps, True, False)
+    if size is not None and prop_attn:
+        _, _, ao16 = ops.attn_keyw_fwd_bf16io(qkv, size, B, n, heads, scale, want_f32=False)
+    else:
+        _, _, _, ao16 = ops.attn_fwd_bf16io(qkv, B, n, heads, scale, want_cls=False, want_f32=False)
+    x1 = ops.linear_fwd(None, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x, a16=ao16)
+    del ao16
+    if r > 0:
+        if plan is None:
+            plan = ops.tome_match_bf16(qkv, B, n, heads, r)[2:]
+        x1, size = ops.tome_merge(x1, size, *plan, B, n, D, r)
+    else:
+        plan = None
+    del qkv
+    rows = B * (n - r)
+    _, h16, _, _ = _norm_linear(x1, ops.contiguous_map(rows, D), n2w, n2b, fc1w, fc1b, eps, True, False, ops.EPI_BIAS_GELU)
+    y = ops.linear_fwd(None, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=h16)
     return y, size, plan
 
 

@@ -1,4 +1,5 @@
-"""ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h).
+"""ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, and include/d2s_hip_ext.h, where
+new entries go).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -138,6 +139,12 @@ _SIGS = {
     "d2s_ratio_rows_bwd": (I, [P, P, F, P, I, I]),
 }
 
+# the entries of include/d2s_hip_ext.h, same form
+_SIGS_EXT = {
+    "d2s_attn_keyw_fwd_bf16": (I, [P, I, P, P, P, P, I, I, I, F]),
+    "d2s_tome_match_bf16": (I, [P, I, I, I, I, P, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -154,7 +161,7 @@ def load():
         raise D2SError(f"{LIB_PATH} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -164,6 +171,10 @@ def load():
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+def extension_symbols():
+    return sorted(_SIGS_EXT)
 
 
 def ptr(t):

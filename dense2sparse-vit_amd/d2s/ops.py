@@ -641,6 +641,20 @@ def tome_match(qkv, B, n, H, r):
     return node_max, node_idx, unm, src, dst
 
 
+def tome_match_bf16(qkv16, B, n, H, r):
+    """tome_match on a bf16 qkv (the qkv GEMM's c16 on the bf16 data path), read in place: bit for bit tome_match(qkv16.float())."""
+    assert qkv16.dtype == torch.bfloat16 and qkv16.is_contiguous(), (qkv16.dtype, qkv16.is_contiguous())
+    B, n, H, r = int(B), int(n), int(H), int(r)
+    Ta = (n + 1) // 2
+    i32 = dict(dtype=torch.int32, device=qkv16.device)
+    node_max = torch.empty((B, Ta), dtype=torch.float32, device=qkv16.device)
+    node_idx, unm = torch.empty((B, Ta), **i32), torch.empty((B, max(Ta - r, 0)), **i32)
+    src, dst = torch.empty((B, max(r, 0)), **i32), torch.empty((B, max(r, 0)), **i32)
+    lib.call("d2s_tome_match_bf16", lib.ptr(qkv16), B, n, H, r, lib.ptr(node_max), lib.ptr(node_idx), lib.ptr(unm),
+             lib.ptr(src) if r > 0 else None, lib.ptr(dst) if r > 0 else None)
+    return node_max, node_idx, unm, src, dst
+
+
 def tome_merge(x, size, unm, src, dst, B, n, D, r):
     """x [B * n, D] (or [B, n, D]), size [B, n] or None (all ones), a plan of tome_match -> (x_out [B * (n - r), D], size_out [B, n - r])"""
     _f32(x)
@@ -849,6 +863,21 @@ def attn_fwd_bf16io(qkv, B, n, H, scale, want_cls=True, want_f32=True):
     lib.call("d2s_attn_fwd_bf16_bf16out", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(out), lib.ptr(out16), lib.ptr(lse),
              lib.ptr(cls_row), B, n, H, float(scale))
     return out, lse, cls_row, out16
+
+
+def attn_keyw_fwd_bf16io(qkv, key_w, B, n, H, scale, want_f32=True):
+    """Key-weighted attention forward (attn_keyw_fwd's definition) on the bf16 matrix cores and the bf16 data path: qkv fp32 or bf16 (the
+    qkv GEMM's c16); always writes the bf16 copy of its output for the projection GEMM.  Inference only.
+    -> (out or None, lse [B,H,n], out16)"""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
+    _f32(key_w)
+    assert tuple(key_w.shape) == (B, n)
+    out = torch.empty((B * n, H * 64), dtype=torch.float32, device=qkv.device) if want_f32 else None
+    out16 = bf16_buffer(B * n, H * 64, qkv.device)
+    lse = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_keyw_fwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(key_w), lib.ptr(out), lib.ptr(out16),
+             lib.ptr(lse), B, n, H, float(scale))
+    return out, lse, out16
 
 
 def attn_bwd(qkv, out, dout, lse, B, n, H, scale, dqkv16=None, want_f32=True):

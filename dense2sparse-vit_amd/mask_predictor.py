@@ -20,6 +20,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
         --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --student-checkpoint deit_small.pth
+    python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --tome-bf16 --student-checkpoint deit_small.pth
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --student-checkpoint deit_small.pth \
         --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
 """
@@ -65,6 +66,14 @@ def check_supported(args):
         bad.append(f"--tome-train with --drop-path {args.drop_path} (stochastic depth is not built for a merging block)")
     if tome_train and args.torch_optim:
         bad.append("--tome-train with --torch-optim (a merging student trains through the fused step only)")
+    if bool(getattr(args, "tome_bf16", False)):
+        if getattr(args, "method", "d2s") != "tome":
+            bad.append(f"--tome-bf16 with --method {getattr(args, 'method', 'd2s')} (it puts the Token Merging baseline on the bf16 data path: "
+                       "--method tome)")
+        if tome_train:
+            bad.append("--tome-bf16 with --tome-train (training through the merges is built in fp32 only)")
+        if not args.eval_only:
+            bad.append("--tome-bf16 without --eval-only (the bf16 merging trunk is built for inference)")
     if getattr(args, "method", "d2s") == "tome":
         if not args.eval_only and not tome_train:
             bad.append("--method tome without --eval-only (token merging is built for inference: training through a merge needs the merge's "
@@ -213,7 +222,8 @@ def build_tome(args):
     """--method tome: the dense DeiT trunk with token merging, weights from --student-checkpoint or the 'model' entry of a --resume file.  A
     dense-to-sparse student's checkpoint carries score predictors this model has no use for: they are ignored (strict=False)."""
     arch = args.arch if args.arch in _TOME else "deit_small"
-    model = getattr(vit_models, _TOME[arch])(args.tome_r, train_merge=bool(getattr(args, "tome_train", False)))
+    model = getattr(vit_models, _TOME[arch])(args.tome_r, train_merge=bool(getattr(args, "tome_train", False)),
+                                             bf16=bool(getattr(args, "tome_bf16", False)))
     path = args.student_checkpoint or args.resume
     if path is None:
         print("--method tome: no --student-checkpoint, the trunk starts from its random initialisation")
@@ -288,7 +298,8 @@ def eval_tome(args, rank, world, distributed):
         metrics["val_acc"] = float(t / world)
         dist.destroy_process_group()
     if rank == 0:
-        print(f"eval only: --method tome --tome-r {args.tome_r}: tokens per block {model.tokens_per_block}, " +
+        path_ran = "bf16 data path" if getattr(model, "bf16", False) else f"fp32 data path, gemm mode {args.gemm_mode}"
+        print(f"eval only: --method tome --tome-r {args.tome_r} ({path_ran}): tokens per block {model.tokens_per_block}, " +
               ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
     return metrics["val_acc"]
 

@@ -168,6 +168,9 @@ def parse_args(argv=None):
     p.add_argument('--tome-train', action='store_true', default=False,
                    help='with --method tome: train through the merges (merge backward, key-weighted attention backward); the objective is '
                         '--cls-weight * CE + --dist-weight * KL to the dense teacher (--dist-weight 0: no teacher)')
+    p.add_argument('--tome-bf16', action='store_true', default=False,
+                   help='with --method tome --eval-only: run the merging trunk on the bf16 data path (bf16 matrix cores for the GEMMs and the '
+                        'key-weighted attention, the match on the bf16 qkv); --gemm-mode stays at exact or split')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

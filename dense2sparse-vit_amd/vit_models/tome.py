@@ -6,6 +6,7 @@ import torch
 
 from d2s import functional as DF
 from d2s import functional_tome as TF
+from d2s import ops
 from .dynamic_vit import VisionTransformerTeacher, _GEOM, _load_local
 
 TOME_TRAINING_ERROR = ("token merging is built for inference only: training through a merge needs the merge's backward and key weights in "
@@ -18,9 +19,11 @@ class VisionTransformerToMe(VisionTransformerTeacher):
     (proportional attention) once something has merged.  forward (eval mode) returns the logits; afterwards tokens_per_block[i] is the
     number of tokens (CLS included) that leave block i, and tome_plans[i] the block's (unm_idx, src_idx, dst_idx) or None.
     train_merge: let the training-mode forward merge too - every block runs through ToMeBlockFn, gradients flow through the merge (a
-    size-weighted average with a constant plan) and the key-weighted attention; off (the default), a merging model refuses to train."""
+    size-weighted average with a constant plan) and the key-weighted attention; off (the default), a merging model refuses to train.
+    bf16: run the eval forward on the bf16 data path (TF.tome_block_forward_bf16) inside ops.gemm_mode(ops.GEMM_BF16), whatever the
+    ambient mode, which is restored afterwards; inference only, so it excludes train_merge."""
 
-    def __init__(self, *args, tome_r=0, prop_attn=True, train_merge=False, **kwargs):
+    def __init__(self, *args, tome_r=0, prop_attn=True, train_merge=False, bf16=False, **kwargs):
         super().__init__(*args, **kwargs)
         depth = len(self.blocks)
         rs = [int(tome_r)] * depth if isinstance(tome_r, int) else [int(v) for v in tome_r]
@@ -29,6 +32,9 @@ class VisionTransformerToMe(VisionTransformerTeacher):
         self.tome_r = rs
         self.prop_attn = bool(prop_attn)
         self.train_merge = bool(train_merge)
+        self.bf16 = bool(bf16)
+        if self.bf16 and self.train_merge:
+            raise ValueError("bf16 with train_merge: training through a merge is built in fp32 only (the bf16 merging trunk is inference only)")
         if self.train_merge and float(getattr(self, "drop_path_rate", 0.0)) > 0.0:
             raise ValueError("train_merge with drop_path_rate > 0: stochastic depth is not built for a merging block")
         self.grad_ready_hook = None          # set by a data-parallel TrainStep: called with i when block i's input gradient exists
@@ -48,6 +54,12 @@ class VisionTransformerToMe(VisionTransformerTeacher):
                 x = blk(x)
             self.tokens_per_block, self.tome_plans = [x.shape[1]] * len(self.blocks), [None] * len(self.blocks)
             return self._head(x)[0]
+        if self.bf16:
+            with ops.gemm_mode(ops.GEMM_BF16):      # the context manager restores the ambient mode on return and on an exception
+                return self._forward_eval(x, plans, TF.tome_block_forward_bf16)
+        return self._forward_eval(x, plans, TF.tome_block_forward)
+
+    def _forward_eval(self, x, plans, block_forward):
         with torch.no_grad():
             x = self._embed(x)
             B, n, D = x.shape
@@ -55,8 +67,8 @@ class VisionTransformerToMe(VisionTransformerTeacher):
             size, counts, used = None, [], []
             for i, blk in enumerate(self.blocks):
                 a = blk.attn
-                x, size, plan = TF.tome_block_forward(x, size, blk._params(), B, n, a.num_heads, blk.norm1.eps, a.scale, self.tome_r[i],
-                                                      self.prop_attn, None if plans is None else plans[i])
+                x, size, plan = block_forward(x, size, blk._params(), B, n, a.num_heads, blk.norm1.eps, a.scale, self.tome_r[i],
+                                              self.prop_attn, None if plans is None else plans[i])
                 n = x.shape[0] // B
                 counts.append(n)
                 used.append(plan)

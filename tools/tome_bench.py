@@ -8,8 +8,12 @@ the table reports the median images/s with the lowest and highest round.  GPU bo
 teacher - dist_weight 0 -, backward, fused AdamW) of a train_merge student, hard labels, same alternating rounds; read every row against
 the r = 0 row of the same run.
 
-  python tools/tome_bench.py [--rounds 5] [--iters 10] [--r 0 8 13 16] [--train]
+--bf16: the same table with bf16=True models (--tome-bf16: the merging trunk on the bf16 data path) and the teacher row timed under
+GEMM_BF16; --bf16 --also-fp32 keeps the fp32 rows in the same run, so that each bf16 row is read against the fp32 row of equal r.
+
+  python tools/tome_bench.py [--rounds 5] [--iters 10] [--r 0 8 13 16] [--train] [--bf16 [--also-fp32]]
   rocprofv3 --kernel-trace --stats -d DIR -o tome -- python tools/tome_bench.py --no-teacher --r 13 --rounds 1      (kernel shares)
+  rocprofv3 --kernel-trace --stats -d DIR -o tome -- python tools/tome_bench.py --bf16 --no-teacher --r 13 --rounds 1      (... on the bf16 data path)
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o tome -- python tools/tome_bench.py --train --r 13 --rounds 1     (... of a train step)
 """
 import argparse
@@ -30,7 +34,13 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--r", type=int, nargs="+", default=[0, 8, 13, 16])
 ap.add_argument("--no-teacher", action="store_true", help="leave the teacher forward out (a kernel trace of one merging configuration alone)")
 ap.add_argument("--train", action="store_true", help="time a TrainStep of a train_merge student (no teacher, dist_weight 0) instead of the eval forward")
+ap.add_argument("--bf16", action="store_true", help="bf16=True models (the bf16 data path); the teacher row runs under GEMM_BF16")
+ap.add_argument("--also-fp32", action="store_true", help="with --bf16: keep the fp32 rows in the same run")
 args = ap.parse_args()
+if args.bf16 and args.train:
+    raise SystemExit("--bf16 with --train: training through the merges is built in fp32 only")
+if args.also_fp32 and not args.bf16:
+    raise SystemExit("--also-fp32 goes with --bf16")
 if not torch.cuda.is_available():
     raise SystemExit("tools/tome_bench.py needs a GPU: nothing here is measured on the CPU")
 
@@ -76,11 +86,26 @@ if args.train:
               f"{' '.join(map(str, step.student.tokens_per_block))}", flush=True)
     sys.exit(0)
 
-configs = [] if args.no_teacher else [("teacher forward", teacher)]
-for r in args.r:
-    m = vit_models.tome_deit_small_patch16_224(r)
-    m.load_state_dict(weights)
-    configs.append((f"tome r = {r}", m.to(dev).eval()))
+class TeacherBf16:
+    """the teacher forward under GEMM_BF16 (a bf16=True merging model enters that mode itself)"""
+
+    def __call__(self, x):
+        with ops.gemm_mode(ops.GEMM_BF16):
+            return teacher(x)
+
+
+# (row name, model, called as); fp32 rows first when both data paths are timed
+paths = ([False] if not args.bf16 else [False, True] if args.also_fp32 else [True])
+configs = []
+for bf16 in paths:
+    tag = " bf16" if bf16 else " fp32" if args.bf16 else ""
+    if not args.no_teacher:
+        configs.append((f"teacher forward{tag}", teacher, TeacherBf16() if bf16 else teacher))
+    for r in args.r:
+        m = vit_models.tome_deit_small_patch16_224(r, bf16=bf16)
+        m.load_state_dict(weights)
+        m = m.to(dev).eval()
+        configs.append((f"tome r = {r}{tag}", m, m))
 
 
 def window(model, iters):
@@ -94,17 +119,18 @@ def window(model, iters):
 
 
 with torch.no_grad():
-    for _, model in configs:
-        window(model, 3)                              # warm-up at this configuration's own shapes
-    ms = {name: [] for name, _ in configs}
+    for _, _, run in configs:
+        window(run, 3)                                # warm-up at this configuration's own shapes
+    ms = {name: [] for name, _, _ in configs}
     for _ in range(args.rounds):
-        for name, model in configs:
-            ms[name].append(window(model, args.iters))
+        for name, _, run in configs:
+            ms[name].append(window(run, args.iters))
 
-print(f"DeiT-S 224, B = {B}, fp32 exact GEMMs, {args.rounds} rounds x {args.iters} forwards per configuration, rounds alternating")
-print(f"{'configuration':16s} {'ms/batch':>9s} {'images/s (median)':>18s} {'min':>8s} {'max':>8s}   tokens leaving each block")
-for name, model in configs:
+gemms = "fp32 exact GEMMs" if not args.bf16 else "bf16 data path and fp32 exact GEMMs" if args.also_fp32 else "bf16 data path"
+print(f"DeiT-S 224, B = {B}, {gemms}, {args.rounds} rounds x {args.iters} forwards per configuration, rounds alternating")
+print(f"{'configuration':21s} {'ms/batch':>9s} {'images/s (median)':>18s} {'min':>8s} {'max':>8s}   tokens leaving each block")
+for name, model, _ in configs:
     rate = sorted(B / t * 1e3 for t in ms[name])
     tokens = getattr(model, "tokens_per_block", None) or [197] * 12
-    print(f"{name:16s} {statistics.median(ms[name]):9.2f} {statistics.median(rate):18.0f} {rate[0]:8.0f} {rate[-1]:8.0f}   "
+    print(f"{name:21s} {statistics.median(ms[name]):9.2f} {statistics.median(rate):18.0f} {rate[0]:8.0f} {rate[-1]:8.0f}   "
           f"{' '.join(map(str, tokens))}", flush=True)
