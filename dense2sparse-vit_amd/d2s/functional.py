@@ -2,11 +2,13 @@
 sequences of C-ABI calls (d2s.ops); torch only owns the tensors and the graph.  No torch arithmetic runs here.
 
 The transformer block's seven launches (LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm, fc1 + GELU, fc2 + residual) are
-written once, in block_forward_sequence.  Its three callers: BlockFn.forward without a backward to serve (the frozen teacher, eval),
-BlockFn.forward in training, and ragged_block_forward; in front of it BlockFn keeps the composite path (ops.block_fwd / block_bwd: one
-C-ABI call for the same launches on the fp32 data path).  Which attention entry runs is decided in attn_forward / attn_backward, for
-BlockFn and AttnCoreFn alike; xarg, cls_or_empty and layernorm_backward are the small shared pieces (the latter also serves the
-predictor and Tokens-to-Token Functions of the neighbouring modules).
+written once, in block_forward_sequence, and their backward once, in block_backward_sequence.  The forward's callers: BlockFn.forward
+without a backward to serve (the frozen teacher, eval), BlockFn.forward in training, ragged_block_forward, and the token-merging block of
+functional_tome (forward only on either data path, and training), which hooks its match and merge in between the two halves; the
+backward's callers: BlockFn.backward and ToMeBlockFn.backward.  In front of both BlockFn keeps the composite path (ops.block_fwd /
+block_bwd: one C-ABI call for the same launches on the fp32 data path).  Which attention entry runs is decided in attn_forward /
+attn_backward, for BlockFn and AttnCoreFn alike; xarg, cls_or_empty and layernorm_backward are the small shared pieces (the latter also
+serves the predictor and Tokens-to-Token Functions of the neighbouring modules).
 
 Reference lines (relative to /root/reference):
   EmbedFn      vit_models/dynamic_vit.py:300-306, 820-823
@@ -238,35 +240,120 @@ def _norm_linear(x, cmap, nw, nb, w, b, eps, io, train, epi=None, aux_out=None):
     return (ln if train else None), y, mean, rstd
 
 
-def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0):
+def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0, mid=None):
     """THE launch sequence of a pre-norm transformer block on [rows, D] tokens: LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm,
-    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward.
+    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward, functional_tome.
     io: bf16 data path - every GEMM input exists in bf16 only, the residual stream stays fp32.
-    train: keep the LayerNorm statistics, the GELU pre-activation and every layer input for BlockFn.backward; otherwise (the frozen
+    train: keep the LayerNorm statistics, the GELU pre-activation and every layer input for block_backward_sequence; otherwise (the frozen
     teacher, eval) nothing is kept and each intermediate dies before the next allocation (the pre-activation alone is 155 MB per block at
     B = 128), on the bf16 data path not even the fp32 form of the attention output is written.
     attn(qkv, *attn_args, io, want_f32) is attn_forward or a function of its shape.  s_attn / s_mlp: stochastic-depth row scales of the
     two branches, one per rows_per_group rows.
-    -> (y, cls_row or None, what BlockFn.backward unpacks after x (None unless train), cinv)"""
+    mid(qkv, x1) -> x1', the hook between the halves (token merging): x1' may have fewer rows than x1, the MLP half runs on them and only
+    x1' is kept; qkv then lives until the hook has returned.
+    -> (y, cls_row or None, what block_backward_sequence unpacks (None unless train), cinv)"""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     rows, D = x.shape
-    cmap = ops.contiguous_map(rows, D)
-    ln1, qkv, mean1, rstd1 = _norm_linear(x, cmap, n1w, n1b, qkvw, qkvb, eps, io, train)
+    assert mid is None or (s_attn is None and s_mlp is None), "stochastic depth is not built for a block with a hook between its halves"
+    ln1, qkv, mean1, rstd1 = _norm_linear(x, ops.contiguous_map(rows, D), n1w, n1b, qkvw, qkvb, eps, io, train)
     ao, lse, cinv, cls_row, aoh = attn(qkv, *attn_args, io, train)      # training keeps the fp32 output for the backward's delta
     if not train:
-        del qkv, lse, cinv
+        del lse, cinv
+        if mid is None:
+            del qkv
     x1 = ops.linear_fwd(ao, projw, projb, epi=ops.EPI_BIAS_RESID, aux=x, a16=aoh, rowscale=s_attn, rows_per_group=rows_per_group)
     if not train:
         del ao, aoh
+    if mid is not None:
+        x1 = mid(qkv, x1)          # the x1 that went in dies here
+        rows = x1.shape[0]
+        if not train:
+            del qkv
     # GELU pre-activation for the backward: fp32, or bf16 on the bf16 data path (what autocast keeps: fc1's output is bf16 there)
     z = torch.empty((rows, fc1w.shape[0]), dtype=torch.bfloat16 if io else torch.float32, device=x.device) if train else None
-    ln2, h, mean2, rstd2 = _norm_linear(x1, cmap, n2w, n2b, fc1w, fc1b, eps, io, train, ops.EPI_BIAS_GELU, z)
+    ln2, h, mean2, rstd2 = _norm_linear(x1, ops.contiguous_map(rows, D), n2w, n2b, fc1w, fc1b, eps, io, train, ops.EPI_BIAS_GELU, z)
     hx, h16 = xarg(h)
     y = ops.linear_fwd(hx, fc2w, fc2b, epi=ops.EPI_BIAS_RESID, aux=x1, a16=h16, rowscale=s_mlp, rows_per_group=rows_per_group)
     if not train:
         return y, cls_row, None, None
     return y, cls_row, (n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
                         n1b, qkvb, projb, n2b, fc1b, fc2b, aoh), cinv      # aoh: bf16 form of ao (bf16 attention only), proj's weight gradient
+
+
+def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, attn_bwd, mid_bwd=None):
+    """The backward of block_forward_sequence (training; per-op, either data path).  gy: the gradient of y; x: the block's input as a
+    [..., D] tensor; saved: what the forward sequence returned for this; wants: which of (x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b,
+    fc1w, fc1b, fc2w, fc2b) take a gradient; s_attn / s_mlp: the forward's stochastic-depth row scales.
+    attn_bwd(qkv, ao, dao, lse, io, dqkv16, want_f32) -> (dqkv or None, dpolicy or None) is attn_backward or a function of its shape.
+    mid_bwd(g1) -> g1 on the rows of x, the backward of the forward's hook: the MLP half runs on the rows of gy, the attention half on the
+    rows of x, and the first LayerNorm backward adds the gradient that left the hook.
+    -> (the 13 gradients in wants' order, gx shaped like x, None where not wanted; dpolicy)"""
+    (n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
+     n1b, qkvb, projb, n2b, fc1b, fc2b, aoh) = saved
+    D = x.shape[-1]
+    M = x.numel() // D
+    dev = gy.device
+    gy = gy.contiguous().view(-1, D)
+    M2 = gy.shape[0]          # rows of the MLP half: M, or fewer behind a hook
+    grads = [None] * 13
+
+    # ---- MLP branch ----
+    hx, h16 = xarg(h)
+    # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
+    io = bf16_data_path(gy, D, z.shape[1])
+    # behind a hook the bf16 shadow of g1 would have to be made again for the rows of x, and the row scales' groups differ between the halves
+    assert mid_bwd is None or (not io and s_attn is None and s_mlp is None), "a hook between the halves: fp32 data path, no stochastic depth"
+    gyh = ops.shadow_take(gy) if io else None
+    if gyh is not None:
+        gyh = gyh.view(M2, D)
+    # stochastic depth: the gradient that enters a branch is s[b] * g (one pass, ops.scale_rows); the residual path - the LayerNorm
+    # backward's add_src - keeps the unscaled one.  The bf16 shadow of the unscaled gradient does not describe the scaled copy.
+    g_res = gy
+    if s_mlp is not None:
+        gy, gyh = ops.scale_rows(g_res, s_mlp, rows_per_group), None
+    # with both operands at hand in bf16 the weight-gradient kernel reads them where they lie (token-major, no transposing pass); the
+    # bias gradient is then the sum of the bf16 gradient values, as under torch.autocast
+    grads[11], grads[12] = ops.linear_param_grads(gy, hx, fc2w, fc2b, wants[11], wants[12], x16=h16, dy16=gyh if h16 is not None else None)
+    dzh = ops.bf16_buffer(M2, z.shape[1], dev) if io else None
+    l2x, l216 = xarg(ln2)
+    # dz = (gy fc2w) * gelu'(z) feeds two bf16 GEMMs and nothing else: on the bf16 data path only its bf16 form is written (fc1's bias
+    # gradient is then the fp32 sum of those bf16 values, as under torch.autocast)
+    dz_bf16_only = dzh is not None and l216 is not None and wants[9]
+    dz = ops.linear_dgrad(gy, fc2w, epi=ops.EPI_MUL_GELU_GRAD, aux=z, a16=gyh, c16=dzh, want_f32=not dz_bf16_only)
+    del gyh
+    grads[9], grads[10] = ops.linear_param_grads(dz, l2x, fc1w, fc1b, wants[9], wants[10], x16=l216, dy16=dzh if dz_bf16_only else None)
+    dln2 = ops.linear_dgrad(dz, fc1w, a16=dzh)
+    del dzh
+    g1h = ops.bf16_buffer(M2, D, dev) if (io and s_attn is None) else None
+    g1, grads[7], grads[8] = layernorm_backward(x1, ops.contiguous_map(M2, D), dln2, n2w, n2b, mean2, rstd2,
+                                                torch.empty((M2, D), dtype=torch.float32, device=dev), M2, D, wants[7], wants[8],
+                                                add_src=g_res, dx16=g1h)
+    if mid_bwd is not None:
+        g1 = mid_bwd(g1)
+    # ---- attention branch ----
+    ga = g1
+    if s_attn is not None:
+        ga, g1h = ops.scale_rows(g1, s_attn, rows_per_group), None
+    grads[5], grads[6] = ops.linear_param_grads(ga, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
+    dao = ops.linear_dgrad(ga, projw, a16=g1h)
+    del g1h
+    l1x, l116 = xarg(ln1)
+    dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev) if io else None
+    dqkv_bf16_only = io and l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
+    dqkv, dpolicy = attn_bwd(qkv, ao, dao, lse, io, dqkvh, not dqkv_bf16_only)
+    grads[3], grads[4] = ops.linear_param_grads(dqkv, l1x, qkvw, qkvb, wants[3], wants[4], x16=l116, dy16=dqkvh if dqkv_bf16_only else None)
+    if wants[0] or wants[1] or wants[2]:
+        dln1 = ops.linear_dgrad(dqkv, qkvw, a16=dqkvh)
+        del dqkvh
+        gxh = ops.bf16_buffer(M, D, dev) if (io and wants[0]) else None
+        gx, grads[1], grads[2] = layernorm_backward(x, ops.contiguous_map(M, D), dln1, n1w, n1b, mean1, rstd1,
+                                                    torch.empty((M, D), dtype=torch.float32, device=dev), M, D, wants[1], wants[2],
+                                                    add_src=g1, dx16=gxh)
+        if wants[0]:
+            grads[0] = gx.view(x.shape)
+        if gxh is not None:
+            ops.shadow_put(grads[0], gxh)
+    return grads, dpolicy
 
 
 @mode_recorded
@@ -330,71 +417,15 @@ class BlockFn(torch.autograd.Function):
     def backward(ctx, gy, _gcls):
         if ctx.composite:
             return BlockFn._backward_composite(ctx, gy)
-        (x, n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
-         n1b, qkvb, projb, n2b, fc1b, fc2b, aoh) = ctx.saved_tensors
+        x, *saved = ctx.saved_tensors
         B, n, D, heads, scale = ctx.dims
-        M = B * n
-        dev = gy.device
-        gy = gy.contiguous().view(M, D)
-        cmap = ops.contiguous_map(M, D)
-        # parameter order: n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> input slots 1..12
-        wants = [_need(ctx, i) for i in range(13)]
-        grads = [None] * 13
-
-        # ---- MLP branch ----
-        hx, h16 = xarg(h)
-        # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
-        io = bf16_data_path(gy, D, z.shape[1])
         policy, cinv = ctx.policy
-        gyh = ops.shadow_take(gy) if io else None
-        if gyh is not None:
-            gyh = gyh.view(M, D)
-        # stochastic depth: the gradient that enters a branch is s[b] * g (one pass, ops.scale_rows); the residual path - the LayerNorm
-        # backward's add_src - keeps the unscaled one.  The bf16 shadow of the unscaled gradient does not describe the scaled copy.
-        s_attn, s_mlp = ctx.drop_path
-        g_res = gy
-        if s_mlp is not None:
-            gy, gyh = ops.scale_rows(g_res, s_mlp, n), None
-        # with both operands at hand in bf16 the weight-gradient kernel reads them where they lie (token-major, no transposing pass); the
-        # bias gradient is then the sum of the bf16 gradient values, as under torch.autocast
-        grads[11], grads[12] = ops.linear_param_grads(gy, hx, fc2w, fc2b, wants[11], wants[12], x16=h16, dy16=gyh if h16 is not None else None)
-        dzh = ops.bf16_buffer(M, z.shape[1], dev) if io else None
-        l2x, l216 = xarg(ln2)
-        # dz = (gy fc2w) * gelu'(z) feeds two bf16 GEMMs and nothing else: on the bf16 data path only its bf16 form is written (fc1's bias
-        # gradient is then the fp32 sum of those bf16 values, as under torch.autocast)
-        dz_bf16_only = dzh is not None and l216 is not None and wants[9]
-        dz = ops.linear_dgrad(gy, fc2w, epi=ops.EPI_MUL_GELU_GRAD, aux=z, a16=gyh, c16=dzh, want_f32=not dz_bf16_only)
-        del gyh
-        grads[9], grads[10] = ops.linear_param_grads(dz, l2x, fc1w, fc1b, wants[9], wants[10], x16=l216, dy16=dzh if dz_bf16_only else None)
-        dln2 = ops.linear_dgrad(dz, fc1w, a16=dzh)
-        del dzh
-        g1h = ops.bf16_buffer(M, D, dev) if (io and s_attn is None) else None
-        g1, grads[7], grads[8] = layernorm_backward(x1, cmap, dln2, n2w, n2b, mean2, rstd2, torch.empty((M, D), dtype=torch.float32, device=dev),
-                                                    M, D, wants[7], wants[8], add_src=g_res, dx16=g1h)
-        # ---- attention branch ----
-        ga = g1
-        if s_attn is not None:
-            ga, g1h = ops.scale_rows(g1, s_attn, n), None
-        grads[5], grads[6] = ops.linear_param_grads(ga, ao, projw, projb, wants[5], wants[6], x16=aoh, dy16=g1h if aoh is not None else None)
-        dao = ops.linear_dgrad(ga, projw, a16=g1h)
-        del g1h
-        l1x, l116 = xarg(ln1)
-        dqkvh = torch.empty(qkv.shape, dtype=torch.bfloat16, device=dev) if io else None
-        dqkv_bf16_only = io and l116 is not None and wants[3]      # both consumers (weight gradient, input gradient) read the bf16 form
-        dqkv, dpolicy = attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh, not dqkv_bf16_only,
-                                      policy is not None and ctx.needs_input_grad[17])
-        grads[3], grads[4] = ops.linear_param_grads(dqkv, l1x, qkvw, qkvb, wants[3], wants[4], x16=l116, dy16=dqkvh if dqkv_bf16_only else None)
-        gx = None
-        if wants[0] or wants[1] or wants[2]:
-            dln1 = ops.linear_dgrad(dqkv, qkvw, a16=dqkvh)
-            del dqkvh
-            gxh = ops.bf16_buffer(M, D, dev) if (io and wants[0]) else None
-            gx, grads[1], grads[2] = layernorm_backward(x, cmap, dln1, n1w, n1b, mean1, rstd1, torch.empty((M, D), dtype=torch.float32, device=dev),
-                                                        M, D, wants[1], wants[2], add_src=g1, dx16=gxh)
-            gx = gx.view(B, n, D) if wants[0] else None
-            if gxh is not None:
-                ops.shadow_put(gx, gxh)
-        grads[0] = gx
+        want_dpolicy = policy is not None and ctx.needs_input_grad[17]
+        # parameter order: n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> input slots 1..12
+        grads, dpolicy = block_backward_sequence(
+            gy, x, saved, [_need(ctx, i) for i in range(13)], *ctx.drop_path, n,
+            lambda qkv, ao, dao, lse, io, dqkvh, want_f32: attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh,
+                                                                         want_f32, want_dpolicy))
         return tuple(grads) + (None, None, None, None) + ((dpolicy,) + (None,) * (ctx.nextra - 1) if ctx.nextra else ())
 
 

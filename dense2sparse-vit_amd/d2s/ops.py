@@ -626,33 +626,29 @@ def tome_clip_r(r, n):
     return max(0, min(int(r), (int(n) - 1) // 2))
 
 
-def tome_match(qkv, B, n, H, r):
-    """Bipartite soft matching of token merging (DESIGN.md section 22) on the keys of a [B * n, 3 * H * 64] qkv, read in place.  r is the
-    effective count (tome_clip_r).  -> (node_max [B,T_a], node_idx [B,T_a], unm_idx [B,T_a-r], src_idx [B,r], dst_idx [B,r]), int32"""
-    _f32(qkv)
+def _tome_match(entry, qkv, B, n, H, r):
     B, n, H, r = int(B), int(n), int(H), int(r)
     Ta = (n + 1) // 2
     i32 = dict(dtype=torch.int32, device=qkv.device)
     node_max = torch.empty((B, Ta), dtype=torch.float32, device=qkv.device)
     node_idx, unm = torch.empty((B, Ta), **i32), torch.empty((B, max(Ta - r, 0)), **i32)
     src, dst = torch.empty((B, max(r, 0)), **i32), torch.empty((B, max(r, 0)), **i32)
-    lib.call("d2s_tome_match", lib.ptr(qkv), B, n, H, r, lib.ptr(node_max), lib.ptr(node_idx), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
+    lib.call(entry, lib.ptr(qkv), B, n, H, r, lib.ptr(node_max), lib.ptr(node_idx), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
              lib.ptr(dst) if r > 0 else None)
     return node_max, node_idx, unm, src, dst
+
+
+def tome_match(qkv, B, n, H, r):
+    """Bipartite soft matching of token merging (DESIGN.md section 22) on the keys of a [B * n, 3 * H * 64] qkv, read in place.  r is the
+    effective count (tome_clip_r).  -> (node_max [B,T_a], node_idx [B,T_a], unm_idx [B,T_a-r], src_idx [B,r], dst_idx [B,r]), int32"""
+    _f32(qkv)
+    return _tome_match("d2s_tome_match", qkv, B, n, H, r)
 
 
 def tome_match_bf16(qkv16, B, n, H, r):
     """tome_match on a bf16 qkv (the qkv GEMM's c16 on the bf16 data path), read in place: bit for bit tome_match(qkv16.float())."""
     assert qkv16.dtype == torch.bfloat16 and qkv16.is_contiguous(), (qkv16.dtype, qkv16.is_contiguous())
-    B, n, H, r = int(B), int(n), int(H), int(r)
-    Ta = (n + 1) // 2
-    i32 = dict(dtype=torch.int32, device=qkv16.device)
-    node_max = torch.empty((B, Ta), dtype=torch.float32, device=qkv16.device)
-    node_idx, unm = torch.empty((B, Ta), **i32), torch.empty((B, max(Ta - r, 0)), **i32)
-    src, dst = torch.empty((B, max(r, 0)), **i32), torch.empty((B, max(r, 0)), **i32)
-    lib.call("d2s_tome_match_bf16", lib.ptr(qkv16), B, n, H, r, lib.ptr(node_max), lib.ptr(node_idx), lib.ptr(unm),
-             lib.ptr(src) if r > 0 else None, lib.ptr(dst) if r > 0 else None)
-    return node_max, node_idx, unm, src, dst
+    return _tome_match("d2s_tome_match_bf16", qkv16, B, n, H, r)
 
 
 def tome_merge(x, size, unm, src, dst, B, n, D, r):

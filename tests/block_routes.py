@@ -1,10 +1,12 @@
 """What the transformer block's host code does, per configuration, through the public entry points only (DF.run(DF.BlockFn, ...),
-DF.ragged_block_forward, DF.AttnCoreFn.apply): the C-ABI entries it issues (forward, backward), the bytes it saves for the backward and
-its peak of allocated memory.  Shared by tools/gen_block_routes.py, which records tests/golden/block_routes.json, and
+DF.ragged_block_forward, DF.AttnCoreFn.apply, and the token-merging block's TF.tome_block_forward, TF.tome_block_forward_bf16 and
+TF.tome_block_train): the C-ABI entries it issues (forward, backward), the bytes it saves for the backward and its peak of allocated
+memory.  Shared by tools/gen_block_routes.py, which records tests/golden/block_routes.json, and
 tests/test_block_routes_gpu.py, which compares a fresh recording with it.
 
 Geometry: the block of tests/test_ragged_bf16_gpu.py (D 128, 2 heads, hidden 512), B = 2, n = 33 (one key tile plus a remainder);
-the ragged case packs the lengths (5, 33)."""
+the ragged case packs the lengths (5, 33); the token-merging block merges r = 5 of the 33 tokens away (28 rows per image in its MLP
+half) or none, with every token one patch (size None) or the fixed patch counts of _size()."""
 import torch
 
 from tests.test_ragged_bf16_gpu import BLOCK_D, BLOCK_H, SCALE, _block_params, _cu, _t
@@ -13,6 +15,7 @@ DEV = "cuda:0"
 B, N = 2, 33
 RAGGED_LENGTHS = (5, 33)
 EPS = 1e-6
+TOME_R = 5
 MODES = ("exact", "split", "bf16", "bf16_noio")          # bf16_noio: bf16 arithmetic with the bf16 data path switched off
 
 
@@ -39,6 +42,34 @@ def configurations():
     for mode in ("exact", "bf16"):
         for policy in ("none", "const", "grad"):
             out.append((f"attn/{mode}/policy_{policy}", dict(kind="attn", mode=mode, policy=policy)))
+    return out + _tome_configurations()          # appended: the caching allocator rounds for the ones above as it did at their recording
+
+
+def _tome_configurations():
+    out = []
+
+    def add(mode, train, r, size, **kw):
+        cfg = dict(kind="tome", mode=mode, train=train, r=r, size=size, replay=False, prop_attn=True, grads="all",
+                   entry="train" if train else "forward")
+        cfg.update(kw)
+        tags = [t for t, on in (("replay", cfg["replay"]), ("noprop", not cfg["prop_attn"]), (f"only_{cfg['grads']}", cfg["grads"] != "all"),
+                                ("fn_nograd", cfg["entry"] == "train" and not train)) if on]
+        out.append(("/".join([f"tome/{mode}/{'train' if train else 'nograd'}/r{r}/size_{'given' if size else 'none'}"] + tags), cfg))
+    for mode in ("exact", "split"):
+        for train in (False, True):
+            for r in (0, TOME_R):
+                for size in (False, True):
+                    add(mode, train, r, size)
+    for train in (False, True):
+        add("exact", train, TOME_R, True, replay=True)
+        add("exact", train, TOME_R, True, prop_attn=False)
+    for grads in ("x", "params"):          # the backward prunes its launches by what wants a gradient
+        add("exact", True, TOME_R, True, grads=grads)
+    add("exact", False, TOME_R, True, entry="train")          # ToMeBlockFn with nothing to keep for a backward
+    for r in (0, TOME_R):          # the bf16 data path, forward only
+        for size in (False, True):
+            add("bf16", False, r, size)
+    add("bf16", False, TOME_R, True, replay=True)
     return out
 
 
@@ -68,11 +99,48 @@ def _policy(kind):
     return p.requires_grad_(kind == "grad")
 
 
+def _size():
+    """patches per token: 1s with some 2s and 3s, CLS at 1"""
+    s = torch.ones(B, N, device=DEV)
+    s[0, 2::5] = 2.0
+    s[1, 3::4] = 3.0
+    s[1, 4::7] = 2.0
+    return s
+
+
+def _make_tome_call(cfg):
+    from d2s import functional_tome as TF, ops
+    r = cfg["r"]
+    size = _size() if cfg["size"] else None
+    # a replayed plan is a recorded one of another input: the match of the synthetic qkv of the attn configurations
+    plan = tuple(ops.tome_match(_synth("qkv", (B * N, 3 * BLOCK_D)), B, N, BLOCK_H, r)[2:]) if cfg["replay"] else None
+    x = _synth("x", (B, N, BLOCK_D)).requires_grad_(cfg["train"] and cfg["grads"] in ("all", "x"))
+    p = [t.requires_grad_(cfg["train"] and cfg["grads"] in ("all", "params")) for t in _params()]
+    leaves = dict(dx=x, **{f"dp{i}": t for i, t in enumerate(p)}) if cfg["train"] else {}
+
+    def outputs(y, size_out, used):
+        unm, src, dst = used if used is not None else (None, None, None)
+        return dict(y=y, size_out=size_out, unm=unm, src=src, dst=dst)
+
+    def call():
+        if cfg["entry"] == "train":
+            with torch.enable_grad() if cfg["train"] else torch.no_grad():
+                y, size_out, used = TF.tome_block_train(x, size, p, BLOCK_H, EPS, SCALE, r, cfg["prop_attn"], plan)
+            return outputs(y, size_out, used), (y if cfg["train"] else None)
+        forward = TF.tome_block_forward_bf16 if cfg["mode"] == "bf16" else TF.tome_block_forward
+        with torch.no_grad():
+            y, size_out, used = forward(x.view(B * N, BLOCK_D), size, p, B, N, BLOCK_H, EPS, SCALE, r, cfg["prop_attn"], plan)
+        return outputs(y, size_out, used), None
+    return call, leaves
+
+
 def _make_call(cfg):
     """-> (call, leaves): call() runs the forward and returns (outputs, the output to run the backward from or None); leaves: the named
     tensors whose .grad the backward fills"""
     from d2s import functional as DF
     leaves = {}
+    if cfg["kind"] == "tome":
+        return _make_tome_call(cfg)
     if cfg["kind"] == "ragged":
         p = _params()
         total = sum(RAGGED_LENGTHS)
@@ -154,7 +222,10 @@ def record(cfg):
         ops._BF16_IO = cfg["mode"] != "bf16_noio"
         ops._BLOCK_COMPOSITE = cfg.get("composite", True)
         call, leaves = _make_call(cfg)
-        gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
+        if cfg["kind"] == "tome":          # the merged block's output: n - r rows per image
+            gy = _synth("gy", (B * (N - cfg["r"]), BLOCK_D)).view(B, N - cfg["r"], BLOCK_D)
+        else:
+            gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
         with ops.gemm_mode(mode):
             _run(call, leaves, gy, names)
             for t in leaves.values():

@@ -1,7 +1,8 @@
 """The host side of the transformer block against tests/golden/block_routes.json (tools/gen_block_routes.py, recorded before the five
-copies of the launch sequence in d2s/functional.py were folded into one): for every configuration of tests/block_routes.py the C-ABI
-entries the forward and the backward issue are the recorded ones in the recorded order, the bytes saved for the backward are the
-recorded ones (nothing under no_grad), and the peak of allocated memory is not above the recorded one."""
+copies of the launch sequence in d2s/functional.py were folded into one, and the token-merging configurations before the copies in
+d2s/functional_tome.py followed them): for every configuration of tests/block_routes.py the C-ABI entries the forward and the backward
+issue are the recorded ones in the recorded order, the bytes saved for the backward are the recorded ones (nothing under no_grad), and
+the peak of allocated memory is not above the recorded one."""
 import json
 import os
 
