@@ -704,7 +704,8 @@ def test_batchnorm_fwd_bwd(ops, R, C, training):
 @pytest.mark.parametrize("B,n,H", [(2, 197, 6), (3, 99, 3), (1, 577, 2), (2, 32, 1), (1, 33, 1), (1, 1, 1), (2, 41, 2), (1, 130, 1)])
 def test_attention_fwd_bf16_mode(ops, B, n, H):
     """d2s_attn_fwd_bf16 (bf16 arithmetic mode): output, log-sum-exp and CLS row against the fp32 reference within bf16 operand rounding
-    (2^-9 relative on q, k, v), and the fp32 backward run from ITS outputs stays close to autograd's gradients."""
+    (2^-9 relative on q, k, v), and the backward of the same mode, d2s_attn_bwd_bf16, run from ITS outputs stays close to autograd's
+    gradients.  The float64 comparison with derived bounds is tests/test_attention_bf16_dense_gpu.py."""
     qkv = _rand("aqb", (B * n, 3 * H * 64), 1.0, seed=n)
     qr = qkv.clone().requires_grad_(True)
     o_ref, cls_ref, lse_ref = _attn_ref(qr, B, n, H)
