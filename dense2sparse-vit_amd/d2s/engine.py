@@ -295,6 +295,7 @@ def checkpoint_config(config):
     theirs.setdefault("tome_r", [])                # ... and before a Token Merging student could be trained: no such student
     theirs.setdefault("prop_attn", False)
     theirs.setdefault("train_merge", False)
+    theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     return theirs
 
 
@@ -690,6 +691,7 @@ class TrainStep:
             "tome_r": [int(v) for v in getattr(s, "tome_r", [])],
             "prop_attn": bool(getattr(s, "prop_attn", False)),
             "train_merge": bool(getattr(s, "train_merge", False)),
+            "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):

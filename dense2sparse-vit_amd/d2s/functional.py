@@ -561,6 +561,39 @@ class GatherFuseFn(torch.autograd.Function):
         return dx if _need(ctx, 0) else None, dp if _need(ctx, 1) else None, None, None, None
 
 
+class GatherSqueezeFn(torch.autograd.Function):
+    """GatherFn with every dropped token squeezed into the kept token it resembles most (squeeze_dropped):
+    x [B,n,D] = [CLS | T scored], kept / dropped the selector's ids -> (y [B,k+1,D], dst, sim).  The plan (dst, sim) is matched here unless
+    `plan` replays one; it is a constant of the backward (no gradient through the cosine) and comes back detached, for inspection.  Saves
+    kept, dropped, dst, sim, Z - not x: the merge is linear in x for a fixed plan.  No host synchronisation, no read-back.  Like GatherFn it
+    works on the fp32 residual stream in every GEMM arithmetic mode and sends no gradient to the selector.  k == 0 is GatherFn: there is
+    nothing to squeeze into."""
+
+    @staticmethod
+    def forward(ctx, x, kept, dropped, plan=None):
+        x = x.contiguous()
+        ctx.n, ctx.k = x.shape[1], kept.shape[1]
+        if ctx.k == 0:
+            ctx.save_for_backward(kept)
+            dst = torch.empty((x.shape[0], 0), dtype=torch.int32, device=x.device)
+            y = ops.gather_pack(x, kept)
+            sim = torch.empty((x.shape[0], 0), dtype=torch.float32, device=x.device)
+        else:
+            dst, sim = ops.squeeze_match(x, kept, dropped) if plan is None else plan
+            y, Z = ops.gather_squeeze_fwd(x, kept, dropped, dst, sim)
+            ctx.save_for_backward(kept, dropped, dst, sim, Z)
+        ctx.mark_non_differentiable(dst, sim)
+        return y, dst, sim
+
+    @staticmethod
+    def backward(ctx, g, _gdst, _gsim):
+        if ctx.k == 0:
+            (kept,) = ctx.saved_tensors
+            return ops.scatter_unpack(g.contiguous(), kept, ctx.n), None, None, None
+        kept, dropped, dst, sim, Z = ctx.saved_tensors
+        return ops.gather_squeeze_bwd(g.contiguous(), kept, dropped, dst, sim, Z, ctx.n), None, None, None
+
+
 @mode_recorded
 class HeadFn(torch.autograd.Function):
     """Final LayerNorm + classifier head on the CLS row.  Returns (logits [B,C], features = normed tokens[:, 1:n - tail]); tail: the

@@ -742,6 +742,61 @@ def gather_fuse_bwd(g, x, p, S, y, kept, dropped, t):
     return dx, dp
 
 
+def _squeeze_shapes(x, kept, dropped):
+    B, n, D = x.shape
+    k = kept.shape[1]
+    assert kept.dtype == torch.int64 and kept.is_contiguous() and dropped.dtype == torch.int64 and dropped.is_contiguous()
+    assert kept.shape == (B, k) and dropped.shape == (B, n - 1 - k), \
+        f"x {tuple(x.shape)}: kept must be [B, k], dropped [B, {n - 1} - k]"
+    return B, n, D, k, n - 1 - k
+
+
+def _squeeze_plan(dst, sim, B, m):
+    assert dst.dtype == torch.int32 and dst.is_contiguous() and tuple(dst.shape) == (B, m), "dst must be int32 [B, m]"
+    _f32(sim)
+    assert tuple(sim.shape) == (B, m), "sim must be [B, m]"
+
+
+def squeeze_match(x, kept, dropped):
+    """x [B,n,D] = [CLS | T scored], kept [B,k], dropped [B,T-k] -> (dst [B,T-k] int32, sim [B,T-k]): for every dropped token the position
+    in `kept` of the kept token with the highest cosine (the lowest position on a tie) and that cosine"""
+    _f32(x)
+    B, n, D, k, m = _squeeze_shapes(x, kept, dropped)
+    dst = torch.empty((B, m), dtype=torch.int32, device=x.device)
+    sim = torch.empty((B, m), dtype=torch.float32, device=x.device)
+    lib.call("d2s_squeeze_match", lib.ptr(x), lib.ptr(kept), lib.ptr(dropped) if m else None, B, n, k, D, lib.ptr(dst) if m else None,
+             lib.ptr(sim) if m else None)
+    return dst, sim
+
+
+def gather_squeeze_fwd(x, kept, dropped, dst, sim):
+    """x, the id lists and a plan of squeeze_match -> (y [B,k+1,D], Z [B,k]): the kept-token gather with every dropped token folded into
+    its destination at weight exp(sim) against the kept token's own exp(1); Z the weight sums"""
+    _f32(x)
+    B, n, D, k, m = _squeeze_shapes(x, kept, dropped)
+    _squeeze_plan(dst, sim, B, m)
+    y = torch.empty((B, k + 1, D), dtype=torch.float32, device=x.device)
+    Z = torch.empty((B, k), dtype=torch.float32, device=x.device)
+    lib.call("d2s_gather_squeeze_fwd", lib.ptr(x), lib.ptr(kept), lib.ptr(dropped) if m else None, lib.ptr(dst) if m else None,
+             lib.ptr(sim) if m else None, B, n, k, D, lib.ptr(y), lib.ptr(Z))
+    return y, Z
+
+
+def gather_squeeze_bwd(g, kept, dropped, dst, sim, Z, n):
+    """g [B,k+1,D], the id lists, the plan and gather_squeeze_fwd's Z -> dx [B,n,D], every element written by the one launch"""
+    _f32(g)
+    _f32(Z)
+    B, k1, D = g.shape
+    k, m = k1 - 1, int(n) - k1
+    assert kept.dtype == torch.int64 and kept.is_contiguous() and dropped.dtype == torch.int64 and dropped.is_contiguous()
+    assert tuple(kept.shape) == (B, k) and tuple(dropped.shape) == (B, m) and tuple(Z.shape) == (B, k)
+    _squeeze_plan(dst, sim, B, m)
+    dx = torch.empty((B, int(n), D), dtype=torch.float32, device=g.device)
+    lib.call("d2s_gather_squeeze_bwd", lib.ptr(g), lib.ptr(kept), lib.ptr(dropped) if m else None, lib.ptr(dst) if m else None,
+             lib.ptr(sim) if m else None, lib.ptr(Z), B, int(n), k, D, lib.ptr(dx))
+    return dx
+
+
 def half_mean_concat(x, B, T, C, relu_mask_src=None):
     out = torch.empty((B * T, C), dtype=torch.float32, device=x.device)
     lib.call("d2s_half_mean_concat", lib.ptr(x), lib.ptr(relu_mask_src), lib.ptr(out), B, T, C)

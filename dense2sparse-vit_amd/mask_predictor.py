@@ -17,6 +17,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --batch-size 64 --accum-steps 8 --clip-grad 1.0     (512 images per optimiser step)
     python dense2sparse-vit_amd/mask_predictor.py --method dynamicvit --arch deit_small --pruning-locs 3 6 9 --keep-ratios 0.7 0.49 0.343
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --attn-selection [--mean-heads] [--fuse-dropped]     (select by the CLS attention)
+    python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --squeeze-dropped     (dropped tokens go into their nearest kept token)
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
         --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --student-checkpoint deit_small.pth
@@ -118,6 +119,19 @@ def check_supported(args):
             bad.append("--fuse-dropped with --patch-score-threshold (no token is removed there: nothing to fuse)")
         if getattr(args, "diff_topk", False):
             bad.append("--fuse-dropped with --diff-topk (the soft gather has no dropped set)")
+    if getattr(args, "squeeze_dropped", False):
+        if getattr(args, "method", "d2s") in ("dynamicvit", "tome"):
+            bad.append(f"--squeeze-dropped with --method {args.method} (dropped tokens are squeezed into kept ones in the dense-to-sparse "
+                       "student only)")
+        if not args.topk_selection:
+            bad.append("--squeeze-dropped without --topk-selection (the kept and dropped sets are those of the hard top-k)")
+        if getattr(args, "fuse_dropped", False):
+            bad.append("--squeeze-dropped with --fuse-dropped (a dropped token goes into the package token or into its nearest kept token, "
+                       "not both)")
+        if getattr(args, "diff_topk", False):
+            bad.append("--squeeze-dropped with --diff-topk (the soft gather has no dropped set)")
+        if args.patch_score_threshold is not None:
+            bad.append("--squeeze-dropped with --patch-score-threshold (no token is removed there: nothing to squeeze)")
     if getattr(args, "attn_selection", False):
         if getattr(args, "method", "d2s") == "dynamicvit":
             bad.append("--method dynamicvit with --attn-selection (the baseline keeps tokens by its own Gumbel decision and predictor)")
@@ -212,6 +226,7 @@ def build_models(args):
                                                    diff_topk=getattr(args, "diff_topk", False),
                                                    topk_num_samples=getattr(args, "topk_samples", 500),
                                                    fuse_dropped=getattr(args, "fuse_dropped", False),
+                                                   squeeze_dropped=getattr(args, "squeeze_dropped", False),
                                                    attn_selection=getattr(args, "attn_selection", False),
                                                    checkpoint_path=args.student_checkpoint)
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)

@@ -180,6 +180,10 @@ def parse_args(argv=None):
     p.add_argument('--fuse-dropped', action='store_true', default=False,
                    help='with --topk-selection: every pruning stage fuses the tokens it drops, weighted by their keep probabilities, into one '
                         'package token that later stages carry along (training and evaluation alike; no new parameters)')
+    p.add_argument('--squeeze-dropped', action='store_true', default=False,
+                   help='with --topk-selection: every pruning stage folds each token it drops into the kept token it resembles most '
+                        '(cosine), weighted by exp(cosine); the stage still keeps k tokens (training and evaluation alike; no new '
+                        'parameters)')
     p.add_argument('--ragged-cascade', action='store_true', default=False,
                    help='with --patch-score-threshold and several --pruning-locs: at inference every threshold stage after the first scores '
                         'and selects, per image, among the tokens that survived, and packs the batch again (this build\'s definition: the '

@@ -74,6 +74,14 @@ FUSE_DROPPED_TOPK_SELECTION_ERROR = ("fuse_dropped needs topk_selection=True: th
                                      "probabilities")
 FUSE_DROPPED_DIFF_TOPK_ERROR = ("fuse_dropped cannot be combined with diff_topk: the perturbed top-k soft gather mixes every token into every "
                                 "kept row and has no dropped set")
+SQUEEZE_DROPPED_FUSE_ERROR = ("squeeze_dropped cannot be combined with fuse_dropped: a dropped token is either averaged into the stage's package "
+                              "token or squeezed into its nearest kept token, not both")
+SQUEEZE_DROPPED_DIFF_TOPK_ERROR = ("squeeze_dropped cannot be combined with diff_topk: the perturbed top-k soft gather mixes every token into "
+                                   "every kept row and has no dropped set")
+SQUEEZE_DROPPED_THRESHOLD_ERROR = ("squeeze_dropped applies to the fixed-ratio path only: with patch_score_threshold no token is removed, there "
+                                   "is nothing to squeeze")
+SQUEEZE_DROPPED_TOPK_SELECTION_ERROR = ("squeeze_dropped needs topk_selection=True: the kept and dropped sets are those of the hard top-k of the "
+                                        "fixed-ratio path")
 ATTN_SELECTION_TOPK_SELECTION_ERROR = ("attn_selection needs topk_selection=True: the CLS attention is ranked by the hard top-k of the fixed-ratio "
                                        "path (the reference's recipe sets both, mask_predictor.py:147-148)")
 ATTN_SELECTION_THRESHOLD_ERROR = ("attn_selection applies to the fixed-ratio path only: it cannot be combined with patch_score_threshold")
@@ -450,16 +458,28 @@ class VisionTransformerDiffPruning(_ViTBase):
     tokens by the CLS attention row that block i - 1 of the same forward returned - max over heads, or the mean with mean_heads=True,
     renormalised over the stage's scored tokens - instead of by the score predictor.  `score_predictor` is still constructed (state-dict keys
     and checkpoints are unchanged) and never called; `pred_logits` then holds each stage's attention PROBABILITIES [B, T], detached (not
-    logits: there is no predictor output), and no gradient reaches the attention row through the selection or the fused package token."""
+    logits: there is no predictor output), and no gradient reaches the attention row through the selection or the fused package token.
+
+    squeeze_dropped=True (pruning and squeezing, the build's own definition): a stage keeps the k tokens its selector
+    chose and folds every token it drops into the kept token with the highest cosine, so the sequence lengths are those of plain pruning;
+    `squeeze_plans` holds each stage's (dst, sim) after a forward."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, qk_scale=None, representation_size=None,
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., hybrid_backbone=None, norm_layer=None,
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
-                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, init_n=14 * 14, diff_topk=False,
-                 topk_num_samples=500):
+                 predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, squeeze_dropped=False,
+                 init_n=14 * 14, diff_topk=False, topk_num_samples=500):
         super().__init__()
+        if squeeze_dropped and fuse_dropped:
+            raise ValueError(SQUEEZE_DROPPED_FUSE_ERROR)
+        if squeeze_dropped and diff_topk:
+            raise ValueError(SQUEEZE_DROPPED_DIFF_TOPK_ERROR)
+        if squeeze_dropped and patch_score_threshold is not None:
+            raise ValueError(SQUEEZE_DROPPED_THRESHOLD_ERROR)
+        if squeeze_dropped and not topk_selection:
+            raise ValueError(SQUEEZE_DROPPED_TOPK_SELECTION_ERROR)
         if fuse_dropped and patch_score_threshold is not None:
             raise ValueError(FUSE_DROPPED_THRESHOLD_ERROR)
         if fuse_dropped and diff_topk:
@@ -527,6 +547,13 @@ class VisionTransformerDiffPruning(_ViTBase):
         # appends sum_{j in dropped} (p_j / sum p) x_j as one extra row, which later stages carry along unscored;
         # training and eval alike - the pruned inference model carries the package tokens too
         self.fuse_dropped = bool(fuse_dropped)
+        # pruning and squeezing (TPS): every stage folds each token it drops into the kept token with the highest cosine, at weight
+        # exp(cosine) against the kept token's own exp(1); the stage still hands on 1 + k rows; training and eval
+        # alike.  squeeze_plans[s] = (dst, sim) of stage s after a forward, detached; squeeze_plan_override replays a list of such plans
+        # (tests: the counterpart of kept_token_override)
+        self.squeeze_dropped = bool(squeeze_dropped)
+        self.squeeze_plans = []
+        self.squeeze_plan_override = None
         self.unpruned = False
         self.distill = distill
         self.pruning_loc, self.token_ratio = pruning_loc, token_ratio
@@ -563,6 +590,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         x = self._embed(x)                                                  # :816-824
         self.num_kept_tokens, self.cls_attns, self.pred_logits = [], [], []
         self.kept_token_indices, self.dropped_token_indices = [], []
+        self.squeeze_plans = []
         p_count = 0
         for i, blk in enumerate(self.blocks):
             if self.grad_ready_hook is not None and x.requires_grad:
@@ -592,6 +620,13 @@ class VisionTransformerDiffPruning(_ViTBase):
                     x = DF.GatherFuseFn.apply(x, pred_logits, kept, dropped.contiguous(), carried)
                 elif self.fuse_dropped:      # the bits of the predictor's own keep_probs, differentiable: the task loss reaches the scores
                     x = DF.GatherFuseFn.apply(x, DF.KeepProbsFn.apply(pred_logits), kept, dropped.contiguous(), carried)
+                elif self.squeeze_dropped:   # the selection decides who survives; every dropped token goes into its nearest survivor
+                    plan = None
+                    if self.squeeze_plan_override is not None:
+                        plan = (self.squeeze_plan_override[p_count][0].to(device=x.device, dtype=torch.int32).contiguous(),
+                                self.squeeze_plan_override[p_count][1].to(device=x.device, dtype=torch.float32).contiguous())
+                    x, dst, sim = DF.GatherSqueezeFn.apply(x, kept, dropped.contiguous(), plan)
+                    self.squeeze_plans.append((dst.detach(), sim.detach()))
                 else:
                     x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
