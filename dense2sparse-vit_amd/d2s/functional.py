@@ -240,9 +240,9 @@ def _norm_linear(x, cmap, nw, nb, w, b, eps, io, train, epi=None, aux_out=None):
     return (ln if train else None), y, mean, rstd
 
 
-def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0, mid=None):
+def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0, mid=None, mid_cls=False):
     """THE launch sequence of a pre-norm transformer block on [rows, D] tokens: LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm,
-    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward, functional_tome.
+    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward, functional_tome, functional_ats.
     io: bf16 data path - every GEMM input exists in bf16 only, the residual stream stays fp32.
     train: keep the LayerNorm statistics, the GELU pre-activation and every layer input for block_backward_sequence; otherwise (the frozen
     teacher, eval) nothing is kept and each intermediate dies before the next allocation (the pre-activation alone is 155 MB per block at
@@ -250,7 +250,8 @@ def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=No
     attn(qkv, *attn_args, io, want_f32) is attn_forward or a function of its shape.  s_attn / s_mlp: stochastic-depth row scales of the
     two branches, one per rows_per_group rows.
     mid(qkv, x1) -> x1', the hook between the halves (token merging): x1' may have fewer rows than x1, the MLP half runs on them and only
-    x1' is kept; qkv then lives until the hook has returned.
+    x1' is kept; qkv then lives until the hook has returned.  mid_cls: the hook is called mid(qkv, x1, cls_row) instead (adaptive token
+    sampling scores by the CLS softmax row the attention emitted).
     -> (y, cls_row or None, what block_backward_sequence unpacks (None unless train), cinv)"""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = params
     rows, D = x.shape
@@ -265,7 +266,7 @@ def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=No
     if not train:
         del ao, aoh
     if mid is not None:
-        x1 = mid(qkv, x1)          # the x1 that went in dies here
+        x1 = mid(qkv, x1, cls_row) if mid_cls else mid(qkv, x1)          # the x1 that went in dies here
         rows = x1.shape[0]
         if not train:
             del qkv

@@ -1,5 +1,5 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
-two entries, and include/d2s_hip_squeeze.h, the entries of a squeezing stage).
+two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, and include/d2s_hip_ats.h, adaptive token sampling).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -152,6 +152,11 @@ _SIGS_SQUEEZE = {
     "d2s_gather_squeeze_bwd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
 }
 
+# the entry of include/d2s_hip_ats.h (adaptive token sampling at inference), same form
+_SIGS_ATS = {
+    "d2s_ats_select": (I, [P, P, I, P, P, I, I, I, I, I, I, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -168,7 +173,7 @@ def load():
         raise D2SError(f"{LIB_PATH} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -186,6 +191,10 @@ def extension_symbols():
 
 def squeeze_symbols():
     return sorted(_SIGS_SQUEEZE)
+
+
+def ats_symbols():
+    return sorted(_SIGS_ATS)
 
 
 def ptr(t):

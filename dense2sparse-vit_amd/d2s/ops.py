@@ -1170,6 +1170,25 @@ def ragged_repack(x, keep, cu_old, cu_new, row_src_old, total_new, B):
     return out, src
 
 
+# ---- adaptive token sampling at inference: a stage on the packed batch (csrc/ats.hip) ----
+def ats_select(cls_row, qkv, cu, row_src, K, N, B, H, max_n, want_dense=True):
+    """cls_row [H, total] fp32 (the varlen attention's CLS softmax rows), qkv [total, 3 * H * 64] fp32 or bf16, read in place
+    -> (score [total] with 0 at the CLS rows, keep [total] float 0/1 with 1 at the CLS rows, counts [B] int32 kept non-CLS rows,
+    dense_mask [B, N] in original patch coordinates or None)."""
+    _f32(cls_row)
+    assert qkv.dtype in (torch.float32, torch.bfloat16) and qkv.is_contiguous(), (qkv.dtype, qkv.is_contiguous())
+    total = qkv.shape[0]
+    assert cls_row.shape == (H, total) and qkv.shape[1] == 3 * H * 64 and row_src.numel() == total and cu.numel() == B + 1
+    dev = qkv.device
+    score = torch.empty((total,), dtype=torch.float32, device=dev)
+    keep = torch.empty((total,), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    dense = torch.empty((B, N), dtype=torch.float32, device=dev) if want_dense else None
+    lib.call("d2s_ats_select", lib.ptr(cls_row), lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(cu), lib.ptr(row_src), int(K), int(N),
+             int(B), int(H), int(total), int(max_n), lib.ptr(score), lib.ptr(keep), lib.ptr(counts), lib.ptr(dense))
+    return score, keep, counts, dense
+
+
 def mask_row_weights(mask):
     m = _f32(mask).reshape(-1)
     w = torch.empty_like(m)

@@ -15,8 +15,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
-    # DynamicViT and Token Merging baselines: eval returns logits alone
-    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe")
+    # DynamicViT, Token Merging and Adaptive Token Sampling baselines: eval returns logits alone
+    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS")
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():

@@ -24,6 +24,8 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --tome-bf16 --student-checkpoint deit_small.pth
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --student-checkpoint deit_small.pth \
         --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
+    python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --eval-only \
+        --student-checkpoint deit_small.pth                               (adaptive token sampling: every image keeps its own count)
 """
 import os
 import sys
@@ -43,11 +45,15 @@ from train import train_one_epoch                    # noqa: E402
 _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": "dynamic_vit_small_patch16_224_student",
              "deit_base": "dynamic_vit_base_patch16_224_student"}
 _TOME = {"deit_tiny": "tome_deit_tiny_patch16_224", "deit_small": "tome_deit_small_patch16_224", "deit_base": "tome_deit_base_patch16_224"}
+_ATS = {"deit_tiny": "ats_deit_tiny_patch16_224", "deit_small": "ats_deit_small_patch16_224", "deit_base": "ats_deit_base_patch16_224"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
 _NOT_WITH_DYNAMICVIT = (("topk_selection", "--topk-selection"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"),
                         ("small_predictor", "--small-predictor"), ("predictor_bn", "--predictor-bn"), ("fuse_dropped", "--fuse-dropped"))
+# --method ats: the selection rules of the dense-to-sparse student, which a sampling stage replaces
+_NOT_WITH_ATS = (("topk_selection", "--topk-selection"), ("attn_selection", "--attn-selection"), ("fuse_dropped", "--fuse-dropped"),
+                 ("squeeze_dropped", "--squeeze-dropped"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"))
 
 
 def check_supported(args):
@@ -83,6 +89,21 @@ def check_supported(args):
             bad.append("--method tome with --gemm-mode bf16 (the key-weighted attention is an fp32 kernel; exact and split run)")
     elif tome_r > 0:
         bad.append(f"--tome-r {tome_r} with --method {getattr(args, 'method', 'd2s')} (tokens are merged by --method tome only)")
+    ats_tokens = getattr(args, "ats_tokens", None)
+    if getattr(args, "method", "d2s") == "ats":
+        if not args.eval_only:
+            bad.append("--method ats without --eval-only (adaptive token sampling is built for inference: a sampling stage has no backward)")
+        for attr, flag in _NOT_WITH_ATS:
+            if getattr(args, attr, None) not in (None, False):
+                bad.append(f"--method ats with {flag} (a sampling stage scores tokens by the block's own CLS attention and value norms and "
+                           "keeps a count of its own)")
+        stages = len(args.pruning_locs or [])
+        if ats_tokens is not None and len(ats_tokens) not in (1, stages):
+            bad.append(f"--ats-tokens with {len(ats_tokens)} values for {stages} stages (one value for every stage, or one per --pruning-locs entry)")
+        if ats_tokens is not None and any(v < 1 for v in ats_tokens):
+            bad.append(f"--ats-tokens {' '.join(str(v) for v in ats_tokens)} (at least 1 token per stage)")
+    elif ats_tokens is not None:
+        bad.append(f"--ats-tokens with --method {getattr(args, 'method', 'd2s')} (tokens are sampled by --method ats only)")
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
@@ -211,6 +232,8 @@ def check_supported(args):
 def build_models(args):
     """mask_predictor.py:170-202 (the arch switch), with local checkpoints instead of URL downloads."""
     arch = args.arch if args.arch in _STUDENTS else "deit_small"
+    if getattr(args, "method", "d2s") == "ats":
+        return build_ats(args), None             # inference only: no teacher
     if getattr(args, "method", "d2s") == "dynamicvit":
         student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
                                                                     drop_path_rate=getattr(args, "drop_path", 0.0),
@@ -239,19 +262,35 @@ def build_tome(args):
     arch = args.arch if args.arch in _TOME else "deit_small"
     model = getattr(vit_models, _TOME[arch])(args.tome_r, train_merge=bool(getattr(args, "tome_train", False)),
                                              bf16=bool(getattr(args, "tome_bf16", False)))
+    return load_trunk(args, model, "tome", "token merging has no predictor")
+
+
+def load_trunk(args, model, method, why):
+    """Weights of a predictor-free baseline from --student-checkpoint or the 'model' entry of a --resume file.  A dense-to-sparse student's
+    checkpoint carries score predictors such a model has no use for: they are counted and ignored (strict=False)."""
     path = args.student_checkpoint or args.resume
     if path is None:
-        print("--method tome: no --student-checkpoint, the trunk starts from its random initialisation")
+        print(f"--method {method}: no --student-checkpoint, the trunk starts from its random initialisation")
         return model.to(args.device)
     sd = vit_models.checkpoint_filter_fn(torch.load(path, map_location="cpu", weights_only=True), model)
     missing, unexpected = model.load_state_dict(sd, strict=False)
     if missing:
         raise SystemExit(f"{path}: no weights for {len(missing)} tensors of the trunk, first {missing[0]}")
     pred = [k for k in unexpected if 'predictor' in k]
-    print(f"--method tome: trunk weights from {path}; ignored {len(pred)} predictor tensors" +
+    print(f"--method {method}: trunk weights from {path}; ignored {len(pred)} predictor tensors" +
           (f" and {len(unexpected) - len(pred)} others, first {[k for k in unexpected if k not in pred][0]}" if len(unexpected) > len(pred) else "") +
-          " (token merging has no predictor)")
+          f" ({why})")
     return model.to(args.device)
+
+
+def build_ats(args):
+    """--method ats: the dense DeiT trunk with a sampling stage in every block of --pruning-locs, at most --ats-tokens tokens each."""
+    arch = args.arch if args.arch in _ATS else "deit_small"
+    toks = getattr(args, "ats_tokens", None)
+    if toks is not None and len(toks) == 1:
+        toks = int(toks[0])
+    model = getattr(vit_models, _ATS[arch])(ats_locs=list(args.pruning_locs), ats_tokens=toks)
+    return load_trunk(args, model, "ats", "adaptive token sampling has no predictor")
 
 
 def folder_loaders(args, samples, split, epoch, rank, world):
@@ -295,8 +334,8 @@ def save_checkpoints(args, optim, student, epoch, best_acc, improved, first):
 
 
 def eval_tome(args, rank, world, distributed):
-    """--method tome --eval-only: no teacher pass, no TrainStep - the model, the validation loader, one evaluation."""
-    model = build_tome(args)
+    """--method tome / --method ats --eval-only: no teacher pass, no TrainStep - the model, the validation loader, one evaluation."""
+    model = build_ats(args) if args.method == "ats" else build_tome(args)
     if args.data_source == "folder":
         from d2s import data
         samples, classes = data.image_folder(args.imgnet_val_dir)
@@ -312,7 +351,12 @@ def eval_tome(args, rank, world, distributed):
         dist.all_reduce(t)
         metrics["val_acc"] = float(t / world)
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and args.method == "ats":
+        per = [c.float() for c in model.tokens_per_stage]       # the last validation batch's
+        print(f"eval only: --method ats --pruning-locs {' '.join(str(v) for v in model.ats_locs)} (gemm mode {args.gemm_mode}): "
+              f"ats tokens per stage: mean {[round(float(c.mean()), 1) for c in per]} min {[int(c.min()) for c in per]} "
+              f"max {[int(c.max()) for c in per]}, " + ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
+    elif rank == 0:
         path_ran = "bf16 data path" if getattr(model, "bf16", False) else f"fp32 data path, gemm mode {args.gemm_mode}"
         print(f"eval only: --method tome --tome-r {args.tome_r} ({path_ran}): tokens per block {model.tokens_per_block}, " +
               ", ".join(f"{k}={v:.4f}" for k, v in sorted(metrics.items()) if isinstance(v, float)))
@@ -336,7 +380,7 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
-    if args.method == "tome" and not args.tome_train:
+    if args.method == "ats" or (args.method == "tome" and not args.tome_train):
         return eval_tome(args, rank, world, distributed)
     if args.method == "tome":
         # --tome-train: the merging student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0

@@ -161,10 +161,14 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome'],
+    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
-                        "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges)")
+                        "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "
+                        "ats: the Adaptive Token Sampling baseline (stages at --pruning-locs, --ats-tokens; no predictor; --eval-only)")
+    p.add_argument('--ats-tokens', nargs='+', type=int, default=None, metavar='K',
+                   help='with --method ats: the most tokens an image keeps at a stage, one value for every stage or one per --pruning-locs '
+                        'entry (default: the number of patches); how many of them an image keeps falls out of its own attention')
     p.add_argument('--tome-train', action='store_true', default=False,
                    help='with --method tome: train through the merges (merge backward, key-weighted attention backward); the objective is '
                         '--cls-weight * CE + --dist-weight * KL to the dense teacher (--dist-weight 0: no teacher)')

@@ -15,3 +15,5 @@ from .default_dynamic_vit import (DefaultVisionTransformerDiffPruning, DefaultVi
                                   default_dynamic_vit_small_patch16_224_teacher, default_dynamic_vit_base_patch16_224_teacher)
 from .tome import (VisionTransformerToMe, tome_deit_tiny_patch16_224, tome_deit_small_patch16_224,  # noqa: F401
                    tome_deit_base_patch16_224)
+from .ats import (VisionTransformerATS, ats_deit_tiny_patch16_224, ats_deit_small_patch16_224,  # noqa: F401
+                  ats_deit_base_patch16_224)
