@@ -298,6 +298,33 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
     }
 }
 
+// the tile fetch of the DPOL dK/dV and the VARLEN dQ instantiations: 32-bit element offsets from the (wave-uniform) panel bases - a head's
+// panel spans n * ld < 2^32 elements (checked by the entries) - so that the loop-invariant per-thread addresses cost one register each, not two
+__device__ __forceinline__ void tile_load_u32(const float* __restrict__ base, unsigned ld, int row0, int nrows, int tid, f32x4 (&r)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int f = tid + i * 256, row = row0 + (f >> 4);
+        const unsigned off = (unsigned)row * ld + (unsigned)((f & 15) * 4);
+        r[i] = row < nrows ? *reinterpret_cast<const f32x4*>(base + off) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// VARLEN tail of the two backward kernels (training through a ragged packed batch): one VarlenSeg after the existing
+// arguments, so that every dense instantiation keeps its spelling, its argument list and its instructions.  Image b owns rows cu[b] ..
+// cu[b+1] of qkv / dout / dqkv, its lse / delta live at [h * total + cu[b] + i] (what attn_fwd_kernel<false, true> writes), `n` arrives as
+// max_n.  The segment is clamped to [0, total) and its length to [0, max_n]: a bad cu is never dereferenced outside the buffers.
+struct VarlenSeg { const int* cu; int total; };
+template <typename... T> struct has_varlen { static constexpr bool value = false; };
+template <> struct has_varlen<VarlenSeg> { static constexpr bool value = true; };
+__device__ __forceinline__ VarlenSeg varlen_seg() { return VarlenSeg{nullptr, 0}; }
+template <typename T> __device__ __forceinline__ VarlenSeg varlen_seg(T) { return VarlenSeg{nullptr, 0}; }
+__device__ __forceinline__ VarlenSeg varlen_seg(VarlenSeg v) { return v; }
+__device__ __forceinline__ int varlen_rows(VarlenSeg v, int b, int max_n, int& row_base) {
+    const int r0 = min(max(v.cu[b], 0), v.total), r1 = min(max(v.cu[b + 1], r0), v.total);
+    row_base = r0;
+    return min(r1 - r0, max_n);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // backward, dQ: one wave per 32 queries, loops over key tiles (same orientation as forward)
 // ---------------------------------------------------------------------------------------------------------
@@ -307,11 +334,13 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 // KEYW (backward of attn_fwd_kernel<false, false, true>, training through token merging): P_ij = w_j exp(S_ij - lse_i) with lse_i = m_i +
 // log sum_j e_ij w_j as that forward wrote it; the weights travel in `policy`, are staged per key tile in pol_s as the forward does, and
 // multiply the exponential - every key, the diagonal included.  They are counts and get no gradient.
-template <bool POLICY, bool KEYW = false>
+// VARLEN (the tail is one VarlenSeg, <false, false, VarlenSeg>): the same tiles on image b's rows of a packed batch; a workgroup whose
+// 128-row tile starts at or past the image's n returns before its first barrier (block-uniform).
+template <bool POLICY, bool KEYW = false, typename... Varlen>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           float* __restrict__ dqkv, int n, int H, float scale,
-                                                          const float* __restrict__ policy) {
+                                                          const float* __restrict__ policy, Varlen... varlen_) {
     __shared__ __attribute__((aligned(16))) float Ks[32 * PITCH];
     __shared__ __attribute__((aligned(16))) float Vs[32 * PITCH];
     __shared__ float pol_s[32];
@@ -320,10 +349,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    const float* qb = qkv + (long)b * n * ld + h * DH;
+    constexpr bool VARLEN = has_varlen<Varlen...>::value;
+    int row_base = 0;
+    if (VARLEN) {
+        n = varlen_rows(varlen_seg(varlen_...), b, n, row_base);
+        if (bx * 128 >= n) return;                      // block-uniform: this image has no queries in this tile
+    }
+    // the dense offsets stay spelled where they are used, as they were: hoisting them into one tok0 / stat0 reorders the dense
+    // instantiations' scalar address arithmetic (same results, other instructions)
+    const long stat0v = VARLEN ? (long)h * varlen_seg(varlen_...).total + row_base : 0;        // the image's first lse / delta entry
+    const float* qb = qkv + (VARLEN ? (long)row_base : (long)b * n) * ld + h * DH;
     const float* kb = qb + (long)H * DH;
     const float* vb = kb + (long)H * DH;
-    const float* dob = dout + (long)b * n * ldo + h * DH;
+    const float* dob = dout + (VARLEN ? (long)row_base : (long)b * n) * ldo + h * DH;
     const int q0 = bx * 128 + wave * 32;
     const bool active = q0 < n;
 
@@ -331,8 +369,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     load_rows_regs(qb, ld, q0 + l31, n, half, scale, qreg);
     load_rows_regs(dob, ldo, q0 + l31, n, half, 1.0f, doreg);
     const bool qok = q0 + l31 < n;
-    const float lse_i = qok ? lse[((long)b * H + h) * n + q0 + l31] : INFINITY;
-    const float dl_i = qok ? delta[((long)b * H + h) * n + q0 + l31] : 0.f;
+    const float lse_i = qok ? lse[(VARLEN ? stat0v : ((long)b * H + h) * n) + q0 + l31] : INFINITY;
+    const float dl_i = qok ? delta[(VARLEN ? stat0v : ((long)b * H + h) * n) + q0 + l31] : 0.f;
 
     f32x16 dq[2];
 #pragma unroll
@@ -342,8 +380,15 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     f32x4 kr[2], vr[2];
     float pr = 0.f;
     const float* polb = (POLICY || KEYW) ? policy + (long)b * n : nullptr;
-    tile_load(kb, ld, 0, n, tid, kr);
-    tile_load(vb, ld, 0, n, tid, vr);
+    // VARLEN: 32-bit element offsets for the tile fetches, as in the DPOL instantiation (an image's panel spans max_n * ld < 2^32 elements,
+    // checked by the entry) - the registers that frees keep this instantiation out of scratch, where the dense one spills 16 bytes
+    if (VARLEN) {
+        tile_load_u32(kb, (unsigned)ld, 0, n, tid, kr);
+        tile_load_u32(vb, (unsigned)ld, 0, n, tid, vr);
+    } else {
+        tile_load(kb, ld, 0, n, tid, kr);
+        tile_load(vb, ld, 0, n, tid, vr);
+    }
     if ((POLICY || KEYW) && tid < 32) pr = tid < n ? polb[tid] : 0.f;
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();
@@ -352,8 +397,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
         if ((POLICY || KEYW) && tid < 32) pol_s[tid] = pr;
         __syncthreads();
         if (t + 1 < ntiles) {
-            tile_load(kb, ld, (t + 1) * 32, n, tid, kr);
-            tile_load(vb, ld, (t + 1) * 32, n, tid, vr);
+            if (VARLEN) {
+                tile_load_u32(kb, (unsigned)ld, (t + 1) * 32, n, tid, kr);
+                tile_load_u32(vb, (unsigned)ld, (t + 1) * 32, n, tid, vr);
+            } else {
+                tile_load(kb, ld, (t + 1) * 32, n, tid, kr);
+                tile_load(vb, ld, (t + 1) * 32, n, tid, vr);
+            }
             if ((POLICY || KEYW) && tid < 32) { const int kj = (t + 1) * 32 + tid; pr = kj < n ? polb[kj] : 0.f; }
         }
         if (!active) continue;
@@ -374,7 +424,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
         mma_reg_lds(s, Ks, l31, half, dq, min(4, (n - kv0 + 7) >> 3));      // dQ[query][d] += sum_key dS^T[key][query] K[key][d]
     }
     if (!active) return;
-    float* dqb = dqkv + (long)b * n * ld + h * DH;
+    float* dqb = dqkv + (VARLEN ? (long)row_base : (long)b * n) * ld + h * DH;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int qi = q0 + mfma32_row(r, half);
@@ -386,16 +436,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     }
 }
 
-// the tile fetch of the DPOL instantiation: 32-bit element offsets from the (wave-uniform) panel bases - a head's panel spans n * ld < 2^32
-// elements (checked by the entry) - so that the loop-invariant per-thread addresses cost one register each, not two
-__device__ __forceinline__ void tile_load_u32(const float* __restrict__ base, unsigned ld, int row0, int nrows, int tid, f32x4 (&r)[2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int f = tid + i * 256, row = row0 + (f >> 4);
-        const unsigned off = (unsigned)row * ld + (unsigned)((f & 15) * 4);
-        r[i] = row < nrows ? *reinterpret_cast<const f32x4*>(base + off) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
 __device__ __forceinline__ void dkv_fetch_next(const float* __restrict__ qb, const float* __restrict__ dob, const float* __restrict__ lse_b,
                                                const float* __restrict__ dl_b, const float* __restrict__ ci_b, unsigned ld, unsigned ldo,
                                                int t1, int n, int tid, f32x4 (&qr)[2], f32x4 (&dr)[2], float& lr, float& dlr, float& cir) {
@@ -417,6 +457,8 @@ __device__ __forceinline__ float* first_arg(KeyWeights) { return nullptr; }
 __device__ __forceinline__ const float* key_weights() { return nullptr; }
 __device__ __forceinline__ const float* key_weights(float*) { return nullptr; }
 __device__ __forceinline__ const float* key_weights(KeyWeights k) { return k.w; }
+__device__ __forceinline__ float* first_arg(VarlenSeg) { return nullptr; }
+__device__ __forceinline__ const float* key_weights(VarlenSeg) { return nullptr; }
 template <typename... T> struct has_key_weights { static constexpr bool value = false; };
 template <> struct has_key_weights<KeyWeights> { static constexpr bool value = true; };
 
@@ -434,6 +476,7 @@ template <> struct has_key_weights<KeyWeights> { static constexpr bool value = t
 // dpol_part [B, H, n]: per-head partials, folded over h in ascending order by attn_dpol_fold_kernel.
 // KEYW (the tail is one KeyWeights, <false, false, KeyWeights>; backward of the key-weighted forward): P_ij = w_j exp(S_ij - lse_i).  The
 // lane owns key j, so w_j is one register loaded once (pol_key's slot) and multiplies p before it feeds dV and dS; no diagonal exception.
+// VARLEN (the tail is one VarlenSeg, <false, false, VarlenSeg>): as in the dQ kernel.
 template <bool POLICY, bool DPOL = false, typename... DpolPart>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
@@ -448,12 +491,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    const float* qb = qkv + (long)b * n * ld + h * DH;
+    constexpr bool VARLEN = has_varlen<DpolPart...>::value;
+    int row_base = 0;
+    if (VARLEN) {
+        n = varlen_rows(varlen_seg(dpol_part_...), b, n, row_base);
+        if (bx * 128 >= n) return;                      // block-uniform: this image has no keys in this tile
+    }
+    const long tok0 = VARLEN ? (long)row_base : (long)b * n;       // first token row of the image
+    const long stat0 = VARLEN ? (long)h * varlen_seg(dpol_part_...).total + row_base : ((long)b * H + h) * n;
+    const float* qb = qkv + tok0 * ld + h * DH;
     const float* kb = qb + (long)H * DH;
     const float* vb = kb + (long)H * DH;
-    const float* dob = dout + (long)b * n * ldo + h * DH;
-    const float* lse_b = lse + ((long)b * H + h) * n;
-    const float* dl_b = delta + ((long)b * H + h) * n;
+    const float* dob = dout + tok0 * ldo + h * DH;
+    const float* lse_b = lse + stat0;
+    const float* dl_b = delta + stat0;
     const int k0 = bx * 128 + wave * 32;
     const bool active = k0 < n;
 
@@ -535,7 +586,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
         dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
         if (halfe == 0 && k0e + l31e < n) dpol_part[((long)b * H + h) * n + k0e + l31e] = dpol_acc;
     }
-    float* dkb = dqkv + (long)b * n * ld + (long)H * DH + h * DH;
+    float* dkb = dqkv + tok0 * ld + (long)H * DH + h * DH;
     float* dvb = dkb + (long)H * DH;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -603,6 +654,36 @@ int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out,
     dim3 grid((max_n + 127) / 128, B * H), block(256);
     AttnFwdArgs a{qkv, out, nullptr, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total};
     hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, cls_row ? (size_t)max_n * sizeof(float) : 0, stream, a);
+    return d2s_check_launch();
+}
+
+// d2s_attn_varlen_fwd_f32 that also keeps lse [H, total] (lse of row cu[b] + i of head h at h * total + cu[b] + i) for
+// d2s_attn_varlen_bwd_f32: the same instantiation and launch geometry, out / cls_row bit for bit that entry's.
+int d2s_attn_varlen_fwd_lse_f32(const float* qkv, const int* cu_seqlens, float* out, float* lse, float* cls_row, int B, int total, int max_n,
+                                int H, float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || !out || !lse || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
+    dim3 grid((max_n + 127) / 128, B * H), block(256);
+    AttnFwdArgs a{qkv, out, lse, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total};
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, cls_row ? (size_t)max_n * sizeof(float) : 0, stream, a);
+    return d2s_check_launch();
+}
+
+// Backward of d2s_attn_varlen_fwd_lse_f32 (out, lse as that call wrote them): dqkv [total, 3*H*64] is fully written when cu_seqlens covers
+// [0, total), every element once, no atomics; delta_ws: [H, total] floats of scratch.  d2s_attn_bwd_f32's three launches with the image's
+// rows taken from cu_seqlens: each image's rows are bit for bit d2s_attn_bwd_f32's on that image alone.
+int d2s_attn_varlen_bwd_f32(const float* qkv, const int* cu_seqlens, const float* out, const float* dout, const float* lse, float* dqkv,
+                            float* delta_ws, int B, int total, int max_n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || !out || !dout || !lse || !dqkv || !delta_ws || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0)
+        return D2S_ERR_ARG;
+    if ((long)max_n * 3 * H * 64 >= (1L << 32)) return D2S_ERR_ARG;      // tile_load_u32: one image's qkv panel must fit 32-bit element offsets
+    // delta [H, total]: the dense kernel's [B, H, n] layout with B = 1, n = total
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)(((long)total + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, (long)total, total, H);
+    dim3 grid((max_n + 127) / 128, B * H), block(256);
+    const VarlenSeg seg{cu_seqlens, total};
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, VarlenSeg>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, max_n, H, scale,
+                       static_cast<const float*>(nullptr), seg);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, VarlenSeg>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, max_n, H, scale,
+                       static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), seg);
     return d2s_check_launch();
 }
 

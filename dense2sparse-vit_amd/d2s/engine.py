@@ -295,6 +295,9 @@ def checkpoint_config(config):
     theirs.setdefault("tome_r", [])                # ... and before a Token Merging student could be trained: no such student
     theirs.setdefault("prop_attn", False)
     theirs.setdefault("train_merge", False)
+    theirs.setdefault("ats_locs", [])              # ... and before an Adaptive Token Sampling student could be trained: no such student
+    theirs.setdefault("ats_tokens", [])
+    theirs.setdefault("train_sample", False)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     return theirs
 
@@ -536,7 +539,24 @@ class TrainStep:
             if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
                 raise lib.D2SError("TrainStep with a Token Merging student and drop_path_rate > 0: stochastic depth is not built for a merging block")
             graph = False
-        elif teacher is None:
+        # an Adaptive Token Sampling student with stages (vit_models/ats.py) takes the same route: logits alone,
+        # ToMeLoss, the teacher optional.  Without stages it is the dense trunk and stays where it was.
+        self.ats = type(student).__name__ == "VisionTransformerATS" and len(getattr(student, "ats_locs", [])) > 0
+        if self.ats:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with an Adaptive Token Sampling student: the warm-up epochs train the score "
+                                 "predictors only (train.py:50-53), and a sampling stage has none - pass warmup_steps=0")
+            if graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with an Adaptive Token Sampling student is not supported: every stage reads its "
+                                   "row count on the host, which a captured step cannot; run the step eagerly (graph=False)")
+            if not getattr(student, "train_sample", False):
+                raise lib.D2SError("TrainStep with a sampling VisionTransformerATS needs train_sample=True (training through the stages is opt-in)")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with an Adaptive Token Sampling student and drop_path_rate > 0: stochastic depth is not built "
+                                   "for a ragged block")
+            graph = False
+        self.logits_only = self.tome or self.ats
+        if not self.logits_only and teacher is None:
             raise lib.D2SError("TrainStep without a teacher: only a Token Merging student trains without one")
         if self.teacher is not None:
             self.teacher.eval()
@@ -550,7 +570,7 @@ class TrainStep:
         # trained with its own objective, the full one in every epoch; the freeze / learning-rate schedule is the d2s one
         self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
         self.tome_loss_fn = None
-        if self.tome:
+        if self.logits_only:
             self.tome_loss_fn = ToMeLoss(args)
             self.mask_loss_fn = self.backbone_loss_fn = None
         elif self.baseline:
@@ -691,6 +711,9 @@ class TrainStep:
             "tome_r": [int(v) for v in getattr(s, "tome_r", [])],
             "prop_attn": bool(getattr(s, "prop_attn", False)),
             "train_merge": bool(getattr(s, "train_merge", False)),
+            "ats_locs": [int(v) for v in getattr(s, "ats_locs", [])],
+            "ats_tokens": [int(v) for v in getattr(s, "ats_tokens", [])],
+            "train_sample": bool(getattr(s, "train_sample", False)),
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -783,7 +806,7 @@ class TrainStep:
         dist_term = fn.dist_weight * fn.last[2]
         return loss, dict(mask_loss=dist_term, backbone_loss=fn.last[0] - dist_term, kept=None, logits_s=logits_s, token_s=None,
                           pred_logits=None, logits_t=logits_t, token_t=None, cls_attn=None,
-                          tokens_per_block=list(self.student.tokens_per_block))
+                          tokens_per_block=list(self.student.tokens_per_stage if self.ats else self.student.tokens_per_block))
 
     def forward_losses(self, images, labels, accumulate=True, next_images=None):
         if self.teacher is None:
@@ -822,7 +845,7 @@ class TrainStep:
                 with torch.no_grad():
                     out_t = self.teacher(images)
                 out_s = self.student(images)
-        if self.tome:
+        if self.logits_only:
             return self._tome_losses(out_s, out_t, labels, accumulate)
         if self.baseline:
             return self._baseline_losses(out_s, out_t, labels, accumulate)

@@ -1,16 +1,70 @@
-"""Adaptive Token Sampling at inference (ATS, Fayyaz et al. 2022; DESIGN.md section 24 - the build's own definition, PARITY UNPINNED): a
-block with a sampling stage between its attention half and its MLP half, on a ragged packed batch.
+"""Adaptive Token Sampling (ATS, Fayyaz et al. 2022; DESIGN.md section 24 - the build's own definition, PARITY UNPINNED): a block with a
+sampling stage between its attention half and its MLP half, on a ragged packed batch - ats_block_forward for inference, RaggedBlockFn to
+train through the stages.
 
 The block attends over every token it received; after the projection and the residual add only the sampled rows and CLS go on into the
 MLP half and the later blocks (rows are independent after attention, so this equals attention for the sampled queries only).  The score
 is the CLS softmax row the varlen attention already emits times the norm of the token's V, read from the block's own qkv; the count falls
 out of the image (d2s_ats_select), so every image keeps its own number of tokens and the batch stays ragged.
 
-ats_block_forward issues block_forward_sequence's launches with a hook between the halves: select (or replay a plan), the new offsets,
-ONE host read of the new row total (it sizes every later launch, as at a threshold stage), the re-pack of the residual stream.  Both data
-paths: fp32, and the bf16 path, where qkv exists in bf16 only and the kernel reads that; the residual stream and the re-pack are fp32."""
+The seven block launches are functional.block_forward_sequence's and their backward is functional.block_backward_sequence's; what is
+stated here is what a ragged block adds (_Ragged): the attention of either direction on the packed batch, and the hook between the
+halves with its backward - select (or replay a plan), the new offsets, ONE host read of the new row total (it sizes every later launch,
+as at a threshold stage), the re-pack of the residual stream.  Inference runs on both data paths: fp32, and the bf16 path, where qkv
+exists in bf16 only and the kernel reads that; the residual stream and the re-pack are fp32.
+
+Training (RaggedBlockFn, fp32 data path): the selection is a constant of the backward - score, keep and counts carry no gradient - so the
+hook's backward is one row move (ops.ragged_repack_bwd: a kept row takes the gradient of the row it became, a dropped row zeros) and a
+dropped row is reached only as a key and a value of the stage's own attention, whose backward is the varlen one (ops.attn_varlen_bwd).
+The MLP half's residual gradient lives on the rows that left the stage, the attention half's on the rows that entered it."""
+import torch
+
 from . import functional as DF
 from . import ops
+from .lib import D2SError
+
+_BF16_REFUSAL = "training through a ragged block runs in the fp32 arithmetic modes (exact, split): the varlen attention backward is an fp32 kernel"
+
+
+class _Ragged:
+    """What a ragged packed batch puts into one block's launch sequence, and the constants of its backward (no gradient reaches them).
+    cu [B+1], row_src [total] (original token index, 0 at CLS), max_n the longest image.  K: the stage's token limit, or None for a
+    block without a stage; plan: (keep, counts) of an earlier forward on the same batch, replayed instead of selecting.  After a stage's
+    forward: cu_new, row_src_new, plan, score / dense (None when replaying); max_n_out either way."""
+
+    def __init__(self, cu, B, max_n, heads, scale, row_src=None, K=None, N=0, plan=None):
+        self.cu, self.B, self.max_n, self.heads, self.scale = cu, int(B), int(max_n), heads, float(scale)
+        self.row_src, self.K, self.N, self.plan = row_src, K, N, plan
+        self.cu_new = self.row_src_new = self.score = self.dense = None
+        self.max_n_out = self.max_n if K is None else min(self.max_n, int(K) + 1)
+
+    def attn_train(self, qkv, io, want_f32):
+        """attn_forward's shape on the fp32 data path, keeping the log-sum-exp for attn_bwd"""
+        out, lse, cls_rows = ops.attn_varlen_fwd_lse(qkv, self.cu, self.B, qkv.shape[0], self.max_n, self.heads, self.scale,
+                                                     want_cls=self.K is not None)
+        return out, lse, None, cls_rows, None
+
+    def attn_bwd(self, qkv, ao, dao, lse, io, dqkv16, want_f32):
+        """attn_backward's shape"""
+        return ops.attn_varlen_bwd(qkv, self.cu, ao, dao, lse, self.B, qkv.shape[0], self.max_n, self.heads, self.scale), None
+
+    def sample(self, qkv, x1, cls_row):
+        """block_forward_sequence's hook (mid_cls): select on the CLS rows and qkv (fp32, or bf16 on the bf16 data path) unless a plan is
+        replayed, re-pack"""
+        if self.plan is None:
+            self.score, keep, counts, self.dense = ops.ats_select(cls_row, qkv, self.cu, self.row_src, self.K, self.N, self.B, self.heads,
+                                                                  self.max_n)
+            self.plan = (keep, counts)
+        keep, counts = self.plan
+        self.cu_new = ops.ragged_offsets(counts, extra=1)
+        total = int(self.cu_new[-1])      # the one device sync of a stage: the packed row count sizes every later launch
+        self.total_in = x1.shape[0]
+        x1, self.row_src_new = ops.ragged_repack(x1, keep, self.cu, self.cu_new, self.row_src, total, self.B)
+        return x1
+
+    def sample_bwd(self, g1):
+        """block_backward_sequence's hook: the gradient on the rows that left the stage -> on the rows that entered it"""
+        return ops.ragged_repack_bwd(g1, self.plan[0], self.cu, self.cu_new, self.total_in, self.B)
 
 
 def ats_block_forward(xp, cu, B, max_n, params, heads, eps, scale, K, N, row_src, plan=None):
@@ -19,19 +73,62 @@ def ats_block_forward(xp, cu, B, max_n, params, heads, eps, scale, K, N, row_src
     -> (y [total', D], cu' [B+1], row_src' [total'], max_n' = min(max_n, K + 1), (keep, counts), score [total] or None when replaying,
     dense_mask [B, N] or None when replaying).  Forward only."""
     io = DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
-    out = {}
-
-    def sample(qkv, x1, cls_row):
-        if plan is None:
-            score, keep, counts, dense = ops.ats_select(cls_row, qkv, cu, row_src, K, N, B, heads, max_n)
-        else:
-            (keep, counts), score, dense = plan, None, None
-        cu_new = ops.ragged_offsets(counts, extra=1)
-        total = int(cu_new[-1])      # the one device sync of a stage: the packed row count sizes every later launch
-        x1, src = ops.ragged_repack(x1, keep, cu, cu_new, row_src, total, B)
-        out.update(cu=cu_new, row_src=src, plan=(keep, counts), score=score, dense=dense)
-        return x1
-
+    r = _Ragged(cu, B, max_n, heads, scale, row_src, K, N, plan)
     y, _, _, _ = DF.block_forward_sequence(xp, params, eps, io, False, DF._varlen_attn_forward, (cu, B, max_n, heads, scale, True),
-                                           mid=sample, mid_cls=True)
-    return y, out["cu"], out["row_src"], min(int(max_n), int(K) + 1), out["plan"], out["score"], out["dense"]
+                                           mid=r.sample, mid_cls=True)
+    return y, r.cu_new, r.row_src_new, r.max_n_out, r.plan, r.score, r.dense
+
+
+@DF.mode_recorded
+class RaggedBlockFn(torch.autograd.Function):
+    """One transformer block on a ragged packed batch as a differentiable Function, with or without a sampling stage: xp [total, D], the 12
+    block parameters, eps, the block's _Ragged -> y [total', D] (total' = total without a stage), differentiable in xp and the parameters.
+    What the stage decided is left on the _Ragged."""
+
+    @staticmethod
+    def forward(ctx, xp, *rest):
+        params, (eps, r) = rest[:12], rest[12:]
+        if ops.get_gemm_mode() == ops.GEMM_BF16:
+            raise D2SError(_BF16_REFUSAL)
+        train = DF.wants_grad(ctx)
+        xp = xp.contiguous()
+        stage = r.K is not None
+        if train:
+            attn, attn_args = r.attn_train, ()
+        else:
+            attn, attn_args = DF._varlen_attn_forward, (r.cu, r.B, r.max_n, r.heads, r.scale, stage)
+        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, False, train, attn, attn_args, mid=r.sample if stage else None,
+                                                   mid_cls=stage)
+        if train:
+            ctx.save_for_backward(xp, *saved)
+            ctx.ragged = r
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xp, *saved = ctx.saved_tensors
+        r = ctx.ragged
+        # input slots: xp 0, then n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> 1..12
+        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd,
+                                              r.sample_bwd if r.K is not None else None)
+        return tuple(grads) + (None, None)
+
+
+def ragged_block_train(xp, params, eps, r):
+    """RaggedBlockFn on the block described by r (a _Ragged) -> y; afterwards r holds cu_new / row_src_new / plan / score / dense of a stage"""
+    return DF.run(RaggedBlockFn, xp, *params, eps, r)
+
+
+class ClsGatherFn(torch.autograd.Function):
+    """The CLS rows of a ragged packed batch: xp [total, D], cu [B+1] -> [B, D]; the backward scatters (zeros for every other row)."""
+
+    @staticmethod
+    def forward(ctx, xp, cu):
+        ctx.save_for_backward(cu)
+        ctx.total = xp.shape[0]
+        return ops.gather_rows_i32(xp.contiguous(), cu, cu.numel() - 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (cu,) = ctx.saved_tensors
+        return ops.ragged_cls_scatter(g.contiguous(), cu, ctx.total), None

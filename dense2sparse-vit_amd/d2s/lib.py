@@ -1,5 +1,6 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
-two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, and include/d2s_hip_ats.h, adaptive token sampling).
+two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling, and
+include/d2s_hip_ragged_train.h, training through a ragged packed batch).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -157,6 +158,14 @@ _SIGS_ATS = {
     "d2s_ats_select": (I, [P, P, I, P, P, I, I, I, I, I, I, P, P, P, P]),
 }
 
+# the entries of include/d2s_hip_ragged_train.h (training through a ragged packed batch), same form
+_SIGS_RAGGED_TRAIN = {
+    "d2s_attn_varlen_fwd_lse_f32": (I, [P, P, P, P, P, I, I, I, I, F]),
+    "d2s_attn_varlen_bwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, F]),
+    "d2s_ragged_repack_bwd": (I, [P, P, P, P, P, I, I]),
+    "d2s_ragged_cls_scatter": (I, [P, P, P, I, I, I]),
+}
+
 _lib = None
 
 
@@ -173,7 +182,8 @@ def load():
         raise D2SError(f"{LIB_PATH} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items()):
+    for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
+                              + list(_SIGS_RAGGED_TRAIN.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -195,6 +205,10 @@ def squeeze_symbols():
 
 def ats_symbols():
     return sorted(_SIGS_ATS)
+
+
+def ragged_train_symbols():
+    return sorted(_SIGS_RAGGED_TRAIN)
 
 
 def ptr(t):

@@ -1284,6 +1284,48 @@ def attn_varlen_fwd(qkv, cu, B, total, max_n, H, scale, want_cls=False):
     return out, cls_row
 
 
+# ---- training through a ragged packed batch (csrc/attention_f32.hip's VARLEN backward, csrc/ragged_train.hip) ----
+def attn_varlen_fwd_lse(qkv, cu, B, total, max_n, H, scale, want_cls=False):
+    """attn_varlen_fwd that keeps the log-sum-exp for attn_varlen_bwd: the same kernel, out / cls_row bit for bit that call's.
+    -> (out [total, H * 64], lse [H, total], cls_row [H, total] or None)"""
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous()
+    out = torch.empty((total, H * 64), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((H, total), dtype=torch.float32, device=qkv.device)
+    cls_row = torch.empty((H, total), dtype=torch.float32, device=qkv.device) if want_cls else None
+    lib.call("d2s_attn_varlen_fwd_lse_f32", lib.ptr(qkv), lib.ptr(cu), lib.ptr(out), lib.ptr(lse), lib.ptr(cls_row), int(B), int(total),
+             int(max_n), int(H), float(scale))
+    return out, lse, cls_row
+
+
+def attn_varlen_bwd(qkv, cu, out, dout, lse, B, total, max_n, H, scale):
+    """Backward of attn_varlen_fwd_lse (out, lse as it returned them) -> dqkv shaped like qkv, every element written once."""
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and tuple(lse.shape) == (H, total)
+    _f32(out), _f32(dout), _f32(lse)
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device)
+    delta = torch.empty((H, total), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_varlen_bwd_f32", lib.ptr(qkv), lib.ptr(cu), lib.ptr(out), lib.ptr(dout), lib.ptr(lse), lib.ptr(dqkv), lib.ptr(delta),
+             int(B), int(total), int(max_n), int(H), float(scale))
+    return dqkv
+
+
+def ragged_repack_bwd(g_new, keep, cu_old, cu_new, total_old, B):
+    """Backward of ragged_repack: g_new [total_new, D] -> g_old [total_old, D], a kept row takes the row it became, a dropped row zeros."""
+    _f32(g_new), _f32(keep)
+    D = g_new.shape[1]
+    g_old = torch.empty((total_old, D), dtype=torch.float32, device=g_new.device)
+    lib.call("d2s_ragged_repack_bwd", lib.ptr(g_new), lib.ptr(keep), lib.ptr(cu_old), lib.ptr(cu_new), lib.ptr(g_old), int(B), D)
+    return g_old
+
+
+def ragged_cls_scatter(g_cls, cu, total):
+    """Backward of gather_rows_i32(x, cu, B): g_cls [B, D] -> g [total, D] with row cu[b] = g_cls[b] and zeros elsewhere."""
+    _f32(g_cls)
+    B, D = g_cls.shape
+    g = torch.empty((total, D), dtype=torch.float32, device=g_cls.device)
+    lib.call("d2s_ragged_cls_scatter", lib.ptr(g_cls), lib.ptr(cu), lib.ptr(g), int(B), int(total), D)
+    return g
+
+
 def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
     """Ragged attention forward on the bf16 matrix cores (bf16 arithmetic mode): qkv [total, 3*H*64] fp32 or bf16 (the qkv GEMM's c16);
     always writes the bf16 copy of its output for the projection GEMM.  -> (out or None, cls_row [H, total] or None, out16)"""

@@ -26,6 +26,8 @@ are outside the path.
         --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
     python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --eval-only \
         --student-checkpoint deit_small.pth                               (adaptive token sampling: every image keeps its own count)
+    python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --ats-train \
+        --student-checkpoint deit_small.pth --teacher-checkpoint deit_small.pth --epochs 30      (fine-tune through the sampling stages)
 """
 import os
 import sys
@@ -90,8 +92,23 @@ def check_supported(args):
     elif tome_r > 0:
         bad.append(f"--tome-r {tome_r} with --method {getattr(args, 'method', 'd2s')} (tokens are merged by --method tome only)")
     ats_tokens = getattr(args, "ats_tokens", None)
+    ats_train = bool(getattr(args, "ats_train", False))
+    if ats_train:
+        if getattr(args, "method", "d2s") != "ats":
+            bad.append(f"--ats-train with --method {getattr(args, 'method', 'd2s')} (it trains the Adaptive Token Sampling baseline: --method ats)")
+        if args.eval_only:
+            bad.append("--ats-train with --eval-only (evaluation runs the inference path: drop one of the two)")
+        if getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--ats-train with --gemm-mode bf16 (training through a sampling stage is built on the fp32 data path; exact and split run)")
+        if getattr(args, "drop_path", 0.0) > 0.0:
+            bad.append(f"--ats-train with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block)")
+        if args.torch_optim:
+            bad.append("--ats-train with --torch-optim (a sampling student trains through the fused step only)")
+        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
+            bad.append(f"--ats-train with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and a "
+                       "sampling stage has none: pass 0 or leave it out)")
     if getattr(args, "method", "d2s") == "ats":
-        if not args.eval_only:
+        if not args.eval_only and not ats_train:
             bad.append("--method ats without --eval-only (adaptive token sampling is built for inference: a sampling stage has no backward)")
         for attr, flag in _NOT_WITH_ATS:
             if getattr(args, attr, None) not in (None, False):
@@ -208,6 +225,8 @@ def check_supported(args):
     if args.output_dir and args.torch_optim and not args.eval_only:
         print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
               "loads through --student-checkpoint, it cannot be resumed")
+    if ats_train:
+        args.warmup_steps = 0                # not given (refused above otherwise): the reference's default of 5 predictor-only epochs has no meaning here
     if tome_train and args.warmup_steps > 0:
         print("Attention: --tome-train trains a model without score predictors, so the predictor warm-up has no meaning "
               "(mask_predictor.py:300): --warmup-steps is set to 0")
@@ -233,7 +252,13 @@ def build_models(args):
     """mask_predictor.py:170-202 (the arch switch), with local checkpoints instead of URL downloads."""
     arch = args.arch if args.arch in _STUDENTS else "deit_small"
     if getattr(args, "method", "d2s") == "ats":
-        return build_ats(args), None             # inference only: no teacher
+        if not getattr(args, "ats_train", False):
+            return build_ats(args), None             # inference only: no teacher
+        # --ats-train: the sampling student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
+        teacher = None
+        if args.dist_weight != 0:
+            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
+        return build_ats(args, train_sample=True), teacher
     if getattr(args, "method", "d2s") == "dynamicvit":
         student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
                                                                     drop_path_rate=getattr(args, "drop_path", 0.0),
@@ -283,13 +308,14 @@ def load_trunk(args, model, method, why):
     return model.to(args.device)
 
 
-def build_ats(args):
-    """--method ats: the dense DeiT trunk with a sampling stage in every block of --pruning-locs, at most --ats-tokens tokens each."""
+def build_ats(args, **kw):
+    """--method ats: the dense DeiT trunk with a sampling stage in every block of --pruning-locs, at most --ats-tokens tokens each.
+    kw: train_sample=True under --ats-train, nothing otherwise."""
     arch = args.arch if args.arch in _ATS else "deit_small"
     toks = getattr(args, "ats_tokens", None)
     if toks is not None and len(toks) == 1:
         toks = int(toks[0])
-    model = getattr(vit_models, _ATS[arch])(ats_locs=list(args.pruning_locs), ats_tokens=toks)
+    model = getattr(vit_models, _ATS[arch])(ats_locs=list(args.pruning_locs), ats_tokens=toks, **kw)
     return load_trunk(args, model, "ats", "adaptive token sampling has no predictor")
 
 
@@ -380,7 +406,7 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
-    if args.method == "ats" or (args.method == "tome" and not args.tome_train):
+    if (args.method == "ats" and not args.ats_train) or (args.method == "tome" and not args.tome_train):
         return eval_tome(args, rank, world, distributed)
     if args.method == "tome":
         # --tome-train: the merging student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
@@ -509,6 +535,10 @@ def main(argv=None):
                 dist.barrier()
         if rank == 0 and args.method == "tome":
             print(f"--method tome --tome-r {args.tome_r} --tome-train: tokens per block {student.tokens_per_block}")
+        if rank == 0 and args.method == "ats":
+            per = [c.float() for c in student.tokens_per_stage]       # the last validation batch's
+            print(f"--method ats --pruning-locs {' '.join(str(v) for v in student.ats_locs)} --ats-train: ats tokens per stage: "
+                  f"mean {[round(float(c.mean()), 1) for c in per]} min {[int(c.min()) for c in per]} max {[int(c.max()) for c in per]}")
         if rank == 0:
             print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))

@@ -25,11 +25,13 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
     fast = isinstance(optimizer, TrainStep)
     if type(model).__name__ == "VisionTransformerToMe" and not fast:
         raise ValueError("a Token Merging student trains through d2s.engine.TrainStep only")
+    if type(model).__name__ == "VisionTransformerATS" and getattr(model, "ats_locs", []) and not fast:
+        raise ValueError("an Adaptive Token Sampling student trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer
         step.metrics = metrics
-        if getattr(step, "tome", False):
+        if getattr(step, "tome", False) or getattr(step, "ats", False):      # the logits-only students
             step.tome_loss_fn = ToMeLoss(args)
         elif baseline:
             step.dynamicvit_loss_fn = DynamicViTLoss(args)

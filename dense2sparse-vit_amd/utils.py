@@ -75,6 +75,10 @@ class SyntheticLoader:
                    torch.randint(0, self.nc, (b,), generator=g, device=self.device))
 
 
+class _Unset(int):
+    """An argparse default that can be told from the same number given on the command line (parse_args sets warmup_steps_given)."""
+
+
 def parse_args(argv=None):
     """The reference's command line (utils.py:182-317): same flag names, types and defaults, so job scripts written for the
     reference run unchanged.  With the default --data-source synthetic the data-set / augmentation flags are accepted and ignored;
@@ -98,7 +102,7 @@ def parse_args(argv=None):
     p.add_argument('--lr', type=float, default=5e-4)
     p.add_argument('--warmup-lr', type=float, default=1e-6)
     p.add_argument('--min-lr', type=float, default=1e-5)
-    p.add_argument('--warmup-steps', default=5, type=int)
+    p.add_argument('--warmup-steps', default=_Unset(5), type=int)
     p.add_argument('--early-exit', action='store_true', default=False)
     p.add_argument('--pruning-locs', nargs='+', default=[3], type=int)
     p.add_argument('--keep-ratios', nargs='+', type=float, default=[0.3])
@@ -165,10 +169,15 @@ def parse_args(argv=None):
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
                         "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "
-                        "ats: the Adaptive Token Sampling baseline (stages at --pruning-locs, --ats-tokens; no predictor; --eval-only)")
+                        "ats: the Adaptive Token Sampling baseline (stages at --pruning-locs, --ats-tokens; no predictor; --eval-only, or --ats-train to "
+                        "train through the stages)")
     p.add_argument('--ats-tokens', nargs='+', type=int, default=None, metavar='K',
                    help='with --method ats: the most tokens an image keeps at a stage, one value for every stage or one per --pruning-locs '
                         'entry (default: the number of patches); how many of them an image keeps falls out of its own attention')
+    p.add_argument('--ats-train', action='store_true', default=False,
+                   help='with --method ats: train through the sampling stages on the ragged packed batch (varlen attention backward, re-pack '
+                        'backward; the selection itself carries no gradient); the objective is --cls-weight * CE + --dist-weight * KL to the '
+                        'dense teacher (--dist-weight 0: no teacher); --gemm-mode exact or split')
     p.add_argument('--tome-train', action='store_true', default=False,
                    help='with --method tome: train through the merges (merge backward, key-weighted attention backward); the objective is '
                         '--cls-weight * CE + --dist-weight * KL to the dense teacher (--dist-weight 0: no teacher)')
@@ -198,7 +207,11 @@ def parse_args(argv=None):
     p.add_argument('--clip-grad', type=float, default=None, metavar='NORM',
                    help="clip the gradient to this global L2 norm before the update (DeiT's flag; default: no clipping); the norm never "
                         "leaves the device, its epoch mean is reported as train_grad_norm")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    # --ats-train refuses a predictor warm-up that was asked for and takes the reference's default as "none"
+    args.warmup_steps_given = not isinstance(args.warmup_steps, _Unset)
+    args.warmup_steps = int(args.warmup_steps)
+    return args
 
 
 def atomic_save(obj, path, writer=torch.save):
