@@ -299,6 +299,7 @@ def checkpoint_config(config):
     theirs.setdefault("ats_tokens", [])
     theirs.setdefault("train_sample", False)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
+    theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
     return theirs
 
 
@@ -556,6 +557,20 @@ class TrainStep:
                                    "for a ragged block")
             graph = False
         self.logits_only = self.tome or self.ats
+        # a dynamic-keep-ratio student that trains on the ragged packed batch (ragged_train=True): the ordinary
+        # route - both losses, warm-up epochs, the freeze schedule - with the packed outputs handed to the losses; the refusals are those
+        # of a ragged block
+        self.ragged_train = bool(getattr(student, "ragged_train", False))
+        if self.ragged_train != bool(getattr(args, "ragged_train", False)):
+            raise lib.D2SError(f"TrainStep: the student was built with ragged_train={self.ragged_train}, args.ragged_train is "
+                               f"{bool(getattr(args, 'ragged_train', False))}: the losses follow args, both must agree")
+        if self.ragged_train:
+            if graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with ragged_train is not supported: every threshold stage reads its row count on "
+                                   "the host (one host read per stage), which a captured step cannot; run the step eagerly (graph=False)")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with ragged_train and drop_path_rate > 0: stochastic depth is not built for a ragged block")
+            graph = False
         if not self.logits_only and teacher is None:
             raise lib.D2SError("TrainStep without a teacher: only a Token Merging student trains without one")
         if self.teacher is not None:
@@ -714,6 +729,7 @@ class TrainStep:
             "ats_locs": [int(v) for v in getattr(s, "ats_locs", [])],
             "ats_tokens": [int(v) for v in getattr(s, "ats_tokens", [])],
             "train_sample": bool(getattr(s, "train_sample", False)),
+            "ragged_train": bool(getattr(s, "ragged_train", False)),
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -851,6 +867,15 @@ class TrainStep:
             return self._baseline_losses(out_s, out_t, labels, accumulate)
         logits_t, token_t, cls_attn = out_t
         logits_s, token_s, pred_logits, kept = out_s
+        if self.ragged_train:       # the packed outputs: every stage's offsets for the mask loss, the last packed batch's for the distillation
+            s = self.student
+            mask_loss = self.mask_loss_fn(pred_logits, cls_attn, kept, self.metrics, accumulate=accumulate,
+                                          ragged=(list(s.cu_seqlens_per_stage), list(s.ragged_row_src_per_stage)))
+            backbone_loss = self.backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept, labels, self.metrics, accumulate=accumulate,
+                                                  ragged=(s.cu_seqlens, s.ragged_row_src))
+            loss = mask_loss if self.epoch < self.warmup_steps else backbone_loss + mask_loss
+            return loss, dict(mask_loss=mask_loss, backbone_loss=backbone_loss, kept=kept, logits_s=logits_s, token_s=token_s,
+                              pred_logits=pred_logits, logits_t=logits_t, token_t=token_t, cls_attn=cls_attn)
         mask_loss = self.mask_loss_fn(pred_logits, cls_attn, kept, self.metrics, accumulate=accumulate, attn_selection=self.attn_selection)
         backbone_loss = self.backbone_loss_fn(logits_s, token_s, logits_t, token_t, kept, labels, self.metrics, accumulate=accumulate)
         loss = mask_loss if self.epoch < self.warmup_steps else backbone_loss + mask_loss     # train.py:50-53

@@ -1,6 +1,7 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
-two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling, and
-include/d2s_hip_ragged_train.h, training through a ragged packed batch).
+two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
+include/d2s_hip_ragged_train.h, training through a ragged packed batch, and include/d2s_hip_ragged_threshold.h, training the dynamic keep
+ratio on it).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -166,6 +167,14 @@ _SIGS_RAGGED_TRAIN = {
     "d2s_ragged_cls_scatter": (I, [P, P, P, I, I, I]),
 }
 
+# the entries of include/d2s_hip_ragged_threshold.h (training the dynamic keep ratio on the ragged batch), same form
+_SIGS_RAGGED_THRESHOLD = {
+    "d2s_half_mean_concat_varlen_bwd": (I, [P, P, P, I, I]),
+    "d2s_ragged_mask_loss_fwd": (I, [P, P, P, P, P, I, I, I, I]),
+    "d2s_ragged_mask_loss_bwd": (I, [P, P, P, P, P, I, I, I, I, F]),
+    "d2s_ragged_teacher_rows": (I, [P, L, P, P, P, P, I, I, I, I]),
+}
+
 _lib = None
 
 
@@ -183,7 +192,7 @@ def load():
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
-                              + list(_SIGS_RAGGED_TRAIN.items())):
+                              + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -209,6 +218,10 @@ def ats_symbols():
 
 def ragged_train_symbols():
     return sorted(_SIGS_RAGGED_TRAIN)
+
+
+def ragged_threshold_symbols():
+    return sorted(_SIGS_RAGGED_THRESHOLD)
 
 
 def ptr(t):

@@ -1326,6 +1326,55 @@ def ragged_cls_scatter(g_cls, cu, total):
     return g
 
 
+# ---- training the dynamic keep ratio on the ragged batch (csrc/ragged_threshold.hip) ----
+def half_mean_concat_varlen_bwd(g, cu, B):
+    """Backward of half_mean_concat_varlen: g [total, C] -> [total, C]; first half copied, second half (1 / T) * the sum over ALL rows of
+    the image at its non-CLS rows and 0 at its CLS row."""
+    _f32(g)
+    total, C = g.shape
+    out = torch.empty((total, C), dtype=torch.float32, device=g.device)
+    lib.call("d2s_half_mean_concat_varlen_bwd", lib.ptr(g), lib.ptr(cu), lib.ptr(out), int(B), C)
+    return out
+
+
+def ragged_mask_loss_fwd(scores, target, cu, row_src, mode):
+    """scores [total] packed, target [B, N] -> loss_rows [B]: per image KL(q || softmax(scores)) (mode KL_PROB_TARGET) or the sum of
+    squared differences (mode MSE_TARGET) over its non-CLS rows, q the target gathered at row_src - 1 and renormalised."""
+    _f32(scores), _f32(target)
+    B, N = target.shape
+    assert cu.numel() == B + 1 and row_src.numel() == scores.numel()
+    loss_rows = torch.empty((B,), dtype=torch.float32, device=scores.device)
+    lib.call("d2s_ragged_mask_loss_fwd", lib.ptr(scores), lib.ptr(target), lib.ptr(cu), lib.ptr(row_src), lib.ptr(loss_rows), B,
+             scores.numel(), N, int(mode))
+    return loss_rows
+
+
+def ragged_mask_loss_bwd(scores, target, cu, row_src, mode, scale=1.0):
+    """-> dscores [total] = scale * d loss_rows / d scores, exactly 0 at the CLS rows"""
+    _f32(scores), _f32(target)
+    B, N = target.shape
+    assert cu.numel() == B + 1 and row_src.numel() == scores.numel()
+    dscores = torch.empty((scores.numel(),), dtype=torch.float32, device=scores.device)
+    lib.call("d2s_ragged_mask_loss_bwd", lib.ptr(scores), lib.ptr(target), lib.ptr(cu), lib.ptr(row_src), lib.ptr(dscores), B,
+             scores.numel(), N, int(mode), float(scale))
+    return dscores
+
+
+def ragged_teacher_rows(token_t, cu, row_src):
+    """token_t [B, N, D] (dense rows; the image stride may be larger, as in the token view of a [B, N + 1, D] tensor), row_src [total]
+    -> (out [total, D]: the teacher token of every packed row, zeros at the CLS rows; w [total]: 1 / (total - B), 0 at the CLS rows)"""
+    assert token_t.dtype == torch.float32 and token_t.dim() == 3
+    if token_t.stride(2) != 1 or token_t.stride(1) != token_t.shape[2]:
+        token_t = token_t.contiguous()
+    B, N, D = token_t.shape
+    total = row_src.numel()
+    out = torch.empty((total, D), dtype=torch.float32, device=token_t.device)
+    w = torch.empty((total,), dtype=torch.float32, device=token_t.device)
+    lib.call("d2s_ragged_teacher_rows", lib.ptr(token_t), int(token_t.stride(0)) if B > 1 else N * D, lib.ptr(cu), lib.ptr(row_src),
+             lib.ptr(out), lib.ptr(w), B, total, N, D)
+    return out, w
+
+
 def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
     """Ragged attention forward on the bf16 matrix cores (bf16 arithmetic mode): qkv [total, 3*H*64] fp32 or bf16 (the qkv GEMM's c16);
     always writes the bf16 copy of its output for the projection GEMM.  -> (out or None, cls_row [H, total] or None, out16)"""

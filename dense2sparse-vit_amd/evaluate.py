@@ -39,8 +39,11 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
             unpruned_preds = torch.argmax(unpruned_logits, dim=1)
             running_unpruned_acc += float((unpruned_preds == val_labels).sum()) / val_labels.shape[0]
             logits, cls_attns, pred_logits, kept_token_idx = outputs
+            # --ragged-train: validation reports the packed stages' mask-loss terms too, the quantity training reports
+            extra = ({"ragged": (model.cu_seqlens_per_stage, model.ragged_row_src_per_stage)}
+                     if thr and getattr(args, "ragged_train", False) else {})
             mask_loss_fn(pred_logits, cls_attn_weights, kept_token_idx, metrics,        # :44
-                         attn_selection=bool(getattr(model, "attn_selection", False)))
+                         attn_selection=bool(getattr(model, "attn_selection", False)), **extra)
             loss = DF.RowLossFn.apply(logits, ops.CE_LABEL, None, None, val_labels.contiguous(), logits.shape[0])   # :46
             preds = torch.argmax(logits, dim=1)
             running_loss += float(loss)

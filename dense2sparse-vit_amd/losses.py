@@ -16,6 +16,12 @@ Differences that are deliberate and documented:
     dense cumulative [B, N] masks against the teacher's threshold mask as above; the KL / MSE term is computed for a stage only when its
     pred_logits is the dense [B, N] tensor.  A packed stage contributes NO loss term: neither the reference nor the training-mode fix
     defines one (val_mask_loss of such a student is the first stage's term).
+  * training the dynamic keep ratio on the ragged batch (args.ragged_train; the build's own definition): a packed
+    stage s >= 1 DOES carry a term, in training and at validation alike.  For image b over its rows of the batch the stage scored, with
+    original patch ids j_r = row_src[r] - 1: q_r = target[b, j_r] / sum_r target[b, j_r] - the gather_renorm(normalize=True) recursion
+    of the fixed-ratio path - and the term is (1 / B) sum_b KL(q_b || softmax(pred_logits_b)) for kl_div, 100 * sum (pred_logit_r -
+    q_r)^2 / (total_{s-1} - B) for mse; an image without a surviving token contributes 0.  The token distillation is the mean over the
+    non-CLS rows of the last packed batch of KL(softmax(token_t[b, j_r]) || softmax(token_s[r])).  Without the flag nothing changes.
 """
 import torch
 
@@ -33,18 +39,32 @@ class MaskLoss(torch.nn.Module):
             raise NotImplementedError("mask_loss_type 'kl_div' (losses.py:75-96) and 'mse' (:61-73) are on the accelerated path; the "
                                       "reference's 'bce' branch is broken as written (:57-58)")
         self.patch_score_threshold = getattr(args, "patch_score_threshold", None)
+        self.ragged_train = bool(getattr(args, "ragged_train", False))
         self.count = 1
         self.running_loss = 0
         self.runnings_accs = [0 for _ in self.keep_ratios]
 
-    def _forward_threshold(self, pred_logits, target, keep_masks, mask_accs):
-        """Dynamic keep ratio: every stage scores all N tokens (nothing was gathered), see the module docstring."""
+    def _packed_stage_term(self, scores, target, cu, row_src):
+        """args.ragged_train: the term of a stage that scored the packed batch (cu, row_src), see the module docstring"""
+        from d2s.functional_ragged import RaggedMaskLossFn
+        B = target.shape[0]
+        if self.loss_type == "mse":
+            rows = scores.numel() - B
+            return RaggedMaskLossFn.apply(scores, target, cu, row_src, ops.MSE_TARGET, 100.0 / rows if rows > 0 else 0.0)
+        return RaggedMaskLossFn.apply(scores, target, cu, row_src, ops.KL_PROB_TARGET, 1.0 / B)
+
+    def _forward_threshold(self, pred_logits, target, keep_masks, mask_accs, ragged=None):
+        """Dynamic keep ratio: every stage scores all N tokens (nothing was gathered), see the module docstring.
+        ragged (args.ragged_train only): ([cu_seqlens per stage], [row_src per stage]) of the forward that produced pred_logits."""
         B, T = target.shape
+        packed_terms = self.ragged_train and ragged is not None
         mask_loss = 0
         with torch.no_grad():
             gt_mask, _ = ops.select_threshold(target, float(self.patch_score_threshold))
         for i in range(len(keep_masks)):
             dense = pred_logits[i].dim() == 2       # a packed stage of the ragged cascade hands over [total] scores: no loss term is defined
+            if not dense and packed_terms:          # stage i scored the batch stage i - 1 packed
+                mask_loss = mask_loss + self._packed_stage_term(pred_logits[i], target, ragged[0][i - 1], ragged[1][i - 1])
             if self.loss_type == "mse":
                 if dense:
                     mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.MSE_TARGET, target, None, None, B * T / 100.0)
@@ -55,7 +75,7 @@ class MaskLoss(torch.nn.Module):
                 mask_loss = mask_loss + DF.RowLossFn.apply(pred_logits[i], ops.KL_PROB_TARGET, target, None, None, B)
         return mask_loss
 
-    def forward(self, pred_logits, cls_attn_weights, kept_token_idx, metrics, accumulate=True, attn_selection=False):
+    def forward(self, pred_logits, cls_attn_weights, kept_token_idx, metrics, accumulate=True, attn_selection=False, ragged=None):
         """accumulate=False: only the loss of this batch is computed (its running mean / accuracies are NOT advanced); the caller hands
         `self.last` to accumulate() later - the split a captured (hipGraph) step needs: the kernels replay, the host-side running
         statistics of losses.py:105-119 are advanced once per replay (d2s.engine.TrainStep).
@@ -67,7 +87,7 @@ class MaskLoss(torch.nn.Module):
         mask_loss = torch.zeros((), dtype=torch.float32, device=target.device) if attn_selection else 0
         mask_accs = [0 for _ in self.keep_ratios]
         if self.patch_score_threshold is not None:
-            mask_loss = self._forward_threshold(pred_logits, target, kept_token_idx, mask_accs)
+            mask_loss = self._forward_threshold(pred_logits, target, kept_token_idx, mask_accs, ragged)
             kept_token_idx = []
         for i in range(len(kept_token_idx)):
             if i > 0:
@@ -117,6 +137,7 @@ class BackboneLoss(torch.nn.Module):
         super().__init__()
         self.soft_targets = getattr(args, "mixup", 0.) > 0.      # losses.py:170-174: SoftTargetCrossEntropy under mixup, else hard labels
         self.patch_score_threshold = getattr(args, "patch_score_threshold", None)
+        self.ragged_train = bool(getattr(args, "ragged_train", False))
         self.count = 1
         self.running_loss = 0
         self.running_cls_loss = 0
@@ -124,8 +145,9 @@ class BackboneLoss(torch.nn.Module):
         self.running_token_dist_loss = 0
         self.runnings_acc = 0
 
-    def forward(self, logits_s, token_s, logits_t, token_t, kept_token_idx, train_labels, metrics, accumulate=True):
-        """accumulate: see MaskLoss.forward."""
+    def forward(self, logits_s, token_s, logits_t, token_t, kept_token_idx, train_labels, metrics, accumulate=True, ragged=None):
+        """accumulate: see MaskLoss.forward.  ragged (args.ragged_train only): (cu_seqlens, row_src) of the last packed batch, token_s then
+        being its normed rows [total, D], CLS rows included."""
         B = logits_s.shape[0]
         if self.soft_targets:      # train_labels are [B, classes] probabilities produced by the caller's mixup_fn (train.py:29-30)
             cls_loss = DF.RowLossFn.apply(logits_s, ops.SOFT_CE, train_labels.float().contiguous(), None, None, B)
@@ -133,7 +155,12 @@ class BackboneLoss(torch.nn.Module):
             cls_loss = DF.RowLossFn.apply(logits_s, ops.CE_LABEL, None, None, train_labels.contiguous(), B)      # :196
         cls_kl_loss = DF.RowLossFn.apply(logits_s, ops.KL_LOGIT_TARGET, logits_t.detach(), None, None, B)       # :198-203
         rows = token_s.shape[0] * token_s.shape[1]
-        if self.patch_score_threshold is not None:
+        if self.ragged_train and ragged is not None and token_s.dim() == 2:
+            # every packed row against the teacher's token at its original position, mean over the non-CLS rows (weights 1 / (total - B),
+            # 0 at the CLS rows); for one stage: the mean over the rows the last mask keeps, as in the branch below
+            t_rows, w = ops.ragged_teacher_rows(token_t.detach(), ragged[0], ragged[1])
+            token_kl_loss = DF.RowLossFn.apply(token_s, ops.KL_LOGIT_TARGET, t_rows, None, None, 1.0, w)
+        elif self.patch_score_threshold is not None:
             # the intent of losses.py:216-225: distil only the tokens the last stage keeps; student and teacher both still hold all N
             # tokens, so the pairing is positional and 'batchmean' becomes the mean over the kept rows (weights = mask / count)
             w = ops.mask_row_weights(kept_token_idx[-1].detach().contiguous())

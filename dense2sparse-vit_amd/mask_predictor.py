@@ -20,6 +20,8 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --squeeze-dropped     (dropped tokens go into their nearest kept token)
     python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
         --ragged-cascade                                                   (dynamic keep ratio, ragged inference through every stage)
+    python dense2sparse-vit_amd/mask_predictor.py ... --topk-selection --patch-score-threshold 0.4 --pruning-locs 3 6 9 --keep-ratios 0.7 0.5 0.3 \
+        --ragged-cascade --ragged-train                                    (... and training on the ragged batch as well)
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --student-checkpoint deit_small.pth
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --tome-bf16 --student-checkpoint deit_small.pth
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --student-checkpoint deit_small.pth \
@@ -121,6 +123,20 @@ def check_supported(args):
             bad.append(f"--ats-tokens {' '.join(str(v) for v in ats_tokens)} (at least 1 token per stage)")
     elif ats_tokens is not None:
         bad.append(f"--ats-tokens with --method {getattr(args, 'method', 'd2s')} (tokens are sampled by --method ats only)")
+    if bool(getattr(args, "ragged_train", False)):
+        if args.patch_score_threshold is None:
+            bad.append("--ragged-train without --patch-score-threshold (it trains the dynamic keep ratio on the ragged packed batch; the "
+                       "fixed-ratio path already trains on the kept tokens alone)")
+        if getattr(args, "method", "d2s") != "d2s":
+            bad.append(f"--ragged-train with --method {args.method} (it trains the dense-to-sparse student's dynamic keep ratio: --method d2s)")
+        if getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--ragged-train with --gemm-mode bf16 (training through a ragged block is built on the fp32 data path; exact and split run)")
+        if getattr(args, "drop_path", 0.0) > 0.0:
+            bad.append(f"--ragged-train with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block)")
+        if args.torch_optim:
+            bad.append("--ragged-train with --torch-optim (the packed outputs go through the fused step only)")
+        if args.eval_only:
+            bad.append("--ragged-train with --eval-only (evaluation runs the inference cascade either way: drop one of the two)")
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
@@ -133,7 +149,12 @@ def check_supported(args):
         elif len(args.pruning_locs) > 1:
             print("Attention: --ragged-cascade: at inference every threshold stage after the first scores and selects, per image, among the "
                   "tokens that survived the stages before it and packs the batch again - this build's definition, the reference's second "
-                  "stage cannot run (dynamic_vit.py:945-946; DESIGN.md section 10); a packed stage adds no mask-loss term at validation")
+                  "stage cannot run (dynamic_vit.py:945-946; DESIGN.md section 10); a packed stage adds no mask-loss term at validation"
+                  + (" (with --ragged-train it does)" if getattr(args, "ragged_train", False) else ""))
+        if getattr(args, "ragged_train", False):
+            print("Attention: --ragged-train: training follows the cascade definition too - the training forward packs every stage's "
+                  "survivors and runs the later blocks on them alone (selection without gradient), a later stage scores the survivors only "
+                  "and adds its own mask-loss term, in training and at validation (this build's definition; DESIGN.md section 10.2)")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:
@@ -276,7 +297,8 @@ def build_models(args):
                                                    fuse_dropped=getattr(args, "fuse_dropped", False),
                                                    squeeze_dropped=getattr(args, "squeeze_dropped", False),
                                                    attn_selection=getattr(args, "attn_selection", False),
-                                                   checkpoint_path=args.student_checkpoint)
+                                                   checkpoint_path=args.student_checkpoint,
+                                                   **({"ragged_train": True} if getattr(args, "ragged_train", False) else {}))
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
 

@@ -27,6 +27,8 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         raise ValueError("a Token Merging student trains through d2s.engine.TrainStep only")
     if type(model).__name__ == "VisionTransformerATS" and getattr(model, "ats_locs", []) and not fast:
         raise ValueError("an Adaptive Token Sampling student trains through d2s.engine.TrainStep only")
+    if getattr(model, "ragged_train", False) and not fast:
+        raise ValueError("a student that trains on the ragged packed batch (ragged_train=True) trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer

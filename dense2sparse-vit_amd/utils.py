@@ -201,6 +201,11 @@ def parse_args(argv=None):
                    help='with --patch-score-threshold and several --pruning-locs: at inference every threshold stage after the first scores '
                         'and selects, per image, among the tokens that survived, and packs the batch again (this build\'s definition: the '
                         'reference\'s second stage cannot run)')
+    p.add_argument('--ragged-train', action='store_true', default=False,
+                   help='with --patch-score-threshold: train on the ragged packed batch - the training forward runs the inference cascade, '
+                        'differentiable (the survivors of every stage are packed and the later blocks run on them alone; the selection '
+                        'carries no gradient), and a packed stage adds its own mask-loss term; several --pruning-locs still need '
+                        '--ragged-cascade; --gemm-mode exact or split (this build\'s definition)')
     p.add_argument('--accum-steps', type=int, default=1, metavar='N',
                    help='one optimiser step per N batches (gradient = mean over the N; effective batch = N x --batch-size x ranks), '
                         'accumulated inside the fused arena step')

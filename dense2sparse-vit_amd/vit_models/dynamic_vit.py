@@ -78,6 +78,9 @@ SQUEEZE_DROPPED_FUSE_ERROR = ("squeeze_dropped cannot be combined with fuse_drop
                               "token or squeezed into its nearest kept token, not both")
 SQUEEZE_DROPPED_DIFF_TOPK_ERROR = ("squeeze_dropped cannot be combined with diff_topk: the perturbed top-k soft gather mixes every token into "
                                    "every kept row and has no dropped set")
+RAGGED_TRAIN_THRESHOLD_ERROR = ("ragged_train trains the dynamic keep ratio on the ragged packed batch: it needs patch_score_threshold (the "
+                                "fixed-ratio path already trains on the kept tokens alone)")
+RAGGED_TRAIN_DROP_PATH_ERROR = "ragged_train with drop_path_rate > 0: stochastic depth is not built for a ragged block"
 SQUEEZE_DROPPED_THRESHOLD_ERROR = ("squeeze_dropped applies to the fixed-ratio path only: with patch_score_threshold no token is removed, there "
                                    "is nothing to squeeze")
 SQUEEZE_DROPPED_TOPK_SELECTION_ERROR = ("squeeze_dropped needs topk_selection=True: the kept and dropped sets are those of the hard top-k of the "
@@ -470,8 +473,12 @@ class VisionTransformerDiffPruning(_ViTBase):
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
                  predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, squeeze_dropped=False,
-                 init_n=14 * 14, diff_topk=False, topk_num_samples=500):
+                 ragged_train=False, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
         super().__init__()
+        if ragged_train and patch_score_threshold is None:
+            raise ValueError(RAGGED_TRAIN_THRESHOLD_ERROR)
+        if ragged_train and float(drop_path_rate) > 0.0:
+            raise ValueError(RAGGED_TRAIN_DROP_PATH_ERROR)
         if squeeze_dropped and fuse_dropped:
             raise ValueError(SQUEEZE_DROPPED_FUSE_ERROR)
         if squeeze_dropped and diff_topk:
@@ -554,6 +561,9 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.squeeze_dropped = bool(squeeze_dropped)
         self.squeeze_plans = []
         self.squeeze_plan_override = None
+        # dynamic keep ratio only: a training forward runs the inference cascade, differentiable, on the ragged packed batch instead of
+        # masking keys over all N tokens; eval() is untouched
+        self.ragged_train = bool(ragged_train)
         self.unpruned = False
         self.distill = distill
         self.pruning_loc, self.token_ratio = pruning_loc, token_ratio
@@ -674,6 +684,8 @@ class VisionTransformerDiffPruning(_ViTBase):
         policy, exactly as the reference does.  A later stage REPLACES the mask (the reference does not intersect them).
         Returns (logits, features [B,N,D], [pred_logits per stage], [keep mask [B,N] per stage]) - lists, where the reference returns the
         last stage's tensors only (:1011): the per-stage mask loss needs every stage.
+        With ragged_train=True the training forward is the inference cascade below instead, differentiable
+        (_forward_threshold_ragged_train).
 
         Inference (:935-949, with the reference's undefined `score` read as `pred_score`): the kept tokens of every image are packed
         into one ragged batch [total, D] (`cu_seqlens` [B+1] gives each image's rows) and the remaining blocks run on it - LayerNorm
@@ -699,6 +711,8 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.cu_seqlens = self.ragged_row_src = None
         self.cu_seqlens_per_stage, self.ragged_row_src_per_stage = [], []
         p_count = 0
+        if self.training and self.ragged_train:
+            return self._forward_threshold_ragged_train(x, thr)
         if self.training:
             policy = torch.ones((B, n), dtype=torch.float32, device=x.device)       # :830,839
             for i, blk in enumerate(self.blocks):
@@ -761,6 +775,68 @@ class VisionTransformerDiffPruning(_ViTBase):
         logits = ops.linear_fwd(cls_rows, self.head.weight, self.head.bias)
         self.ragged_features = xn
         return logits, self.cls_attns, self.pred_logits, self.kept_token_indices
+
+    def _forward_threshold_ragged_train(self, x, thr):
+        """ragged_train=True, training mode (the build's own definition; PARITY UNPINNED): the inference cascade
+        above made differentiable.  x [B, n, D] is the embedded batch.  Plain dense blocks up to the first stage; the first stage scores
+        all N tokens with the dense predictor exactly as the policy-mode training forward does and packs the survivors (RaggedPackFn); its
+        block and every later block is a RaggedBlockFn without a stage of its own; a later stage scores the packed rows
+        (RaggedPredictorFn), selects per image among the survivors and packs again (RaggedRepackFn); the final LayerNorm runs over the
+        packed rows, the head on the gathered CLS rows.  Selections carry no gradient; ONE host read of the new row total per stage.
+        Returns (logits, the normed packed batch [total, D] with its CLS rows, [pred_logits: dense [B, N], then packed [total_{s-1}]],
+        [cumulative dense [B, N] keep mask per stage]); cu_seqlens / ragged_row_src and the _per_stage lists are set as at inference."""
+        from d2s import functional_ats as AF
+        from d2s import functional_ragged as RF
+        from d2s import ops
+        from d2s.lib import D2SError
+        if ops.get_gemm_mode() == ops.GEMM_BF16:
+            raise D2SError(AF._BF16_REFUSAL)
+        if len(self.pruning_loc) > 1 and any(p.use_bn for p in self.score_predictor):
+            raise NotImplementedError("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
+                                      "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
+                                      "predictor; one stage works with either")
+        B, n, D = x.shape
+        N = n - 1
+        p_count = 0
+        cu = row_src = None
+        max_n = n
+        for i, blk in enumerate(self.blocks):
+            if self.grad_ready_hook is not None and x.requires_grad:
+                x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
+            if i in self.pruning_loc:
+                if cu is None:
+                    pred_logits, pred_score = _scores(self.score_predictor[p_count], x)
+                    policy, counts = ops.select_threshold(pred_score.detach().contiguous(), thr, lead=1)
+                    mask = policy[:, 1:]
+                    cu = ops.ragged_offsets(counts, extra=1)
+                    total = int(cu[-1])      # the one device sync of a stage: the packed row count sizes every later launch
+                    x, row_src = RF.RaggedPackFn.apply(x, policy, cu, total)
+                else:
+                    pred_logits = RF.ragged_predictor_train(self.score_predictor[p_count], x, cu, B)          # packed [total]
+                    keep, counts, mask, _ = ops.ragged_select_threshold(pred_logits.detach(), cu, row_src, thr, N, B)
+                    cu_new = ops.ragged_offsets(counts, extra=1)
+                    total = int(cu_new[-1])
+                    x, row_src = RF.RaggedRepackFn.apply(x, keep, cu, cu_new, row_src, total, B)
+                    cu = cu_new
+                self.keep_ratios = counts.float() / N
+                self.pred_logits.append(pred_logits)
+                self.kept_token_indices.append(mask)
+                self.dropped_token_indices.append(1.0 - mask)
+                self.cu_seqlens, self.ragged_row_src = cu, row_src
+                self.cu_seqlens_per_stage.append(cu)
+                self.ragged_row_src_per_stage.append(row_src)
+                p_count += 1
+            if cu is None:
+                x = blk(x)
+            else:
+                a = blk.attn
+                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(cu, B, max_n, a.num_heads, a.scale))
+        if cu is None:       # no stage at all: the dense head
+            logits, features = self._head(x)
+            return logits, features, self.pred_logits, self.kept_token_indices
+        logits, xn = RF.ragged_head(x, cu, self.norm, self.head)
+        self.ragged_features = xn.detach()
+        return logits, xn, self.pred_logits, self.kept_token_indices
 
     def forward_cls_attn(self, x):
         """:1018-1033."""
