@@ -10,10 +10,16 @@ block_bwd: one C-ABI call for the same launches on the fp32 data path).  Which a
 attn_backward, for BlockFn and AttnCoreFn alike; xarg, cls_or_empty and layernorm_backward are the small shared pieces (the latter also
 serves the predictor and Tokens-to-Token Functions of the neighbouring modules).
 
+The LayerNorm score predictor is written once in the same way: predictor_forward_sequence / predictor_backward_sequence, parameterised by
+where the rows are (PredictorRows: dense or packed), the activation (ReLU: large, exact-erf GELU: small), the bf16 data path and whether
+anything is kept for a backward.  Callers: PredictorFn here (dense; both predictors) and, for a ragged packed batch, functional_ragged's
+ragged_predictor_forward and RaggedPredictorFn.  The BatchNorm predictor (functional_bn) and the DynamicViT baseline's
+(functional_dynamicvit) are sequences of their own.
+
 Reference lines (relative to /root/reference):
   EmbedFn      vit_models/dynamic_vit.py:300-306, 820-823
   BlockFn      vit_models/dynamic_vit.py:263-269 (Block), :216-236 (Attention), :169-175 (Mlp)
-  PredictorFn  vit_models/dynamic_vit.py:536-551 with layers :491-531
+  PredictorFn  vit_models/dynamic_vit.py:536-551 with layers :491-531 (large) and :409-426 (small, --small-predictor)
   GatherFn     vit_models/dynamic_vit.py:907-912
   HeadFn       vit_models/dynamic_vit.py:993-1006
 """
@@ -430,100 +436,156 @@ class BlockFn(torch.autograd.Function):
         return tuple(grads) + (None, None, None, None) + ((dpolicy,) + (None,) * (ctx.nextra - 1) if ctx.nextra else ())
 
 
+class PredictorRows:
+    """Where the score predictor's rows are.  Dense (cu None): x [B, n, D], the rows x[:, 1:] read in place through skip_cls_map, the input
+    gradient a [B, n, D] tensor whose CLS rows are zero.  Packed: x [total, D] of a ragged batch with the offsets cu [B+1]; the B CLS rows
+    are computed and ignored (B extra rows instead of a strip copy), the token mean runs over each image's non-CLS rows."""
+
+    def __init__(self, x, B, cu=None):
+        self.B, self.cu, self.shape = int(B), cu, tuple(x.shape)
+        if cu is None:
+            self.T = x.shape[1] - 1
+            self.count, self.in_map = self.B * self.T, ops.skip_cls_map(x.shape[1], x.shape[2])
+        else:
+            self.count, self.in_map = x.shape[0], ops.contiguous_map(*x.shape)
+
+    def mean_concat(self, a):
+        """the split / token mean / concat behind the first activation (:540-544)"""
+        if self.cu is None:
+            return ops.half_mean_concat(a, self.B, self.T, a.shape[1])
+        return ops.half_mean_concat_varlen(a, self.cu, self.B)
+
+    def mean_concat_backward(self, d, act, z):
+        """d: the gradient of mean_concat's output -> the gradient of the first Linear's pre-activation; z: what the first activation's
+        backward reads (the ReLU's output, the GELU's pre-activation).  Only the dense kernel can fold the ReLU mask in."""
+        if self.cu is not None:
+            return ops.act_grad(ops.half_mean_concat_varlen_bwd(d, self.cu, self.B), z, act)
+        if act == "relu":
+            return ops.half_mean_concat(d, self.B, self.T, d.shape[1], relu_mask_src=z)
+        return ops.act_grad(ops.half_mean_concat(d, self.B, self.T, d.shape[1]), z, act)
+
+    def input_grad_buffer(self, device):
+        return (torch.zeros if self.cu is None else torch.empty)(self.shape, dtype=torch.float32, device=device)
+
+
+def predictor_bf16_data_path(x, act):
+    """bf16 arithmetic mode with the bf16 data path on, for the large predictor only: the small one keeps fp32 activations"""
+    return act == "relu" and ops.bf16_io() and x.is_cuda and x.shape[-1] % 32 == 0
+
+
+def _predictor_exact_from(nl, act):
+    """the first layer of the large predictor's tail (its last two Linear layers, D/2 -> D/4 -> 1: 0.3 % of its FLOPs), which like the
+    softmax and the selection behind it always runs in exact fp32 - also in the bf16 arithmetic mode (kept-id stability).  The
+    small predictor has no such tail."""
+    return nl - 2 if act == "relu" else nl
+
+
+def predictor_forward_sequence(x, rows, params, act, io, train):
+    """THE launch sequence of the LayerNorm score predictor (PredictorLG :409-426 small, :491-531 large, forward :536-551): LN -> Linear ->
+    activation on every row, split / token mean / concat, then a stack of LN -> Linear -> activation whose last Linear is 1 wide and bare.
+    Callers: PredictorFn (dense rows) and functional_ragged's ragged_predictor_forward and RaggedPredictorFn (packed rows).
+    rows: a PredictorRows; params: (ln_w, ln_b, fc_w, fc_b) of the input layer, then of each layer behind the concat.
+    act: "relu" - the large predictor, five layers behind the concat - or "gelu" - the small one, three layers, exact-erf GELU.
+    io: bf16 data path (predictor_bf16_data_path) - the LayerNorm in front of a bf16-mode Linear writes only the bf16 form that GEMM
+    multiplies, as in BlockFn; the weight gradients read it too.  The exact-fp32 tail keeps fp32 activations.
+    train: keep the LayerNorm statistics, every layer input and what the activations' backward reads; otherwise nothing is kept.
+    -> (scores [rows.count, 1], what predictor_backward_sequence unpacks, 5 entries per layer (None unless train))"""
+    M, eps = rows.count, 1e-5
+    nl = len(params) // 4
+    act_epi = ops.EPI_BIAS_RELU if act == "relu" else ops.EPI_BIAS_GELU
+    saved = []
+    cur = x
+    for j in range(nl):
+        lw, lb, fw, fb = params[4 * j: 4 * j + 4]
+        width = fw.shape[1]
+        cmap = rows.in_map if j == 0 else ops.contiguous_map(M, width)
+        last = j == nl - 1
+        exact = j >= _predictor_exact_from(nl, act)
+        z = None
+        if io and not exact:
+            _, mean, rstd, ln = ops.layernorm_fwd_bf16(cur, cmap, lw, lb, M, width, eps, stats=train, want_f32=False)
+            nxt = ops.linear_fwd(None, fw, fb, epi=act_epi, a16=ln)
+        else:
+            ln, mean, rstd = ops.layernorm_fwd(cur, cmap, lw, lb, M, width, eps, stats=train)
+            if train and act == "gelu" and not last:      # the GELU's backward reads the pre-activation: written only when training
+                z = torch.empty((M, fw.shape[0]), dtype=torch.float32, device=x.device)
+            with ops.gemm_mode(ops.GEMM_EXACT if exact else ops.get_gemm_mode()):
+                nxt = ops.linear_fwd(ln, fw, fb, epi=ops.EPI_BIAS if last else act_epi, aux_out=z)
+        if train:
+            # a ReLU's backward reads its output: the next layer keeps that as its input, only the one in front of the concat is kept here
+            saved += [cur, ln, mean, rstd, nxt if (act == "relu" and j == 0) else z]
+        cur = rows.mean_concat(nxt) if j == 0 else nxt
+    return cur, (saved if train else None)
+
+
+def predictor_backward_sequence(gscores, rows, saved, params, act, wants):
+    """The backward of predictor_forward_sequence.  gscores: the gradient of the scores; saved: what the forward sequence returned for
+    this; wants: which of (x, *params) take a gradient.  -> the gradients in wants' order, None where not wanted"""
+    M = rows.count
+    nl = len(params) // 4
+    dev = gscores.device
+    relu = act == "relu"
+    grads = [None] * (1 + len(params))
+    io = ops.bf16_io() and gscores.is_cuda
+    d = gscores.contiguous().view(M, 1)
+    d16 = None                      # bf16 copy of d, written by the LayerNorm backward that produced it, when the next GEMMs run in bf16
+    for j in reversed(range(nl)):
+        cur, ln, mean, rstd, _ = saved[5 * j: 5 * j + 5]
+        lw, lb, fw, fb = params[4 * j: 4 * j + 4]
+        p = 1 + 4 * j                   # lw's slot in wants / grads
+        width = fw.shape[1]
+        lnx, ln16 = xarg(ln)            # bf16 on the bf16 data path
+        # d is the gradient w.r.t. the pre-activation of layer j's Linear (the activation's backward was applied upstream)
+        with ops.gemm_mode(ops.GEMM_EXACT if j >= _predictor_exact_from(nl, act) else ops.get_gemm_mode()):      # as this layer's forward
+            grads[p + 2], grads[p + 3] = ops.linear_param_grads(d, lnx, fw, fb, wants[p + 2], wants[p + 3], x16=ln16)
+            if j == 0 and not (wants[0] or wants[p] or wants[p + 1]):
+                break
+            dln = ops.linear_dgrad(d, fw, a16=d16 if ln16 is not None else None)
+        # the layer below multiplies d in bf16 if it is a bf16-mode layer: its saved input is bf16 then (no bf16 form crosses the concat)
+        d16 = ops.bf16_buffer(M, width, dev) if (io and j >= 2 and saved[5 * (j - 1) + 1].dtype == torch.bfloat16) else None
+        dx = rows.input_grad_buffer(dev) if j == 0 else torch.empty((M, width), dtype=torch.float32, device=dev)
+        # cur is the activation of layer j - 1 for j >= 2: the ReLU's backward folds into the LayerNorm backward, the GELU's is one
+        # elementwise kernel on the saved pre-activation; for j == 1 cur is the split / mean / concat output
+        d, grads[p], grads[p + 1] = layernorm_backward(cur, rows.in_map if j == 0 else ops.contiguous_map(M, width), dln, lw, lb, mean, rstd,
+                                                       dx, M, width, wants[p], wants[p + 1], relu_mask=(relu and j >= 2), dx16=d16)
+        if j >= 2 and not relu:
+            d = ops.act_grad(d, saved[5 * (j - 1) + 4], "gelu")
+        elif j == 1:
+            d = rows.mean_concat_backward(d, act, saved[4])
+        elif j == 0 and wants[0]:
+            grads[0] = d
+    return grads
+
+
 @mode_recorded
 class PredictorFn(torch.autograd.Function):
-    """Large LayerNorm predictor (PredictorLG, topk_selection=True) on x[:, 1:] of a [B, n, D] tensor.
+    """LayerNorm predictor (PredictorLG, topk_selection=True) on x[:, 1:] of a [B, n, D] tensor: the large one (ReLU), or - a trailing
+    "gelu" behind the parameters - the small one (--small-predictor, exact-erf GELU).
     Returns (scores [B, n-1] differentiable, keep_probs [B, n-1] non-differentiable)."""
 
     @staticmethod
     def forward(ctx, x, *params):
-        # params: in_ln_w, in_ln_b, in_fc_w, in_fc_b, then 5 x (ln_w, ln_b, fc_w, fc_b)
+        # params: in_ln_w, in_ln_b, in_fc_w, in_fc_b, then 5 (small: 3) x (ln_w, ln_b, fc_w, fc_b)
+        ctx.act = params[-1] if isinstance(params[-1], str) else "relu"
+        params = params[:len(params) // 4 * 4]
         B, n, D = x.shape
-        T = n - 1
-        M = B * T
         x = x.contiguous()
-        eps = 1e-5
         train = wants_grad(ctx)
-        # bf16 arithmetic mode: as in BlockFn, each LayerNorm in front of a bf16-mode Linear also (training: only) writes the bf16 form
-        # that GEMM multiplies; the weight gradients read it too.  The exact-fp32 tail keeps fp32 activations.
-        io = ops.bf16_io() and x.is_cuda and D % 32 == 0
-        if io:
-            h0, mean0, rstd0, h0h = ops.layernorm_fwd_bf16(x, ops.skip_cls_map(n, D), params[0], params[1], M, D, eps, stats=train, want_f32=False)
-            a1 = ops.linear_fwd(None, params[2], params[3], epi=ops.EPI_BIAS_RELU, a16=h0h)
-            h0 = h0h
-        else:
-            h0, mean0, rstd0 = ops.layernorm_fwd(x, ops.skip_cls_map(n, D), params[0], params[1], M, D, eps, stats=train)
-            a1 = ops.linear_fwd(h0, params[2], params[3], epi=ops.EPI_BIAS_RELU)
-        C = a1.shape[1]
-        cur = ops.half_mean_concat(a1, B, T, C)
-        saved = [x, h0, mean0, rstd0, a1]
-        nl = (len(params) - 4) // 4
-        for j in range(nl):
-            lw, lb, fw, fb = params[4 + 4 * j: 8 + 4 * j]
-            width = cur.shape[1]
-            last = j == nl - 1
-            exact_tail = j >= nl - 2
-            # the predictor's tail (its last two Linear layers, D/2 -> D/4 -> 1: 0.3 % of its FLOPs), like the softmax and the selection
-            # behind it, always runs in exact fp32 - also in the bf16 arithmetic mode (SURVEY 8c: kept-id stability)
-            if io and not exact_tail and width % 32 == 0:
-                _, mean, rstd, ln = ops.layernorm_fwd_bf16(cur, ops.contiguous_map(M, width), lw, lb, M, width, eps, stats=train, want_f32=False)
-                nxt = ops.linear_fwd(None, fw, fb, epi=ops.EPI_BIAS_RELU, a16=ln)
-            else:
-                ln, mean, rstd = ops.layernorm_fwd(cur, ops.contiguous_map(M, width), lw, lb, M, width, eps, stats=train)
-                with ops.gemm_mode(ops.GEMM_EXACT if exact_tail else ops.get_gemm_mode()):
-                    nxt = ops.linear_fwd(ln, fw, fb, epi=ops.EPI_BIAS if last else ops.EPI_BIAS_RELU)
-            saved += [cur, ln, mean, rstd]
-            cur = nxt
-        scores = cur.view(B, T)
+        scores, saved = predictor_forward_sequence(x, PredictorRows(x, B), params, ctx.act, predictor_bf16_data_path(x, ctx.act), train)
+        scores = scores.view(B, n - 1)
         probs = ops.softmax_rows(scores)
         if train:
-            ctx.save_for_backward(*saved, *params)
-            ctx.meta = (B, n, D, T, M, C, nl, len(saved))
+            ctx.save_for_backward(*saved, *params)          # saved[0] is x
+            ctx.B = B
         ctx.mark_non_differentiable(probs)
         return scores, probs
 
     @staticmethod
     def backward(ctx, gscores, _gprobs):
-        B, n, D, T, M, C, nl, nsaved = ctx.meta
-        saved = ctx.saved_tensors[:nsaved]
-        params = ctx.saved_tensors[nsaved:]
-        x, h0, mean0, rstd0, a1 = saved[:5]
-        dev = gscores.device
-        np_ = len(params)
-        grads = [None] * np_
-        want = [_need(ctx, 1 + i) for i in range(np_)]
-        d = gscores.contiguous().view(M, 1)
-        d16 = None                      # bf16 copy of d, written by the LayerNorm backward that produced it, when the next GEMMs run in bf16
-        io = ops.bf16_io() and gscores.is_cuda
-        for j in reversed(range(nl)):
-            cur, ln, mean, rstd = saved[5 + 4 * j: 9 + 4 * j]
-            lw, lb, fw, fb = params[4 + 4 * j: 8 + 4 * j]
-            base = 4 + 4 * j
-            width = cur.shape[1]
-            lnx, ln16 = xarg(ln)
-            # d is the gradient w.r.t. the pre-activation of layer j's Linear (the ReLU mask was applied upstream)
-            with ops.gemm_mode(ops.GEMM_EXACT if j >= nl - 2 else ops.get_gemm_mode()):      # same arithmetic as the forward of this layer
-                grads[base + 2], grads[base + 3] = ops.linear_param_grads(d, lnx, fw, fb, want[base + 2], want[base + 3], x16=ln16)
-                dln = ops.linear_dgrad(d, fw, a16=d16 if ln16 is not None else None)
-            # the layer below (j - 1) multiplies d in bf16 if it is a bf16-mode layer: its saved input is bf16 then
-            below_bf16 = io and j >= 1 and saved[5 + 4 * (j - 1) + 1].dtype == torch.bfloat16 and width % 32 == 0
-            d16 = ops.bf16_buffer(M, width, dev) if below_bf16 else None
-            # cur is the ReLU output of layer j-1 for j >= 1 -> fold that ReLU's backward in; for j == 0 cur is the
-            # split/mean/concat output and the mask is applied by half_mean_concat below
-            d, grads[base], grads[base + 1] = layernorm_backward(cur, ops.contiguous_map(M, width), dln, lw, lb, mean, rstd,
-                                                                 torch.empty((M, width), dtype=torch.float32, device=dev), M, width,
-                                                                 want[base], want[base + 1], relu_mask=(j >= 1), dx16=d16)
-        dz1 = ops.half_mean_concat(d, B, T, C, relu_mask_src=a1)
-        h0x, h016 = xarg(h0)
-        grads[2], grads[3] = ops.linear_param_grads(dz1, h0x, params[2], params[3], want[2], want[3], x16=h016)
-        gx = None
-        if _need(ctx, 0) or want[0] or want[1]:
-            dh0 = ops.linear_dgrad(dz1, params[2])
-            gx, grads[0], grads[1] = layernorm_backward(x, ops.skip_cls_map(n, D), dh0, params[0], params[1], mean0, rstd0,
-                                                        torch.zeros((B, n, D), dtype=torch.float32, device=dev), M, D, want[0], want[1])
-            if not _need(ctx, 0):
-                gx = None
-        return (gx,) + tuple(grads)
+        np_ = (len(ctx.needs_input_grad) - 1) // 4 * 4
+        saved, params = ctx.saved_tensors[:-np_], ctx.saved_tensors[-np_:]
+        grads = predictor_backward_sequence(gscores, PredictorRows(saved[0], ctx.B), saved, params, ctx.act, ctx.needs_input_grad)
+        return tuple(grads) + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 class GatherFn(torch.autograd.Function):

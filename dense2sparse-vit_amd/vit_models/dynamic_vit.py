@@ -81,6 +81,9 @@ SQUEEZE_DROPPED_DIFF_TOPK_ERROR = ("squeeze_dropped cannot be combined with diff
 RAGGED_TRAIN_THRESHOLD_ERROR = ("ragged_train trains the dynamic keep ratio on the ragged packed batch: it needs patch_score_threshold (the "
                                 "fixed-ratio path already trains on the kept tokens alone)")
 RAGGED_TRAIN_DROP_PATH_ERROR = "ragged_train with drop_path_rate > 0: stochastic depth is not built for a ragged block"
+RAGGED_CASCADE_BN_ERROR = ("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
+                           "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
+                           "predictor; one stage works with either")
 SQUEEZE_DROPPED_THRESHOLD_ERROR = ("squeeze_dropped applies to the fixed-ratio path only: with patch_score_threshold no token is removed, there "
                                    "is nothing to squeeze")
 SQUEEZE_DROPPED_TOPK_SELECTION_ERROR = ("squeeze_dropped needs topk_selection=True: the kept and dropped sets are those of the hard top-k of the "
@@ -389,10 +392,7 @@ class PredictorLG(nn.Module):
                 for bn in bns:
                     bn.num_batches_tracked += 1
             return out
-        if self.small_predictor:
-            from d2s.functional_small import SmallPredictorFn
-            return DF.run(SmallPredictorFn, x_with_cls, *self._params())
-        return DF.run(DF.PredictorFn, x_with_cls, *self._params())
+        return DF.run(DF.PredictorFn, x_with_cls, *self._params(), *(("gelu",) if self.small_predictor else ()))
 
     def forward(self, x, policy=None, current_sigma=0.0005, cls_attn=None):
         """Reference signature: x is the CLS-free token tensor [B, N, D] (:855 passes x[:, 1:])."""
@@ -730,9 +730,7 @@ class VisionTransformerDiffPruning(_ViTBase):
             logits, features = self._head(x)
             return logits, features, self.pred_logits, self.kept_token_indices
         if len(self.pruning_loc) > 1 and any(p.use_bn for p in self.score_predictor):
-            raise NotImplementedError("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
-                                      "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
-                                      "predictor; one stage works with either")
+            raise NotImplementedError(RAGGED_CASCADE_BN_ERROR)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("ragged inference is forward only: call it under torch.no_grad()")
         cu = None
@@ -792,9 +790,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         if ops.get_gemm_mode() == ops.GEMM_BF16:
             raise D2SError(AF._BF16_REFUSAL)
         if len(self.pruning_loc) > 1 and any(p.use_bn for p in self.score_predictor):
-            raise NotImplementedError("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
-                                      "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
-                                      "predictor; one stage works with either")
+            raise NotImplementedError(RAGGED_CASCADE_BN_ERROR)
         B, n, D = x.shape
         N = n - 1
         p_count = 0

@@ -180,11 +180,13 @@ def _make_call(cfg):
     return call, leaves
 
 
-def _run(call, leaves, gy, names):
-    saved = [0]
+def _run(call, leaves, gy, names, distinct=False):
+    saved, seen = [0], set()
 
     def pack(t):
-        saved[0] += t.numel() * t.element_size()
+        if not (distinct and t.data_ptr() in seen):          # distinct: a storage saved in two slots (a placeholder) counts once
+            saved[0] += t.numel() * t.element_size()
+        seen.add(t.data_ptr())
         return t
     for t in leaves.values():
         t.grad = None
@@ -207,10 +209,23 @@ def _run(call, leaves, gy, names):
 
 
 def record(cfg):
-    """One configuration: a warm-up call, then the measured one from an emptied allocator cache.
-    -> ({forward, backward, saved_bytes, peak_bytes}, {name: output or gradient tensor})"""
+    """One configuration of configurations().  -> ({forward, backward, saved_bytes, peak_bytes}, {name: output or gradient tensor})"""
+    def make():
+        call, leaves = _make_call(cfg)
+        if cfg["kind"] == "tome":          # the merged block's output: n - r rows per image
+            gy = _synth("gy", (B * (N - cfg["r"]), BLOCK_D)).view(B, N - cfg["r"], BLOCK_D)
+        else:
+            gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
+        return call, leaves, gy
+    return record_call(make, cfg["mode"], cfg.get("composite", True))
+
+
+def record_call(make, mode, composite=True, distinct=False):
+    """The spy on the C-ABI and the allocator discipline, shared with tests/predictor_routes.py: make() -> (call, leaves, gy) as of
+    _make_call, run in the arithmetic mode `mode` (one of MODES): a warm-up call, then the measured one from an emptied allocator cache.
+    distinct: count the saved bytes once per storage.  -> (route, tensors) as record's"""
     from d2s import lib, ops
-    mode = {"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT}.get(cfg["mode"], ops.GEMM_BF16)
+    gmode = {"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT}.get(mode, ops.GEMM_BF16)
     switches = ops._BF16_IO, ops._BLOCK_COMPOSITE
     names, real = [], lib.call
 
@@ -219,22 +234,18 @@ def record(cfg):
         return real(name, *args)
     lib.call = spy
     try:
-        ops._BF16_IO = cfg["mode"] != "bf16_noio"
-        ops._BLOCK_COMPOSITE = cfg.get("composite", True)
-        call, leaves = _make_call(cfg)
-        if cfg["kind"] == "tome":          # the merged block's output: n - r rows per image
-            gy = _synth("gy", (B * (N - cfg["r"]), BLOCK_D)).view(B, N - cfg["r"], BLOCK_D)
-        else:
-            gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
-        with ops.gemm_mode(mode):
-            _run(call, leaves, gy, names)
+        ops._BF16_IO = mode != "bf16_noio"
+        ops._BLOCK_COMPOSITE = composite
+        call, leaves, gy = make()
+        with ops.gemm_mode(gmode):
+            _run(call, leaves, gy, names, distinct)
             for t in leaves.values():
                 t.grad = None
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
-            route, outs = _run(call, leaves, gy, names)
+            route, outs = _run(call, leaves, gy, names, distinct)
             route["peak_bytes"] = torch.cuda.max_memory_allocated() - base
     finally:
         lib.call = real

@@ -287,7 +287,8 @@ def _student(case, **kw):
 
 @pytest.mark.parametrize("name", ["micro_thr2", "micro_thr3s"])
 def test_packed_predictor_function_is_the_inference_launch_sequence(name):
-    """RaggedPredictorFn's training forward gives ragged_predictor_forward's bits (large and small LayerNorm predictor)"""
+    """RaggedPredictorFn's training forward gives ragged_predictor_forward's bits (large and small LayerNorm predictor): both run
+    functional.predictor_forward_sequence, one keeping what the backward reads"""
     from d2s.functional_ragged import ragged_predictor_forward, ragged_predictor_train
     case = R.train_cases()[name]
     student, _ = _student(case)

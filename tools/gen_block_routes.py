@@ -18,25 +18,28 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (REPO, os.path.join(REPO, "dense2sparse-vit_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
-FIXTURE = os.path.join(REPO, "tests", "golden", "block_routes.json")
 
 
-def main():
+def main(stem="block_routes"):
+    """stem: the recorder under tests/ (tools/gen_predictor_routes.py passes its own), also the name of the fixture and of the dump"""
+    import importlib
+
     import torch
-    from tests import block_routes
+    recorder = importlib.import_module(f"tests.{stem}")
+    fixture_path = os.path.join(REPO, "tests", "golden", f"{stem}.json")
     ap = argparse.ArgumentParser()
     ap.add_argument("--dump", metavar="DIR")
     ap.add_argument("--compare", metavar="DIR")
     args = ap.parse_args()
-    routes, tensors = block_routes.record_all()
+    routes, tensors = recorder.record_all()
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
-        torch.save(tensors, os.path.join(args.dump, "block_routes.pt"))
+        torch.save(tensors, os.path.join(args.dump, f"{stem}.pt"))
         print(f"{len(tensors)} configurations, {sum(len(v) for v in tensors.values())} tensors -> {args.dump}")
         return 0
     if args.compare:
-        want = torch.load(os.path.join(args.compare, "block_routes.pt"))
-        with open(FIXTURE) as f:
+        want = torch.load(os.path.join(args.compare, f"{stem}.pt"))
+        with open(fixture_path) as f:
             fixture = json.load(f)
         bad = [f"{name}: configurations differ" for name in set(want) ^ set(tensors)]
         for name in sorted(set(want) & set(tensors)):
@@ -52,9 +55,9 @@ def main():
         print("\n".join(bad) if bad else
               f"{len(tensors)} configurations, {sum(len(v) for v in tensors.values())} tensors: bit for bit equal, routes as recorded")
         return 1 if bad else 0
-    with open(FIXTURE, "w") as f:
+    with open(fixture_path, "w") as f:
         f.write("{\n" + ",\n".join(f" {json.dumps(k)}: {json.dumps(routes[k], sort_keys=True)}" for k in sorted(routes)) + "\n}\n")      # one line each
-    print(f"{len(routes)} configurations -> {FIXTURE}")
+    print(f"{len(routes)} configurations -> {fixture_path}")
     return 0
 
 
