@@ -23,21 +23,20 @@
 //     [B, H, n] partials, an ordered fold over the heads follows, column 0 = 0; a masked key keeps its non-zero dpolicy, nothing is skipped.
 //     As in the fp32 kernels the O(eps) gradient through the row maximum (which the reference's autograd carries because it does not
 //     detach the max) is left out: it is <= eps = 1e-6 relative.
-// The policy arguments are a variadic tail of each kernel, so the mask-free instantiations keep their argument lists and instructions.
 //
 // VARLEN (the 32-key-tile forward only; no policy, no backward): a ragged packed batch, inference with a dynamic keep ratio
 // (vit_models/dynamic_vit.py:935-949).  Image b owns rows cu[b] .. cu[b+1] of qkv [total, 3, H, 64], of out [total, H*64] and of its bf16
 // copy; n = cu[b+1] - cu[b] is per image and the kernel's n argument is the bound that sized the grid.  A block whose first query lies past
 // its image returns before any barrier (block-uniform).  The CLS softmax row goes to cls_row[h * total + cu[b] + j]; no log-sum-exp is
-// written (forward only).  The arguments are the same kind of variadic tail (AttnVarlen), the code sits under `if constexpr`.  With
-// cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same bits.
+// written (forward only).  With cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same
+// bits.
 //
 // KEYW (the 32-key-tile forward only; no policy, no ragged form, no backward): attention whose keys carry weights, token merging at
 // inference on the bf16 data path.  out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B, n] >= 1: the
 // tile's 32 weights travel through pol_s as a policy does, e_ij = 2^(s log2 e - m log2 e) * w_j (one more fp32 rounding) feeds both the
 // row sum and the bf16 P; no diagonal exception.  The running maximum stays the one over the raw scores (w >= 1 keeps e w >= e), so
-// lse_i = m_i + log(l_i) is the log of the weighted denominator, d2s_attn_keyw_fwd_f32's definition.  The arguments are a variadic tail
-// (AttnKeyW).  With unit weights the multiply is by 1.0: the bits of the plain kernel.
+// lse_i = m_i + log(l_i) is the log of the weighted denominator, d2s_attn_keyw_fwd_f32's definition.  The weights travel in `policy`.
+// With unit weights the multiply is by 1.0: the bits of the plain kernel.
 #include "d2s_common.h"
 #include <cstdlib>
 
@@ -70,19 +69,6 @@ __device__ __forceinline__ void load8(const __bf16* __restrict__ p, f32x4 (&r)[2
     for (int j = 0; j < 4; ++j) { r[0][j] = (float)v[j]; r[1][j] = (float)v[4 + j]; }
 }
 
-// the variadic tails of the POLICY instantiations
-struct AttnPolFwd { const float* policy; float* cinv; float eps; };
-struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
-// the variadic tail of the VARLEN instantiations
-struct AttnVarlen { const int* cu; int total; };
-template <typename... T> struct is_varlen_tail { static constexpr bool value = false; };
-template <> struct is_varlen_tail<AttnVarlen> { static constexpr bool value = true; };
-// the variadic tail of the KEYW instantiations: the keys carry weights (token merging), w [B, n], >= 1
-struct AttnKeyW { const float* w; };
-template <typename... T> struct is_keyw_tail { static constexpr bool value = false; };
-template <> struct is_keyw_tail<AttnKeyW> { static constexpr bool value = true; };
-template <typename T>
-__device__ __forceinline__ T tail_arg(T a) { return a; }
 // mk of the 16 keys a lane holds in accumulator order (registers 4g .. 4g+3 = tile rows 8g + 4 half + 0..3) from the tile's policy in LDS.
 // A wave's 32 queries start at a multiple of 32, so the diagonal i == j lies in one key tile only (diag_tile, wave-uniform), at row l31.
 __device__ __forceinline__ void tile_policy(const float* __restrict__ pol_s, int half, int l31, bool diag_tile, f32x4 (&pg)[4]) {
@@ -95,13 +81,15 @@ __device__ __forceinline__ void tile_policy(const float* __restrict__ pol_s, int
     }
 }
 
-template <typename QT, bool POLICY = false, typename... Pol>
+// policy: POLICY's keep policy or KEYW's key weights, [B, n]; cinv, eps: POLICY; cu, total: VARLEN.  The other instantiations read none of them.
+// cinv carries no __restrict__: with it the POLICY instantiations spill 6 SGPRs instead of 2.
+template <typename QT, bool POLICY = false, bool VARLEN = false, bool KEYW = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restrict__ qkv, float* __restrict__ out,
                                                                __bf16* __restrict__ out16, float* __restrict__ lse, float* __restrict__ cls_row, int n, int H,
-                                                               float scale, Pol... pol_) {
+                                                               float scale, const float* __restrict__ policy, float* cinv, float eps,
+                                                               const int* __restrict__ cu, int total) {
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];      // [key][d]
     __shared__ __attribute__((aligned(16))) __bf16 Vt[DH * VP];      // [d][pos(key)]
-    constexpr bool KEYW = is_keyw_tail<Pol...>::value;
     __shared__ __attribute__((aligned(16))) float pol_s[(POLICY || KEYW) ? 32 : 1];  // the tile's policy (KEYW: its key weights)
     __shared__ __attribute__((aligned(16))) float vred[POLICY ? 32 * DH : 1];        // [staging key row][d] partial column sums of V
     __shared__ float vsum_s[POLICY ? DH : 1];                                        // (eps/n) * column sums of V
@@ -111,18 +99,16 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH;
-    constexpr bool VARLEN = is_varlen_tail<Pol...>::value;
     static_assert(!(POLICY && VARLEN), "the ragged form has no policy");
     static_assert(!(KEYW && (POLICY || VARLEN)), "key weights combine with neither the policy nor the ragged form");
     long tok0 = (long)b * n;                       // first token row of the image
     [[maybe_unused]] long cls0 = 0;                // VARLEN: start of the image's CLS softmax row inside cls_row [H, total]
     if constexpr (VARLEN) {
-        const AttnVarlen va = tail_arg(pol_...);
-        const int row_base = va.cu[b];
-        n = va.cu[b + 1] - row_base;
+        const int row_base = cu[b];
+        n = cu[b + 1] - row_base;
         if (bx * 128 >= n) return;                 // block-uniform, before any barrier: this image has no queries in this tile
         tok0 = row_base;
-        cls0 = (long)h * va.total + row_base;
+        cls0 = (long)h * total + row_base;
     }
     const QT* qb = qkv + tok0 * ld + h * DH;
     const QT* kb = qb + (long)H * DH;
@@ -131,18 +117,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const bool active = q0 < n;
     const bool want_cls = cls_row != nullptr && bx == 0 && wave == 0;
     const float* polb = nullptr;
-    float* cinv = nullptr;
-    float eps = 0.f;
-    if constexpr (POLICY) {
-        const AttnPolFwd pa = tail_arg(pol_...);
-        polb = pa.policy + (long)b * n;
-        cinv = pa.cinv;
-        eps = pa.eps;
-    }
-    if constexpr (KEYW) {
-        const AttnKeyW ka = tail_arg(pol_...);
-        polb = ka.w + (long)b * n;
-    }
+    if constexpr (POLICY || KEYW) polb = policy + (long)b * n;
 
     // B operand of S^T = K Q^T: this lane's query, d = 16 kk + 8 half + j, scaled, as bf16 (scale = 2^-3 for 64-wide heads: the product
     // is exact, so fp32 and bf16 qkv inputs round to the same operand).  The softmax is evaluated as 2^(s log2 e - m log2 e): one FMA and
@@ -593,11 +568,12 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[2], float* __restric
 }
 
 // ---- backward, dQ: a lane owns one query; loop over key tiles (S^T, dP^T, dS^T lane-local, dQ^T = K^T dS^T) ------------------------
-template <typename QT, bool POLICY = false, typename... Pol>
+// `policy` is read by the POLICY instantiations only and carries no __restrict__: with it the one on fp32 qkv re-schedules.
+template <typename QT, bool POLICY = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
-                                                                  Pol... pol_) {
+                                                                  const float* policy) {
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Vs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Kt[DH * VP];
@@ -632,7 +608,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
         pr = kj < n ? p0 : 0.f;
     };
     if constexpr (POLICY) {
-        polb = tail_arg(pol_...) + (long)b * n;
+        polb = policy + (long)b * n;
         fetch_pol(0);
     }
     stage_rows(kb, ld, 0, n, tid, kr);
@@ -683,11 +659,15 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
 }
 
 // ---- backward, dK / dV: a lane owns one key; loop over query tiles ------------------------------------------------------------------
-template <typename QT, bool POLICY = false, bool DPOL = false, typename... Pol>
+// The policy arguments, read by the POLICY / DPOL instantiations only (dpol_part [B, H, n]: DPOL).  One struct: as three plain arguments the
+// DPOL instantiations load them in other groups, and the backward with dpolicy measured 0.3 us slower (118.8 -> 119.1 us at B 128, H 6, n 197).
+struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
+template <typename QT, bool POLICY = false, bool DPOL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                                    float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
-                                                                   Pol... pol_) {
+                                                                   AttnPolBwd pol) {
+    static_assert(!DPOL || POLICY, "the policy's gradient needs a policy");
     __shared__ __attribute__((aligned(16))) __bf16 Qs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Ds[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Qt[DH * VP];
@@ -718,13 +698,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
     f32x4 qr[2], dr[2];
     float lr, dlr;
     const float* ci_b = nullptr;
-    float* dpol_part = nullptr;
     float pol_key = 0.f, cir = 0.f, dpol_acc = 0.f;      // POLICY: this lane's key's policy, the staged query's cinv; DPOL: the column sum
     if constexpr (POLICY) {
-        const AttnPolBwd pa = tail_arg(pol_...);
-        ci_b = pa.cinv + ((long)b * H + h) * n;
-        dpol_part = pa.dpol_part;
-        pol_key = kok ? pa.policy[(long)b * n + k0 + l31] : 0.f;
+        ci_b = pol.cinv + ((long)b * H + h) * n;
+        pol_key = kok ? pol.policy[(long)b * n + k0 + l31] : 0.f;
     }
     auto fetch = [&](int row0) {
         stage_rows(qb, ld, row0, n, tid, qr);
@@ -776,7 +753,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
     }
     if (DPOL && active) {
         dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
-        if (half == 0 && kok) dpol_part[((long)b * H + h) * n + k0 + l31] = dpol_acc;
+        if (half == 0 && kok) pol.dpol_part[((long)b * H + h) * n + k0 + l31] = dpol_acc;
     }
     if (active && kok) {
         const long row = ((long)b * n + k0 + l31) * ld + h * DH;
@@ -807,36 +784,60 @@ static bool attn_t64(int n) {
     return mode >= 2 || (mode == 1 && (n >= 384 || (n + 63) / 64 * 64 == (n + 31) / 32 * 32));
 }
 
-// Backward of the same mode (same contract as d2s_attn_bwd_f32): dqkv [B,n,3,H,64] fully written; delta_ws: [B,H,n] floats of scratch.
-template <typename QT>
-static int attn_bwd_bf16_impl(const QT* qkv, const float* out, const float* dout, const float* lse, float* dqkv, __bf16* dqkv16,
-                              float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
-    if (!qkv || !out || !dout || !lse || (!dqkv && !dqkv16) || !delta_ws || B <= 0 || n <= 0 || H <= 0) return D2S_ERR_ARG;
-    const int rc = d2s_attn_delta(out, dout, delta_ws, B, n, H, stream);
-    if (rc != D2S_OK) return rc;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<QT>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<QT>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale);
+// (qkv, qkv_is_bf16) of the C ABI -> f(qkv as const float* or as const __bf16*): every kernel is instantiated for both
+template <typename F>
+static int with_qkv_type(const void* qkv, int qkv_is_bf16, F f) {
+    return qkv_is_bf16 ? f(static_cast<const __bf16*>(qkv)) : f(static_cast<const float*>(qkv));
+}
+
+// forward launch of the 32-key-tile kernel; n bounds the longest image: it sizes the grid and, when the CLS softmax row is wanted, its LDS
+template <bool POLICY, bool VARLEN, bool KEYW, typename QT>
+static int attn_fwd_bf16_launch(const QT* qkv, float* out, void* out_bf16, float* lse, float* cls_row, int B, int n, int H, float scale,
+                                hipStream_t stream, const float* policy = nullptr, float* cinv = nullptr, float eps = 0.f,
+                                const int* cu = nullptr, int total = 0) {
+    hipLaunchKernelGGL((attn_fwd_bf16_kernel<QT, POLICY, VARLEN, KEYW>), dim3((n + 127) / 128, B * H), dim3(256),
+                       cls_row ? (size_t)n * sizeof(float) : 0, stream, qkv, out, static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, policy,
+                       cinv, eps, cu, total);
     return d2s_check_launch();
 }
 
-// Backward of d2s_attn_policy_fwd_bf16: delta, dQ, dK/dV (with the policy's column sums when dpolicy is asked for) and the fold over heads.
+// the dense forward: 64-key tiles where attn_t64 says so
 template <typename QT>
-static int attn_policy_bwd_bf16_impl(const QT* qkv, const float* policy, const float* out, const float* dout, const float* lse, const float* cinv,
-                                     float* dqkv, __bf16* dqkv16, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H, float scale,
-                                     hipStream_t stream) {
+static int attn_fwd_bf16_dense(const QT* qkv, float* out, void* out_bf16, float* lse, float* cls_row, int B, int n, int H, float scale,
+                               hipStream_t stream) {
+    if (!attn_t64(n)) return attn_fwd_bf16_launch<false, false, false>(qkv, out, out_bf16, lse, cls_row, B, n, H, scale, stream);
+    hipLaunchKernelGGL(attn_fwd_bf16_kernel64<QT>, dim3((n + 127) / 128, B * H), dim3(256), cls_row ? (size_t)n * sizeof(float) : 0, stream, qkv,
+                       out, static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale);
+    return d2s_check_launch();
+}
+
+// backward launches: delta, dQ, dK/dV (with the policy's column sums when dpolicy is asked for) and then the fold over the heads
+template <bool POLICY, typename QT>
+static int attn_bwd_bf16_launch(const QT* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* dqkv_bf16,
+                                float* delta_ws, int B, int n, int H, float scale, hipStream_t stream, const float* policy = nullptr,
+                                const float* cinv = nullptr, float* dpolicy = nullptr, float* dpol_ws = nullptr) {
     const int rc = d2s_attn_delta(out, dout, delta_ws, B, n, H, stream);
     if (rc != D2S_OK) return rc;
     dim3 grid((n + 127) / 128, B * H), block(256);
-    const AttnPolBwd pa{policy, cinv, dpolicy ? dpol_ws : nullptr};
-    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, true, const float*>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, policy);
-    if (dpolicy) {
-        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, true, true, AttnPolBwd>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, pa);
+    __bf16* dqkv16 = static_cast<__bf16*>(dqkv_bf16);
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, POLICY>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, policy);
+    if (POLICY && dpolicy) {
+        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, POLICY, POLICY>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale,
+                           AttnPolBwd{policy, cinv, dpol_ws});
         hipLaunchKernelGGL(attn_dpol_fold_bf16_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, stream, dpol_ws, dpolicy, B, n, H);
     } else {
-        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, true, false, AttnPolBwd>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, pa);
+        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, POLICY, false>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale,
+                           AttnPolBwd{policy, cinv, nullptr});
     }
     return d2s_check_launch();
+}
+
+// Backward of the same mode (same contract as d2s_attn_bwd_f32): dqkv [B,n,3,H,64] fully written; delta_ws: [B,H,n] floats of scratch.
+template <typename QT>
+static int attn_bwd_bf16_impl(const QT* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* dqkv_bf16,
+                              float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !out || !dout || !lse || (!dqkv && !dqkv_bf16) || !delta_ws || B <= 0 || n <= 0 || H <= 0) return D2S_ERR_ARG;
+    return attn_bwd_bf16_launch<false>(qkv, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, n, H, scale, stream);
 }
 
 extern "C" {
@@ -845,14 +846,7 @@ extern "C" {
 int d2s_attn_fwd_bf16(const float* qkv, float* out, float* lse, float* cls_row, int B, int n, int H, float scale,
                       hipStream_t stream) {
     if (!qkv || !out || !lse || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    if (attn_t64(n))
-        hipLaunchKernelGGL(attn_fwd_bf16_kernel64<float>, grid, block, cls_row ? (size_t)n * sizeof(float) : 0, stream, qkv, out,
-                           static_cast<__bf16*>(nullptr), lse, cls_row, n, H, scale);
-    else
-        hipLaunchKernelGGL(attn_fwd_bf16_kernel<float>, grid, block, cls_row ? (size_t)n * sizeof(float) : 0, stream, qkv, out,
-                           static_cast<__bf16*>(nullptr), lse, cls_row, n, H, scale);
-    return d2s_check_launch();
+    return attn_fwd_bf16_dense(qkv, out, nullptr, lse, cls_row, B, n, H, scale, stream);
 }
 
 // The same forward on the bf16 data path: qkv may be given in bf16 (qkv_is_bf16 != 0: the c_bf16 of the qkv GEMM, same [B,n,3,H,64]
@@ -861,38 +855,20 @@ int d2s_attn_fwd_bf16(const float* qkv, float* out, float* lse, float* cls_row, 
 int d2s_attn_fwd_bf16_bf16out(const void* qkv, int qkv_is_bf16, float* out, void* out_bf16, float* lse, float* cls_row, int B, int n, int H,
                               float scale, hipStream_t stream) {
     if (!qkv || !out_bf16 || !lse || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    const size_t sh = cls_row ? (size_t)n * sizeof(float) : 0;
-    if (attn_t64(n)) {
-        if (qkv_is_bf16)
-            hipLaunchKernelGGL(attn_fwd_bf16_kernel64<__bf16>, grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
-                               static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale);
-        else
-            hipLaunchKernelGGL(attn_fwd_bf16_kernel64<float>, grid, block, sh, stream, static_cast<const float*>(qkv), out,
-                               static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale);
-        return d2s_check_launch();
-    }
-    if (qkv_is_bf16)
-        hipLaunchKernelGGL(attn_fwd_bf16_kernel<__bf16>, grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale);
-    else
-        hipLaunchKernelGGL(attn_fwd_bf16_kernel<float>, grid, block, sh, stream, static_cast<const float*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale);
-    return d2s_check_launch();
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) { return attn_fwd_bf16_dense(q, out, out_bf16, lse, cls_row, B, n, H, scale, stream); });
 }
 
 int d2s_attn_bwd_bf16(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta_ws, int B, int n,
                       int H, float scale, hipStream_t stream) {
-    return attn_bwd_bf16_impl<float>(qkv, out, dout, lse, dqkv, nullptr, delta_ws, B, n, H, scale, stream);
+    return attn_bwd_bf16_impl(qkv, out, dout, lse, dqkv, nullptr, delta_ws, B, n, H, scale, stream);
 }
 // ... on the bf16 data path: qkv optionally in bf16 (as in the forward), and a bf16 copy of dqkv (same [B,n,3,H,64] layout): the a_bf16
 // of the qkv Linear's input-gradient GEMM and the dy_bf16 of its weight gradient; dqkv may be NULL when only that form is consumed
 int d2s_attn_bwd_bf16_bf16out(const void* qkv, int qkv_is_bf16, const float* out, const float* dout, const float* lse, float* dqkv,
                               void* dqkv_bf16, float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
     if (!dqkv_bf16) return D2S_ERR_ARG;
-    if (qkv_is_bf16)
-        return attn_bwd_bf16_impl<__bf16>(static_cast<const __bf16*>(qkv), out, dout, lse, dqkv, static_cast<__bf16*>(dqkv_bf16), delta_ws, B, n, H, scale, stream);
-    return attn_bwd_bf16_impl<float>(static_cast<const float*>(qkv), out, dout, lse, dqkv, static_cast<__bf16*>(dqkv_bf16), delta_ws, B, n, H, scale, stream);
+    return with_qkv_type(qkv, qkv_is_bf16,
+                         [&](auto q) { return attn_bwd_bf16_impl(q, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, n, H, scale, stream); });
 }
 
 // Policy attention (d2s_attn_policy_fwd_f32's contract and outputs) on the bf16 matrix cores and the bf16 data path: qkv fp32 or bf16 as in
@@ -901,16 +877,9 @@ int d2s_attn_bwd_bf16_bf16out(const void* qkv, int qkv_is_bf16, const float* out
 int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, float* out, void* out_bf16, float* lse, float* cinv,
                              float* cls_row, int B, int n, int H, float scale, float eps, hipStream_t stream) {
     if (!qkv || !policy || (!out && !out_bf16) || !lse || !cinv || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    const size_t sh = cls_row ? (size_t)n * sizeof(float) : 0;
-    const AttnPolFwd pa{policy, cinv, eps};
-    if (qkv_is_bf16)
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, true, AttnPolFwd>), grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, pa);
-    else
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, true, AttnPolFwd>), grid, block, sh, stream, static_cast<const float*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, pa);
-    return d2s_check_launch();
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_fwd_bf16_launch<true, false, false>(q, out, out_bf16, lse, cls_row, B, n, H, scale, stream, policy, cinv, eps);
+    });
 }
 
 // Ragged packed batch on the bf16 matrix cores and the bf16 data path (d2s_attn_varlen_fwd_f32's contract; inference with a dynamic keep
@@ -922,16 +891,10 @@ int d2s_attn_policy_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
 int d2s_attn_varlen_fwd_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seqlens, float* out, void* out_bf16, float* cls_row, int B,
                              int total, int max_n, int H, float scale, hipStream_t stream) {
     if (!qkv || !cu_seqlens || (!out && !out_bf16) || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
-    dim3 grid((max_n + 127) / 128, B * H), block(256);
-    const size_t sh = cls_row ? (size_t)max_n * sizeof(float) : 0;
-    const AttnVarlen va{cu_seqlens, total};
-    if (qkv_is_bf16)
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, false, AttnVarlen>), grid, block, sh, stream, static_cast<const __bf16*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), static_cast<float*>(nullptr), cls_row, max_n, H, scale, va);
-    else
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, false, AttnVarlen>), grid, block, sh, stream, static_cast<const float*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), static_cast<float*>(nullptr), cls_row, max_n, H, scale, va);
-    return d2s_check_launch();
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_fwd_bf16_launch<false, true, false>(q, out, out_bf16, nullptr, cls_row, B, max_n, H, scale, stream, nullptr, nullptr, 0.f,
+                                                        cu_seqlens, total);
+    });
 }
 
 // Its backward (lse, cinv as that call wrote them; out its fp32 output): dqkv and / or dqkv_bf16 fully written - at least one.  dpolicy
@@ -943,11 +906,9 @@ int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
     if (!qkv || !policy || !out || !dout || !lse || !cinv || (!dqkv && !dqkv_bf16) || !delta_ws || (dpolicy && !dpol_ws) || B <= 0 || n <= 0 ||
         H <= 0)
         return D2S_ERR_ARG;
-    if (qkv_is_bf16)
-        return attn_policy_bwd_bf16_impl<__bf16>(static_cast<const __bf16*>(qkv), policy, out, dout, lse, cinv, dqkv, static_cast<__bf16*>(dqkv_bf16),
-                                                 delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
-    return attn_policy_bwd_bf16_impl<float>(static_cast<const float*>(qkv), policy, out, dout, lse, cinv, dqkv, static_cast<__bf16*>(dqkv_bf16),
-                                            delta_ws, dpolicy, dpol_ws, B, n, H, scale, stream);
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_bwd_bf16_launch<true>(q, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, n, H, scale, stream, policy, cinv, dpolicy, dpol_ws);
+    });
 }
 
 // Key-weighted attention (d2s_attn_keyw_fwd_f32's definition; token merging at inference) on the bf16 matrix cores and the bf16 data path:
@@ -957,15 +918,9 @@ int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* poli
 int d2s_attn_keyw_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* key_w, float* out, void* out_bf16, float* lse, int B, int n, int H,
                            float scale, hipStream_t stream) {
     if (!qkv || !key_w || (!out && !out_bf16) || !lse || B <= 0 || n < 2 || n > 8192 || H <= 0) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    const AttnKeyW ka{key_w};
-    if (qkv_is_bf16)
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, false, AttnKeyW>), grid, block, 0, stream, static_cast<const __bf16*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, static_cast<float*>(nullptr), n, H, scale, ka);
-    else
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, false, AttnKeyW>), grid, block, 0, stream, static_cast<const float*>(qkv), out,
-                           static_cast<__bf16*>(out_bf16), lse, static_cast<float*>(nullptr), n, H, scale, ka);
-    return d2s_check_launch();
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_fwd_bf16_launch<false, false, true>(q, out, out_bf16, lse, nullptr, B, n, H, scale, stream, key_w);
+    });
 }
 
 }  // extern "C"

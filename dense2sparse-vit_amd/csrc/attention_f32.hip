@@ -309,16 +309,11 @@ __device__ __forceinline__ void tile_load_u32(const float* __restrict__ base, un
     }
 }
 
-// VARLEN tail of the two backward kernels (training through a ragged packed batch): one VarlenSeg after the existing
-// arguments, so that every dense instantiation keeps its spelling, its argument list and its instructions.  Image b owns rows cu[b] ..
-// cu[b+1] of qkv / dout / dqkv, its lse / delta live at [h * total + cu[b] + i] (what attn_fwd_kernel<false, true> writes), `n` arrives as
-// max_n.  The segment is clamped to [0, total) and its length to [0, max_n]: a bad cu is never dereferenced outside the buffers.
+// VARLEN in the two backward kernels (training through a ragged packed batch): image b owns rows cu[b] .. cu[b+1] of
+// qkv / dout / dqkv, its lse / delta live at [h * total + cu[b] + i] (what attn_fwd_kernel<false, true> writes), `n` arrives as max_n.
+// The segment is clamped to [0, total) and its length to [0, max_n]: a bad cu is never dereferenced outside the buffers.  The dense
+// instantiations are handed VarlenSeg{} and never read it.
 struct VarlenSeg { const int* cu; int total; };
-template <typename... T> struct has_varlen { static constexpr bool value = false; };
-template <> struct has_varlen<VarlenSeg> { static constexpr bool value = true; };
-__device__ __forceinline__ VarlenSeg varlen_seg() { return VarlenSeg{nullptr, 0}; }
-template <typename T> __device__ __forceinline__ VarlenSeg varlen_seg(T) { return VarlenSeg{nullptr, 0}; }
-__device__ __forceinline__ VarlenSeg varlen_seg(VarlenSeg v) { return v; }
 __device__ __forceinline__ int varlen_rows(VarlenSeg v, int b, int max_n, int& row_base) {
     const int r0 = min(max(v.cu[b], 0), v.total), r1 = min(max(v.cu[b + 1], r0), v.total);
     row_base = r0;
@@ -334,13 +329,15 @@ __device__ __forceinline__ int varlen_rows(VarlenSeg v, int b, int max_n, int& r
 // KEYW (backward of attn_fwd_kernel<false, false, true>, training through token merging): P_ij = w_j exp(S_ij - lse_i) with lse_i = m_i +
 // log sum_j e_ij w_j as that forward wrote it; the weights travel in `policy`, are staged per key tile in pol_s as the forward does, and
 // multiply the exponential - every key, the diagonal included.  They are counts and get no gradient.
-// VARLEN (the tail is one VarlenSeg, <false, false, VarlenSeg>): the same tiles on image b's rows of a packed batch; a workgroup whose
-// 128-row tile starts at or past the image's n returns before its first barrier (block-uniform).
-template <bool POLICY, bool KEYW = false, typename... Varlen>
+// VARLEN: the same tiles on image b's rows of a packed batch; a workgroup whose 128-row tile starts at or past the image's n returns
+// before its first barrier (block-uniform).
+template <bool POLICY, bool KEYW = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           float* __restrict__ dqkv, int n, int H, float scale,
-                                                          const float* __restrict__ policy, Varlen... varlen_) {
+                                                          const float* __restrict__ policy, VarlenSeg varlen) {
+    static_assert(!(KEYW && POLICY), "key weights travel in the policy's argument");
+    static_assert(!(VARLEN && (POLICY || KEYW)), "the ragged form has neither a policy nor key weights");
     __shared__ __attribute__((aligned(16))) float Ks[32 * PITCH];
     __shared__ __attribute__((aligned(16))) float Vs[32 * PITCH];
     __shared__ float pol_s[32];
@@ -349,15 +346,14 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const float* __rest
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    constexpr bool VARLEN = has_varlen<Varlen...>::value;
     int row_base = 0;
-    if (VARLEN) {
-        n = varlen_rows(varlen_seg(varlen_...), b, n, row_base);
+    if constexpr (VARLEN) {
+        n = varlen_rows(varlen, b, n, row_base);
         if (bx * 128 >= n) return;                      // block-uniform: this image has no queries in this tile
     }
     // the dense offsets stay spelled where they are used, as they were: hoisting them into one tok0 / stat0 reorders the dense
     // instantiations' scalar address arithmetic (same results, other instructions)
-    const long stat0v = VARLEN ? (long)h * varlen_seg(varlen_...).total + row_base : 0;        // the image's first lse / delta entry
+    const long stat0v = VARLEN ? (long)h * varlen.total + row_base : 0;        // the image's first lse / delta entry
     const float* qb = qkv + (VARLEN ? (long)row_base : (long)b * n) * ld + h * DH;
     const float* kb = qb + (long)H * DH;
     const float* vb = kb + (long)H * DH;
@@ -448,41 +444,31 @@ __device__ __forceinline__ void dkv_fetch_next(const float* __restrict__ qb, con
         cir = qi < (unsigned)n ? ci_b[qi] : 0.f;
     }
 }
-__device__ __forceinline__ float* first_arg() { return nullptr; }
-__device__ __forceinline__ float* first_arg(float* a) { return a; }
-// the dK/dV kernel's tail of the key-weighted instantiation (below): a type of its own, so that <POLICY, DPOL> and the float* tail of DPOL
-// keep their spelling, their argument lists and their instructions
-struct KeyWeights { const float* w; };
-__device__ __forceinline__ float* first_arg(KeyWeights) { return nullptr; }
-__device__ __forceinline__ const float* key_weights() { return nullptr; }
-__device__ __forceinline__ const float* key_weights(float*) { return nullptr; }
-__device__ __forceinline__ const float* key_weights(KeyWeights k) { return k.w; }
-__device__ __forceinline__ float* first_arg(VarlenSeg) { return nullptr; }
-__device__ __forceinline__ const float* key_weights(VarlenSeg) { return nullptr; }
-template <typename... T> struct has_key_weights { static constexpr bool value = false; };
-template <> struct has_key_weights<KeyWeights> { static constexpr bool value = true; };
 
 // ---------------------------------------------------------------------------------------------------------
 // backward, dK / dV: one wave per 32 keys, loops over query tiles (natural orientation S = Q K^T)
 // ---------------------------------------------------------------------------------------------------------
 // POLICY: P_ij = exp(S_ij - lse_i) mk_ij + cinv_i feeds dV (the eps/n term reaches every key, masked or not); dS as in the dQ kernel.
-// DPOL (its one extra argument, float* dpol_part, is the variadic tail, so that the two existing instantiations keep their argument
-// lists and their instructions): the gradient of the policy itself, for the DynamicViT baseline whose predictor learns through the mask of this softmax only.  With
+// DPOL: the gradient of the policy itself, for the DynamicViT baseline whose predictor learns through the mask of this softmax only.  With
 // m_ij = p_j + (1 - p_j) [i == j]:  dL/dm_ij = exp(S_ij - lse_i) (dP_ij - delta_i) - the product below BEFORE the mask multiplies it - and
 // dpolicy[b, j] = sum_h sum_{i != j} dL/dm_ij.  The lane owns key j and walks every query, so its column sum needs no atomics: 16 rows per
 // tile in register order, tiles in ascending order, then the two half-waves (rows 4 half + ...) are added once.  Each wave of a workgroup
 // owns 32 keys of its own, so nothing is reduced across waves.  A masked key (p_j = 0) has dS = 0 but a non-zero column sum (that is the
 // straight-through estimator's signal) and the policy is real-valued here: nothing is skipped and 0/1 is not assumed.
-// dpol_part [B, H, n]: per-head partials, folded over h in ascending order by attn_dpol_fold_kernel.
-// KEYW (the tail is one KeyWeights, <false, false, KeyWeights>; backward of the key-weighted forward): P_ij = w_j exp(S_ij - lse_i).  The
-// lane owns key j, so w_j is one register loaded once (pol_key's slot) and multiplies p before it feeds dV and dS; no diagonal exception.
-// VARLEN (the tail is one VarlenSeg, <false, false, VarlenSeg>): as in the dQ kernel.
-template <bool POLICY, bool DPOL = false, typename... DpolPart>
+// dpol_part [B, H, n]: per-head partials, folded over h in ascending order by attn_dpol_fold_kernel (no __restrict__ on it: with it this
+// instantiation re-schedules).
+// KEYW (backward of the key-weighted forward): P_ij = w_j exp(S_ij - lse_i), the weights in `policy` as in the dQ kernel.  The lane owns
+// key j, so w_j is one register loaded once (pol_key's slot) and multiplies p before it feeds dV and dS; no diagonal exception.
+// VARLEN: as in the dQ kernel.
+template <bool POLICY, bool DPOL = false, bool KEYW = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            float* __restrict__ dqkv, int n, int H, float scale,
                                                            const float* __restrict__ policy, const float* __restrict__ cinv,
-                                                           DpolPart... dpol_part_) {
+                                                           float* dpol_part, VarlenSeg varlen) {
+    static_assert(!DPOL || POLICY, "the policy's gradient needs a policy");
+    static_assert(!(KEYW && POLICY), "key weights travel in the policy's argument");
+    static_assert(!(VARLEN && (POLICY || DPOL || KEYW)), "the ragged form has neither a policy nor key weights");
     __shared__ __attribute__((aligned(16))) float Qs[32 * PITCH];
     __shared__ __attribute__((aligned(16))) float Ds[32 * PITCH];
     __shared__ float lse_s[32], dl_s[32], ci_s[32];
@@ -491,14 +477,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    constexpr bool VARLEN = has_varlen<DpolPart...>::value;
     int row_base = 0;
-    if (VARLEN) {
-        n = varlen_rows(varlen_seg(dpol_part_...), b, n, row_base);
+    if constexpr (VARLEN) {
+        n = varlen_rows(varlen, b, n, row_base);
         if (bx * 128 >= n) return;                      // block-uniform: this image has no keys in this tile
     }
     const long tok0 = VARLEN ? (long)row_base : (long)b * n;       // first token row of the image
-    const long stat0 = VARLEN ? (long)h * varlen_seg(dpol_part_...).total + row_base : ((long)b * H + h) * n;
+    const long stat0 = VARLEN ? (long)h * varlen.total + row_base : ((long)b * H + h) * n;
     const float* qb = qkv + tok0 * ld + h * DH;
     const float* kb = qb + (long)H * DH;
     const float* vb = kb + (long)H * DH;
@@ -521,9 +506,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     float lr = 0.f, dlr = 0.f, cir = 0.f;
     float dpol_acc = 0.f;
     const float* ci_b = POLICY ? cinv + ((long)b * H + h) * n : nullptr;
-    constexpr bool KEYW = has_key_weights<DpolPart...>::value;
-    const float* polk = KEYW ? key_weights(dpol_part_...) : policy;
-    const float pol_key = ((POLICY || KEYW) && k0 + l31 < n) ? polk[(long)b * n + k0 + l31] : 0.f;   // this lane's key
+    const float pol_key = ((POLICY || KEYW) && k0 + l31 < n) ? policy[(long)b * n + k0 + l31] : 0.f;   // this lane's key
     tile_load(qb, ld, 0, n, tid, qr);
     tile_load(dob, ldo, 0, n, tid, dr);
     if (tid < 32) { lr = tid < n ? lse_b[tid] : INFINITY; dlr = tid < n ? dl_b[tid] : 0.f; if (POLICY) cir = tid < n ? ci_b[tid] : 0.f; }
@@ -578,11 +561,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const float* __res
     if (!active) return;
     // DPOL: the epilogue's lane coordinates are derived afresh from an opaque copy of the thread id, so that the loop does not carry them
     int l31e = l31, halfe = half, k0e = k0;
-    if (DPOL) {
+    if constexpr (DPOL) {
         int t2 = (int)threadIdx.x;
         asm volatile("" : "+v"(t2));
         l31e = t2 & 31; halfe = (t2 >> 5) & 1; k0e = bx * 128 + (t2 >> 6) * 32;
-        float* dpol_part = first_arg(dpol_part_...);
         dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
         if (halfe == 0 && k0e + l31e < n) dpol_part[((long)b * H + h) * n + k0e + l31e] = dpol_acc;
     }
@@ -621,16 +603,46 @@ extern "C" int d2s_debug_read_attn_stamps(unsigned long long* host_out, int n_wg
 }
 #endif
 
+// forward launch; n_max bounds the longest image: it sizes the grid and, when the CLS softmax row is wanted, that row's dynamic LDS
+template <bool POLICY, bool VARLEN, bool KEYW = false>
+static int attn_fwd_launch(const AttnFwdArgs& a, int B, int n_max, hipStream_t stream) {
+    hipLaunchKernelGGL((attn_fwd_kernel<POLICY, VARLEN, KEYW>), dim3((n_max + 127) / 128, B * a.H), dim3(256),
+                       a.cls_row ? (size_t)n_max * sizeof(float) : 0, stream, a);
+    return d2s_check_launch();
+}
+
+// backward launches: delta, dQ, dK/dV and (DPOL) the fold of the policy's gradient over the heads.  `policy` carries the key weights with
+// KEYW; with VARLEN n is max_n and delta_ws is [H, total]: the dense kernel's [B, H, n] layout with B = 1, n = total
+template <bool POLICY, bool DPOL = false, bool KEYW = false, bool VARLEN = false>
+static int attn_bwd_launch(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta_ws, int B, int n,
+                           int H, float scale, hipStream_t stream, const float* policy = nullptr, const float* cinv = nullptr,
+                           float* dpolicy = nullptr, float* dpol_ws = nullptr, VarlenSeg seg = VarlenSeg{nullptr, 0}) {
+    const long rows = VARLEN ? (long)seg.total : (long)B * n;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows,
+                       VARLEN ? seg.total : n, H);
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<POLICY, KEYW, VARLEN>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy, seg);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<POLICY, DPOL, KEYW, VARLEN>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
+                       policy, cinv, dpol_ws, seg);
+    if (DPOL)
+        hipLaunchKernelGGL(attn_dpol_fold_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, dpol_ws, dpolicy, B, n, H);
+    return d2s_check_launch();
+}
+
+// the two ragged forward entries: one instantiation, one launch geometry; lse is null for the entry that keeps none
+static int attn_varlen_fwd(const float* qkv, const int* cu_seqlens, float* out, float* lse, float* cls_row, int B, int total, int max_n, int H,
+                           float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || !out || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
+    return attn_fwd_launch<false, true>(AttnFwdArgs{qkv, out, lse, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total}, B, max_n, stream);
+}
+
 extern "C" {
 
 // qkv [B,n,3,H,64] -> out [B,n,H*64], lse [B,H,n]; cls_row [B,H,n] (softmax row of query 0) if non-null.
 int d2s_attn_fwd_f32(const float* qkv, float* out, float* lse, float* cls_row, int B, int n, int H, float scale,
                      hipStream_t stream) {
     if (!qkv || !out || !lse || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    AttnFwdArgs a{qkv, out, lse, cls_row, nullptr, nullptr, nullptr, n, H, scale, 0.f, 0};
-    hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, block, cls_row ? (size_t)n * sizeof(float) : 0, stream, a);
-    return d2s_check_launch();
+    return attn_fwd_launch<false, false>(AttnFwdArgs{qkv, out, lse, cls_row, nullptr, nullptr, nullptr, n, H, scale, 0.f, 0}, B, n, stream);
 }
 
 // Attention with the keep policy of the dynamic-keep-ratio training path fused in (vit_models/dynamic_vit.py:195-214,216-236 with
@@ -639,10 +651,7 @@ int d2s_attn_fwd_f32(const float* qkv, float* out, float* lse, float* cls_row, i
 int d2s_attn_policy_fwd_f32(const float* qkv, const float* policy, float* out, float* lse, float* cinv, float* cls_row, int B, int n,
                             int H, float scale, float eps, hipStream_t stream) {
     if (!qkv || !policy || !out || !lse || !cinv || B <= 0 || n <= 0 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    AttnFwdArgs a{qkv, out, lse, cls_row, policy, cinv, nullptr, n, H, scale, eps, 0};
-    hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, block, cls_row ? (size_t)n * sizeof(float) : 0, stream, a);
-    return d2s_check_launch();
+    return attn_fwd_launch<true, false>(AttnFwdArgs{qkv, out, lse, cls_row, policy, cinv, nullptr, n, H, scale, eps, 0}, B, n, stream);
 }
 
 // Ragged packed batch (inference with a dynamic keep ratio, vit_models/dynamic_vit.py:935-949): qkv [total,3,H,64], image b = rows
@@ -650,22 +659,15 @@ int d2s_attn_policy_fwd_f32(const float* qkv, const float* policy, float* out, f
 // max_n bounds the longest image (sizes the grid; any upper bound works).  Forward only.
 int d2s_attn_varlen_fwd_f32(const float* qkv, const int* cu_seqlens, float* out, float* cls_row, int B, int total, int max_n, int H,
                             float scale, hipStream_t stream) {
-    if (!qkv || !cu_seqlens || !out || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
-    dim3 grid((max_n + 127) / 128, B * H), block(256);
-    AttnFwdArgs a{qkv, out, nullptr, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total};
-    hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, cls_row ? (size_t)max_n * sizeof(float) : 0, stream, a);
-    return d2s_check_launch();
+    return attn_varlen_fwd(qkv, cu_seqlens, out, nullptr, cls_row, B, total, max_n, H, scale, stream);
 }
 
 // d2s_attn_varlen_fwd_f32 that also keeps lse [H, total] (lse of row cu[b] + i of head h at h * total + cu[b] + i) for
 // d2s_attn_varlen_bwd_f32: the same instantiation and launch geometry, out / cls_row bit for bit that entry's.
 int d2s_attn_varlen_fwd_lse_f32(const float* qkv, const int* cu_seqlens, float* out, float* lse, float* cls_row, int B, int total, int max_n,
                                 int H, float scale, hipStream_t stream) {
-    if (!qkv || !cu_seqlens || !out || !lse || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
-    dim3 grid((max_n + 127) / 128, B * H), block(256);
-    AttnFwdArgs a{qkv, out, lse, cls_row, nullptr, nullptr, cu_seqlens, 0, H, scale, 0.f, total};
-    hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, cls_row ? (size_t)max_n * sizeof(float) : 0, stream, a);
-    return d2s_check_launch();
+    if (!lse) return D2S_ERR_ARG;
+    return attn_varlen_fwd(qkv, cu_seqlens, out, lse, cls_row, B, total, max_n, H, scale, stream);
 }
 
 // Backward of d2s_attn_varlen_fwd_lse_f32 (out, lse as that call wrote them): dqkv [total, 3*H*64] is fully written when cu_seqlens covers
@@ -676,15 +678,8 @@ int d2s_attn_varlen_bwd_f32(const float* qkv, const int* cu_seqlens, const float
     if (!qkv || !cu_seqlens || !out || !dout || !lse || !dqkv || !delta_ws || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0)
         return D2S_ERR_ARG;
     if ((long)max_n * 3 * H * 64 >= (1L << 32)) return D2S_ERR_ARG;      // tile_load_u32: one image's qkv panel must fit 32-bit element offsets
-    // delta [H, total]: the dense kernel's [B, H, n] layout with B = 1, n = total
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)(((long)total + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, (long)total, total, H);
-    dim3 grid((max_n + 127) / 128, B * H), block(256);
-    const VarlenSeg seg{cu_seqlens, total};
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, VarlenSeg>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, max_n, H, scale,
-                       static_cast<const float*>(nullptr), seg);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, VarlenSeg>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, max_n, H, scale,
-                       static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), seg);
-    return d2s_check_launch();
+    return attn_bwd_launch<false, false, false, true>(qkv, out, dout, lse, dqkv, delta_ws, B, max_n, H, scale, stream, nullptr, nullptr, nullptr,
+                                                      nullptr, VarlenSeg{cu_seqlens, total});
 }
 
 // Attention whose keys carry weights (token merging at inference): key_w [B,n], key j of image b counts key_w[b,j]
@@ -692,10 +687,7 @@ int d2s_attn_varlen_bwd_f32(const float* qkv, const int* cu_seqlens, const float
 // With every weight 1.0 the output is bit for bit d2s_attn_fwd_f32's.  Its backward is d2s_attn_keyw_bwd_f32.
 int d2s_attn_keyw_fwd_f32(const float* qkv, const float* key_w, float* out, float* lse, int B, int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !key_w || !out || B <= 0 || n < 2 || H <= 0 || n > 8192) return D2S_ERR_ARG;      // a merged sequence keeps CLS and a token
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    AttnFwdArgs a{qkv, out, lse, nullptr, key_w, nullptr, nullptr, n, H, scale, 0.f, 0};
-    hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), grid, block, 0, stream, a);
-    return d2s_check_launch();
+    return attn_fwd_launch<false, false, true>(AttnFwdArgs{qkv, out, lse, nullptr, key_w, nullptr, nullptr, n, H, scale, 0.f, 0}, B, n, stream);
 }
 
 // delta[b,h,i] = sum_d dout[b,i,h,d] * out[b,i,h,d]: the row term of the softmax backward, shared by the fp32 and bf16 backward kernels
@@ -710,14 +702,7 @@ int d2s_attn_delta(const float* out, const float* dout, float* delta, int B, int
 int d2s_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta_ws, int B,
                      int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !out || !dout || !lse || !dqkv || !delta_ws || B <= 0 || n <= 0 || H <= 0) return D2S_ERR_ARG;
-    const long rows = (long)B * n;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
-                       static_cast<const float*>(nullptr));
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
-                       static_cast<const float*>(nullptr), static_cast<const float*>(nullptr));
-    return d2s_check_launch();
+    return attn_bwd_launch<false>(qkv, out, dout, lse, dqkv, delta_ws, B, n, H, scale, stream);
 }
 
 // Backward of d2s_attn_keyw_fwd_f32 (training through token merging): lse as that call wrote it, P_ij = w_j
@@ -726,25 +711,14 @@ int d2s_attn_bwd_f32(const float* qkv, const float* out, const float* dout, cons
 int d2s_attn_keyw_bwd_f32(const float* qkv, const float* key_w, const float* out, const float* dout, const float* lse, float* dqkv,
                           float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !key_w || !out || !dout || !lse || !dqkv || !delta_ws || B <= 0 || n < 2 || H <= 0 || n > 8192) return D2S_ERR_ARG;
-    const long rows = (long)B * n;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, key_w);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, KeyWeights>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale,
-                       static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), KeyWeights{key_w});
-    return d2s_check_launch();
+    return attn_bwd_launch<false, false, true>(qkv, out, dout, lse, dqkv, delta_ws, B, n, H, scale, stream, key_w);
 }
 
 // Backward of d2s_attn_policy_fwd_f32 (lse, cinv as that call wrote them).
 int d2s_attn_policy_bwd_f32(const float* qkv, const float* policy, const float* out, const float* dout, const float* lse,
                             const float* cinv, float* dqkv, float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !policy || !out || !dout || !lse || !cinv || !dqkv || !delta_ws || B <= 0 || n <= 0 || H <= 0) return D2S_ERR_ARG;
-    const long rows = (long)B * n;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy, cinv);
-    return d2s_check_launch();
+    return attn_bwd_launch<true>(qkv, out, dout, lse, dqkv, delta_ws, B, n, H, scale, stream, policy, cinv);
 }
 
 // d2s_attn_policy_bwd_f32 plus the gradient of the policy: dpolicy [B, n] is fully written (column 0 = 0), dpol_ws: [B, H, n] floats of
@@ -755,13 +729,7 @@ int d2s_attn_policy_bwd_dpol_f32(const float* qkv, const float* policy, const fl
     if (!qkv || !policy || !out || !dout || !lse || !cinv || !dqkv || !delta_ws || !dpolicy || !dpol_ws || B <= 0 || n <= 0 || H <= 0)
         return D2S_ERR_ARG;
     if ((long)n * 3 * H * 64 >= (1L << 32)) return D2S_ERR_ARG;      // tile_load_u32: one image's qkv panel must fit 32-bit element offsets
-    const long rows = (long)B * n;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, out, dout, delta_ws, rows, n, H);
-    dim3 grid((n + 127) / 128, B * H), block(256);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true, float*>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, n, H, scale, policy, cinv, dpol_ws);
-    hipLaunchKernelGGL(attn_dpol_fold_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, dpol_ws, dpolicy, B, n, H);
-    return d2s_check_launch();
+    return attn_bwd_launch<true, true>(qkv, out, dout, lse, dqkv, delta_ws, B, n, H, scale, stream, policy, cinv, dpolicy, dpol_ws);
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@ tests/test_block_routes_gpu.py, which compares a fresh recording with it.
 
 Geometry: the block of tests/test_ragged_bf16_gpu.py (D 128, 2 heads, hidden 512), B = 2, n = 33 (one key tile plus a remainder);
 the ragged case packs the lengths (5, 33); the token-merging block merges r = 5 of the 33 tokens away (28 rows per image in its MLP
-half) or none, with every token one patch (size None) or the fixed patch counts of _size()."""
+half) or none, with every token one patch (size None) or the fixed patch counts of _size().  The attention configurations appended
+last run longer sequences: n = 70 (two full key tiles plus a 6-row remainder; the dense bf16 forward takes its 32-key-tile kernel there)
+and n = 161 (a second workgroup, of 33 queries), and the packed lengths (70, 161)."""
 import torch
 
 from tests.test_ragged_bf16_gpu import BLOCK_D, BLOCK_H, SCALE, _block_params, _cu, _t
@@ -16,6 +18,7 @@ B, N = 2, 33
 RAGGED_LENGTHS = (5, 33)
 EPS = 1e-6
 TOME_R = 5
+ATTN_LENGTHS = (70, 161)
 MODES = ("exact", "split", "bf16", "bf16_noio")          # bf16_noio: bf16 arithmetic with the bf16 data path switched off
 
 
@@ -42,7 +45,8 @@ def configurations():
     for mode in ("exact", "bf16"):
         for policy in ("none", "const", "grad"):
             out.append((f"attn/{mode}/policy_{policy}", dict(kind="attn", mode=mode, policy=policy)))
-    return out + _tome_configurations()          # appended: the caching allocator rounds for the ones above as it did at their recording
+    # appended: the caching allocator rounds for the ones above as it did at their recording
+    return out + _tome_configurations() + _attention_configurations()
 
 
 def _tome_configurations():
@@ -73,6 +77,23 @@ def _tome_configurations():
     return out
 
 
+def _attention_configurations():
+    """every instantiation of the attention kernels past one key tile and past one workgroup, the varlen backward among them"""
+    out = []
+    for n in ATTN_LENGTHS:
+        for mode in ("exact", "bf16"):
+            for policy in ("none", "const", "grad"):
+                out.append((f"attn/{mode}/policy_{policy}/n{n}", dict(kind="attn", mode=mode, policy=policy, n=n)))
+    for mode in ("exact", "bf16"):
+        out.append((f"ragged/{mode}/cls/n70_161", dict(kind="ragged", mode=mode, want_cls=True, lengths=ATTN_LENGTHS)))
+    for lengths in (RAGGED_LENGTHS, ATTN_LENGTHS):          # RaggedBlockFn without a sampling stage: the varlen forward with lse and its backward
+        out.append((f"ragged_train/exact/n{lengths[0]}_{lengths[1]}", dict(kind="ragged_train", mode="exact", train=True, lengths=lengths)))
+    for mode in ("bf16", "bf16_noio"):          # the dense bf16 kernels on bf16 and on fp32 qkv, the forward on 32-key tiles
+        out.append((f"block/{mode}/train/policy_none/nodp/n70",
+                    dict(kind="block", mode=mode, train=True, policy="none", dp=False, composite=True, grads="all", n=70)))
+    return out
+
+
 _HOST = {}
 
 
@@ -90,10 +111,10 @@ def _params():
     return [t.to(DEV) for t in _HOST["params"]]
 
 
-def _policy(kind):
+def _policy(kind, n=N):
     if kind == "none":
         return None
-    p = torch.ones(B, N, device=DEV)
+    p = torch.ones(B, n, device=DEV)
     p[0, 3::4] = 0.0
     p[1, 2::3] = 0.0
     return p.requires_grad_(kind == "grad")
@@ -141,30 +162,41 @@ def _make_call(cfg):
     leaves = {}
     if cfg["kind"] == "tome":
         return _make_tome_call(cfg)
-    if cfg["kind"] == "ragged":
+    if cfg["kind"] in ("ragged", "ragged_train"):
         p = _params()
-        total = sum(RAGGED_LENGTHS)
-        xp, cu = _synth("xr", (total, BLOCK_D)), _cu(RAGGED_LENGTHS).to(DEV)
+        lengths = cfg.get("lengths", RAGGED_LENGTHS)
+        total = sum(lengths)
+        xp, cu = _synth("xr", (total, BLOCK_D)), _cu(lengths).to(DEV)
+        if cfg["kind"] == "ragged_train":
+            from d2s import functional_ats as AF
+            xp.requires_grad_(True)
+            p = [t.requires_grad_(True) for t in p]
+            leaves.update(dx=xp, **{f"dp{i}": t for i, t in enumerate(p)})
+
+            def call():
+                y = AF.ragged_block_train(xp, p, EPS, AF._Ragged(cu, len(lengths), max(lengths), BLOCK_H, SCALE))
+                return dict(y=y), y
+            return call, leaves
 
         def call():
             with torch.no_grad():
-                y, cls_rows = DF.ragged_block_forward(xp, cu, len(RAGGED_LENGTHS), max(RAGGED_LENGTHS), p, BLOCK_H, EPS, SCALE,
-                                                      want_cls=cfg["want_cls"])
+                y, cls_rows = DF.ragged_block_forward(xp, cu, len(lengths), max(lengths), p, BLOCK_H, EPS, SCALE, want_cls=cfg["want_cls"])
             return dict(y=y, cls=cls_rows), None
         return call, leaves
-    policy = _policy(cfg["policy"])
+    n = cfg.get("n", N)
+    policy = _policy(cfg["policy"], n)
     if policy is not None and policy.requires_grad:
         leaves["dpolicy"] = policy
     if cfg["kind"] == "attn":
-        qkv = _synth("qkv", (B * N, 3 * BLOCK_D)).requires_grad_(True)
+        qkv = _synth("qkv", (B * n, 3 * BLOCK_D)).requires_grad_(True)
         leaves["dqkv"] = qkv
         extra = () if policy is None else (policy,)
 
         def call():
-            out, cls_row = DF.AttnCoreFn.apply(qkv, B, N, BLOCK_H, SCALE, True, *extra)
+            out, cls_row = DF.AttnCoreFn.apply(qkv, B, n, BLOCK_H, SCALE, True, *extra)
             return dict(y=out, cls=cls_row), out
         return call, leaves
-    x = _synth("x", (B, N, BLOCK_D)).requires_grad_(cfg["grads"] in ("all", "x"))
+    x = _synth("x", (B, n, BLOCK_D)).requires_grad_(cfg["grads"] in ("all", "x"))
     p = [t.requires_grad_(cfg["grads"] in ("all", "params")) for t in _params()]
     leaves.update(dx=x, **{f"dp{i}": t for i, t in enumerate(p)})
     rows = (torch.tensor([1.25, 0.0], device=DEV), torch.tensor([0.0, 1.25], device=DEV)) if cfg["dp"] else ()
@@ -214,8 +246,11 @@ def record(cfg):
         call, leaves = _make_call(cfg)
         if cfg["kind"] == "tome":          # the merged block's output: n - r rows per image
             gy = _synth("gy", (B * (N - cfg["r"]), BLOCK_D)).view(B, N - cfg["r"], BLOCK_D)
+        elif cfg["kind"] == "ragged_train":
+            gy = _synth("gy", (sum(cfg["lengths"]), BLOCK_D))
         else:
-            gy = _synth("gy", (B * N, BLOCK_D)).view(B, N, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * N, BLOCK_D))
+            n = cfg.get("n", N)
+            gy = _synth("gy", (B * n, BLOCK_D)).view(B, n, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * n, BLOCK_D))
         return call, leaves, gy
     return record_call(make, cfg["mode"], cfg.get("composite", True))
 

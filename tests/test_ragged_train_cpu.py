@@ -174,7 +174,9 @@ def test_ragged_threshold_header_and_binding_tables():
     for fn in ("RaggedPackFn", "RaggedRepackFn", "RaggedPredictorFn", "RaggedMaskLossFn"):
         assert callable(getattr(RF, fn).apply)
     assert callable(RF.ragged_head) and callable(RF.ragged_predictor_forward)
-    assert "ragged-threshold-resources:" in open(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "Makefile")).read()
+    # one pattern target prints every file's resource report; ragged_threshold.hip is a source it serves
+    assert re.search(r"^resources-%: %\.hip$", open(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "Makefile")).read(), flags=re.M)
+    assert os.path.exists(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "ragged_threshold.hip"))
 
 
 def test_library_resolves_the_new_entries():
