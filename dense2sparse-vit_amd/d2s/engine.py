@@ -298,6 +298,9 @@ def checkpoint_config(config):
     theirs.setdefault("ats_locs", [])              # ... and before an Adaptive Token Sampling student could be trained: no such student
     theirs.setdefault("ats_tokens", [])
     theirs.setdefault("train_sample", False)
+    theirs.setdefault("avit_gate_scale", None)     # ... and before the A-ViT baseline existed: no such student
+    theirs.setdefault("avit_gate_center", None)
+    theirs.setdefault("avit_eps_halt", None)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
     return theirs
@@ -504,7 +507,7 @@ class TrainStep:
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
-        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss
+        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss
         if int(accum_steps) != accum_steps or accum_steps < 1:
             raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
         if clip_grad is not None and not float(clip_grad) > 0.0:
@@ -556,7 +559,20 @@ class TrainStep:
                 raise lib.D2SError("TrainStep with an Adaptive Token Sampling student and drop_path_rate > 0: stochastic depth is not built "
                                    "for a ragged block")
             graph = False
-        self.logits_only = self.tome or self.ats
+        # the A-ViT baseline (vit_models/avit.py): logits alone as well, AViTLoss (ToMeLoss plus the two penalty
+        # terms the forward leaves on the model), the teacher optional; every block is a ragged block and reads its row counts on the host
+        self.avit = type(student).__name__ == "VisionTransformerAViT"
+        if self.avit:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with an A-ViT student: the warm-up epochs train the score predictors only "
+                                 "(train.py:50-53), and adaptive depth has none - pass warmup_steps=0")
+            if graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with an A-ViT student is not supported: every block reads its row counts on "
+                                   "the host, which a captured step cannot; run the step eagerly (graph=False)")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with an A-ViT student and drop_path_rate > 0: stochastic depth is not built for a ragged block")
+            graph = False
+        self.logits_only = self.tome or self.ats or self.avit
         # a dynamic-keep-ratio student that trains on the ragged packed batch (ragged_train=True): the ordinary
         # route - both losses, warm-up epochs, the freeze schedule - with the packed outputs handed to the losses; the refusals are those
         # of a ragged block
@@ -586,7 +602,7 @@ class TrainStep:
         self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
         self.tome_loss_fn = None
         if self.logits_only:
-            self.tome_loss_fn = ToMeLoss(args)
+            self.tome_loss_fn = AViTLoss(args) if self.avit else ToMeLoss(args)
             self.mask_loss_fn = self.backbone_loss_fn = None
         elif self.baseline:
             if not getattr(student, "distill", False):
@@ -699,6 +715,7 @@ class TrainStep:
         pe = getattr(s, "patch_embed", None)
         pred = s.score_predictor[0] if len(getattr(s, "score_predictor", [])) else None
         thr = getattr(s, "patch_score_threshold", None)
+        avit = type(s).__name__ == "VisionTransformerAViT"
         return {
             "format": CHECKPOINT_FORMAT,
             "model": type(s).__name__,
@@ -730,6 +747,9 @@ class TrainStep:
             "ats_tokens": [int(v) for v in getattr(s, "ats_tokens", [])],
             "train_sample": bool(getattr(s, "train_sample", False)),
             "ragged_train": bool(getattr(s, "ragged_train", False)),
+            "avit_gate_scale": float(s.gate_scale) if avit else None,
+            "avit_gate_center": float(s.gate_center) if avit else None,
+            "avit_eps_halt": float(s.eps_halt) if avit else None,
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -818,11 +838,16 @@ class TrainStep:
         """ToMeLoss on the merging student's logits; 'mask_loss' reports the weighted distillation term (0 without a teacher)."""
         fn = self.tome_loss_fn
         logits_t = None if out_t is None else out_t[0]
-        loss = fn(logits_s, logits_t, labels, self.metrics, accumulate=accumulate)
+        s = self.student
+        if self.avit:
+            loss = fn(logits_s, logits_t, labels, self.metrics, s.ponder_loss, s.prior_loss, s.avg_depth, accumulate=accumulate)
+            per_block = list(s.tokens_per_layer)
+        else:
+            loss = fn(logits_s, logits_t, labels, self.metrics, accumulate=accumulate)
+            per_block = list(s.tokens_per_stage if self.ats else s.tokens_per_block)
         dist_term = fn.dist_weight * fn.last[2]
         return loss, dict(mask_loss=dist_term, backbone_loss=fn.last[0] - dist_term, kept=None, logits_s=logits_s, token_s=None,
-                          pred_logits=None, logits_t=logits_t, token_t=None, cls_attn=None,
-                          tokens_per_block=list(self.student.tokens_per_stage if self.ats else self.student.tokens_per_block))
+                          pred_logits=None, logits_t=logits_t, token_t=None, cls_attn=None, tokens_per_block=per_block)
 
     def forward_losses(self, images, labels, accumulate=True, next_images=None):
         if self.teacher is None:

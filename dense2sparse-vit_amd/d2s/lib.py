@@ -1,7 +1,7 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
-include/d2s_hip_ragged_train.h, training through a ragged packed batch, and include/d2s_hip_ragged_threshold.h, training the dynamic keep
-ratio on it).
+include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
+ratio on it, and include/d2s_hip_avit.h, per-token adaptive depth).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -175,6 +175,14 @@ _SIGS_RAGGED_THRESHOLD = {
     "d2s_ragged_teacher_rows": (I, [P, L, P, P, P, P, I, I, I, I]),
 }
 
+# the entries of include/d2s_hip_avit.h (the A-ViT baseline: per-token adaptive depth on the ragged batch), same form
+_SIGS_AVIT = {
+    "d2s_avit_halt": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, F]),
+    "d2s_avit_halt_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F]),
+    "d2s_avit_penalty_fwd": (I, [P, P, P, P, P, I, I, I]),
+    "d2s_avit_penalty_bwd": (I, [P, P, P, P, P, P, I, I, I]),
+}
+
 _lib = None
 
 
@@ -192,7 +200,7 @@ def load():
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
-                              + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items())):
+                              + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -222,6 +230,10 @@ def ragged_train_symbols():
 
 def ragged_threshold_symbols():
     return sorted(_SIGS_RAGGED_THRESHOLD)
+
+
+def avit_symbols():
+    return sorted(_SIGS_AVIT)
 
 
 def ptr(t):

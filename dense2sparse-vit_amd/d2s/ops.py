@@ -1375,6 +1375,77 @@ def ragged_teacher_rows(token_t, cu, row_src):
     return out, w
 
 
+# ---- the A-ViT baseline: per-token adaptive depth on the ragged batch (csrc/avit.hip) ----
+def avit_state(B, N, D, L, device):
+    """The cleared state of one forward: c, R [B, N] fp32 and halt_layer [B, N] int32 (0: live), acc and ysave [B, D], part [L, B, 3]."""
+    z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=device)
+    return dict(c=z(B, N), R=z(B, N), nh=z(B, N, dtype=torch.int32), acc=z(B, D), ysave=z(B, D), part=z(L, B, 3))
+
+
+_AVIT_THR = {}
+
+
+def avit_halt(y, cu, row_src, st, layer, last, gamma, beta, eps_halt, save=True):
+    """The halting step of block `layer` (1-based) on y [total, D]: updates st (avit_state) in place.
+    -> (keep [total], counts [B] int32, w [B], h [total] or None, ycls [B, D] or None); the last two only with save (a backward follows)."""
+    _f32(y)
+    total, D = y.shape
+    B, N = st["c"].shape
+    assert cu.numel() == B + 1 and row_src.numel() == total and cu.dtype == torch.int32 and row_src.dtype == torch.int32
+    assert 1 <= layer <= st["part"].shape[0] and st["acc"].shape == (B, D)
+    dev = y.device
+    keep = torch.empty((total,), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    w = torch.empty((B,), dtype=torch.float32, device=dev)
+    h = torch.empty((total,), dtype=torch.float32, device=dev) if save else None
+    ycls = torch.empty((B, D), dtype=torch.float32, device=dev) if save else None
+    thr = _AVIT_THR.get(eps_halt)
+    if thr is None:                       # 1 - eps as the fp32 subtraction gives it: the kernel compares against this value, strictly
+        thr = _AVIT_THR[eps_halt] = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(float(eps_halt), dtype=torch.float32))
+    lib.call("d2s_avit_halt", lib.ptr(y), lib.ptr(cu), lib.ptr(row_src), lib.ptr(st["c"]), lib.ptr(st["R"]), lib.ptr(st["nh"]), lib.ptr(h),
+             lib.ptr(w), lib.ptr(st["acc"]), lib.ptr(ycls), lib.ptr(st["ysave"]) if save else None, lib.ptr(keep), lib.ptr(counts),
+             lib.ptr(st["part"][layer - 1]), B, N, D, total, int(layer), int(bool(last)), float(gamma), float(beta), thr)
+    return keep, counts, w, h, ycls
+
+
+def avit_halt_bwd(g, h, cu, row_src, st, w, dacc, ycls, gsc, layer, gamma):
+    """Backward of avit_halt for block `layer` after the finished forward.  g [total, D]: the gradient that arrived through the re-pack,
+    updated in place - or None (the last layer), then a new tensor is written in full.  -> g"""
+    B, N = st["c"].shape
+    total = h.numel()
+    D = dacc.shape[1]
+    L = gsc.numel() - 1
+    fresh = g is None
+    if fresh:
+        g = torch.empty((total, D), dtype=torch.float32, device=h.device)
+    assert g.is_contiguous() and g.dtype == torch.float32 and tuple(g.shape) == (total, D)
+    _f32(dacc), _f32(ycls), _f32(gsc)
+    lib.call("d2s_avit_halt_bwd", lib.ptr(g), lib.ptr(h), lib.ptr(cu), lib.ptr(row_src), lib.ptr(st["nh"]), lib.ptr(w), lib.ptr(dacc),
+             lib.ptr(ycls), lib.ptr(st["ysave"]), lib.ptr(gsc), B, N, D, total, int(layer), L, int(fresh), float(gamma))
+    return g
+
+
+def avit_penalty_fwd(part, tgt, N):
+    """part [L, B, 3], tgt [L] -> (out [2] = {ponder mean, distribution prior}, hbar [L], cnt [L])"""
+    L, B, _ = part.shape
+    _f32(part), _f32(tgt)
+    dev = part.device
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    hbar = torch.empty((L,), dtype=torch.float32, device=dev)
+    cnt = torch.empty((L,), dtype=torch.float32, device=dev)
+    lib.call("d2s_avit_penalty_fwd", lib.ptr(part), lib.ptr(tgt), lib.ptr(out), lib.ptr(hbar), lib.ptr(cnt), L, B, int(N))
+    return out, hbar, cnt
+
+
+def avit_penalty_bwd(hbar, cnt, tgt, dponder, dprior, B, N):
+    """dponder, dprior: device scalars -> gsc [L + 1], the factors avit_halt_bwd applies"""
+    L = hbar.numel()
+    gsc = torch.empty((L + 1,), dtype=torch.float32, device=hbar.device)
+    lib.call("d2s_avit_penalty_bwd", lib.ptr(hbar), lib.ptr(cnt), lib.ptr(_f32(tgt)), lib.ptr(_f32(dponder)), lib.ptr(_f32(dprior)),
+             lib.ptr(gsc), L, int(B), int(N))
+    return gsc
+
+
 def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
     """Ragged attention forward on the bf16 matrix cores (bf16 arithmetic mode): qkv [total, 3*H*64] fp32 or bf16 (the qkv GEMM's c16);
     always writes the bf16 copy of its output for the projection GEMM.  -> (out or None, cls_row [H, total] or None, out16)"""

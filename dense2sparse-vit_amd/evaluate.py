@@ -15,8 +15,11 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
-    # DynamicViT, Token Merging and Adaptive Token Sampling baselines: eval returns logits alone
-    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS")
+    # DynamicViT, Token Merging, Adaptive Token Sampling and A-ViT baselines: eval returns logits alone
+    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS",
+                                        "VisionTransformerAViT")
+    avit = type(model).__name__ == "VisionTransformerAViT"
+    depth_sum = 0.0
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():
@@ -29,6 +32,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
                 correct = float((torch.argmax(logits, dim=1) == val_labels).sum()) / val_labels.shape[0]
                 running_loss += float(loss)
                 running_acc += correct
+                if avit:
+                    depth_sum = depth_sum + model.avg_depth
                 n += 1
                 continue
             cls_attn_weights = teacher_model.forward_cls_attention(val_inputs)          # :33
@@ -58,6 +63,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
          metrics["val_max_keep_ratio"]) = keep_ratio_summary(keep_ratio_batches)
     metrics["val_loss"] = running_loss / n
     metrics["val_acc"] = running_acc / n
+    if avit:
+        metrics["val_avg_depth"] = float(depth_sum) / n
     if not baseline:
         metrics["unpruned_acc"] = running_unpruned_acc / n
     args.epoch_acc = metrics["val_acc"]

@@ -286,3 +286,38 @@ class ToMeLoss(torch.nn.Module):
         for key, r in zip(("train_tome_loss", "train_cls_loss", "train_cls_kl_loss"), self.running):
             metrics[key] = r / self.count
         self.count += 1
+
+
+class AViTLoss(ToMeLoss):
+    """The objective of the A-ViT baseline (the reference has no A-ViT): ToMeLoss's two terms plus the two penalty
+    terms the model's forward leaves behind (VisionTransformerAViT.ponder_loss / prior_loss, computed by d2s_avit_penalty_fwd):
+
+        L = cls_weight * CE + dist_weight * KL(student || teacher) + ponder_scale * mean_{b,t}(n + R) + prior_alpha * P
+
+    The running means are 0-d device tensors, `float(v)` reads them."""
+
+    def __init__(self, args):
+        super().__init__(args)
+        self.ponder_scale = float(getattr(args, "avit_ponder_scale", 5e-4))
+        self.prior_alpha = float(getattr(args, "avit_prior_alpha", 0.01))
+        self.running_avit = [0, 0, 0]
+
+    def forward(self, logits_s, logits_t, train_labels, metrics, ponder, prior, avg_depth, accumulate=True):
+        """ponder, prior: the model's two penalty terms (0-d, differentiable); avg_depth: its mean halting layer (0-d)"""
+        loss = super().forward(logits_s, logits_t, train_labels, metrics, accumulate=False)
+        loss = loss + self.ponder_scale * ponder + self.prior_alpha * prior
+        self.last = (loss.detach(),) + tuple(self.last[1:])
+        self.last_avit = (ponder.detach(), prior.detach(), avg_depth.detach())
+        if accumulate:
+            self.accumulate(metrics, self.last, self.last_avit)
+        return loss
+
+    def accumulate(self, metrics, last, last_avit):
+        """Advance the running means by one batch."""
+        self.running = [r + v for r, v in zip(self.running, last)]
+        self.running_avit = [r + v for r, v in zip(self.running_avit, last_avit)]
+        for key, r in zip(("train_avit_loss", "train_cls_loss", "train_cls_kl_loss"), self.running):
+            metrics[key] = r / self.count
+        for key, r in zip(("train_ponder_loss", "train_prior_loss", "train_avg_depth"), self.running_avit):
+            metrics[key] = r / self.count
+        self.count += 1

@@ -28,6 +28,7 @@ are outside the path.
         --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
     python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --eval-only \
         --student-checkpoint deit_small.pth                               (adaptive token sampling: every image keeps its own count)
+    python dense2sparse-vit_amd/mask_predictor.py --method avit --arch deit_small --student-checkpoint deit_small.pth --dist-weight 0
     python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --ats-train \
         --student-checkpoint deit_small.pth --teacher-checkpoint deit_small.pth --epochs 30      (fine-tune through the sampling stages)
 """
@@ -50,6 +51,7 @@ _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": 
              "deit_base": "dynamic_vit_base_patch16_224_student"}
 _TOME = {"deit_tiny": "tome_deit_tiny_patch16_224", "deit_small": "tome_deit_small_patch16_224", "deit_base": "tome_deit_base_patch16_224"}
 _ATS = {"deit_tiny": "ats_deit_tiny_patch16_224", "deit_small": "ats_deit_small_patch16_224", "deit_base": "ats_deit_base_patch16_224"}
+_AVIT = {"deit_tiny": "avit_deit_tiny_patch16_224", "deit_small": "avit_deit_small_patch16_224", "deit_base": "avit_deit_base_patch16_224"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
@@ -58,6 +60,10 @@ _NOT_WITH_DYNAMICVIT = (("topk_selection", "--topk-selection"), ("diff_topk", "-
 # --method ats: the selection rules of the dense-to-sparse student, which a sampling stage replaces
 _NOT_WITH_ATS = (("topk_selection", "--topk-selection"), ("attn_selection", "--attn-selection"), ("fuse_dropped", "--fuse-dropped"),
                  ("squeeze_dropped", "--squeeze-dropped"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"))
+# --method avit: its five flags with their defaults (parse_args leaves them None so that a flag given under another method is seen)
+_AVIT_FLAGS = (("avit_gate_scale", "--avit-gate-scale", 10.0), ("avit_gate_center", "--avit-gate-center", 30.0),
+               ("avit_ponder_scale", "--avit-ponder-scale", 5e-4), ("avit_prior_alpha", "--avit-prior-alpha", 0.01),
+               ("avit_target_depth", "--avit-target-depth", 7.0))
 
 
 def check_supported(args):
@@ -123,6 +129,25 @@ def check_supported(args):
             bad.append(f"--ats-tokens {' '.join(str(v) for v in ats_tokens)} (at least 1 token per stage)")
     elif ats_tokens is not None:
         bad.append(f"--ats-tokens with --method {getattr(args, 'method', 'd2s')} (tokens are sampled by --method ats only)")
+    avit = getattr(args, "method", "d2s") == "avit"
+    if avit:
+        for attr, flag in _NOT_WITH_ATS:
+            if getattr(args, attr, None) not in (None, False):
+                bad.append(f"--method avit with {flag} (every token halts by its own cumulative score: there is no selection stage)")
+        if not args.eval_only and getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--method avit with --gemm-mode bf16 (training through a ragged block is built on the fp32 data path; exact and "
+                       "split run, --eval-only runs in all three)")
+        if getattr(args, "drop_path", 0.0) > 0.0:
+            bad.append(f"--method avit with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block)")
+        if args.torch_optim:
+            bad.append("--method avit with --torch-optim (an adaptive-depth student trains through the fused step only)")
+        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
+            bad.append(f"--method avit with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and "
+                       "adaptive depth has none: pass 0 or leave it out)")
+    else:
+        for attr, flag, _ in _AVIT_FLAGS:
+            if getattr(args, attr, None) is not None:
+                bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the A-ViT baseline: --method avit)")
     if bool(getattr(args, "ragged_train", False)):
         if args.patch_score_threshold is None:
             bad.append("--ragged-train without --patch-score-threshold (it trains the dynamic keep ratio on the ragged packed batch; the "
@@ -246,6 +271,11 @@ def check_supported(args):
     if args.output_dir and args.torch_optim and not args.eval_only:
         print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
               "loads through --student-checkpoint, it cannot be resumed")
+    if avit:
+        args.warmup_steps = 0                # not given (refused above otherwise)
+        for attr, _, default in _AVIT_FLAGS:
+            if getattr(args, attr, None) is None:
+                setattr(args, attr, default)
     if ats_train:
         args.warmup_steps = 0                # not given (refused above otherwise): the reference's default of 5 predictor-only epochs has no meaning here
     if tome_train and args.warmup_steps > 0:
@@ -280,6 +310,12 @@ def build_models(args):
         if args.dist_weight != 0:
             teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
         return build_ats(args, train_sample=True), teacher
+    if getattr(args, "method", "d2s") == "avit":
+        # the adaptive-depth student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
+        teacher = None
+        if args.dist_weight != 0:
+            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
+        return build_avit(args), teacher
     if getattr(args, "method", "d2s") == "dynamicvit":
         student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
                                                                     drop_path_rate=getattr(args, "drop_path", 0.0),
@@ -339,6 +375,16 @@ def build_ats(args, **kw):
         toks = int(toks[0])
     model = getattr(vit_models, _ATS[arch])(ats_locs=list(args.pruning_locs), ats_tokens=toks, **kw)
     return load_trunk(args, model, "ats", "adaptive token sampling has no predictor")
+
+
+def build_avit(args):
+    """--method avit: the dense DeiT trunk with per-token adaptive depth; the gate constants and the prior's target depth from --avit-*."""
+    arch = args.arch if args.arch in _AVIT else "deit_small"
+    d = {attr: default for attr, _, default in _AVIT_FLAGS}
+    get = lambda attr: d[attr] if getattr(args, attr, None) is None else getattr(args, attr)
+    model = getattr(vit_models, _AVIT[arch])(gate_scale=get("avit_gate_scale"), gate_center=get("avit_gate_center"),
+                                             target_depth=get("avit_target_depth"))
+    return load_trunk(args, model, "avit", "adaptive depth has no predictor")
 
 
 def folder_loaders(args, samples, split, epoch, rank, world):
@@ -561,6 +607,10 @@ def main(argv=None):
             per = [c.float() for c in student.tokens_per_stage]       # the last validation batch's
             print(f"--method ats --pruning-locs {' '.join(str(v) for v in student.ats_locs)} --ats-train: ats tokens per stage: "
                   f"mean {[round(float(c.mean()), 1) for c in per]} min {[int(c.min()) for c in per]} max {[int(c.max()) for c in per]}")
+        if rank == 0 and args.method == "avit":
+            print(f"--method avit: tokens per layer {student.tokens_per_layer} (the last validation batch's), "
+                  f"train_avg_depth={float(epoch_metrics['train_avg_depth']):.3f}, train_ponder_loss={float(epoch_metrics['train_ponder_loss']):.4f}, "
+                  f"train_prior_loss={float(epoch_metrics['train_prior_loss']):.4f}")
         if rank == 0:
             print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))

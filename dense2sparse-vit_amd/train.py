@@ -10,7 +10,7 @@ the mean over the window, clipped to the global L2 norm M.  A TrainStep carries 
 step) and is flushed at the end of the epoch; for a torch optimizer the same window is spelled out here with torch."""
 import torch
 
-from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss
+from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss
 
 
 def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mixup_fn=None):
@@ -27,13 +27,17 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         raise ValueError("a Token Merging student trains through d2s.engine.TrainStep only")
     if type(model).__name__ == "VisionTransformerATS" and getattr(model, "ats_locs", []) and not fast:
         raise ValueError("an Adaptive Token Sampling student trains through d2s.engine.TrainStep only")
+    if type(model).__name__ == "VisionTransformerAViT" and not fast:
+        raise ValueError("an A-ViT student trains through d2s.engine.TrainStep only")
     if getattr(model, "ragged_train", False) and not fast:
         raise ValueError("a student that trains on the ragged packed batch (ragged_train=True) trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer
         step.metrics = metrics
-        if getattr(step, "tome", False) or getattr(step, "ats", False):      # the logits-only students
+        if getattr(step, "avit", False):            # the A-ViT baseline: train_ponder_loss, train_prior_loss, train_avg_depth beside ToMeLoss's
+            step.tome_loss_fn = AViTLoss(args)
+        elif getattr(step, "tome", False) or getattr(step, "ats", False):      # the logits-only students
             step.tome_loss_fn = ToMeLoss(args)
         elif baseline:
             step.dynamicvit_loss_fn = DynamicViTLoss(args)

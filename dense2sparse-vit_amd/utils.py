@@ -165,12 +165,23 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats'],
+    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
                         "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "
                         "ats: the Adaptive Token Sampling baseline (stages at --pruning-locs, --ats-tokens; no predictor; --eval-only, or --ats-train to "
-                        "train through the stages)")
+                        "train through the stages); "
+                        "avit: the A-ViT baseline (per-token adaptive depth: every token halts by its own cumulative score and leaves the ragged "
+                        "packed batch, in training too; no predictor; --avit-* set the gate and the two penalty terms)")
+    p.add_argument('--avit-gate-scale', type=float, default=None, metavar='G',
+                   help='with --method avit: the halting score is sigmoid(G * channel 0 - C) (default 10)')
+    p.add_argument('--avit-gate-center', type=float, default=None, metavar='C', help='with --method avit: see --avit-gate-scale (default 30)')
+    p.add_argument('--avit-ponder-scale', type=float, default=None, metavar='W',
+                   help='with --method avit: weight of the ponder term, the mean over all tokens of halting layer + remainder (default 5e-4)')
+    p.add_argument('--avit-prior-alpha', type=float, default=None, metavar='A',
+                   help='with --method avit: weight of the distribution prior, KL(target || mean halting score per layer) (default 0.01)')
+    p.add_argument('--avit-target-depth', type=float, default=None, metavar='T',
+                   help='with --method avit: centre of the Gaussian target of the distribution prior, in layers (default 7)')
     p.add_argument('--ats-tokens', nargs='+', type=int, default=None, metavar='K',
                    help='with --method ats: the most tokens an image keeps at a stage, one value for every stage or one per --pruning-locs '
                         'entry (default: the number of patches); how many of them an image keeps falls out of its own attention')

@@ -17,3 +17,5 @@ from .tome import (VisionTransformerToMe, tome_deit_tiny_patch16_224, tome_deit_
                    tome_deit_base_patch16_224)
 from .ats import (VisionTransformerATS, ats_deit_tiny_patch16_224, ats_deit_small_patch16_224,  # noqa: F401
                   ats_deit_base_patch16_224)
+from .avit import (VisionTransformerAViT, avit_deit_tiny_patch16_224, avit_deit_small_patch16_224,  # noqa: F401
+                   avit_deit_base_patch16_224)
