@@ -301,6 +301,9 @@ def checkpoint_config(config):
     theirs.setdefault("avit_gate_scale", None)     # ... and before the A-ViT baseline existed: no such student
     theirs.setdefault("avit_gate_center", None)
     theirs.setdefault("avit_eps_halt", None)
+    theirs.setdefault("evo_start", None)           # ... and before the Evo-ViT baseline existed: no such student
+    theirs.setdefault("evo_keep", None)
+    theirs.setdefault("evo_tradeoff", None)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
     return theirs
@@ -572,7 +575,16 @@ class TrainStep:
             if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
                 raise lib.D2SError("TrainStep with an A-ViT student and drop_path_rate > 0: stochastic depth is not built for a ragged block")
             graph = False
-        self.logits_only = self.tome or self.ats or self.avit
+        # the Evo-ViT baseline (vit_models/evo.py): logits alone, ToMeLoss, the teacher optional.  Every block sees a
+        # dense batch of a fixed size and nothing is read back on the host: the step may be captured and runs in all three arithmetic modes
+        self.evo = type(student).__name__ == "VisionTransformerEvo"
+        if self.evo:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with an Evo-ViT student: the warm-up epochs train the score predictors only "
+                                 "(train.py:50-53), and the slow-fast update has none - pass warmup_steps=0")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with an Evo-ViT student and drop_path_rate > 0: stochastic depth is not built for a slow-fast block")
+        self.logits_only = self.tome or self.ats or self.avit or self.evo
         # a dynamic-keep-ratio student that trains on the ragged packed batch (ragged_train=True): the ordinary
         # route - both losses, warm-up epochs, the freeze schedule - with the packed outputs handed to the losses; the refusals are those
         # of a ragged block
@@ -716,6 +728,7 @@ class TrainStep:
         pred = s.score_predictor[0] if len(getattr(s, "score_predictor", [])) else None
         thr = getattr(s, "patch_score_threshold", None)
         avit = type(s).__name__ == "VisionTransformerAViT"
+        evo = type(s).__name__ == "VisionTransformerEvo"
         return {
             "format": CHECKPOINT_FORMAT,
             "model": type(s).__name__,
@@ -750,6 +763,9 @@ class TrainStep:
             "avit_gate_scale": float(s.gate_scale) if avit else None,
             "avit_gate_center": float(s.gate_center) if avit else None,
             "avit_eps_halt": float(s.eps_halt) if avit else None,
+            "evo_start": int(s.evo_start) if evo else None,
+            "evo_keep": float(s.evo_keep) if evo else None,
+            "evo_tradeoff": float(s.evo_tradeoff) if evo else None,
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -1130,8 +1146,11 @@ class TrainStep:
         self.last_step_captured = True
         scale = self.reducer.finish() if self.reducer is not None else 1.0
         self.opt.step(grad_scale=scale)
-        self.mask_loss_fn.accumulate(self.metrics, ent["mask_last"])
-        self.backbone_loss_fn.accumulate(self.metrics, ent["backbone_last"])
+        if self.logits_only:                     # the one student of that route a captured step serves: the Evo-ViT baseline
+            self.tome_loss_fn.accumulate(self.metrics, ent["tome_last"])
+        else:
+            self.mask_loss_fn.accumulate(self.metrics, ent["mask_last"])
+            self.backbone_loss_fn.accumulate(self.metrics, ent["backbone_last"])
         return ent["info"]          # static tensors: overwritten by the next replay of this graph
 
     def _capture(self, ent, images, labels):
@@ -1157,4 +1176,7 @@ class TrainStep:
         ent["graph"], ent["info"] = g, info
         ent["ws_refs"] = list(ops._ws.values())       # scratch buffers the recorded kernels point at: must outlive the graph even if an
                                                       # eager call with a larger shape replaces them in ops._ws later
-        ent["mask_last"], ent["backbone_last"] = self.mask_loss_fn.last, self.backbone_loss_fn.last
+        if self.logits_only:
+            ent["tome_last"] = self.tome_loss_fn.last
+        else:
+            ent["mask_last"], ent["backbone_last"] = self.mask_loss_fn.last, self.backbone_loss_fn.last

@@ -1,7 +1,7 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
-ratio on it, and include/d2s_hip_avit.h, per-token adaptive depth).
+ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, and include/d2s_hip_evo.h, the slow-fast token update).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -183,6 +183,14 @@ _SIGS_AVIT = {
     "d2s_avit_penalty_bwd": (I, [P, P, P, P, P, P, I, I, I]),
 }
 
+# the entries of include/d2s_hip_evo.h (the Evo-ViT baseline: slow-fast token update), same form
+_SIGS_EVO = {
+    "d2s_evo_select": (I, [P, P, P, P, P, P, I, I, I, I, F]),
+    "d2s_evo_scatter_fwd": (I, [P, P, P, P, P, I, I, I, I]),
+    "d2s_evo_scatter_bwd": (I, [P, P, P, P, I, I, I, I]),
+    "d2s_evo_gather_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I]),
+}
+
 _lib = None
 
 
@@ -200,7 +208,8 @@ def load():
                        "(or `make -C dense2sparse-vit_amd/csrc`). The d2s path has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
-                              + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())):
+                              + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
+                              + list(_SIGS_EVO.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -234,6 +243,10 @@ def ragged_threshold_symbols():
 
 def avit_symbols():
     return sorted(_SIGS_AVIT)
+
+
+def evo_symbols():
+    return sorted(_SIGS_EVO)
 
 
 def ptr(t):

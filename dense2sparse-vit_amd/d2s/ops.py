@@ -1446,6 +1446,69 @@ def avit_penalty_bwd(hbar, cnt, tgt, dponder, dprior, B, N):
     return gsc
 
 
+# ---- the Evo-ViT baseline: slow-fast token update (csrc/evo.hip) ----
+def _evo_shapes(X, kept, dropped):
+    B, n, D = X.shape
+    T, k = n - 1, kept.shape[1]
+    assert kept.dtype == torch.int64 and kept.is_contiguous() and dropped.dtype == torch.int64 and dropped.is_contiguous()
+    assert kept.shape == (B, k) and dropped.shape == (B, T - k), f"X {tuple(X.shape)}: kept must be [B, k], dropped [B, {T} - k]"
+    return B, T, k, D
+
+
+def evo_select(cls_row, k, tau=0.0, g=None, kept_prev=None):
+    """The score evolution and the re-selection of a slow-fast block in one launch.  Without kept_prev: cls_row [B,H,1+T] starts the score,
+    g = mean over heads of its token columns.  With it: cls_row [B,H,k+2] is the row of the block that ran on kept_prev [B,k] and
+    g_out = g with g_out[kept_prev_i] = (1 - tau) g[kept_prev_i] + tau mean_h cls_row[:, h, 1+i].  -> (g_out [B,T], kept [B,k],
+    dropped [B,T-k]), the lists as select_topk(g_out, k) gives them"""
+    _f32(cls_row)
+    B, H, n_c = cls_row.shape
+    k = int(k)
+    if kept_prev is None:
+        T = n_c - 1
+    else:
+        _f32(g)
+        T = g.shape[1]
+        assert kept_prev.dtype == torch.int64 and kept_prev.is_contiguous() and tuple(kept_prev.shape) == (B, k) and n_c == k + 2 \
+            and g.shape[0] == B, (tuple(cls_row.shape), tuple(g.shape), tuple(kept_prev.shape), k)
+    dev = cls_row.device
+    g_out = torch.empty((B, T), dtype=torch.float32, device=dev)
+    kept = torch.empty((B, k), dtype=torch.int64, device=dev)
+    dropped = torch.empty((B, max(T - k, 0)), dtype=torch.int64, device=dev)
+    lib.call("d2s_evo_select", lib.ptr(g), lib.ptr(kept_prev), lib.ptr(cls_row), lib.ptr(g_out), lib.ptr(kept), lib.ptr(dropped), B, H, T,
+             k, float(tau))
+    return g_out, kept, dropped
+
+
+def evo_scatter_fwd(X, yc, xc, kept, dropped):
+    """The write-back of a slow-fast block, in place on X [B,1+T,D]: CLS and kept rows from yc [B,k+2,D], every dropped row
+    += yc[:, k+1] - xc[:, k+1].  -> X"""
+    _f32(X), _f32(yc), _f32(xc)
+    B, T, k, D = _evo_shapes(X, kept, dropped)
+    assert yc.shape == xc.shape == (B, k + 2, D)
+    lib.call("d2s_evo_scatter_fwd", lib.ptr(yc), lib.ptr(xc), lib.ptr(kept), lib.ptr(dropped), lib.ptr(X), B, T, k, D)
+    return X
+
+
+def evo_scatter_bwd(dX, kept, dropped):
+    """dX [B,1+T,D], the gradient of the written-back X -> dyc [B,k+2,D]; its last row is delta, the sum of the dropped rows of dX"""
+    _f32(dX)
+    B, T, k, D = _evo_shapes(dX, kept, dropped)
+    dyc = torch.empty((B, k + 2, D), dtype=torch.float32, device=dX.device)
+    lib.call("d2s_evo_scatter_bwd", lib.ptr(dX), lib.ptr(kept), lib.ptr(dropped), lib.ptr(dyc), B, T, k, D)
+    return dyc
+
+
+def evo_gather_bwd(dX, dxc, dyc, g, S, kept, dropped):
+    """In place on dX [B,1+T,D] (in: the gradient of the written-back X; out: the gradient of X before the block): CLS and kept rows from
+    dxc [B,k+2,D], dropped row j += (g_j / S) (dxc[:, k+1] - dyc[:, k+1]).  -> dX"""
+    _f32(dX), _f32(dxc), _f32(dyc), _f32(g), _f32(S)
+    B, T, k, D = _evo_shapes(dX, kept, dropped)
+    assert dxc.shape == dyc.shape == (B, k + 2, D) and g.shape == (B, T) and S.shape == (B,)
+    lib.call("d2s_evo_gather_bwd", lib.ptr(dxc), lib.ptr(dyc), lib.ptr(g), lib.ptr(S), lib.ptr(kept), lib.ptr(dropped), lib.ptr(dX), B, T,
+             k, D)
+    return dX
+
+
 def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
     """Ragged attention forward on the bf16 matrix cores (bf16 arithmetic mode): qkv [total, 3*H*64] fp32 or bf16 (the qkv GEMM's c16);
     always writes the bf16 copy of its output for the projection GEMM.  -> (out or None, cls_row [H, total] or None, out16)"""

@@ -15,9 +15,9 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
-    # DynamicViT, Token Merging, Adaptive Token Sampling and A-ViT baselines: eval returns logits alone
+    # DynamicViT, Token Merging, Adaptive Token Sampling, A-ViT and Evo-ViT baselines: eval returns logits alone
     baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS",
-                                        "VisionTransformerAViT")
+                                        "VisionTransformerAViT", "VisionTransformerEvo")
     avit = type(model).__name__ == "VisionTransformerAViT"
     depth_sum = 0.0
     thr = getattr(args, "patch_score_threshold", None) is not None

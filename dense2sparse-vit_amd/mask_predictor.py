@@ -52,6 +52,7 @@ _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": 
 _TOME = {"deit_tiny": "tome_deit_tiny_patch16_224", "deit_small": "tome_deit_small_patch16_224", "deit_base": "tome_deit_base_patch16_224"}
 _ATS = {"deit_tiny": "ats_deit_tiny_patch16_224", "deit_small": "ats_deit_small_patch16_224", "deit_base": "ats_deit_base_patch16_224"}
 _AVIT = {"deit_tiny": "avit_deit_tiny_patch16_224", "deit_small": "avit_deit_small_patch16_224", "deit_base": "avit_deit_base_patch16_224"}
+_EVO = {"deit_tiny": "evo_deit_tiny_patch16_224", "deit_small": "evo_deit_small_patch16_224", "deit_base": "evo_deit_base_patch16_224"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
@@ -64,6 +65,9 @@ _NOT_WITH_ATS = (("topk_selection", "--topk-selection"), ("attn_selection", "--a
 _AVIT_FLAGS = (("avit_gate_scale", "--avit-gate-scale", 10.0), ("avit_gate_center", "--avit-gate-center", 30.0),
                ("avit_ponder_scale", "--avit-ponder-scale", 5e-4), ("avit_prior_alpha", "--avit-prior-alpha", 0.01),
                ("avit_target_depth", "--avit-target-depth", 7.0))
+# --method evo: its three flags with their defaults, handled as _AVIT_FLAGS are
+_EVO_FLAGS = (("evo_start", "--evo-start", 4), ("evo_keep", "--evo-keep", 0.5), ("evo_tradeoff", "--evo-tradeoff", 0.5))
+_EVO_DEPTH, _EVO_PATCHES = 12, 196           # the factories' trunk: 12 blocks on the 14 x 14 patches of a 224 image
 
 
 def check_supported(args):
@@ -148,6 +152,31 @@ def check_supported(args):
         for attr, flag, _ in _AVIT_FLAGS:
             if getattr(args, attr, None) is not None:
                 bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the A-ViT baseline: --method avit)")
+    evo = getattr(args, "method", "d2s") == "evo"
+    if evo:
+        for attr, flag in _NOT_WITH_ATS:
+            if getattr(args, attr, None) not in (None, False):
+                bad.append(f"--method evo with {flag} (the slow-fast update ranks tokens by its own global score: there is no selection stage)")
+        if getattr(args, "drop_path", 0.0) > 0.0:
+            bad.append(f"--method evo with --drop-path {args.drop_path} (stochastic depth is not built for a slow-fast block)")
+        if args.torch_optim:
+            bad.append("--method evo with --torch-optim (a slow-fast student trains through the fused step only)")
+        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
+            bad.append(f"--method evo with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and the "
+                       "slow-fast update has none: pass 0 or leave it out)")
+        start = getattr(args, "evo_start", None)
+        if start is not None and not 1 <= start <= _EVO_DEPTH:
+            bad.append(f"--evo-start {start} (a block in 1..{_EVO_DEPTH}, the depth)")
+        keep = getattr(args, "evo_keep", None)
+        if keep is not None and not 1 <= int(_EVO_PATCHES * keep) <= _EVO_PATCHES - 1:
+            bad.append(f"--evo-keep {keep} (k = int({_EVO_PATCHES} * keep) must lie in 1..{_EVO_PATCHES - 1})")
+        tau = getattr(args, "evo_tradeoff", None)
+        if tau is not None and not 0.0 <= tau <= 1.0:
+            bad.append(f"--evo-tradeoff {tau} (0 <= tau <= 1)")
+    else:
+        for attr, flag, _ in _EVO_FLAGS:
+            if getattr(args, attr, None) is not None:
+                bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the Evo-ViT baseline: --method evo)")
     if bool(getattr(args, "ragged_train", False)):
         if args.patch_score_threshold is None:
             bad.append("--ragged-train without --patch-score-threshold (it trains the dynamic keep ratio on the ragged packed batch; the "
@@ -276,6 +305,11 @@ def check_supported(args):
         for attr, _, default in _AVIT_FLAGS:
             if getattr(args, attr, None) is None:
                 setattr(args, attr, default)
+    if evo:
+        args.warmup_steps = 0                # not given (refused above otherwise)
+        for attr, _, default in _EVO_FLAGS:
+            if getattr(args, attr, None) is None:
+                setattr(args, attr, default)
     if ats_train:
         args.warmup_steps = 0                # not given (refused above otherwise): the reference's default of 5 predictor-only epochs has no meaning here
     if tome_train and args.warmup_steps > 0:
@@ -316,6 +350,12 @@ def build_models(args):
         if args.dist_weight != 0:
             teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
         return build_avit(args), teacher
+    if getattr(args, "method", "d2s") == "evo":
+        # the slow-fast student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
+        teacher = None
+        if args.dist_weight != 0:
+            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
+        return build_evo(args), teacher
     if getattr(args, "method", "d2s") == "dynamicvit":
         student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
                                                                     drop_path_rate=getattr(args, "drop_path", 0.0),
@@ -385,6 +425,15 @@ def build_avit(args):
     model = getattr(vit_models, _AVIT[arch])(gate_scale=get("avit_gate_scale"), gate_center=get("avit_gate_center"),
                                              target_depth=get("avit_target_depth"))
     return load_trunk(args, model, "avit", "adaptive depth has no predictor")
+
+
+def build_evo(args):
+    """--method evo: the dense DeiT trunk with the slow-fast token update from block --evo-start on."""
+    arch = args.arch if args.arch in _EVO else "deit_small"
+    d = {attr: default for attr, _, default in _EVO_FLAGS}
+    get = lambda attr: d[attr] if getattr(args, attr, None) is None else getattr(args, attr)
+    model = getattr(vit_models, _EVO[arch])(evo_start=get("evo_start"), evo_keep=get("evo_keep"), evo_tradeoff=get("evo_tradeoff"))
+    return load_trunk(args, model, "evo", "the slow-fast update has no predictor")
 
 
 def folder_loaders(args, samples, split, epoch, rank, world):
@@ -611,6 +660,9 @@ def main(argv=None):
             print(f"--method avit: tokens per layer {student.tokens_per_layer} (the last validation batch's), "
                   f"train_avg_depth={float(epoch_metrics['train_avg_depth']):.3f}, train_ponder_loss={float(epoch_metrics['train_ponder_loss']):.4f}, "
                   f"train_prior_loss={float(epoch_metrics['train_prior_loss']):.4f}")
+        if rank == 0 and args.method == "evo":
+            print(f"--method evo --evo-start {args.evo_start} --evo-keep {args.evo_keep} --evo-tradeoff {args.evo_tradeoff}: "
+                  f"tokens per block {student.tokens_per_block}")
         if rank == 0:
             print(f"epoch {epoch + 1}: {n_images * world / dt:.1f} train images/s, " +
                   ", ".join(f"{k}={v:.4f}" for k, v in sorted(epoch_metrics.items()) if isinstance(v, float)))

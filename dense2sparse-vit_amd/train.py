@@ -29,6 +29,8 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         raise ValueError("an Adaptive Token Sampling student trains through d2s.engine.TrainStep only")
     if type(model).__name__ == "VisionTransformerAViT" and not fast:
         raise ValueError("an A-ViT student trains through d2s.engine.TrainStep only")
+    if type(model).__name__ == "VisionTransformerEvo" and not fast:
+        raise ValueError("an Evo-ViT student trains through d2s.engine.TrainStep only")
     if getattr(model, "ragged_train", False) and not fast:
         raise ValueError("a student that trains on the ragged packed batch (ragged_train=True) trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
@@ -37,7 +39,7 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         step.metrics = metrics
         if getattr(step, "avit", False):            # the A-ViT baseline: train_ponder_loss, train_prior_loss, train_avg_depth beside ToMeLoss's
             step.tome_loss_fn = AViTLoss(args)
-        elif getattr(step, "tome", False) or getattr(step, "ats", False):      # the logits-only students
+        elif getattr(step, "tome", False) or getattr(step, "ats", False) or getattr(step, "evo", False):      # the logits-only students
             step.tome_loss_fn = ToMeLoss(args)
         elif baseline:
             step.dynamicvit_loss_fn = DynamicViTLoss(args)

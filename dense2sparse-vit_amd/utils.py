@@ -165,14 +165,22 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit'],
+    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit', 'evo'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
                         "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "
                         "ats: the Adaptive Token Sampling baseline (stages at --pruning-locs, --ats-tokens; no predictor; --eval-only, or --ats-train to "
                         "train through the stages); "
                         "avit: the A-ViT baseline (per-token adaptive depth: every token halts by its own cumulative score and leaves the ragged "
-                        "packed batch, in training too; no predictor; --avit-* set the gate and the two penalty terms)")
+                        "packed batch, in training too; no predictor; --avit-* set the gate and the two penalty terms); "
+                        "evo: the Evo-ViT baseline (slow-fast token update: no token is removed, from block --evo-start on a block runs on the "
+                        "--evo-keep share of the tokens with the highest global score plus one representative of the rest; no predictor)")
+    p.add_argument('--evo-start', type=int, default=None, metavar='S',
+                   help='with --method evo: the first slow-fast block, 1..depth; the blocks before it are dense (default 4)')
+    p.add_argument('--evo-keep', type=float, default=None, metavar='R',
+                   help='with --method evo: a slow-fast block runs on k = int(patches * R) tokens (default 0.5)')
+    p.add_argument('--evo-tradeoff', type=float, default=None, metavar='TAU',
+                   help="with --method evo: a kept token's global score becomes (1 - TAU) * score + TAU * the block's CLS attention (default 0.5)")
     p.add_argument('--avit-gate-scale', type=float, default=None, metavar='G',
                    help='with --method avit: the halting score is sigmoid(G * channel 0 - C) (default 10)')
     p.add_argument('--avit-gate-center', type=float, default=None, metavar='C', help='with --method avit: see --avit-gate-scale (default 30)')

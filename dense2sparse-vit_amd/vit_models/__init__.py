@@ -19,3 +19,5 @@ from .ats import (VisionTransformerATS, ats_deit_tiny_patch16_224, ats_deit_smal
                   ats_deit_base_patch16_224)
 from .avit import (VisionTransformerAViT, avit_deit_tiny_patch16_224, avit_deit_small_patch16_224,  # noqa: F401
                    avit_deit_base_patch16_224)
+from .evo import (VisionTransformerEvo, evo_deit_tiny_patch16_224, evo_deit_small_patch16_224,  # noqa: F401
+                  evo_deit_base_patch16_224)
