@@ -729,6 +729,23 @@ static int splitk_slices(int tiles, int K) {
     return slices;
 }
 
+// Tile and K slices of the exact kernels of this file (mode 0; the weight gradient, layout 2, also in mode 1), written once: the launch
+// (gemm_impl), the workspace query and the plan query (d2s_gemm_f32_plan) all read them here.  The weight gradient always runs 128x128
+// tiles (64x64 wgrad tiles for the small 384x384 weights: measured slower).  `slices` is the count after k_per_slice was rounded up
+// to whole K-steps, i.e. the z extent of the grid.
+struct ExactPlan { Tile tile; int tiles, slices, k_per_slice; };
+static ExactPlan exact_plan(int layout, int M, int N, int K) {
+    ExactPlan pl;
+    pl.tile = layout == 2 ? Tile{128, 128, 1.f} : pick_tile(M, N);
+    pl.tiles = ((M + pl.tile.bm - 1) / pl.tile.bm) * ((N + pl.tile.bn - 1) / pl.tile.bn);
+    const int want = layout == 2 ? splitk_slices(pl.tiles, K) : nt_slices(pl.tiles, K);
+    int kper = (K + want - 1) / want;
+    kper = ((kper + BK - 1) / BK) * BK;
+    pl.k_per_slice = kper;
+    pl.slices = (K + kper - 1) / kper;
+    return pl;
+}
+
 #ifdef D2S_STAMPS
 extern "C" int d2s_debug_read_stamps_f32(unsigned long long* host_out, int n_wg) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps_f32), (size_t)n_wg * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
@@ -745,13 +762,12 @@ extern "C" {
 size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode) {
     if (layout != 2 && mode != 0) return split_workspace_bytes(mode == 1 ? 3 : 1, M, N, K);   // bf16 piece matrices
     if (layout != 2) {
-        const Tile t = pick_tile(M, N);
-        const int sl = nt_slices(((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn), K);
+        const int sl = exact_plan(layout, M, N, K).slices;
         return sl > 1 ? (size_t)sl * M * N * sizeof(float) : 0;
     }
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);      // (64x64 wgrad tiles for the small 384x384 weights: measured slower)
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     if (mode != 2) {      // C slabs + fused bias-gradient slabs
-        const int slices = splitk_slices(tiles, K);
+        const int slices = exact_plan(2, M, N, K).slices;
         return slices <= 1 ? 0 : ((size_t)slices * M * N + (size_t)slices * M) * sizeof(float);
     }
     // mode 2: C slabs + bf16 pieces of both operands + scratch of the separate bias-gradient pass (see gemm_impl)
@@ -759,8 +775,19 @@ size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode) {
     return ws_align(((size_t)(slices + 1) * M * N) * sizeof(float)) + ws_align(split_tn_pieces_bytes(1, M, N, K)) + (size_t)split_tn_colsum_partials(K) * M * sizeof(float);
 }
 
+// What d2s_gemm_f32 (d2s_linear_wgrad_f32 for layout 2, with M = n_out, N = n_in, K = tokens) launches for a problem: tile_m | tile_n << 16 |
+// k_slices << 32, or 0 for invalid arguments and for the calls that gemm_split.hip runs (layouts 0 / 1 in modes 1 / 2, layout 2 in mode 2).
+// Host arithmetic only (include/d2s_hip_gemm_plan.h).
+size_t d2s_gemm_f32_plan(int layout, int M, int N, int K, int mode) {
+    if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || K <= 0 || mode < 0 || mode > 2) return 0;
+    if (mode != 0 && (layout != 2 || mode == 2)) return 0;
+    const ExactPlan pl = exact_plan(layout, M, N, K);
+    return (size_t)pl.tile.bm | ((size_t)pl.tile.bn << 16) | ((size_t)pl.slices << 32);
+}
+
 // layout 0 = NT (A[M,K], B[N,K]); 1 = NN (A[M,K], B[K,N]); 2 = TN (A[K,M], B[K,N]).
-// epilogue: see enum Epi.  accumulate != 0 (TN only): C += result.  remap_*: see GemmArgs.
+// epilogue: see enum Epi.  accumulate != 0: C += result (TN; on NT / NN it is EPI_ACCUM and goes with epilogue 0 or 8 only).
+// remap_*: see GemmArgs (EPI_BIAS_ROWADD only).
 static int gemm_impl(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                      int K, int epilogue, const float* bias, const float* aux, long ldaux, float* aux_out, int aux_rows,
                      int remap_rows_per_img, int remap_skip, int accumulate, void* workspace, size_t workspace_bytes,
@@ -791,6 +818,11 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
     if ((epilogue == EPI_BIAS_RESID || epilogue == EPI_MUL_GELU_GRAD || epilogue == EPI_MUL_RELU_MASK ||
          epilogue == EPI_BIAS_ROWADD) && !aux)
         return D2S_ERR_ARG;
+    // accumulate on the NT / NN layouts is the epilogue EPI_ACCUM: it does not combine with a bias, residual or activation epilogue
+    // (the single-pass store would drop that epilogue, the split-K combine would drop the accumulation)
+    if (layout != 2 && accumulate && epilogue != EPI_NONE && epilogue != EPI_ACCUM) return D2S_ERR_ARG;
+    // the output row remap belongs to the patch embedding's EPI_BIAS_ROWADD store; no other epilogue applies it
+    if (remap_rows_per_img > 0 && epilogue != EPI_BIAS_ROWADD) return D2S_ERR_ARG;
     GemmArgs p;
     p.aux_bf16 = aux_bf16;
     p.A = A; p.B = B; p.C = C; p.bias = bias; p.aux = aux; p.aux_out = aux_out;
@@ -845,13 +877,10 @@ static int gemm_impl(int layout, const float* A, long lda, const float* B, long 
                                colsum_out, accumulate);
         return d2s_check_launch();
     }
-    Tile tile = layout == 2 ? Tile{128, 128, 1.f} : pick_tile(M, N);
-    const int tiles = ((M + tile.bm - 1) / tile.bm) * ((N + tile.bn - 1) / tile.bn);
-    int slices = layout == 2 ? splitk_slices(tiles, K) : nt_slices(tiles, K);
-    int kper = (K + slices - 1) / slices;
-    kper = ((kper + BK - 1) / BK) * BK;
-    slices = (K + kper - 1) / kper;
-    p.k_per_slice = kper;
+    const ExactPlan plan = exact_plan(layout, M, N, K);
+    const Tile tile = plan.tile;
+    const int tiles = plan.tiles, slices = plan.slices;
+    p.k_per_slice = plan.k_per_slice;
     p.slab_stride = 0;
     float* realC = C;
     if (accumulate && layout != 2 && p.epi == EPI_NONE) p.epi = EPI_ACCUM;

@@ -1,7 +1,8 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
-ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, and include/d2s_hip_evo.h, the slow-fast token update).
+ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, and include/d2s_hip_gemm_plan.h, the
+plan query of the exact fp32 GEMM).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -191,6 +192,12 @@ _SIGS_EVO = {
     "d2s_evo_gather_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I]),
 }
 
+# the entry of include/d2s_hip_gemm_plan.h (which tile and how many K slices the exact fp32 GEMM runs): a size_t query
+# like the workspace ones, no stream
+_SIGS_GEMM_PLAN = {
+    "d2s_gemm_f32_plan": (Z, [I, I, I, I, I]),
+}
+
 _lib = None
 
 
@@ -209,7 +216,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
-                              + list(_SIGS_EVO.items())):
+                              + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -247,6 +254,10 @@ def avit_symbols():
 
 def evo_symbols():
     return sorted(_SIGS_EVO)
+
+
+def gemm_plan_symbols():
+    return sorted(_SIGS_GEMM_PLAN)
 
 
 def ptr(t):
