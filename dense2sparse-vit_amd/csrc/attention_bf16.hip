@@ -24,12 +24,16 @@
 //     As in the fp32 kernels the O(eps) gradient through the row maximum (which the reference's autograd carries because it does not
 //     detach the max) is left out: it is <= eps = 1e-6 relative.
 //
-// VARLEN (the 32-key-tile forward only; no policy, no backward): a ragged packed batch, inference with a dynamic keep ratio
-// (vit_models/dynamic_vit.py:935-949).  Image b owns rows cu[b] .. cu[b+1] of qkv [total, 3, H, 64], of out [total, H*64] and of its bf16
+// VARLEN (the 32-key-tile forward, dQ and dK/dV; no policy): a ragged packed batch, inference with a dynamic keep ratio
+// (vit_models/dynamic_vit.py:935-949) and, with VLSE and the two backward kernels, training on it in the bf16 mode (DESIGN.md section
+// 10.3).  Image b owns rows cu[b] .. cu[b+1] of qkv [total, 3, H, 64], of out [total, H*64] and of its bf16
 // copy; n = cu[b+1] - cu[b] is per image and the kernel's n argument is the bound that sized the grid.  A block whose first query lies past
 // its image returns before any barrier (block-uniform).  The CLS softmax row goes to cls_row[h * total + cu[b] + j]; no log-sum-exp is
-// written (forward only).  With cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same
-// bits.
+// written unless VLSE asks for it: lse[h * total + cu[b] + i] = m + log(l) then, the layout of d2s_attn_varlen_fwd_lse_f32.  With
+// cu = [0, n, 2n, ...] every block does the dense kernel's arithmetic in the dense kernel's order: the same bits.  In the backward kernels
+// lse and delta are read at that place, the 128-row tiles count from the image's own row 0, a workgroup whose tile starts at or past its
+// image's n returns before any barrier, and the segment is clamped to [0, total), its length to [0, max_n] (VarlenSeg): the rows of an
+// image are the bits of the dense backward on that image alone.
 //
 // KEYW (the 32-key-tile forward only; no policy, no ragged form, no backward): attention whose keys carry weights, token merging at
 // inference on the bf16 data path.  out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B, n] >= 1: the
@@ -39,6 +43,7 @@
 // With unit weights the multiply is by 1.0: the bits of the plain kernel.
 #include "d2s_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -83,7 +88,7 @@ __device__ __forceinline__ void tile_policy(const float* __restrict__ pol_s, int
 
 // policy: POLICY's keep policy or KEYW's key weights, [B, n]; cinv, eps: POLICY; cu, total: VARLEN.  The other instantiations read none of them.
 // cinv carries no __restrict__: with it the POLICY instantiations spill 6 SGPRs instead of 2.
-template <typename QT, bool POLICY = false, bool VARLEN = false, bool KEYW = false>
+template <typename QT, bool POLICY = false, bool VARLEN = false, bool KEYW = false, bool VLSE = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restrict__ qkv, float* __restrict__ out,
                                                                __bf16* __restrict__ out16, float* __restrict__ lse, float* __restrict__ cls_row, int n, int H,
                                                                float scale, const float* __restrict__ policy, float* cinv, float eps,
@@ -101,6 +106,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
     const long ld = 3L * H * DH;
     static_assert(!(POLICY && VARLEN), "the ragged form has no policy");
     static_assert(!(KEYW && (POLICY || VARLEN)), "key weights combine with neither the policy nor the ragged form");
+    static_assert(!VLSE || VARLEN, "VLSE: the ragged form that keeps its log-sum-exp for the backward");
     long tok0 = (long)b * n;                       // first token row of the image
     [[maybe_unused]] long cls0 = 0;                // VARLEN: start of the image's CLS softmax row inside cls_row [H, total]
     if constexpr (VARLEN) {
@@ -290,6 +296,9 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_bf16_kernel(const QT* __restr
                 lse[((long)b * H + h) * n + q0 + l31] = m_run + logf(POLICY ? l_run + eps : l_run);
                 if (POLICY) cinv[((long)b * H + h) * n + q0 + l31] = c * inv_l;
             }
+        }
+        if constexpr (VLSE) {
+            if (half == 0) lse[cls0 + q0 + l31] = m_run + logf(l_run);      // [H, total]: the image's rows start where its CLS row does
         }
     }
     if (want_cls) {
@@ -567,13 +576,32 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[2], float* __restric
         }
 }
 
+// VARLEN in the two backward kernels: image b owns rows cu[b] .. cu[b+1] of qkv / dout / dqkv, `n` arrives as max_n.  The segment is clamped
+// to [0, total) and its length to [0, max_n]: no cu value is dereferenced outside the buffers.  The ragged form has no policy, so the
+// segment travels in the place of the kernels' last (policy) argument: the dense and POLICY instantiations keep the argument list, the
+// argument layout and with them the instructions they had (one more argument, even an empty one, moves the hidden grid-size words and
+// re-schedules the DPOL dK/dV).
+struct VarlenSeg { const int* cu; int total; };
+__device__ __forceinline__ int varlen_rows(VarlenSeg v, int b, int max_n, int& row_base) {
+    const int r0 = min(max(v.cu[b], 0), v.total), r1 = min(max(v.cu[b + 1], r0), v.total);
+    row_base = r0;
+    return min(r1 - r0, max_n);
+}
+
 // ---- backward, dQ: a lane owns one query; loop over key tiles (S^T, dP^T, dS^T lane-local, dQ^T = K^T dS^T) ------------------------
-// `policy` is read by the POLICY instantiations only and carries no __restrict__: with it the one on fp32 qkv re-schedules.
-template <typename QT, bool POLICY = false>
+// ONE_KEY (both backward kernels): an image of one key - a CLS-only image of a ragged batch, or the dense entry at n = 1 - has the constant
+// softmax row 1, so dS = 0 and dQ = dK = 0 exactly.  The tile loop leaves (rb(dO) - dO) . v there (dP multiplies the bf16-rounded dO, delta
+// the unrounded one: one bf16 rounding of dO); with the flag the exact zeros are written instead.  The ragged launch sets it and the dense
+// launch picks the flagged instantiation at n = 1 only, so an image's rows stay the bits of the dense backward on that image alone and
+// every instantiation that runs at n > 1 keeps its code.  The POLICY kernels do not take it.
+// `tail` is the policy (const float*; read by the POLICY instantiations only; no __restrict__: with it the one on fp32 qkv re-schedules) or,
+// VARLEN, the segment table.
+template <typename QT, bool POLICY = false, bool VARLEN = false, bool ONE_KEY = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
-                                                                  const float* policy) {
+                                                                  std::conditional_t<VARLEN, VarlenSeg, const float*> tail) {
+    static_assert(!(POLICY && (VARLEN || ONE_KEY)), "the ragged form has no policy, the policy kernels no one-key form");
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Vs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Kt[DH * VP];
@@ -583,18 +611,26 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    const QT* qb = qkv + (long)b * n * ld + h * DH;
+    [[maybe_unused]] int row_base = 0;             // VARLEN: the image's first row of the packed batch
+    [[maybe_unused]] long stat0v = 0;              // VARLEN: the image's first lse / delta entry of [H, total]
+    if constexpr (VARLEN) {
+        n = varlen_rows(tail, b, n, row_base);
+        if (bx * 128 >= n) return;                 // block-uniform, before any barrier: this image has no queries in this tile
+        stat0v = (long)h * tail.total + row_base;
+    }
+    // the dense offsets stay spelled where they are used: the dense instantiations keep their address arithmetic
+    const QT* qb = qkv + (VARLEN ? (long)row_base : (long)b * n) * ld + h * DH;
     const QT* kb = qb + (long)H * DH;
     const QT* vb = kb + (long)H * DH;
-    const float* dob = dout + (long)b * n * ldo + h * DH;
+    const float* dob = dout + (VARLEN ? (long)row_base : (long)b * n) * ldo + h * DH;
     const int q0 = bx * 128 + wave * 32;
     const bool active = q0 < n, qok = q0 + l31 < n;
     bf16x8 qf[4], dof[4];
     row_frags(qb, ld, q0 + l31, n, half, scale, qf);
     constexpr float L2E = 1.44269504088896340736f;      // p = 2^(s log2 e - lse log2 e): one FMA and one v_exp_f32 per element
     row_frags(dob, ldo, q0 + l31, n, half, 1.0f, dof);
-    const float lse_i = qok ? lse[((long)b * H + h) * n + q0 + l31] * 1.44269504088896340736f : INFINITY;
-    const float dl_i = qok ? delta[((long)b * H + h) * n + q0 + l31] : 0.f;
+    const float lse_i = qok ? lse[(VARLEN ? stat0v : ((long)b * H + h) * n) + q0 + l31] * 1.44269504088896340736f : INFINITY;
+    const float dl_i = qok ? delta[(VARLEN ? stat0v : ((long)b * H + h) * n) + q0 + l31] : 0.f;
     f32x16 dq[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dq[0][r] = 0.f; dq[1][r] = 0.f; }
@@ -608,7 +644,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
         pr = kj < n ? p0 : 0.f;
     };
     if constexpr (POLICY) {
-        polb = policy + (long)b * n;
+        polb = tail + (long)b * n;
         fetch_pol(0);
     }
     stage_rows(kb, ld, 0, n, tid, kr);
@@ -655,19 +691,27 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
         pack2(s, pf);
         mma_t(Kt, pf, l31, half, dq);                    // dQ^T[d][query] += sum_key K[key][d] dS^T[key][query]
     }
-    if (active && qok) store_t(dq, dqkv, dqkv16, ((long)b * n + q0 + l31) * ld + h * DH, half, scale);
+    if constexpr (ONE_KEY) {
+        if (n == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { dq[0][r] = 0.f; dq[1][r] = 0.f; }
+        }
+    }
+    if (active && qok) store_t(dq, dqkv, dqkv16, ((VARLEN ? (long)row_base : (long)b * n) + q0 + l31) * ld + h * DH, half, scale);
 }
 
 // ---- backward, dK / dV: a lane owns one key; loop over query tiles ------------------------------------------------------------------
 // The policy arguments, read by the POLICY / DPOL instantiations only (dpol_part [B, H, n]: DPOL).  One struct: as three plain arguments the
 // DPOL instantiations load them in other groups, and the backward with dpolicy measured 0.3 us slower (118.8 -> 119.1 us at B 128, H 6, n 197).
+// VARLEN: the segment table takes the struct's place, as in the dQ kernel.
 struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
-template <typename QT, bool POLICY = false, bool DPOL = false>
+template <typename QT, bool POLICY = false, bool DPOL = false, bool VARLEN = false, bool ONE_KEY = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                                    float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
-                                                                   AttnPolBwd pol) {
+                                                                   std::conditional_t<VARLEN, VarlenSeg, AttnPolBwd> pol) {
     static_assert(!DPOL || POLICY, "the policy's gradient needs a policy");
+    static_assert(!(POLICY && (VARLEN || ONE_KEY)), "the ragged form has no policy, the policy kernels no one-key form");
     __shared__ __attribute__((aligned(16))) __bf16 Qs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Ds[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Qt[DH * VP];
@@ -679,12 +723,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
     const int b = by / H, h = by % H;
     const long ld = 3L * H * DH, ldo = (long)H * DH;
-    const QT* qb = qkv + (long)b * n * ld + h * DH;
+    [[maybe_unused]] int row_base = 0;             // VARLEN: the image's first row of the packed batch
+    [[maybe_unused]] long stat0v = 0;              // VARLEN: the image's first lse / delta entry of [H, total]
+    if constexpr (VARLEN) {
+        n = varlen_rows(pol, b, n, row_base);      // `pol` is the segment table here
+        if (bx * 128 >= n) return;                 // block-uniform, before any barrier: this image has no keys in this tile
+        stat0v = (long)h * pol.total + row_base;
+    }
+    const QT* qb = qkv + (VARLEN ? (long)row_base : (long)b * n) * ld + h * DH;
     const QT* kb = qb + (long)H * DH;
     const QT* vb = kb + (long)H * DH;
-    const float* dob = dout + (long)b * n * ldo + h * DH;
-    const float* lse_b = lse + ((long)b * H + h) * n;
-    const float* dl_b = delta + ((long)b * H + h) * n;
+    const float* dob = dout + (VARLEN ? (long)row_base : (long)b * n) * ldo + h * DH;
+    const float* lse_b = lse + (VARLEN ? stat0v : ((long)b * H + h) * n);
+    const float* dl_b = delta + (VARLEN ? stat0v : ((long)b * H + h) * n);
     const int k0 = bx * 128 + wave * 32;
     const bool active = k0 < n, kok = k0 + l31 < n;
     bf16x8 kf[4], vf[4];
@@ -751,12 +802,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
         mma_t(Dt, pf, l31, half, dv);                    // dV^T[d][key] += sum_query dO[query][d] P[query][key]
         mma_t(Qt, dsf, l31, half, dk);                   // dK^T[d][key] += sum_query Q[query][d] dS[query][key]
     }
-    if (DPOL && active) {
-        dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
-        if (half == 0 && kok) pol.dpol_part[((long)b * H + h) * n + k0 + l31] = dpol_acc;
+    if constexpr (DPOL) {
+        if (active) {
+            dpol_acc += __shfl_xor(dpol_acc, 32, 64);      // the other half-wave's 16 rows of every tile (commutative: both halves hold the same bits)
+            if (half == 0 && kok) pol.dpol_part[((long)b * H + h) * n + k0 + l31] = dpol_acc;
+        }
+    }
+    if constexpr (ONE_KEY) {      // as in the dQ kernel; dV = P^T dO is untouched
+        if (n == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; }
+        }
     }
     if (active && kok) {
-        const long row = ((long)b * n + k0 + l31) * ld + h * DH;
+        const long row = ((VARLEN ? (long)row_base : (long)b * n) + k0 + l31) * ld + h * DH;
         store_t(dk, dqkv, dqkv16, row + (long)H * DH, half, scale);
         store_t(dv, dqkv, dqkv16, row + 2L * H * DH, half, 1.0f);
     }
@@ -791,11 +850,11 @@ static int with_qkv_type(const void* qkv, int qkv_is_bf16, F f) {
 }
 
 // forward launch of the 32-key-tile kernel; n bounds the longest image: it sizes the grid and, when the CLS softmax row is wanted, its LDS
-template <bool POLICY, bool VARLEN, bool KEYW, typename QT>
+template <bool POLICY, bool VARLEN, bool KEYW, bool VLSE = false, typename QT>
 static int attn_fwd_bf16_launch(const QT* qkv, float* out, void* out_bf16, float* lse, float* cls_row, int B, int n, int H, float scale,
                                 hipStream_t stream, const float* policy = nullptr, float* cinv = nullptr, float eps = 0.f,
                                 const int* cu = nullptr, int total = 0) {
-    hipLaunchKernelGGL((attn_fwd_bf16_kernel<QT, POLICY, VARLEN, KEYW>), dim3((n + 127) / 128, B * H), dim3(256),
+    hipLaunchKernelGGL((attn_fwd_bf16_kernel<QT, POLICY, VARLEN, KEYW, VLSE>), dim3((n + 127) / 128, B * H), dim3(256),
                        cls_row ? (size_t)n * sizeof(float) : 0, stream, qkv, out, static_cast<__bf16*>(out_bf16), lse, cls_row, n, H, scale, policy,
                        cinv, eps, cu, total);
     return d2s_check_launch();
@@ -820,6 +879,15 @@ static int attn_bwd_bf16_launch(const QT* qkv, const float* out, const float* do
     if (rc != D2S_OK) return rc;
     dim3 grid((n + 127) / 128, B * H), block(256);
     __bf16* dqkv16 = static_cast<__bf16*>(dqkv_bf16);
+    if constexpr (!POLICY) {
+        if (n == 1) {      // one key: the instantiations that write the exact zeros of dQ and dK (ONE_KEY)
+            hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, false, false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H,
+                               scale, policy);
+            hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, false, false, false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16,
+                               n, H, scale, AttnPolBwd{nullptr, nullptr, nullptr});
+            return d2s_check_launch();
+        }
+    }
     hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, POLICY>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale, policy);
     if (POLICY && dpolicy) {
         hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, POLICY, POLICY>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H, scale,
@@ -838,6 +906,23 @@ static int attn_bwd_bf16_impl(const QT* qkv, const float* out, const float* dout
                               float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
     if (!qkv || !out || !dout || !lse || (!dqkv && !dqkv_bf16) || !delta_ws || B <= 0 || n <= 0 || H <= 0) return D2S_ERR_ARG;
     return attn_bwd_bf16_launch<false>(qkv, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, n, H, scale, stream);
+}
+
+// the ragged backward: d2s_attn_delta over the packed rows (the dense [B, H, n] layout with B = 1, n = total), then the VARLEN dQ and dK/dV;
+// max_n sizes the grid as in the forward
+template <typename QT>
+static int attn_varlen_bwd_bf16_launch(const QT* qkv, const int* cu, const float* out, const float* dout, const float* lse, float* dqkv,
+                                       void* dqkv_bf16, float* delta_ws, int B, int total, int max_n, int H, float scale, hipStream_t stream) {
+    const int rc = d2s_attn_delta(out, dout, delta_ws, 1, total, H, stream);
+    if (rc != D2S_OK) return rc;
+    dim3 grid((max_n + 127) / 128, B * H), block(256);
+    __bf16* dqkv16 = static_cast<__bf16*>(dqkv_bf16);
+    const VarlenSeg seg{cu, total};
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, false, true, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, max_n, H, scale,
+                       seg);
+    hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, false, false, true, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, max_n, H,
+                       scale, seg);
+    return d2s_check_launch();
 }
 
 extern "C" {
@@ -897,8 +982,34 @@ int d2s_attn_varlen_fwd_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seq
     });
 }
 
-// Its backward (lse, cinv as that call wrote them; out its fp32 output): dqkv and / or dqkv_bf16 fully written - at least one.  dpolicy
-// (optional) [B, n]: the gradient of the policy, column 0 = 0; it needs dpol_ws, [B, H, n] floats of scratch.  dqkv does not depend on
+// d2s_attn_varlen_fwd_bf16 that also keeps lse [H, total] (row cu_seqlens[b] + i of head h at h * total + cu_seqlens[b] + i, the layout of
+// d2s_attn_varlen_fwd_lse_f32) for d2s_attn_varlen_bwd_bf16: an instantiation of its own beside the inference one, the same launch geometry,
+// out / out_bf16 / cls_row bit for bit that entry's.
+int d2s_attn_varlen_fwd_lse_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seqlens, float* out, void* out_bf16, float* lse, float* cls_row,
+                                 int B, int total, int max_n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || (!out && !out_bf16) || !lse || B <= 0 || total <= 0 || max_n <= 0 || max_n > 8192 || H <= 0) return D2S_ERR_ARG;
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_fwd_bf16_launch<false, true, false, true>(q, out, out_bf16, lse, cls_row, B, max_n, H, scale, stream, nullptr, nullptr, 0.f,
+                                                              cu_seqlens, total);
+    });
+}
+
+// Its backward (out, lse as that call wrote them; dout [total, H*64]): dqkv [total, 3, H, 64] and / or dqkv_bf16 written - at least one; fully
+// when cu_seqlens covers [0, total), every element once, no atomics; delta_ws: [H, total] floats of scratch.  The dense backward's three
+// launches with every image's rows and statistics taken from cu_seqlens: each image's rows are bit for bit d2s_attn_bwd_bf16_bf16out's on
+// that image alone, in both forms.  64-bit offsets: no panel limit.
+int d2s_attn_varlen_bwd_bf16(const void* qkv, int qkv_is_bf16, const int* cu_seqlens, const float* out, const float* dout, const float* lse,
+                             float* dqkv, void* dqkv_bf16, float* delta_ws, int B, int total, int max_n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !cu_seqlens || !out || !dout || !lse || (!dqkv && !dqkv_bf16) || !delta_ws || B <= 0 || total <= 0 || max_n <= 0 ||
+        max_n > 8192 || H <= 0)
+        return D2S_ERR_ARG;
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_varlen_bwd_bf16_launch(q, cu_seqlens, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, total, max_n, H, scale, stream);
+    });
+}
+
+// Backward of d2s_attn_policy_fwd_bf16 (lse, cinv as that call wrote them; out its fp32 output): dqkv and / or dqkv_bf16 fully written -
+// at least one.  dpolicy (optional) [B, n]: the gradient of the policy, column 0 = 0; it needs dpol_ws, [B, H, n] floats of scratch.  dqkv does not depend on
 // whether dpolicy is asked for; no atomics, two launches are bit-identical.  The kernels address with 64-bit offsets: no panel limit.
 int d2s_attn_policy_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* policy, const float* out, const float* dout, const float* lse,
                              const float* cinv, float* dqkv, void* dqkv_bf16, float* delta_ws, float* dpolicy, float* dpol_ws, int B, int n, int H,

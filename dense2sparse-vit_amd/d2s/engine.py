@@ -306,6 +306,7 @@ def checkpoint_config(config):
     theirs.setdefault("evo_tradeoff", None)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
+    theirs.setdefault("ragged_bf16", False)        # ... and before it could do so in the bf16 arithmetic mode: fp32 modes only
     return theirs
 
 
@@ -760,6 +761,7 @@ class TrainStep:
             "ats_tokens": [int(v) for v in getattr(s, "ats_tokens", [])],
             "train_sample": bool(getattr(s, "train_sample", False)),
             "ragged_train": bool(getattr(s, "ragged_train", False)),
+            "ragged_bf16": bool(getattr(s, "ragged_bf16", False)),
             "avit_gate_scale": float(s.gate_scale) if avit else None,
             "avit_gate_center": float(s.gate_center) if avit else None,
             "avit_eps_halt": float(s.eps_halt) if avit else None,

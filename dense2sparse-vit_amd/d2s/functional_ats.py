@@ -16,7 +16,11 @@ exists in bf16 only and the kernel reads that; the residual stream and the re-pa
 Training (RaggedBlockFn, fp32 data path): the selection is a constant of the backward - score, keep and counts carry no gradient - so the
 hook's backward is one row move (ops.ragged_repack_bwd: a kept row takes the gradient of the row it became, a dropped row zeros) and a
 dropped row is reached only as a key and a value of the stage's own attention, whose backward is the varlen one (ops.attn_varlen_bwd).
-The MLP half's residual gradient lives on the rows that left the stage, the attention half's on the rows that entered it."""
+The MLP half's residual gradient lives on the rows that left the stage, the attention half's on the rows that entered it.
+
+Training in the bf16 arithmetic mode (_Ragged(..., bf16=True)): a block without a stage runs the same sequence
+on the bf16 data path, its attention and the backward on the bf16 matrix cores (ops.attn_varlen_fwd_lse_bf16io / attn_varlen_bwd_bf16io).
+The flag, not the mode, selects the path: without it the bf16 mode is refused as before."""
 import torch
 
 from . import functional as DF
@@ -24,28 +28,41 @@ from . import ops
 from .lib import D2SError
 
 _BF16_REFUSAL = "training through a ragged block runs in the fp32 arithmetic modes (exact, split): the varlen attention backward is an fp32 kernel"
+_BF16_STAGE_REFUSAL = (_BF16_REFUSAL + ".  A block with a sampling stage stays there with bf16=True too: behind the hook between the halves "
+                       "(sample_bwd) the bf16 shadow of the gradient would have to be made again")
+_BF16_MODE_REFUSAL = "a ragged block with bf16=True runs in the bf16 arithmetic mode only (ops.gemm_mode(GEMM_BF16))"
 
 
 class _Ragged:
     """What a ragged packed batch puts into one block's launch sequence, and the constants of its backward (no gradient reaches them).
     cu [B+1], row_src [total] (original token index, 0 at CLS), max_n the longest image.  K: the stage's token limit, or None for a
     block without a stage; plan: (keep, counts) of an earlier forward on the same batch, replayed instead of selecting.  After a stage's
-    forward: cu_new, row_src_new, plan, score / dense (None when replaying); max_n_out either way."""
+    forward: cu_new, row_src_new, plan, score / dense (None when replaying); max_n_out either way.
+    bf16: train on the bf16 data path in the bf16 arithmetic mode (a block without a stage) - attn_train and attn_bwd then honour io,
+    dqkv16 and want_f32 as attn_forward / attn_backward do."""
 
-    def __init__(self, cu, B, max_n, heads, scale, row_src=None, K=None, N=0, plan=None):
+    def __init__(self, cu, B, max_n, heads, scale, row_src=None, K=None, N=0, plan=None, bf16=False):
         self.cu, self.B, self.max_n, self.heads, self.scale = cu, int(B), int(max_n), heads, float(scale)
+        self.bf16 = bool(bf16)
         self.row_src, self.K, self.N, self.plan = row_src, K, N, plan
         self.cu_new = self.row_src_new = self.score = self.dense = None
         self.max_n_out = self.max_n if K is None else min(self.max_n, int(K) + 1)
 
     def attn_train(self, qkv, io, want_f32):
-        """attn_forward's shape on the fp32 data path, keeping the log-sum-exp for attn_bwd"""
+        """attn_forward's shape, keeping the log-sum-exp for attn_bwd: the fp32 kernel, or (bf16, on the bf16 data path) the bf16 one"""
+        if self.bf16 and io:
+            out, lse, cls_rows, out16 = ops.attn_varlen_fwd_lse_bf16io(qkv, self.cu, self.B, qkv.shape[0], self.max_n, self.heads, self.scale,
+                                                                       want_cls=self.K is not None, want_f32=want_f32)
+            return out, lse, None, cls_rows, out16
         out, lse, cls_rows = ops.attn_varlen_fwd_lse(qkv, self.cu, self.B, qkv.shape[0], self.max_n, self.heads, self.scale,
                                                      want_cls=self.K is not None)
         return out, lse, None, cls_rows, None
 
     def attn_bwd(self, qkv, ao, dao, lse, io, dqkv16, want_f32):
         """attn_backward's shape"""
+        if self.bf16 and io:
+            return ops.attn_varlen_bwd_bf16io(qkv, self.cu, ao, dao, lse, self.B, qkv.shape[0], self.max_n, self.heads, self.scale,
+                                              dqkv16=dqkv16, want_f32=want_f32), None
         return ops.attn_varlen_bwd(qkv, self.cu, ao, dao, lse, self.B, qkv.shape[0], self.max_n, self.heads, self.scale), None
 
     def sample(self, qkv, x1, cls_row):
@@ -88,16 +105,27 @@ class RaggedBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xp, *rest):
         params, (eps, r) = rest[:12], rest[12:]
+        stage = r.K is not None
         if ops.get_gemm_mode() == ops.GEMM_BF16:
-            raise D2SError(_BF16_REFUSAL)
+            if not r.bf16:
+                raise D2SError(_BF16_REFUSAL)
+            if stage:
+                raise D2SError(_BF16_STAGE_REFUSAL)
+        elif r.bf16:
+            raise D2SError(_BF16_MODE_REFUSAL)
         train = DF.wants_grad(ctx)
         xp = xp.contiguous()
-        stage = r.K is not None
+        # bf16=True: the bf16 data path (every GEMM input in bf16 only, the residual stream fp32), as BlockFn runs a dense block in that mode
+        io = r.bf16 and DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
+        if r.bf16:
+            if not io:
+                raise D2SError("a ragged block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
         if train:
             attn, attn_args = r.attn_train, ()
         else:
             attn, attn_args = DF._varlen_attn_forward, (r.cu, r.B, r.max_n, r.heads, r.scale, stage)
-        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, False, train, attn, attn_args, mid=r.sample if stage else None,
+        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, io, train, attn, attn_args, mid=r.sample if stage else None,
                                                    mid_cls=stage)
         if train:
             ctx.save_for_backward(xp, *saved)

@@ -14,7 +14,8 @@ rows.
 Training on the ragged batch (--ragged-train) makes that cascade differentiable: RaggedPackFn / RaggedRepackFn hand
 the gradient back along the rows they moved (dropped rows get zeros), RaggedPredictorFn is the same sequence on the same rows with its
 backward (functional.predictor_backward_sequence; fp32 data path, d2s_half_mean_concat_varlen_bwd and one d2s_act_grad where the dense
-half-mean-concat backward stands), ragged_head the final LayerNorm and classifier, RaggedMaskLossFn the mask loss of a packed stage.  The selection carries no gradient."""
+half-mean-concat backward stands), ragged_head the final LayerNorm and classifier, RaggedMaskLossFn the mask loss of a packed stage.  The selection carries no gradient.
+In the bf16 arithmetic mode RaggedPredictorFn runs only when asked to (bf16=True), then on PredictorFn's data path."""
 import torch
 
 from . import ops
@@ -90,18 +91,26 @@ class RaggedPredictorFn(torch.autograd.Function):
     """The LayerNorm score predictor (large: ReLU, or small_predictor: exact-erf GELU) over a packed batch as a differentiable Function:
     xp [total, D], cu [B+1], B, small, then the predictor's parameters -> scores [total].  ragged_predictor_forward's launch sequence on
     the fp32 data path - a training forward also keeps the LayerNorm statistics and, for the small predictor, the GELU pre-activations -
-    and its backward."""
+    and its backward.  A trailing True behind the parameters (as PredictorFn's trailing "gelu") selects the bf16 arithmetic mode: the
+    sequence then runs with PredictorFn's data path (predictor_bf16_data_path: the large predictor's LayerNorms feed bf16 GEMMs, its tail
+    stays exact fp32, the small predictor keeps fp32 activations; no bf16 form crosses the concat).  Without it that mode is refused."""
 
     @staticmethod
     def forward(ctx, xp, cu, B, small, *params):
-        from .functional_ats import _BF16_REFUSAL
+        from .functional_ats import _BF16_MODE_REFUSAL, _BF16_REFUSAL
         from .lib import D2SError
+        bf16 = bool(params) and params[-1] is True
+        params = params[:len(params) // 4 * 4]
         if ops.get_gemm_mode() == ops.GEMM_BF16:
-            raise D2SError(_BF16_REFUSAL)
+            if not bf16:
+                raise D2SError(_BF16_REFUSAL)
+        elif bf16:
+            raise D2SError(_BF16_MODE_REFUSAL)
         xp = xp.contiguous()
         train = wants_grad(ctx)
         act = "gelu" if small else "relu"
-        scores, saved = predictor_forward_sequence(xp, PredictorRows(xp, B, cu), params, act, False, train)
+        io = bf16 and predictor_bf16_data_path(xp, act)
+        scores, saved = predictor_forward_sequence(xp, PredictorRows(xp, B, cu), params, act, io, train)
         if train:
             ctx.save_for_backward(cu, *saved, *params)          # saved[0] is xp
             ctx.meta = (int(B), act)
@@ -110,19 +119,21 @@ class RaggedPredictorFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gscores):
         B, act = ctx.meta
-        np_ = len(ctx.needs_input_grad) - 4
+        np_ = (len(ctx.needs_input_grad) - 4) // 4 * 4
         cu, saved, params = ctx.saved_tensors[0], ctx.saved_tensors[1:-np_], ctx.saved_tensors[-np_:]
         grads = predictor_backward_sequence(gscores, PredictorRows(saved[0], B, cu), saved, params, act,
-                                            ctx.needs_input_grad[:1] + ctx.needs_input_grad[4:])
-        return (grads[0], None, None, None) + tuple(grads[1:])
+                                            ctx.needs_input_grad[:1] + ctx.needs_input_grad[4:4 + np_])
+        return (grads[0], None, None, None) + tuple(grads[1:]) + (None,) * (len(ctx.needs_input_grad) - 4 - np_)
 
 
-def ragged_predictor_train(predictor, xp, cu, B):
-    """RaggedPredictorFn on a PredictorLG (LayerNorm variants) -> scores [total]; the BatchNorm predictor is refused as at inference"""
+def ragged_predictor_train(predictor, xp, cu, B, bf16=False):
+    """RaggedPredictorFn on a PredictorLG (LayerNorm variants) -> scores [total]; the BatchNorm predictor is refused as at inference.
+    bf16: run in the bf16 arithmetic mode, on PredictorFn's data path (refused in an fp32 mode; without it the bf16 mode is refused)"""
     from . import functional as DF
     if predictor.use_bn:
         raise NotImplementedError(RAGGED_PREDICTOR_BN_ERROR)
-    return DF.run(RaggedPredictorFn, xp, cu, int(B), bool(predictor.small_predictor), *predictor._params())
+    extra = (True,) if bf16 else ()
+    return DF.run(RaggedPredictorFn, xp, cu, int(B), bool(predictor.small_predictor), *predictor._params(), *extra)
 
 
 def ragged_head(xp, cu, norm, head):

@@ -1,8 +1,8 @@
 """ctypes binding of lib/libd2s_hip.so (the C ABI declared in include/d2s_hip.h, the frozen core, include/d2s_hip_ext.h, closed at its
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
-ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, and include/d2s_hip_gemm_plan.h, the
-plan query of the exact fp32 GEMM).
+ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, include/d2s_hip_gemm_plan.h, the
+plan query of the exact fp32 GEMM, and include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -198,6 +198,12 @@ _SIGS_GEMM_PLAN = {
     "d2s_gemm_f32_plan": (Z, [I, I, I, I, I]),
 }
 
+# the entries of include/d2s_hip_ragged_bf16.h (training on the ragged batch in the bf16 arithmetic mode), same form
+_SIGS_RAGGED_BF16 = {
+    "d2s_attn_varlen_fwd_lse_bf16": (I, [P, I, P, P, P, P, P, I, I, I, I, F]),
+    "d2s_attn_varlen_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, F]),
+}
+
 _lib = None
 
 
@@ -216,7 +222,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
-                              + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items())):
+                              + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -258,6 +264,10 @@ def evo_symbols():
 
 def gemm_plan_symbols():
     return sorted(_SIGS_GEMM_PLAN)
+
+
+def ragged_bf16_symbols():
+    return sorted(_SIGS_RAGGED_BF16)
 
 
 def ptr(t):

@@ -1521,6 +1521,35 @@ def attn_varlen_fwd_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, w
     return out, cls_row, out16
 
 
+# ---- training on the ragged batch in the bf16 arithmetic mode (csrc/attention_bf16.hip's VLSE forward and VARLEN backward) ----
+def attn_varlen_fwd_lse_bf16io(qkv, cu, B, total, max_n, H, scale, want_cls=False, want_f32=True):
+    """attn_varlen_fwd_bf16io that keeps the log-sum-exp for attn_varlen_bwd_bf16io: out / out16 / cls_row bit for bit that call's; qkv fp32
+    or bf16.  -> (out or None, lse [H, total], cls_row [H, total] or None, out16)"""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
+    out = torch.empty((total, H * 64), dtype=torch.float32, device=qkv.device) if want_f32 else None
+    out16 = bf16_buffer(total, H * 64, qkv.device)
+    lse = torch.empty((H, total), dtype=torch.float32, device=qkv.device)
+    cls_row = torch.empty((H, total), dtype=torch.float32, device=qkv.device) if want_cls else None
+    lib.call("d2s_attn_varlen_fwd_lse_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(cu), lib.ptr(out), lib.ptr(out16),
+             lib.ptr(lse), lib.ptr(cls_row), int(B), int(total), int(max_n), int(H), float(scale))
+    return out, lse, cls_row, out16
+
+
+def attn_varlen_bwd_bf16io(qkv, cu, out, dout, lse, B, total, max_n, H, scale, dqkv16=None, want_f32=True):
+    """Backward of attn_varlen_fwd_lse_bf16io (out its fp32 output, lse as it returned them); qkv fp32 or bf16.  dqkv16: bf16 buffer shaped
+    like qkv that receives a copy of dqkv; want_f32=False (needs dqkv16): only that form is written and None is returned."""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16) and tuple(lse.shape) == (H, total)
+    _f32(out), _f32(dout), _f32(lse)
+    assert out.numel() == dout.numel() == total * H * 64 and qkv.numel() == 3 * total * H * 64
+    if dqkv16 is not None:
+        assert dqkv16.dtype == torch.bfloat16 and dqkv16.is_contiguous() and dqkv16.numel() == qkv.numel()
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device) if (want_f32 or dqkv16 is None) else None
+    delta = torch.empty((H, total), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_varlen_bwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(cu), lib.ptr(out), lib.ptr(dout), lib.ptr(lse),
+             lib.ptr(dqkv), lib.ptr(dqkv16), lib.ptr(delta), int(B), int(total), int(max_n), int(H), float(scale))
+    return dqkv
+
+
 def sum_scalar(v, scale=1.0):
     out = torch.empty((), dtype=torch.float32, device=v.device)
     lib.call("d2s_sum_scalar", lib.ptr(v), v.numel(), float(scale), lib.ptr(out))

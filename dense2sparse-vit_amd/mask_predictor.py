@@ -191,6 +191,12 @@ def check_supported(args):
             bad.append("--ragged-train with --torch-optim (the packed outputs go through the fused step only)")
         if args.eval_only:
             bad.append("--ragged-train with --eval-only (evaluation runs the inference cascade either way: drop one of the two)")
+    if bool(getattr(args, "ragged_bf16", False)):
+        # the flag, not the mode, selects the path (as --tome-bf16): it sets the bf16 arithmetic mode itself, --gemm-mode bf16 stays refused above
+        if not getattr(args, "ragged_train", False):
+            bad.append("--ragged-bf16 without --ragged-train (it puts training on the ragged packed batch into the bf16 arithmetic mode)")
+        if getattr(args, "gemm_mode", "exact") == "split":
+            bad.append("--ragged-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
     if args.patch_score_threshold is not None:
         print("Attention: --patch-score-threshold: the reference's losses and inference branch cannot run on this path (losses.py:81,216-218, "
               "dynamic_vit.py:936); this build follows its training forward line by line and the documented fix for the rest (DESIGN.md section 10)")
@@ -209,6 +215,10 @@ def check_supported(args):
             print("Attention: --ragged-train: training follows the cascade definition too - the training forward packs every stage's "
                   "survivors and runs the later blocks on them alone (selection without gradient), a later stage scores the survivors only "
                   "and adds its own mask-loss term, in training and at validation (this build's definition; DESIGN.md section 10.2)")
+        if getattr(args, "ragged_train", False) and getattr(args, "ragged_bf16", False):
+            print("Attention: --ragged-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the ragged attention "
+                  "and its backward on the bf16 matrix cores, the residual stream, the selection and the row moves in fp32 (DESIGN.md "
+                  "section 10.3)")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:
@@ -374,7 +384,8 @@ def build_models(args):
                                                    squeeze_dropped=getattr(args, "squeeze_dropped", False),
                                                    attn_selection=getattr(args, "attn_selection", False),
                                                    checkpoint_path=args.student_checkpoint,
-                                                   **({"ragged_train": True} if getattr(args, "ragged_train", False) else {}))
+                                                   **({"ragged_train": True} if getattr(args, "ragged_train", False) else {}),
+                                                   **({"ragged_bf16": True} if getattr(args, "ragged_bf16", False) else {}))
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
 
@@ -521,7 +532,9 @@ def main(argv=None):
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
-    ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[args.gemm_mode])
+    # --ragged-bf16 sets the bf16 arithmetic mode itself, as --gemm-mode bf16 would (which stays refused with --ragged-train)
+    ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[
+        "bf16" if getattr(args, "ragged_bf16", False) else args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
     if (args.method == "ats" and not args.ats_train) or (args.method == "tome" and not args.tome_train):
         return eval_tome(args, rank, world, distributed)

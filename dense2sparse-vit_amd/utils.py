@@ -225,6 +225,10 @@ def parse_args(argv=None):
                         'differentiable (the survivors of every stage are packed and the later blocks run on them alone; the selection '
                         'carries no gradient), and a packed stage adds its own mask-loss term; several --pruning-locs still need '
                         '--ragged-cascade; --gemm-mode exact or split (this build\'s definition)')
+    p.add_argument('--ragged-bf16', action='store_true', default=False,
+                   help='with --ragged-train: train on the ragged packed batch in the bf16 arithmetic mode (bf16 matrix cores for the GEMMs, '
+                        'the ragged attention and its backward; the bf16 data path) - the flag sets that mode itself, --gemm-mode stays at '
+                        'exact (its default); --gemm-mode bf16 without this path stays refused')
     p.add_argument('--accum-steps', type=int, default=1, metavar='N',
                    help='one optimiser step per N batches (gradient = mean over the N; effective batch = N x --batch-size x ranks), '
                         'accumulated inside the fused arena step')

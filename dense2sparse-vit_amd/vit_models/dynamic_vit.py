@@ -80,6 +80,8 @@ SQUEEZE_DROPPED_DIFF_TOPK_ERROR = ("squeeze_dropped cannot be combined with diff
                                    "every kept row and has no dropped set")
 RAGGED_TRAIN_THRESHOLD_ERROR = ("ragged_train trains the dynamic keep ratio on the ragged packed batch: it needs patch_score_threshold (the "
                                 "fixed-ratio path already trains on the kept tokens alone)")
+RAGGED_BF16_ERROR = ("ragged_bf16 puts training on the ragged packed batch into the bf16 arithmetic mode: it needs ragged_train=True "
+                     "(--ragged-train)")
 RAGGED_TRAIN_DROP_PATH_ERROR = "ragged_train with drop_path_rate > 0: stochastic depth is not built for a ragged block"
 RAGGED_CASCADE_BN_ERROR = ("ragged inference through more than one threshold stage is not built for the BatchNorm score predictor "
                            "(predictor_bn=True): a stage after the first scores a ragged packed batch, which needs the LayerNorm "
@@ -473,8 +475,10 @@ class VisionTransformerDiffPruning(_ViTBase):
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
                  predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, squeeze_dropped=False,
-                 ragged_train=False, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
+                 ragged_train=False, ragged_bf16=False, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
         super().__init__()
+        if ragged_bf16 and not ragged_train:
+            raise ValueError(RAGGED_BF16_ERROR)
         if ragged_train and patch_score_threshold is None:
             raise ValueError(RAGGED_TRAIN_THRESHOLD_ERROR)
         if ragged_train and float(drop_path_rate) > 0.0:
@@ -564,6 +568,9 @@ class VisionTransformerDiffPruning(_ViTBase):
         # dynamic keep ratio only: a training forward runs the inference cascade, differentiable, on the ragged packed batch instead of
         # masking keys over all N tokens; eval() is untouched
         self.ragged_train = bool(ragged_train)
+        # ... and does so in the bf16 arithmetic mode too: the flag, not the mode, selects the path - without it
+        # that mode is refused; in an fp32 mode it changes nothing
+        self.ragged_bf16 = bool(ragged_bf16)
         self.unpruned = False
         self.distill = distill
         self.pruning_loc, self.token_ratio = pruning_loc, token_ratio
@@ -787,7 +794,8 @@ class VisionTransformerDiffPruning(_ViTBase):
         from d2s import functional_ragged as RF
         from d2s import ops
         from d2s.lib import D2SError
-        if ops.get_gemm_mode() == ops.GEMM_BF16:
+        bf16 = ops.get_gemm_mode() == ops.GEMM_BF16
+        if bf16 and not self.ragged_bf16:
             raise D2SError(AF._BF16_REFUSAL)
         if len(self.pruning_loc) > 1 and any(p.use_bn for p in self.score_predictor):
             raise NotImplementedError(RAGGED_CASCADE_BN_ERROR)
@@ -808,7 +816,7 @@ class VisionTransformerDiffPruning(_ViTBase):
                     total = int(cu[-1])      # the one device sync of a stage: the packed row count sizes every later launch
                     x, row_src = RF.RaggedPackFn.apply(x, policy, cu, total)
                 else:
-                    pred_logits = RF.ragged_predictor_train(self.score_predictor[p_count], x, cu, B)          # packed [total]
+                    pred_logits = RF.ragged_predictor_train(self.score_predictor[p_count], x, cu, B, bf16=bf16)          # packed [total]
                     keep, counts, mask, _ = ops.ragged_select_threshold(pred_logits.detach(), cu, row_src, thr, N, B)
                     cu_new = ops.ragged_offsets(counts, extra=1)
                     total = int(cu_new[-1])
@@ -826,7 +834,7 @@ class VisionTransformerDiffPruning(_ViTBase):
                 x = blk(x)
             else:
                 a = blk.attn
-                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(cu, B, max_n, a.num_heads, a.scale))
+                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(cu, B, max_n, a.num_heads, a.scale, bf16=bf16))
         if cu is None:       # no stage at all: the dense head
             logits, features = self._head(x)
             return logits, features, self.pred_logits, self.kept_token_indices

@@ -7,8 +7,13 @@ fraction after every stage in the last step - the figure means nothing without i
 stage it also prints the policy-versus-ragged differences of the first step's logits and gradient norms (recorded, not asserted: policy
 attention carries eps terms the ragged definition does not have).  GPU box only.
 
+--bf16: the policy-mode step in the bf16 arithmetic mode - how a threshold student trains in bf16 without
+--ragged-bf16 - and the ragged step in that mode (ragged_bf16=True) alternate the same way, with the fp32 ragged step of --gemm-mode
+beside them for orientation (every step runs in its own arithmetic mode, set before each of its timed blocks).
+
   python tools/ragged_train_bench.py [--gemm-mode exact|split] [--pruning-locs 3] [--threshold 0.5]
   python tools/ragged_train_bench.py --pruning-locs 3 6 9 --threshold 0.3
+  python tools/ragged_train_bench.py --bf16 [--pruning-locs 3] [--threshold 0.5]
 """
 import argparse
 import os
@@ -31,6 +36,7 @@ ap.add_argument("--batch-size", type=int, default=128)
 ap.add_argument("--student-checkpoint", default=None, help="DeiT-S weights for both students (default: seeded random weights)")
 ap.add_argument("--teacher-checkpoint", default=None)
 ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--bf16", action="store_true", help="policy-mode step and ragged step in the bf16 arithmetic mode, the fp32 ragged step beside them")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -44,16 +50,22 @@ mode, mname = MODES[args.gemm_mode]
 ops.set_gemm_mode(mode)
 
 
-def step_of(ragged):
+def step_of(ragged, step_mode=mode):
+    ops.set_gemm_mode(step_mode)
     torch.manual_seed(0)                                        # the same initial weights for both students
+    kw = {"ragged_train": True} if ragged else {}
+    if ragged and step_mode == ops.GEMM_BF16:
+        kw["ragged_bf16"] = True
     student = vit_models.dynamic_vit_small_patch16_224_student(args.pruning_locs, ratios, topk_selection=True, predictor_loss_type="kl_div",
                                                                patch_score_threshold=args.threshold, checkpoint_path=args.student_checkpoint,
-                                                               **({"ragged_train": True} if ragged else {}))
+                                                               **kw)
     torch.manual_seed(1)
     teacher = vit_models.dynamic_vit_small_patch16_224_teacher(checkpoint_path=args.teacher_checkpoint)
     a = types.SimpleNamespace(keep_ratios=ratios, mask_loss_type="kl_div", mixup=0.0, patch_score_threshold=args.threshold, step=0,
                               ragged_train=ragged)
-    return TrainStep(student.to(dev).train(), teacher.to(dev), a, lr=1e-5, graph=False)
+    ts = TrainStep(student.to(dev).train(), teacher.to(dev), a, lr=1e-5, graph=False)
+    ts.bench_mode = step_mode
+    return ts
 
 
 def grad_norms(ts):
@@ -67,6 +79,7 @@ def grad_norms(ts):
 
 
 def timed(ts, warm):
+    ops.set_gemm_mode(ts.bench_mode)
     for _ in range(WARMUP if warm else 0):
         ts(x, y)
     torch.cuda.synchronize()
@@ -79,15 +92,22 @@ def timed(ts, warm):
     return s.elapsed_time(e) / TIMED
 
 
-steps = [("policy attention (all N tokens)", step_of(False)), ("ragged packed batch", step_of(True))]
-if S == 1:      # the first step of both, on identical weights: how far apart the two definitions are
-    infos = [ts(x, y) for _, ts in steps]
+if args.bf16:
+    steps = [("bf16: policy attention (all N tokens)", step_of(False, ops.GEMM_BF16)), ("bf16: ragged packed batch", step_of(True, ops.GEMM_BF16)),
+             (f"{mname}: ragged packed batch", step_of(True))]
+else:
+    steps = [("policy attention (all N tokens)", step_of(False)), ("ragged packed batch", step_of(True))]
+if S == 1:      # the first step of the first two, on identical weights: how far apart the two definitions are
+    infos = []
+    for _, ts in steps[:2]:
+        ops.set_gemm_mode(ts.bench_mode)
+        infos.append(ts(x, y))
     torch.cuda.synchronize()
     la, lb = (i["logits_s"].detach().double() for i in infos)
     print(f"one stage, first step, policy vs ragged: loss {float(infos[0]['loss']):.6f} vs {float(infos[1]['loss']):.6f}, "
           f"max |logits difference| {float((la - lb).abs().max()):.3e} (max |logit| {float(la.abs().max()):.3e}), "
           f"masks equal: {all(torch.equal(a, b) for a, b in zip(infos[0]['kept'], infos[1]['kept']))}")
-    na, nb = (grad_norms(ts) for _, ts in steps)
+    na, nb = (grad_norms(ts) for _, ts in steps[:2])
     worst = max(na, key=lambda k: abs(na[k] - nb.get(k, 0.0)) / max(na[k], 1e-30))
     print(f"  gradient norms per module: largest relative difference {abs(na[worst] - nb[worst]) / max(na[worst], 1e-30):.3e} at {worst} "
           f"({na[worst]:.6e} vs {nb[worst]:.6e})")
@@ -97,7 +117,7 @@ for r in range(args.rounds):
         times[i].append(timed(ts, r == 0))
 for (name, ts), t in zip(steps, times):
     ms, spread = sum(t) / len(t), max(t) - min(t)
-    line = f"{mname:12s} locs {args.pruning_locs} t {args.threshold}  {name:32s} {ms:7.2f} ms/step (spread {spread:.2f}; rounds {[round(v, 2) for v in t]})  {B / ms * 1e3:7.0f} images/s"
+    line = f"{mname if not args.bf16 else 'bf16 bench':12s} locs {args.pruning_locs} t {args.threshold}  {name:38s} {ms:7.2f} ms/step (spread {spread:.2f}; rounds {[round(v, 2) for v in t]})  {B / ms * 1e3:7.0f} images/s"
     kept = [float(m.mean()) for m in ts.student.kept_token_indices]
     line += f"   mean kept fraction per stage {[round(k, 3) for k in kept]}, host reads per step {S if ts.ragged_train else 0}"
     print(line, flush=True)
