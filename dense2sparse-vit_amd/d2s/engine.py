@@ -304,6 +304,10 @@ def checkpoint_config(config):
     theirs.setdefault("evo_start", None)           # ... and before the Evo-ViT baseline existed: no such student
     theirs.setdefault("evo_keep", None)
     theirs.setdefault("evo_tradeoff", None)
+    theirs.setdefault("ltp_phase", None)           # ... and before the LTP baseline existed: no such student
+    theirs.setdefault("ltp_temperature", None)
+    theirs.setdefault("ltp_lambda", None)
+    theirs.setdefault("ltp_init_threshold", None)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
     theirs.setdefault("ragged_bf16", False)        # ... and before it could do so in the bf16 arithmetic mode: fp32 modes only
@@ -511,7 +515,7 @@ class TrainStep:
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
-        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss
+        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss, LTPLoss
         if int(accum_steps) != accum_steps or accum_steps < 1:
             raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
         if clip_grad is not None and not float(clip_grad) > 0.0:
@@ -585,7 +589,25 @@ class TrainStep:
                                  "(train.py:50-53), and the slow-fast update has none - pass warmup_steps=0")
             if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
                 raise lib.D2SError("TrainStep with an Evo-ViT student and drop_path_rate > 0: stochastic depth is not built for a slow-fast block")
-        self.logits_only = self.tome or self.ats or self.avit or self.evo
+        # the LTP baseline (vit_models/ltp.py): logits alone, LTPLoss (ToMeLoss plus lambda times the regulariser the
+        # forward leaves on the model), the teacher optional.  The hard phase reads its row counts on the host at every stage; the soft
+        # phase is dense, but its captured step is not built either.  Both phases are built on the fp32 data path.
+        self.ltp = type(student).__name__ == "VisionTransformerLTP"
+        if self.ltp:
+            if warmup_steps > 0:
+                raise ValueError(f"warmup_steps {warmup_steps} with an LTP student: the warm-up epochs train the score predictors only "
+                                 "(train.py:50-53), and learned thresholds have none - pass warmup_steps=0")
+            if graph is True:
+                raise lib.D2SError("TrainStep(graph=True) with an LTP student is not supported: a hard stage reads its row counts on the "
+                                   "host, which a captured step cannot, and a captured soft step is not built; run the step eagerly (graph=False)")
+            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
+                raise lib.D2SError("TrainStep with an LTP student and drop_path_rate > 0: stochastic depth is not built for a ragged block "
+                                   "or a block with a learnt policy")
+            if ops.get_gemm_mode() == ops.GEMM_BF16:
+                from .functional_ltp import BF16_REFUSAL
+                raise lib.D2SError("TrainStep with an LTP student in the bf16 arithmetic mode: " + BF16_REFUSAL)
+            graph = False
+        self.logits_only = self.tome or self.ats or self.avit or self.evo or self.ltp
         # a dynamic-keep-ratio student that trains on the ragged packed batch (ragged_train=True): the ordinary
         # route - both losses, warm-up epochs, the freeze schedule - with the packed outputs handed to the losses; the refusals are those
         # of a ragged block
@@ -615,7 +637,7 @@ class TrainStep:
         self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
         self.tome_loss_fn = None
         if self.logits_only:
-            self.tome_loss_fn = AViTLoss(args) if self.avit else ToMeLoss(args)
+            self.tome_loss_fn = AViTLoss(args) if self.avit else LTPLoss(args) if self.ltp else ToMeLoss(args)
             self.mask_loss_fn = self.backbone_loss_fn = None
         elif self.baseline:
             if not getattr(student, "distill", False):
@@ -730,6 +752,7 @@ class TrainStep:
         thr = getattr(s, "patch_score_threshold", None)
         avit = type(s).__name__ == "VisionTransformerAViT"
         evo = type(s).__name__ == "VisionTransformerEvo"
+        ltp = type(s).__name__ == "VisionTransformerLTP"
         return {
             "format": CHECKPOINT_FORMAT,
             "model": type(s).__name__,
@@ -768,6 +791,10 @@ class TrainStep:
             "evo_start": int(s.evo_start) if evo else None,
             "evo_keep": float(s.evo_keep) if evo else None,
             "evo_tradeoff": float(s.evo_tradeoff) if evo else None,
+            "ltp_phase": str(s.ltp_phase) if ltp else None,
+            "ltp_temperature": float(s.ltp_temperature) if ltp else None,
+            "ltp_lambda": float(0.01 if getattr(self.args, "ltp_lambda", None) is None else self.args.ltp_lambda) if ltp else None,
+            "ltp_init_threshold": float(s.ltp_init_threshold) if ltp else None,
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -860,6 +887,9 @@ class TrainStep:
         if self.avit:
             loss = fn(logits_s, logits_t, labels, self.metrics, s.ponder_loss, s.prior_loss, s.avg_depth, accumulate=accumulate)
             per_block = list(s.tokens_per_layer)
+        elif self.ltp:
+            loss = fn(logits_s, logits_t, labels, self.metrics, s.ltp_reg, s.avg_tokens, accumulate=accumulate)
+            per_block = list(s.tokens_per_block)
         else:
             loss = fn(logits_s, logits_t, labels, self.metrics, accumulate=accumulate)
             per_block = list(s.tokens_per_stage if self.ats else s.tokens_per_block)

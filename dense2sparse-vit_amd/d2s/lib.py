@@ -2,7 +2,7 @@
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
 ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, include/d2s_hip_gemm_plan.h, the
-plan query of the exact fp32 GEMM, and include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training).
+plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, and include/d2s_hip_ltp.h, learned token thresholds).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -204,6 +204,16 @@ _SIGS_RAGGED_BF16 = {
     "d2s_attn_varlen_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, F]),
 }
 
+# the entries of include/d2s_hip_ltp.h (the LTP baseline: learned per-block token thresholds), same form; the
+# workspace query is a size_t one without a stream
+_SIGS_LTP = {
+    "d2s_ltp_score_workspace_bytes": (Z, [L, I]),
+    "d2s_ltp_score_f32": (I, [P, P, P, P, P, P, P, Z, I, I, I, I, F]),
+    "d2s_ltp_select": (I, [P, P, P, P, P, P, P, I, I, I]),
+    "d2s_ltp_soft_mask_fwd": (I, [P, P, P, P, P, P, I, I, F]),
+    "d2s_ltp_soft_mask_bwd": (I, [P, P, P, P, P, P, P, P, I, I, F, I, I]),
+}
+
 _lib = None
 
 
@@ -222,7 +232,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
-                              + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())):
+                              + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())
+                              + list(_SIGS_LTP.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -268,6 +279,10 @@ def gemm_plan_symbols():
 
 def ragged_bf16_symbols():
     return sorted(_SIGS_RAGGED_BF16)
+
+
+def ltp_symbols():
+    return sorted(_SIGS_LTP)
 
 
 def ptr(t):

@@ -1446,6 +1446,74 @@ def avit_penalty_bwd(hbar, cnt, tgt, dponder, dprior, B, N):
     return gsc
 
 
+# ---- the LTP baseline: learned per-block token thresholds (csrc/ltp.hip) ----
+def ltp_score(qkv, lse, B, n, H, scale, policy=None, cinv=None, cu=None, total=None):
+    """The attention every token receives in one block: qkv [rows, 3 * H * 64] and the lse (and cinv) that block's attention forward wrote.
+    Plain: lse [B, H, n]; policy: policy [B, n], cinv [B, H, n] as attn_policy_fwd returned them; varlen: cu [B + 1] int32, lse [H, total],
+    n = max_n (any upper bound).  -> score [rows] fp32, each image's entries summing to 1."""
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous()
+    _f32(lse)
+    rows = int(total) if cu is not None else B * n
+    assert qkv.numel() == rows * 3 * H * 64 and lse.numel() == rows * H, (tuple(qkv.shape), tuple(lse.shape), rows, H)
+    if policy is not None:
+        assert cu is None and cinv is not None and policy.numel() == rows and cinv.numel() == rows * H
+        _f32(policy), _f32(cinv)
+    if cu is not None:
+        assert cu.dtype == torch.int32 and cu.numel() == B + 1 and cu.is_contiguous()
+    score = torch.empty((rows,), dtype=torch.float32, device=qkv.device)
+    need = lib.query("d2s_ltp_score_workspace_bytes", rows, int(H))
+    ws = torch.empty((need // 4,), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_ltp_score_f32", lib.ptr(qkv), lib.ptr(lse), lib.ptr(policy), lib.ptr(cinv), lib.ptr(cu), lib.ptr(score), lib.ptr(ws), need,
+             int(B), int(n), rows, int(H), float(scale))
+    return score
+
+
+def ltp_select(score, cu, theta, B, row_src=None, T=0):
+    """score [total] packed, theta: a 1-element fp32 device tensor (a view of the parameter; never read on the host)
+    -> (keep [total] float 0/1 with 1 at the CLS rows, counts [B] int32 kept non-CLS rows, dense [B, T] in patch coordinates or None)."""
+    _f32(score), _f32(theta)
+    assert theta.numel() == 1 and cu.dtype == torch.int32 and cu.numel() == B + 1
+    total = score.numel()
+    keep = torch.empty((total,), dtype=torch.float32, device=score.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=score.device)
+    dense = None
+    if row_src is not None:
+        assert row_src.dtype == torch.int32 and row_src.numel() == total and T > 0
+        dense = torch.empty((B, T), dtype=torch.float32, device=score.device)
+    lib.call("d2s_ltp_select", lib.ptr(score), lib.ptr(cu), lib.ptr(row_src), lib.ptr(theta), lib.ptr(keep), lib.ptr(counts), lib.ptr(dense),
+             int(B), int(T), total)
+    return keep, counts, dense
+
+
+def ltp_soft_mask_fwd(score, m_in, theta, tau):
+    """score [B, N], m_in [B, N] or None (all ones), theta a 1-element device tensor -> (M [B, N], m_out = m_in * M, msum [B])"""
+    _f32(score), _f32(theta)
+    B, N = score.shape
+    assert theta.numel() == 1 and (m_in is None or tuple(_f32(m_in).shape) == (B, N))
+    M, m_out = torch.empty_like(score), torch.empty_like(score)
+    msum = torch.empty((B,), dtype=torch.float32, device=score.device)
+    lib.call("d2s_ltp_soft_mask_fwd", lib.ptr(score), lib.ptr(m_in), lib.ptr(theta), lib.ptr(M), lib.ptr(m_out), lib.ptr(msum), B, N,
+             1.0 / float(tau))
+    return M, m_out, msum
+
+
+def ltp_soft_mask_bwd(g_out, M, m_in, tau, dtheta, greg=None, gm_in=None, want_gm=True, accumulate_dtheta=False):
+    """Backward of ltp_soft_mask_fwd.  greg [B] or None: the gradient of msum; dtheta: the 1-element gradient slot, written (or added
+    to); gm_in: a [B, N] tensor to add g_out * M to, or None: a fresh one is written when want_gm.  -> (gM [B, N], gm_in or None)"""
+    _f32(g_out), _f32(M), _f32(dtheta)
+    B, N = M.shape
+    assert dtheta.numel() == 1 and tuple(g_out.shape) == (B, N) and (m_in is None or tuple(_f32(m_in).shape) == (B, N))
+    assert greg is None or _f32(greg).numel() == B
+    accumulate_gm = gm_in is not None
+    if gm_in is None and want_gm:
+        gm_in = torch.empty_like(M)
+    gM = torch.empty_like(M)
+    part = torch.empty((B,), dtype=torch.float32, device=M.device)
+    lib.call("d2s_ltp_soft_mask_bwd", lib.ptr(g_out), lib.ptr(M), lib.ptr(m_in), lib.ptr(greg), lib.ptr(gM), lib.ptr(gm_in), lib.ptr(dtheta),
+             lib.ptr(part), B, N, 1.0 / float(tau), int(accumulate_gm), int(bool(accumulate_dtheta)))
+    return gM, gm_in
+
+
 # ---- the Evo-ViT baseline: slow-fast token update (csrc/evo.hip; DESIGN.md section 26) ----
 def _evo_shapes(X, kept, dropped):
     B, n, D = X.shape

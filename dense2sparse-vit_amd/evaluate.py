@@ -15,11 +15,12 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     teacher_model.eval()
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
-    # DynamicViT, Token Merging, Adaptive Token Sampling, A-ViT and Evo-ViT baselines: eval returns logits alone
+    # DynamicViT, Token Merging, Adaptive Token Sampling, A-ViT, Evo-ViT and LTP baselines: eval returns logits alone
     baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS",
-                                        "VisionTransformerAViT", "VisionTransformerEvo")
+                                        "VisionTransformerAViT", "VisionTransformerEvo", "VisionTransformerLTP")
     avit = type(model).__name__ == "VisionTransformerAViT"
-    depth_sum = 0.0
+    ltp = type(model).__name__ == "VisionTransformerLTP"
+    depth_sum, tokens_sum = 0.0, 0.0
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():
@@ -34,6 +35,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
                 running_acc += correct
                 if avit:
                     depth_sum = depth_sum + model.avg_depth
+                if ltp:
+                    tokens_sum += model.avg_tokens
                 n += 1
                 continue
             cls_attn_weights = teacher_model.forward_cls_attention(val_inputs)          # :33
@@ -65,6 +68,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     metrics["val_acc"] = running_acc / n
     if avit:
         metrics["val_avg_depth"] = float(depth_sum) / n
+    if ltp:
+        metrics["val_avg_tokens"] = float(tokens_sum) / n       # tokens per image and block, CLS included (the hard forward)
     if not baseline:
         metrics["unpruned_acc"] = running_unpruned_acc / n
     args.epoch_acc = metrics["val_acc"]

@@ -321,3 +321,39 @@ class AViTLoss(ToMeLoss):
         for key, r in zip(("train_ponder_loss", "train_prior_loss", "train_avg_depth"), self.running_avit):
             metrics[key] = r / self.count
         self.count += 1
+
+
+class LTPLoss(ToMeLoss):
+    """The objective of the LTP baseline (the reference has no LTP): ToMeLoss's two terms plus the regulariser the
+    model's forward leaves behind (VisionTransformerLTP.ltp_reg: the mean of every soft mask entry over stages, images and patches):
+
+        L = cls_weight * CE + dist_weight * KL(student || teacher) + ltp_lambda * R
+
+    In the hard phase R is a constant (the kept fraction) and only reported.  The running means are 0-d device tensors."""
+
+    def __init__(self, args):
+        super().__init__(args)
+        lam = getattr(args, "ltp_lambda", None)
+        self.ltp_lambda = 0.01 if lam is None else float(lam)
+        self.running_ltp = [0, 0]
+
+    def forward(self, logits_s, logits_t, train_labels, metrics, reg, avg_tokens, accumulate=True):
+        """reg: the model's regulariser (0-d; differentiable in the soft phase); avg_tokens: its mean token count per image and block"""
+        loss = super().forward(logits_s, logits_t, train_labels, metrics, accumulate=False)
+        if reg.requires_grad:
+            loss = loss + self.ltp_lambda * reg
+        self.last = (loss.detach(),) + tuple(self.last[1:])
+        self.last_ltp = (reg.detach(), torch.as_tensor(float(avg_tokens), dtype=torch.float32, device=logits_s.device))
+        if accumulate:
+            self.accumulate(metrics, self.last, self.last_ltp)
+        return loss
+
+    def accumulate(self, metrics, last, last_ltp):
+        """Advance the running means by one batch."""
+        self.running = [r + v for r, v in zip(self.running, last)]
+        self.running_ltp = [r + v for r, v in zip(self.running_ltp, last_ltp)]
+        for key, r in zip(("train_ltp_loss", "train_cls_loss", "train_cls_kl_loss"), self.running):
+            metrics[key] = r / self.count
+        for key, r in zip(("train_ltp_reg", "train_avg_tokens"), self.running_ltp):
+            metrics[key] = r / self.count
+        self.count += 1

@@ -10,7 +10,7 @@ the mean over the window, clipped to the global L2 norm M.  A TrainStep carries 
 step) and is flushed at the end of the epoch; for a torch optimizer the same window is spelled out here with torch."""
 import torch
 
-from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss
+from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss, LTPLoss
 
 
 def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mixup_fn=None):
@@ -31,6 +31,8 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         raise ValueError("an A-ViT student trains through d2s.engine.TrainStep only")
     if type(model).__name__ == "VisionTransformerEvo" and not fast:
         raise ValueError("an Evo-ViT student trains through d2s.engine.TrainStep only")
+    if type(model).__name__ == "VisionTransformerLTP" and not fast:
+        raise ValueError("an LTP student trains through d2s.engine.TrainStep only")
     if getattr(model, "ragged_train", False) and not fast:
         raise ValueError("a student that trains on the ragged packed batch (ragged_train=True) trains through d2s.engine.TrainStep only")
     baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
@@ -39,6 +41,8 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
         step.metrics = metrics
         if getattr(step, "avit", False):            # the A-ViT baseline: train_ponder_loss, train_prior_loss, train_avg_depth beside ToMeLoss's
             step.tome_loss_fn = AViTLoss(args)
+        elif getattr(step, "ltp", False):           # the LTP baseline: train_ltp_reg, train_avg_tokens beside ToMeLoss's
+            step.tome_loss_fn = LTPLoss(args)
         elif getattr(step, "tome", False) or getattr(step, "ats", False) or getattr(step, "evo", False):      # the logits-only students
             step.tome_loss_fn = ToMeLoss(args)
         elif baseline:

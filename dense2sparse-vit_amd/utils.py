@@ -165,7 +165,7 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit', 'evo'],
+    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit', 'evo', 'ltp'],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
                         "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "
@@ -174,7 +174,19 @@ def parse_args(argv=None):
                         "avit: the A-ViT baseline (per-token adaptive depth: every token halts by its own cumulative score and leaves the ragged "
                         "packed batch, in training too; no predictor; --avit-* set the gate and the two penalty terms); "
                         "evo: the Evo-ViT baseline (slow-fast token update: no token is removed, from block --evo-start on a block runs on the "
-                        "--evo-keep share of the tokens with the highest global score plus one representative of the rest; no predictor)")
+                        "--evo-keep share of the tokens with the highest global score plus one representative of the rest; no predictor); "
+                        "ltp: the LTP baseline (learned token thresholds: the blocks at --pruning-locs each own one learnable threshold on the "
+                        "attention a token receives; --ltp-phase soft trains the thresholds on the dense batch through a sigmoid mask, hard "
+                        "prunes on the ragged packed batch with the thresholds fixed; evaluation is always hard; no predictor)")
+    p.add_argument('--ltp-phase', choices=['soft', 'hard'], default=None,
+                   help='with --method ltp: what training runs (default soft); go from soft to hard with --student-checkpoint, which loads the '
+                        'weights including the thresholds')
+    p.add_argument('--ltp-temperature', type=float, default=None, metavar='TAU',
+                   help='with --method ltp: the soft mask is sigmoid((score - threshold) / TAU) (default 1e-3)')
+    p.add_argument('--ltp-lambda', type=float, default=None, metavar='W',
+                   help='with --method ltp: weight of the regulariser, the mean of every soft mask entry (default 0.01)')
+    p.add_argument('--ltp-init-threshold', type=float, default=None, metavar='TH',
+                   help='with --method ltp: stage k of S starts at TH * (k + 1) / S (default 0.005, about 1 / tokens at 224 x 224)')
     p.add_argument('--evo-start', type=int, default=None, metavar='S',
                    help='with --method evo: the first slow-fast block, 1..depth; the blocks before it are dense (default 4)')
     p.add_argument('--evo-keep', type=float, default=None, metavar='R',

@@ -21,3 +21,5 @@ from .avit import (VisionTransformerAViT, avit_deit_tiny_patch16_224, avit_deit_
                    avit_deit_base_patch16_224)
 from .evo import (VisionTransformerEvo, evo_deit_tiny_patch16_224, evo_deit_small_patch16_224,  # noqa: F401
                   evo_deit_base_patch16_224)
+from .ltp import (VisionTransformerLTP, ltp_deit_tiny_patch16_224, ltp_deit_small_patch16_224,  # noqa: F401
+                  ltp_deit_base_patch16_224)
