@@ -14,6 +14,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+import methods
+
 from . import lib, ops
 
 
@@ -298,16 +300,9 @@ def checkpoint_config(config):
     theirs.setdefault("ats_locs", [])              # ... and before an Adaptive Token Sampling student could be trained: no such student
     theirs.setdefault("ats_tokens", [])
     theirs.setdefault("train_sample", False)
-    theirs.setdefault("avit_gate_scale", None)     # ... and before the A-ViT baseline existed: no such student
-    theirs.setdefault("avit_gate_center", None)
-    theirs.setdefault("avit_eps_halt", None)
-    theirs.setdefault("evo_start", None)           # ... and before the Evo-ViT baseline existed: no such student
-    theirs.setdefault("evo_keep", None)
-    theirs.setdefault("evo_tradeoff", None)
-    theirs.setdefault("ltp_phase", None)           # ... and before the LTP baseline existed: no such student
-    theirs.setdefault("ltp_temperature", None)
-    theirs.setdefault("ltp_lambda", None)
-    theirs.setdefault("ltp_init_threshold", None)
+    for m in methods.METHODS:                      # ... and before the A-ViT, Evo-ViT or LTP baseline existed: no such student
+        for k in m.config_keys:
+            theirs.setdefault(k, None)
     theirs.setdefault("squeeze_dropped", False)    # ... and before pruning and squeezing existed: dropped tokens were discarded
     theirs.setdefault("ragged_train", False)       # ... and before the dynamic keep ratio could train on the ragged batch: policy attention
     theirs.setdefault("ragged_bf16", False)        # ... and before it could do so in the bf16 arithmetic mode: fp32 modes only
@@ -515,7 +510,6 @@ class TrainStep:
         Off by default: on ROCm 7.2 the replay of the ~1400-node graph is SLOWER than issuing the kernels (config 3, 32 images per GPU:
         2064 vs 2310 images/s; the replay call itself keeps the host busy for 11.4 ms against 12.5 ms of eager enqueue, and the GPU side
         gains nothing: profiles/r03_a_graph_vs_eager.txt) - the runtime walks the graph node by node on the host."""
-        from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss, LTPLoss
         if int(accum_steps) != accum_steps or accum_steps < 1:
             raise lib.D2SError(f"accum_steps {accum_steps!r}: expected an integer >= 1")
         if clip_grad is not None and not float(clip_grad) > 0.0:
@@ -536,78 +530,25 @@ class TrainStep:
                                  "predictors only (train.py:50-53), and attention selection has none to train - pass warmup_steps=0")
             for p in student.score_predictor.parameters():
                 p.requires_grad_(False)       # listed in self.frozen below: the epoch schedule leaves them alone, AdamW marks their chunks idle
-        # a Token Merging student (vit_models/tome.py) returns logits alone and is trained with its own objective;
-        # its teacher is optional (None: no teacher forward, no side stream).  Every refusal comes before anything touches the device.
-        self.tome = type(student).__name__ == "VisionTransformerToMe"
-        if self.tome:
+        # the logits-only families (methods.py; DESIGN.md sections 22 and 24 to 27) return logits alone and train with one objective of their
+        # own; the teacher is optional (None: no teacher forward, no side stream).  Every refusal comes before anything touches the device.
+        # A step is captured only where no block reads a row count on the host and the captured step is built: the Evo-ViT baseline's.
+        self.method = m = methods.of(student)
+        self.logits_only = m.logits_only
+        if m.logits_only:
             if warmup_steps > 0:
-                raise ValueError(f"warmup_steps {warmup_steps} with a Token Merging student: the warm-up epochs train the score predictors "
-                                 "only (train.py:50-53), and token merging has none - pass warmup_steps=0")
-            if graph is True:
-                raise lib.D2SError("TrainStep(graph=True) with a Token Merging student is not supported: a captured merging step is not "
-                                   "built; run the step eagerly (graph=False)")
-            if any(v > 0 for v in student.tome_r) and not getattr(student, "train_merge", False):
-                raise lib.D2SError("TrainStep with a merging VisionTransformerToMe needs train_merge=True (training through the merge is opt-in)")
+                raise ValueError(f"warmup_steps {warmup_steps} with {m.student}: the warm-up epochs train the score predictors only "
+                                 f"(train.py:50-53), and {m.has_none} - pass warmup_steps=0")
+            if graph is True and m.no_graph:
+                raise lib.D2SError(f"TrainStep(graph=True) with {m.student} is not supported: {m.no_graph}; run the step eagerly (graph=False)")
+            if m.opt_in and m.opt_in[1](student) and not getattr(student, m.opt_in[0], False):
+                raise lib.D2SError(f"TrainStep with {m.opt_in[2]}")
             if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
-                raise lib.D2SError("TrainStep with a Token Merging student and drop_path_rate > 0: stochastic depth is not built for a merging block")
-            graph = False
-        # an Adaptive Token Sampling student with stages (vit_models/ats.py) takes the same route: logits alone,
-        # ToMeLoss, the teacher optional.  Without stages it is the dense trunk and stays where it was.
-        self.ats = type(student).__name__ == "VisionTransformerATS" and len(getattr(student, "ats_locs", [])) > 0
-        if self.ats:
-            if warmup_steps > 0:
-                raise ValueError(f"warmup_steps {warmup_steps} with an Adaptive Token Sampling student: the warm-up epochs train the score "
-                                 "predictors only (train.py:50-53), and a sampling stage has none - pass warmup_steps=0")
-            if graph is True:
-                raise lib.D2SError("TrainStep(graph=True) with an Adaptive Token Sampling student is not supported: every stage reads its "
-                                   "row count on the host, which a captured step cannot; run the step eagerly (graph=False)")
-            if not getattr(student, "train_sample", False):
-                raise lib.D2SError("TrainStep with a sampling VisionTransformerATS needs train_sample=True (training through the stages is opt-in)")
-            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
-                raise lib.D2SError("TrainStep with an Adaptive Token Sampling student and drop_path_rate > 0: stochastic depth is not built "
-                                   "for a ragged block")
-            graph = False
-        # the A-ViT baseline (vit_models/avit.py): logits alone as well, AViTLoss (ToMeLoss plus the two penalty
-        # terms the forward leaves on the model), the teacher optional; every block is a ragged block and reads its row counts on the host
-        self.avit = type(student).__name__ == "VisionTransformerAViT"
-        if self.avit:
-            if warmup_steps > 0:
-                raise ValueError(f"warmup_steps {warmup_steps} with an A-ViT student: the warm-up epochs train the score predictors only "
-                                 "(train.py:50-53), and adaptive depth has none - pass warmup_steps=0")
-            if graph is True:
-                raise lib.D2SError("TrainStep(graph=True) with an A-ViT student is not supported: every block reads its row counts on "
-                                   "the host, which a captured step cannot; run the step eagerly (graph=False)")
-            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
-                raise lib.D2SError("TrainStep with an A-ViT student and drop_path_rate > 0: stochastic depth is not built for a ragged block")
-            graph = False
-        # the Evo-ViT baseline (vit_models/evo.py): logits alone, ToMeLoss, the teacher optional.  Every block sees a
-        # dense batch of a fixed size and nothing is read back on the host: the step may be captured and runs in all three arithmetic modes
-        self.evo = type(student).__name__ == "VisionTransformerEvo"
-        if self.evo:
-            if warmup_steps > 0:
-                raise ValueError(f"warmup_steps {warmup_steps} with an Evo-ViT student: the warm-up epochs train the score predictors only "
-                                 "(train.py:50-53), and the slow-fast update has none - pass warmup_steps=0")
-            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
-                raise lib.D2SError("TrainStep with an Evo-ViT student and drop_path_rate > 0: stochastic depth is not built for a slow-fast block")
-        # the LTP baseline (vit_models/ltp.py): logits alone, LTPLoss (ToMeLoss plus lambda times the regulariser the
-        # forward leaves on the model), the teacher optional.  The hard phase reads its row counts on the host at every stage; the soft
-        # phase is dense, but its captured step is not built either.  Both phases are built on the fp32 data path.
-        self.ltp = type(student).__name__ == "VisionTransformerLTP"
-        if self.ltp:
-            if warmup_steps > 0:
-                raise ValueError(f"warmup_steps {warmup_steps} with an LTP student: the warm-up epochs train the score predictors only "
-                                 "(train.py:50-53), and learned thresholds have none - pass warmup_steps=0")
-            if graph is True:
-                raise lib.D2SError("TrainStep(graph=True) with an LTP student is not supported: a hard stage reads its row counts on the "
-                                   "host, which a captured step cannot, and a captured soft step is not built; run the step eagerly (graph=False)")
-            if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
-                raise lib.D2SError("TrainStep with an LTP student and drop_path_rate > 0: stochastic depth is not built for a ragged block "
-                                   "or a block with a learnt policy")
-            if ops.get_gemm_mode() == ops.GEMM_BF16:
-                from .functional_ltp import BF16_REFUSAL
-                raise lib.D2SError("TrainStep with an LTP student in the bf16 arithmetic mode: " + BF16_REFUSAL)
-            graph = False
-        self.logits_only = self.tome or self.ats or self.avit or self.evo or self.ltp
+                raise lib.D2SError(f"TrainStep with {m.student} and drop_path_rate > 0: stochastic depth is not built for {m.block}")
+            if m.bf16_refusal and ops.get_gemm_mode() == ops.GEMM_BF16:
+                raise lib.D2SError(f"TrainStep with {m.student} in the bf16 arithmetic mode: " + m.bf16_refusal())
+            if m.no_graph:
+                graph = False
         # a dynamic-keep-ratio student that trains on the ragged packed batch (ragged_train=True): the ordinary
         # route - both losses, warm-up epochs, the freeze schedule - with the packed outputs handed to the losses; the refusals are those
         # of a ragged block
@@ -634,19 +575,9 @@ class TrainStep:
         self.opt = FusedAdamW(self.arena, lr=lr, weight_decay=weight_decay)
         # the DynamicViT baseline (vit_models/default_dynamic_vit.py) returns (logits, features, decision, [decision per stage]) and is
         # trained with its own objective, the full one in every epoch; the freeze / learning-rate schedule is the d2s one
-        self.baseline = type(student).__name__ == "DefaultVisionTransformerDiffPruning"
-        self.tome_loss_fn = None
-        if self.logits_only:
-            self.tome_loss_fn = AViTLoss(args) if self.avit else LTPLoss(args) if self.ltp else ToMeLoss(args)
-            self.mask_loss_fn = self.backbone_loss_fn = None
-        elif self.baseline:
-            if not getattr(student, "distill", False):
-                raise lib.D2SError("TrainStep with the DynamicViT baseline needs distill=True: the objective reads the student's features")
-            self.dynamicvit_loss_fn = DynamicViTLoss(args)
-            self.mask_loss_fn = self.backbone_loss_fn = None
-        else:
-            self.mask_loss_fn = MaskLoss(args, "train")
-            self.backbone_loss_fn = BackboneLoss(args)
+        if m.name == "dynamicvit" and not getattr(student, "distill", False):
+            raise lib.D2SError("TrainStep with the DynamicViT baseline needs distill=True: the objective reads the student's features")
+        self.fresh_losses(args)
         self.metrics = {}
         self.lr, self.min_lr, self.epochs, self.warmup_steps = lr, min_lr, epochs, warmup_steps
         self.reducer = GradReducer(self.arena, bucket_mb=bucket_mb, collective=collective) if distributed else None
@@ -676,7 +607,7 @@ class TrainStep:
                 raise lib.D2SError("TrainStep(graph=True) with diff_topk is not supported: a replayed step would reuse the perturbation "
                                    "noise and the sigma it was captured with; run the step eagerly (graph=False)")
             self.graph = False
-        if self.baseline:
+        if m.name == "dynamicvit":
             # same reason: the Gumbel noise of every stage comes from a seed drawn on the host inside the model's forward (one draw per step)
             if self.graph is True:
                 raise lib.D2SError("TrainStep(graph=True) with the DynamicViT baseline is not supported: a replayed step would reuse the "
@@ -710,6 +641,15 @@ class TrainStep:
         if self._pending:
             raise lib.D2SError(f"{what} with {self._pending} of {self.accum_steps} micro-steps of an accumulation window pending: "
                                "call flush() first (a window never crosses an epoch or a checkpoint)")
+
+    def fresh_losses(self, args):
+        """New loss modules, the family's own: their running means start over (train.py:14-15; train_one_epoch calls this once per epoch)."""
+        from losses import MaskLoss, BackboneLoss
+        m = self.method
+        self.tome_loss_fn = m.loss(args) if m.logits_only else None
+        self.dynamicvit_loss_fn = m.loss(args) if m.name == "dynamicvit" else None
+        self.mask_loss_fn, self.backbone_loss_fn = (None, None) if m.loss else (MaskLoss(args, "train"), BackboneLoss(args))
+        self._loss_extras, self._token_record = m.loss_extras, m.token_record
 
     def set_epoch(self, epoch):
         self._no_open_window("set_epoch")
@@ -750,9 +690,7 @@ class TrainStep:
         pe = getattr(s, "patch_embed", None)
         pred = s.score_predictor[0] if len(getattr(s, "score_predictor", [])) else None
         thr = getattr(s, "patch_score_threshold", None)
-        avit = type(s).__name__ == "VisionTransformerAViT"
-        evo = type(s).__name__ == "VisionTransformerEvo"
-        ltp = type(s).__name__ == "VisionTransformerLTP"
+        own = methods.of(s)
         return {
             "format": CHECKPOINT_FORMAT,
             "model": type(s).__name__,
@@ -785,16 +723,9 @@ class TrainStep:
             "train_sample": bool(getattr(s, "train_sample", False)),
             "ragged_train": bool(getattr(s, "ragged_train", False)),
             "ragged_bf16": bool(getattr(s, "ragged_bf16", False)),
-            "avit_gate_scale": float(s.gate_scale) if avit else None,
-            "avit_gate_center": float(s.gate_center) if avit else None,
-            "avit_eps_halt": float(s.eps_halt) if avit else None,
-            "evo_start": int(s.evo_start) if evo else None,
-            "evo_keep": float(s.evo_keep) if evo else None,
-            "evo_tradeoff": float(s.evo_tradeoff) if evo else None,
-            "ltp_phase": str(s.ltp_phase) if ltp else None,
-            "ltp_temperature": float(s.ltp_temperature) if ltp else None,
-            "ltp_lambda": float(0.01 if getattr(self.args, "ltp_lambda", None) is None else self.args.ltp_lambda) if ltp else None,
-            "ltp_init_threshold": float(s.ltp_init_threshold) if ltp else None,
+            # every family's own keys: its values for the student's family, None for the others
+            **{k: v for m in methods.METHODS if m.config_keys
+               for k, v in zip(m.config_keys, m.config(s, self.args) if m is own else (None,) * len(m.config_keys))},
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
         }
 
@@ -884,15 +815,8 @@ class TrainStep:
         fn = self.tome_loss_fn
         logits_t = None if out_t is None else out_t[0]
         s = self.student
-        if self.avit:
-            loss = fn(logits_s, logits_t, labels, self.metrics, s.ponder_loss, s.prior_loss, s.avg_depth, accumulate=accumulate)
-            per_block = list(s.tokens_per_layer)
-        elif self.ltp:
-            loss = fn(logits_s, logits_t, labels, self.metrics, s.ltp_reg, s.avg_tokens, accumulate=accumulate)
-            per_block = list(s.tokens_per_block)
-        else:
-            loss = fn(logits_s, logits_t, labels, self.metrics, accumulate=accumulate)
-            per_block = list(s.tokens_per_stage if self.ats else s.tokens_per_block)
+        loss = fn(logits_s, logits_t, labels, self.metrics, *self._loss_extras(s), accumulate=accumulate)      # what the forward left on the model
+        per_block = list(getattr(s, self._token_record))
         dist_term = fn.dist_weight * fn.last[2]
         return loss, dict(mask_loss=dist_term, backbone_loss=fn.last[0] - dist_term, kept=None, logits_s=logits_s, token_s=None,
                           pred_logits=None, logits_t=logits_t, token_t=None, cls_attn=None, tokens_per_block=per_block)
@@ -936,7 +860,7 @@ class TrainStep:
                 out_s = self.student(images)
         if self.logits_only:
             return self._tome_losses(out_s, out_t, labels, accumulate)
-        if self.baseline:
+        if self.dynamicvit_loss_fn is not None:
             return self._baseline_losses(out_s, out_t, labels, accumulate)
         logits_t, token_t, cls_attn = out_t
         logits_s, token_s, pred_logits, kept = out_s
@@ -1178,7 +1102,7 @@ class TrainStep:
         self.last_step_captured = True
         scale = self.reducer.finish() if self.reducer is not None else 1.0
         self.opt.step(grad_scale=scale)
-        if self.logits_only:                     # the one student of that route a captured step serves: the Evo-ViT baseline
+        if self.logits_only:                     # of that route a captured step serves the families whose record names no refusal
             self.tome_loss_fn.accumulate(self.metrics, ent["tome_last"])
         else:
             self.mask_loss_fn.accumulate(self.metrics, ent["mask_last"])

@@ -6,6 +6,7 @@ import torch
 
 from d2s import functional as DF
 from d2s import ops
+import methods
 from losses import MaskLoss
 
 
@@ -16,11 +17,9 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
     mask_loss_fn = MaskLoss(args, "val")
     metrics = {}
     # DynamicViT, Token Merging, Adaptive Token Sampling, A-ViT, Evo-ViT and LTP baselines: eval returns logits alone
-    baseline = type(model).__name__ in ("DefaultVisionTransformerDiffPruning", "VisionTransformerToMe", "VisionTransformerATS",
-                                        "VisionTransformerAViT", "VisionTransformerEvo", "VisionTransformerLTP")
-    avit = type(model).__name__ == "VisionTransformerAViT"
-    ltp = type(model).__name__ == "VisionTransformerLTP"
-    depth_sum, tokens_sum = 0.0, 0.0
+    baseline = methods.eval_returns_logits_alone(model)
+    extras = methods.of(model).eval_extras      # what the family's forward leaves on the model, reported as a mean over the batches
+    sums = {key: 0.0 for _, key in extras}
     thr = getattr(args, "patch_score_threshold", None) is not None
     keep_ratio_batches = []
     with torch.no_grad():
@@ -33,10 +32,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
                 correct = float((torch.argmax(logits, dim=1) == val_labels).sum()) / val_labels.shape[0]
                 running_loss += float(loss)
                 running_acc += correct
-                if avit:
-                    depth_sum = depth_sum + model.avg_depth
-                if ltp:
-                    tokens_sum += model.avg_tokens
+                for attr, key in extras:
+                    sums[key] = sums[key] + getattr(model, attr)
                 n += 1
                 continue
             cls_attn_weights = teacher_model.forward_cls_attention(val_inputs)          # :33
@@ -66,10 +63,8 @@ def evaluate_performance(args, model, teacher_model, val_data_loader):
          metrics["val_max_keep_ratio"]) = keep_ratio_summary(keep_ratio_batches)
     metrics["val_loss"] = running_loss / n
     metrics["val_acc"] = running_acc / n
-    if avit:
-        metrics["val_avg_depth"] = float(depth_sum) / n
-    if ltp:
-        metrics["val_avg_tokens"] = float(tokens_sum) / n       # tokens per image and block, CLS included (the hard forward)
+    for key in sums:                   # val_avg_depth; val_avg_tokens: tokens per image and block, CLS included (the hard forward)
+        metrics[key] = float(sums[key]) / n
     if not baseline:
         metrics["unpruned_acc"] = running_unpruned_acc / n
     args.epoch_acc = metrics["val_acc"]

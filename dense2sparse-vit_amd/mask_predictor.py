@@ -44,6 +44,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import methods                                       # noqa: E402
 import utils                                         # noqa: E402
 import vit_models                                    # noqa: E402
 from d2s import ops                                  # noqa: E402
@@ -53,10 +54,6 @@ from train import train_one_epoch                    # noqa: E402
 
 _STUDENTS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_student", "deit_small": "dynamic_vit_small_patch16_224_student",
              "deit_base": "dynamic_vit_base_patch16_224_student"}
-_TOME = {"deit_tiny": "tome_deit_tiny_patch16_224", "deit_small": "tome_deit_small_patch16_224", "deit_base": "tome_deit_base_patch16_224"}
-_ATS = {"deit_tiny": "ats_deit_tiny_patch16_224", "deit_small": "ats_deit_small_patch16_224", "deit_base": "ats_deit_base_patch16_224"}
-_AVIT = {"deit_tiny": "avit_deit_tiny_patch16_224", "deit_small": "avit_deit_small_patch16_224", "deit_base": "avit_deit_base_patch16_224"}
-_EVO = {"deit_tiny": "evo_deit_tiny_patch16_224", "deit_small": "evo_deit_small_patch16_224", "deit_base": "evo_deit_base_patch16_224"}
 _TEACHERS = {"deit_tiny": "dynamic_vit_tiny_patch16_224_teacher", "deit_small": "dynamic_vit_small_patch16_224_teacher",
              "deit_base": "dynamic_vit_base_patch16_224_teacher"}
 # --method dynamicvit: flags of the d2s selection rules that the baseline's Gumbel keep decision has no counterpart for
@@ -65,24 +62,52 @@ _NOT_WITH_DYNAMICVIT = (("topk_selection", "--topk-selection"), ("diff_topk", "-
 # --method ats: the selection rules of the dense-to-sparse student, which a sampling stage replaces
 _NOT_WITH_ATS = (("topk_selection", "--topk-selection"), ("attn_selection", "--attn-selection"), ("fuse_dropped", "--fuse-dropped"),
                  ("squeeze_dropped", "--squeeze-dropped"), ("diff_topk", "--diff-topk"), ("patch_score_threshold", "--patch-score-threshold"))
-# --method avit: its five flags with their defaults (parse_args leaves them None so that a flag given under another method is seen)
-_AVIT_FLAGS = (("avit_gate_scale", "--avit-gate-scale", 10.0), ("avit_gate_center", "--avit-gate-center", 30.0),
-               ("avit_ponder_scale", "--avit-ponder-scale", 5e-4), ("avit_prior_alpha", "--avit-prior-alpha", 0.01),
-               ("avit_target_depth", "--avit-target-depth", 7.0))
-# --method evo: its three flags with their defaults, handled as _AVIT_FLAGS are
-_EVO_FLAGS = (("evo_start", "--evo-start", 4), ("evo_keep", "--evo-keep", 0.5), ("evo_tradeoff", "--evo-tradeoff", 0.5))
-# --method ltp: its four flags with their defaults, handled as _AVIT_FLAGS are.  The three numbers are this build's guesses: no trained
-# checkpoint exists here to tune them on
-_LTP = {"deit_tiny": "ltp_deit_tiny_patch16_224", "deit_small": "ltp_deit_small_patch16_224", "deit_base": "ltp_deit_base_patch16_224"}
-_LTP_FLAGS = (("ltp_phase", "--ltp-phase", "soft"), ("ltp_temperature", "--ltp-temperature", 1e-3), ("ltp_lambda", "--ltp-lambda", 0.01),
-              ("ltp_init_threshold", "--ltp-init-threshold", 0.005))
 _EVO_DEPTH, _EVO_PATCHES = 12, 196           # the factories' trunk: 12 blocks on the 14 x 14 patches of a 224 image
+
+
+def _training_refusals(m, args, bad, warmup=True):
+    """What no logits-only family trains with, under the family's own subject (m.cli) and in its own words."""
+    if m.cli_bf16 and getattr(args, "gemm_mode", "exact") == "bf16" and not (m.cli_bf16[1] and args.eval_only):
+        bad.append(f"{m.cli} with --gemm-mode bf16 ({m.cli_bf16[0]})")
+    if getattr(args, "drop_path", 0.0) > 0.0:
+        bad.append(f"{m.cli} with --drop-path {args.drop_path} (stochastic depth is not built for {m.block})")
+    if args.torch_optim:
+        bad.append(f"{m.cli} with --torch-optim ({m.optim_noun} trains through the fused step only)")
+    if warmup and getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
+        bad.append(f"{m.cli} with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and "
+                   f"{m.has_none}: pass 0 or leave it out)")
+
+
+def _evo_ranges(args, bad):
+    start = getattr(args, "evo_start", None)
+    if start is not None and not 1 <= start <= _EVO_DEPTH:
+        bad.append(f"--evo-start {start} (a block in 1..{_EVO_DEPTH}, the depth)")
+    keep = getattr(args, "evo_keep", None)
+    if keep is not None and not 1 <= int(_EVO_PATCHES * keep) <= _EVO_PATCHES - 1:
+        bad.append(f"--evo-keep {keep} (k = int({_EVO_PATCHES} * keep) must lie in 1..{_EVO_PATCHES - 1})")
+    tau = getattr(args, "evo_tradeoff", None)
+    if tau is not None and not 0.0 <= tau <= 1.0:
+        bad.append(f"--evo-tradeoff {tau} (0 <= tau <= 1)")
+
+
+def _ltp_ranges(args, bad):
+    locs = list(args.pruning_locs or [])
+    if not locs or any(v < 0 or v > _EVO_DEPTH - 2 for v in locs) or any(a >= b for a, b in zip(locs, locs[1:])):
+        bad.append(f"--method ltp with --pruning-locs {' '.join(str(v) for v in locs)} (ascending blocks in 0..{_EVO_DEPTH - 2}: a stage "
+                   "acts on the blocks after it)")
+    tau = getattr(args, "ltp_temperature", None)
+    if tau is not None and not tau > 0.0:
+        bad.append(f"--ltp-temperature {tau} (tau > 0)")
+    lam = getattr(args, "ltp_lambda", None)
+    if lam is not None and not lam >= 0.0:
+        bad.append(f"--ltp-lambda {lam} (lambda >= 0)")
 
 
 def check_supported(args):
     """Flags whose code path is outside the accelerated hot path fail here, loudly, instead of silently training something else."""
     bad = []
-    if getattr(args, "method", "d2s") == "dynamicvit":
+    method = getattr(args, "method", "d2s")
+    if method == "dynamicvit":
         for attr, flag in _NOT_WITH_DYNAMICVIT:
             if getattr(args, attr, None) not in (None, False):
                 bad.append(f"--method dynamicvit with {flag} (the baseline keeps tokens by its own Gumbel decision and predictor)")
@@ -90,138 +115,68 @@ def check_supported(args):
     if tome_r < 0:
         bad.append(f"--tome-r {tome_r} (0 or more tokens per block)")
     tome_train = bool(getattr(args, "tome_train", False))
-    if tome_train and getattr(args, "method", "d2s") != "tome":
-        bad.append(f"--tome-train with --method {getattr(args, 'method', 'd2s')} (it trains the Token Merging baseline: --method tome)")
-    if tome_train and getattr(args, "drop_path", 0.0) > 0.0:
-        bad.append(f"--tome-train with --drop-path {args.drop_path} (stochastic depth is not built for a merging block)")
-    if tome_train and args.torch_optim:
-        bad.append("--tome-train with --torch-optim (a merging student trains through the fused step only)")
+    if tome_train and method != "tome":
+        bad.append(f"--tome-train with --method {method} (it trains the Token Merging baseline: --method tome)")
+    if tome_train:
+        _training_refusals(methods.by_name("tome"), args, bad, warmup=False)      # its warm-up is printed and zeroed below, not refused
     if bool(getattr(args, "tome_bf16", False)):
-        if getattr(args, "method", "d2s") != "tome":
-            bad.append(f"--tome-bf16 with --method {getattr(args, 'method', 'd2s')} (it puts the Token Merging baseline on the bf16 data path: "
+        if method != "tome":
+            bad.append(f"--tome-bf16 with --method {method} (it puts the Token Merging baseline on the bf16 data path: "
                        "--method tome)")
         if tome_train:
             bad.append("--tome-bf16 with --tome-train (training through the merges is built in fp32 only)")
         if not args.eval_only:
             bad.append("--tome-bf16 without --eval-only (the bf16 merging trunk is built for inference)")
-    if getattr(args, "method", "d2s") == "tome":
+    if method == "tome":
         if not args.eval_only and not tome_train:
             bad.append("--method tome without --eval-only (token merging is built for inference: training through a merge needs the merge's "
                        "backward and key weights in both attention-backward kernels)")
         if getattr(args, "gemm_mode", "exact") == "bf16":
             bad.append("--method tome with --gemm-mode bf16 (the key-weighted attention is an fp32 kernel; exact and split run)")
     elif tome_r > 0:
-        bad.append(f"--tome-r {tome_r} with --method {getattr(args, 'method', 'd2s')} (tokens are merged by --method tome only)")
+        bad.append(f"--tome-r {tome_r} with --method {method} (tokens are merged by --method tome only)")
     ats_tokens = getattr(args, "ats_tokens", None)
     ats_train = bool(getattr(args, "ats_train", False))
     if ats_train:
-        if getattr(args, "method", "d2s") != "ats":
-            bad.append(f"--ats-train with --method {getattr(args, 'method', 'd2s')} (it trains the Adaptive Token Sampling baseline: --method ats)")
+        if method != "ats":
+            bad.append(f"--ats-train with --method {method} (it trains the Adaptive Token Sampling baseline: --method ats)")
         if args.eval_only:
             bad.append("--ats-train with --eval-only (evaluation runs the inference path: drop one of the two)")
-        if getattr(args, "gemm_mode", "exact") == "bf16":
-            bad.append("--ats-train with --gemm-mode bf16 (training through a sampling stage is built on the fp32 data path; exact and split run)")
-        if getattr(args, "drop_path", 0.0) > 0.0:
-            bad.append(f"--ats-train with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block)")
-        if args.torch_optim:
-            bad.append("--ats-train with --torch-optim (a sampling student trains through the fused step only)")
-        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
-            bad.append(f"--ats-train with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and a "
-                       "sampling stage has none: pass 0 or leave it out)")
-    if getattr(args, "method", "d2s") == "ats":
+        _training_refusals(methods.by_name("ats"), args, bad)
+    if method == "ats":
         if not args.eval_only and not ats_train:
             bad.append("--method ats without --eval-only (adaptive token sampling is built for inference: a sampling stage has no backward)")
         for attr, flag in _NOT_WITH_ATS:
             if getattr(args, attr, None) not in (None, False):
-                bad.append(f"--method ats with {flag} (a sampling stage scores tokens by the block's own CLS attention and value norms and "
-                           "keeps a count of its own)")
+                bad.append(f"--method ats with {flag} ({methods.by_name('ats').cli_selection})")
         stages = len(args.pruning_locs or [])
         if ats_tokens is not None and len(ats_tokens) not in (1, stages):
             bad.append(f"--ats-tokens with {len(ats_tokens)} values for {stages} stages (one value for every stage, or one per --pruning-locs entry)")
         if ats_tokens is not None and any(v < 1 for v in ats_tokens):
             bad.append(f"--ats-tokens {' '.join(str(v) for v in ats_tokens)} (at least 1 token per stage)")
     elif ats_tokens is not None:
-        bad.append(f"--ats-tokens with --method {getattr(args, 'method', 'd2s')} (tokens are sampled by --method ats only)")
-    avit = getattr(args, "method", "d2s") == "avit"
-    if avit:
+        bad.append(f"--ats-tokens with --method {method} (tokens are sampled by --method ats only)")
+    for m in methods.METHODS:                # the families that --method alone selects and that bring flags of their own: avit, evo, ltp
+        if not m.flags:
+            continue
+        if method != m.name:
+            for attr, flag, _ in m.flags:
+                if getattr(args, attr, None) is not None:
+                    bad.append(f"{flag} with --method {method} (it sets the {m.title} baseline: --method {m.name})")
+            continue
         for attr, flag in _NOT_WITH_ATS:
             if getattr(args, attr, None) not in (None, False):
-                bad.append(f"--method avit with {flag} (every token halts by its own cumulative score: there is no selection stage)")
-        if not args.eval_only and getattr(args, "gemm_mode", "exact") == "bf16":
-            bad.append("--method avit with --gemm-mode bf16 (training through a ragged block is built on the fp32 data path; exact and "
-                       "split run, --eval-only runs in all three)")
-        if getattr(args, "drop_path", 0.0) > 0.0:
-            bad.append(f"--method avit with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block)")
-        if args.torch_optim:
-            bad.append("--method avit with --torch-optim (an adaptive-depth student trains through the fused step only)")
-        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
-            bad.append(f"--method avit with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and "
-                       "adaptive depth has none: pass 0 or leave it out)")
-    else:
-        for attr, flag, _ in _AVIT_FLAGS:
-            if getattr(args, attr, None) is not None:
-                bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the A-ViT baseline: --method avit)")
-    evo = getattr(args, "method", "d2s") == "evo"
-    if evo:
-        for attr, flag in _NOT_WITH_ATS:
-            if getattr(args, attr, None) not in (None, False):
-                bad.append(f"--method evo with {flag} (the slow-fast update ranks tokens by its own global score: there is no selection stage)")
-        if getattr(args, "drop_path", 0.0) > 0.0:
-            bad.append(f"--method evo with --drop-path {args.drop_path} (stochastic depth is not built for a slow-fast block)")
-        if args.torch_optim:
-            bad.append("--method evo with --torch-optim (a slow-fast student trains through the fused step only)")
-        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
-            bad.append(f"--method evo with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and the "
-                       "slow-fast update has none: pass 0 or leave it out)")
-        start = getattr(args, "evo_start", None)
-        if start is not None and not 1 <= start <= _EVO_DEPTH:
-            bad.append(f"--evo-start {start} (a block in 1..{_EVO_DEPTH}, the depth)")
-        keep = getattr(args, "evo_keep", None)
-        if keep is not None and not 1 <= int(_EVO_PATCHES * keep) <= _EVO_PATCHES - 1:
-            bad.append(f"--evo-keep {keep} (k = int({_EVO_PATCHES} * keep) must lie in 1..{_EVO_PATCHES - 1})")
-        tau = getattr(args, "evo_tradeoff", None)
-        if tau is not None and not 0.0 <= tau <= 1.0:
-            bad.append(f"--evo-tradeoff {tau} (0 <= tau <= 1)")
-    else:
-        for attr, flag, _ in _EVO_FLAGS:
-            if getattr(args, attr, None) is not None:
-                bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the Evo-ViT baseline: --method evo)")
-    ltp = getattr(args, "method", "d2s") == "ltp"
-    if ltp:
-        for attr, flag in _NOT_WITH_ATS:
-            if getattr(args, attr, None) not in (None, False):
-                bad.append(f"--method ltp with {flag} (a token stays while the attention it receives reaches its block's learned threshold: "
-                           "there is no other selection stage)")
-        if getattr(args, "gemm_mode", "exact") == "bf16":
-            bad.append("--method ltp with --gemm-mode bf16 (the score is recomputed from the fp32 attention's log-sum-exp, and both phases "
-                       "train on the fp32 data path; exact and split run)")
-        if getattr(args, "drop_path", 0.0) > 0.0:
-            bad.append(f"--method ltp with --drop-path {args.drop_path} (stochastic depth is not built for a ragged block or a block with a "
-                       "learnt policy)")
-        if args.torch_optim:
-            bad.append("--method ltp with --torch-optim (a learned-threshold student trains through the fused step only)")
-        if getattr(args, "warmup_steps_given", True) and args.warmup_steps > 0:
-            bad.append(f"--method ltp with --warmup-steps {args.warmup_steps} (the warm-up epochs train the score predictors only and "
-                       "learned thresholds have none: pass 0 or leave it out)")
-        locs = list(args.pruning_locs or [])
-        if not locs or any(v < 0 or v > _EVO_DEPTH - 2 for v in locs) or any(a >= b for a, b in zip(locs, locs[1:])):
-            bad.append(f"--method ltp with --pruning-locs {' '.join(str(v) for v in locs)} (ascending blocks in 0..{_EVO_DEPTH - 2}: a stage "
-                       "acts on the blocks after it)")
-        tau = getattr(args, "ltp_temperature", None)
-        if tau is not None and not tau > 0.0:
-            bad.append(f"--ltp-temperature {tau} (tau > 0)")
-        lam = getattr(args, "ltp_lambda", None)
-        if lam is not None and not lam >= 0.0:
-            bad.append(f"--ltp-lambda {lam} (lambda >= 0)")
-    else:
-        for attr, flag, _ in _LTP_FLAGS:
-            if getattr(args, attr, None) is not None:
-                bad.append(f"{flag} with --method {getattr(args, 'method', 'd2s')} (it sets the LTP baseline: --method ltp)")
+                bad.append(f"{m.cli} with {flag} ({m.cli_selection})")
+        _training_refusals(m, args, bad)
+        if m.name == "evo":
+            _evo_ranges(args, bad)
+        if m.name == "ltp":
+            _ltp_ranges(args, bad)
     if bool(getattr(args, "ragged_train", False)):
         if args.patch_score_threshold is None:
             bad.append("--ragged-train without --patch-score-threshold (it trains the dynamic keep ratio on the ragged packed batch; the "
                        "fixed-ratio path already trains on the kept tokens alone)")
-        if getattr(args, "method", "d2s") != "d2s":
+        if method != "d2s":
             bad.append(f"--ragged-train with --method {args.method} (it trains the dense-to-sparse student's dynamic keep ratio: --method d2s)")
         if getattr(args, "gemm_mode", "exact") == "bf16":
             bad.append("--ragged-train with --gemm-mode bf16 (training through a ragged block is built on the fp32 data path; exact and split run)")
@@ -283,7 +238,7 @@ def check_supported(args):
         if getattr(args, "diff_topk", False):
             bad.append("--fuse-dropped with --diff-topk (the soft gather has no dropped set)")
     if getattr(args, "squeeze_dropped", False):
-        if getattr(args, "method", "d2s") in ("dynamicvit", "tome"):
+        if method in ("dynamicvit", "tome"):
             bad.append(f"--squeeze-dropped with --method {args.method} (dropped tokens are squeezed into kept ones in the dense-to-sparse "
                        "student only)")
         if not args.topk_selection:
@@ -296,7 +251,7 @@ def check_supported(args):
         if args.patch_score_threshold is not None:
             bad.append("--squeeze-dropped with --patch-score-threshold (no token is removed there: nothing to squeeze)")
     if getattr(args, "attn_selection", False):
-        if getattr(args, "method", "d2s") == "dynamicvit":
+        if method == "dynamicvit":
             bad.append("--method dynamicvit with --attn-selection (the baseline keeps tokens by its own Gumbel decision and predictor)")
         if not args.topk_selection:
             bad.append("--attn-selection without --topk-selection (the CLS attention is ranked by the hard top-k of the fixed-ratio path; "
@@ -350,21 +305,10 @@ def check_supported(args):
     if args.output_dir and args.torch_optim and not args.eval_only:
         print("Attention: --output-dir with --torch-optim saves the student's weights only ('model', epoch, best_acc): such a file "
               "loads through --student-checkpoint, it cannot be resumed")
-    if avit:
+    if methods.by_name(method).flags:
         args.warmup_steps = 0                # not given (refused above otherwise)
-        for attr, _, default in _AVIT_FLAGS:
-            if getattr(args, attr, None) is None:
-                setattr(args, attr, default)
-    if evo:
-        args.warmup_steps = 0                # not given (refused above otherwise)
-        for attr, _, default in _EVO_FLAGS:
-            if getattr(args, attr, None) is None:
-                setattr(args, attr, default)
-    if ltp:
-        args.warmup_steps = 0                # not given (refused above otherwise)
-        for attr, _, default in _LTP_FLAGS:
-            if getattr(args, attr, None) is None:
-                setattr(args, attr, default)
+        for attr, value in methods.flag_values(methods.by_name(method), args).items():
+            setattr(args, attr, value)
     if ats_train:
         args.warmup_steps = 0                # not given (refused above otherwise): the reference's default of 5 predictor-only epochs has no meaning here
     if tome_train and args.warmup_steps > 0:
@@ -391,33 +335,15 @@ def check_supported(args):
 def build_models(args):
     """mask_predictor.py:170-202 (the arch switch), with local checkpoints instead of URL downloads."""
     arch = args.arch if args.arch in _STUDENTS else "deit_small"
-    if getattr(args, "method", "d2s") == "ats":
-        if not getattr(args, "ats_train", False):
-            return build_ats(args), None             # inference only: no teacher
-        # --ats-train: the sampling student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
-        teacher = None
-        if args.dist_weight != 0:
-            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
-        return build_ats(args, train_sample=True), teacher
-    if getattr(args, "method", "d2s") == "avit":
-        # the adaptive-depth student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
-        teacher = None
-        if args.dist_weight != 0:
-            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
-        return build_avit(args), teacher
-    if getattr(args, "method", "d2s") == "evo":
-        # the slow-fast student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
-        teacher = None
-        if args.dist_weight != 0:
-            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
-        return build_evo(args), teacher
-    if getattr(args, "method", "d2s") == "ltp":
-        # the learned-threshold student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
-        teacher = None
-        if args.dist_weight != 0:
-            teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
-        return build_ltp(args), teacher
-    if getattr(args, "method", "d2s") == "dynamicvit":
+    method = getattr(args, "method", "d2s")
+    if method == "ats" and not getattr(args, "ats_train", False):
+        return build_ats(args), None                 # inference only: no teacher
+    build = {"ats": lambda a: build_ats(a, train_sample=True), "avit": build_avit, "evo": build_evo, "ltp": build_ltp}.get(method)
+    if build is not None:
+        # the family's student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
+        teacher = _teacher(args)
+        return build(args), teacher
+    if method == "dynamicvit":
         student = getattr(vit_models, "default_" + _STUDENTS[arch])(args.pruning_locs, args.keep_ratios,
                                                                     drop_path_rate=getattr(args, "drop_path", 0.0),
                                                                     checkpoint_path=args.student_checkpoint)
@@ -441,13 +367,25 @@ def build_models(args):
     return student.to(args.device), teacher.to(args.device)
 
 
+def _teacher(args):
+    """The dense teacher of a logits-only student, or None under --dist-weight 0: such a student trains without one."""
+    if args.dist_weight == 0:
+        return None
+    arch = args.arch if args.arch in _TEACHERS else "deit_small"
+    return getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device)
+
+
+def _trunk(name, args, *a, **kw):
+    """The family's factory for --arch, called with a and kw; weights as load_trunk finds them."""
+    m = methods.by_name(name)
+    model = getattr(vit_models, m.factory(args.arch if args.arch in _STUDENTS else "deit_small"))(*a, **kw)
+    return load_trunk(args, model, m.name, m.no_predictor)
+
+
 def build_tome(args):
     """--method tome: the dense DeiT trunk with token merging, weights from --student-checkpoint or the 'model' entry of a --resume file.  A
     dense-to-sparse student's checkpoint carries score predictors this model has no use for: they are ignored (strict=False)."""
-    arch = args.arch if args.arch in _TOME else "deit_small"
-    model = getattr(vit_models, _TOME[arch])(args.tome_r, train_merge=bool(getattr(args, "tome_train", False)),
-                                             bf16=bool(getattr(args, "tome_bf16", False)))
-    return load_trunk(args, model, "tome", "token merging has no predictor")
+    return _trunk("tome", args, args.tome_r, train_merge=bool(getattr(args, "tome_train", False)), bf16=bool(getattr(args, "tome_bf16", False)))
 
 
 def load_trunk(args, model, method, why):
@@ -472,43 +410,30 @@ def load_trunk(args, model, method, why):
 def build_ats(args, **kw):
     """--method ats: the dense DeiT trunk with a sampling stage in every block of --pruning-locs, at most --ats-tokens tokens each.
     kw: train_sample=True under --ats-train, nothing otherwise."""
-    arch = args.arch if args.arch in _ATS else "deit_small"
     toks = getattr(args, "ats_tokens", None)
     if toks is not None and len(toks) == 1:
         toks = int(toks[0])
-    model = getattr(vit_models, _ATS[arch])(ats_locs=list(args.pruning_locs), ats_tokens=toks, **kw)
-    return load_trunk(args, model, "ats", "adaptive token sampling has no predictor")
+    return _trunk("ats", args, ats_locs=list(args.pruning_locs), ats_tokens=toks, **kw)
 
 
 def build_avit(args):
     """--method avit: the dense DeiT trunk with per-token adaptive depth; the gate constants and the prior's target depth from --avit-*."""
-    arch = args.arch if args.arch in _AVIT else "deit_small"
-    d = {attr: default for attr, _, default in _AVIT_FLAGS}
-    get = lambda attr: d[attr] if getattr(args, attr, None) is None else getattr(args, attr)
-    model = getattr(vit_models, _AVIT[arch])(gate_scale=get("avit_gate_scale"), gate_center=get("avit_gate_center"),
-                                             target_depth=get("avit_target_depth"))
-    return load_trunk(args, model, "avit", "adaptive depth has no predictor")
+    v = methods.flag_values(methods.by_name("avit"), args)
+    return _trunk("avit", args, gate_scale=v["avit_gate_scale"], gate_center=v["avit_gate_center"], target_depth=v["avit_target_depth"])
 
 
 def build_evo(args):
     """--method evo: the dense DeiT trunk with the slow-fast token update from block --evo-start on."""
-    arch = args.arch if args.arch in _EVO else "deit_small"
-    d = {attr: default for attr, _, default in _EVO_FLAGS}
-    get = lambda attr: d[attr] if getattr(args, attr, None) is None else getattr(args, attr)
-    model = getattr(vit_models, _EVO[arch])(evo_start=get("evo_start"), evo_keep=get("evo_keep"), evo_tradeoff=get("evo_tradeoff"))
-    return load_trunk(args, model, "evo", "the slow-fast update has no predictor")
+    return _trunk("evo", args, **methods.flag_values(methods.by_name("evo"), args))
 
 
 def build_ltp(args):
     """--method ltp: the dense DeiT trunk with one learnable threshold per block of --pruning-locs; phase, temperature and the initial
     thresholds from --ltp-*.  A DeiT checkpoint has no ltp_threshold: the thresholds then keep their initial values; a checkpoint of an
     earlier LTP run (the soft phase's best.pt) brings its own."""
-    arch = args.arch if args.arch in _LTP else "deit_small"
-    d = {attr: default for attr, _, default in _LTP_FLAGS}
-    get = lambda attr: d[attr] if getattr(args, attr, None) is None else getattr(args, attr)
-    model = getattr(vit_models, _LTP[arch])(pruning_loc=list(args.pruning_locs), ltp_temperature=get("ltp_temperature"),
-                                            ltp_init_threshold=get("ltp_init_threshold"), ltp_phase=get("ltp_phase"))
-    return load_trunk(args, model, "ltp", "learned thresholds have no predictor")
+    v = methods.flag_values(methods.by_name("ltp"), args)
+    return _trunk("ltp", args, pruning_loc=list(args.pruning_locs), ltp_temperature=v["ltp_temperature"],
+                  ltp_init_threshold=v["ltp_init_threshold"], ltp_phase=v["ltp_phase"])
 
 
 def folder_loaders(args, samples, split, epoch, rank, world):
@@ -604,9 +529,7 @@ def main(argv=None):
         return eval_tome(args, rank, world, distributed)
     if args.method == "tome":
         # --tome-train: the merging student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
-        student = build_tome(args)
-        arch = args.arch if args.arch in _TEACHERS else "deit_small"
-        teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint).to(args.device) if args.dist_weight != 0 else None
+        student, teacher = build_tome(args), _teacher(args)
     else:
         student, teacher = build_models(args)
     if rank == 0:

@@ -10,7 +10,8 @@ the mean over the window, clipped to the global L2 norm M.  A TrainStep carries 
 step) and is flushed at the end of the epoch; for a torch optimizer the same window is spelled out here with torch."""
 import torch
 
-from losses import MaskLoss, BackboneLoss, DynamicViTLoss, ToMeLoss, AViTLoss, LTPLoss
+import methods
+from losses import MaskLoss, BackboneLoss
 
 
 def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mixup_fn=None):
@@ -23,35 +24,19 @@ def train_one_epoch(args, model, teacher_model, train_data_loader, optimizer, mi
     if teacher_model is not None:
         teacher_model.eval()
     fast = isinstance(optimizer, TrainStep)
-    if type(model).__name__ == "VisionTransformerToMe" and not fast:
-        raise ValueError("a Token Merging student trains through d2s.engine.TrainStep only")
-    if type(model).__name__ == "VisionTransformerATS" and getattr(model, "ats_locs", []) and not fast:
-        raise ValueError("an Adaptive Token Sampling student trains through d2s.engine.TrainStep only")
-    if type(model).__name__ == "VisionTransformerAViT" and not fast:
-        raise ValueError("an A-ViT student trains through d2s.engine.TrainStep only")
-    if type(model).__name__ == "VisionTransformerEvo" and not fast:
-        raise ValueError("an Evo-ViT student trains through d2s.engine.TrainStep only")
-    if type(model).__name__ == "VisionTransformerLTP" and not fast:
-        raise ValueError("an LTP student trains through d2s.engine.TrainStep only")
+    method = methods.of(model)
+    if method.logits_only and not fast:
+        raise ValueError(f"{method.student} trains through d2s.engine.TrainStep only")
     if getattr(model, "ragged_train", False) and not fast:
         raise ValueError("a student that trains on the ragged packed batch (ragged_train=True) trains through d2s.engine.TrainStep only")
-    baseline = type(model).__name__ == "DefaultVisionTransformerDiffPruning"      # the DynamicViT baseline: its own outputs and objective
+    baseline = method.name == "dynamicvit"      # the DynamicViT baseline: its own outputs and objective
     if fast:
         step = optimizer
         step.metrics = metrics
-        if getattr(step, "avit", False):            # the A-ViT baseline: train_ponder_loss, train_prior_loss, train_avg_depth beside ToMeLoss's
-            step.tome_loss_fn = AViTLoss(args)
-        elif getattr(step, "ltp", False):           # the LTP baseline: train_ltp_reg, train_avg_tokens beside ToMeLoss's
-            step.tome_loss_fn = LTPLoss(args)
-        elif getattr(step, "tome", False) or getattr(step, "ats", False) or getattr(step, "evo", False):      # the logits-only students
-            step.tome_loss_fn = ToMeLoss(args)
-        elif baseline:
-            step.dynamicvit_loss_fn = DynamicViTLoss(args)
-        else:
-            step.mask_loss_fn, step.backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)   # fresh running means per epoch (:14-15)
+        step.fresh_losses(args)          # fresh running means per epoch (:14-15), the family's extra metrics with them
     else:
         if baseline:
-            dynamicvit_loss_fn = DynamicViTLoss(args)
+            dynamicvit_loss_fn = method.loss(args)
         else:
             mask_loss_fn, backbone_loss_fn = MaskLoss(args, "train"), BackboneLoss(args)
         accum, clip = max(1, int(getattr(args, "accum_steps", 1) or 1)), getattr(args, "clip_grad", None)

@@ -85,6 +85,7 @@ def parse_args(argv=None):
     with --data-source folder they drive d2s.data (the tracking flags are always ignored).  The run flags added at the end are not in
     the reference."""
     import argparse
+    import methods
     p = argparse.ArgumentParser(description='Transformers')
     p.add_argument('--arch', default='deit_small', type=str)
     p.add_argument('--is-sbatch', action='store_true', default=False)
@@ -165,7 +166,7 @@ def parse_args(argv=None):
     p.add_argument('--model-ema', action='store_true', default=False,
                    help='keep an exponential moving average of the student inside the fused AdamW launch; adds val_acc_ema to the epoch metrics')
     p.add_argument('--model-ema-decay', type=float, default=0.99996, help="decay of --model-ema (DeiT's default)")
-    p.add_argument('--method', default='d2s', choices=['d2s', 'dynamicvit', 'tome', 'ats', 'avit', 'evo', 'ltp'],
+    p.add_argument('--method', default='d2s', choices=[m.name for m in methods.METHODS],
                    help="d2s: the dense-to-sparse student (default); dynamicvit: the DynamicViT baseline (Gumbel keep decisions through policy "
                         "attention, dense training) with --ratio-weight / --dist-weight / --cls-weight as the weights of its objective; "
                         "tome: the Token Merging baseline (--tome-r; no predictor; --eval-only, or --tome-train to train through the merges); "

@@ -216,5 +216,14 @@ def test_training_mode_with_a_stage_is_refused_before_anything_runs():
 
 
 def test_evaluate_treats_the_model_as_a_baseline():
-    src = open(os.path.join(REPO, "dense2sparse-vit_amd", "evaluate.py")).read()
-    assert '"VisionTransformerATS"' in src
+    """evaluate_performance asks methods.eval_returns_logits_alone: with and without stages the model's eval() returns logits alone."""
+    import methods
+    import vit_models
+    for kw in (dict(ats_locs=[1], ats_tokens=4), dict()):
+        m = vit_models.VisionTransformerATS(**MICRO, **kw)
+        assert methods.eval_returns_logits_alone(m) is True
+        assert methods.of(m).eval_extras == ()
+    assert methods.of(vit_models.VisionTransformerATS(**MICRO, ats_locs=[1])).name == "ats"
+    assert methods.of(vit_models.VisionTransformerATS(**MICRO)).name == "d2s"          # no stage: the dense trunk, where it was
+    import evaluate
+    assert evaluate.methods is methods

@@ -376,7 +376,7 @@ def test_train_step_loss_three_steps_and_checkpoint(with_teacher):
     case = cases.MODEL_CASES["micro1"]
     x, y = images.to(DEV), torch.from_numpy(cases.make_labels(case)).to(DEV)
     ts = _step(with_teacher)
-    assert ts.ats and ts.logits_only and not ts.tome and ts.graph is False and (ts._teacher_stream is None) == (not with_teacher)
+    assert ts.method.name == "ats" and ts.logits_only and ts.graph is False and (ts._teacher_stream is None) == (not with_teacher)
     info = ts(x, y)
     torch.cuda.synchronize()
     kept = _kept_sets(ts.student, images.shape[0])                           # of the forward that made the loss (the weights have moved since)

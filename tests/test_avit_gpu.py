@@ -444,7 +444,7 @@ def test_train_step_two_runs_bit_identical_and_resume(with_teacher):
     runs = []
     for _ in range(2):
         ts = _step(with_teacher)
-        assert ts.avit and ts.logits_only and ts.graph is False
+        assert ts.method.name == "avit" and ts.logits_only and ts.graph is False
         losses = [float(ts(x, y)["loss"]) for _ in range(2)]
         torch.cuda.synchronize()
         runs.append((losses, ts.arena.params.clone(), ts))

@@ -319,7 +319,7 @@ def test_train_step_loss_determinism_and_checkpoint(with_teacher):
     _, sd, images, _ = _models("micro1")
     x, y = _batch()
     ts = _step(with_teacher)
-    assert ts.tome and ts.graph is False and (ts._teacher_stream is None) == (not with_teacher)
+    assert ts.method.name == "tome" and ts.graph is False and (ts._teacher_stream is None) == (not with_teacher)
     info = ts(x, y)
     torch.cuda.synchronize()
     assert info["stepped"] and info["tokens_per_block"] == [15, 13, 11, 9]

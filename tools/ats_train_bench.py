@@ -88,7 +88,7 @@ for r in range(args.rounds):
 for (name, ts), t in zip(steps, times):
     ms, spread = sum(t) / len(t), max(t) - min(t)
     line = f"{mname:12s} {name:30s} {ms:7.2f} ms/step (spread {spread:.2f})  {B / ms * 1e3:8.0f} images/s"
-    if ts.ats:
+    if ts.method.name == "ats":
         per = [c.float() for c in ts.student.tokens_per_stage]
         line += f"   tokens per stage: mean {[round(float(c.mean()), 1) for c in per]} min {[int(c.min()) for c in per]} max {[int(c.max()) for c in per]}"
     print(line, flush=True)

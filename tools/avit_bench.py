@@ -89,7 +89,7 @@ for r in range(args.rounds):
 for (name, ts), t in zip(steps, times):
     ms, spread = sum(t) / len(t), max(t) - min(t)
     line = f"{mname:12s} {name:36s} {ms:7.2f} ms/step (spread {spread:.2f})  {B / ms * 1e3:8.0f} images/s"
-    if ts.avit:
+    if ts.method.name == "avit":
         line += f"   average depth {float(ts.student.avg_depth):.2f}, rows per block {ts.student.tokens_per_layer}"
     else:
         line += f"   tokens after the stage: mean {float(ts.student.tokens_per_stage[0].float().mean()):.1f} of 196"
