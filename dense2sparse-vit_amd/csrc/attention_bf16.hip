@@ -35,12 +35,15 @@
 // image's n returns before any barrier, and the segment is clamped to [0, total), its length to [0, max_n] (VarlenSeg): the rows of an
 // image are the bits of the dense backward on that image alone.
 //
-// KEYW (the 32-key-tile forward only; no policy, no ragged form, no backward): attention whose keys carry weights, token merging at
-// inference on the bf16 data path.  out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B, n] >= 1: the
+// KEYW (the 32-key-tile forward, dQ and dK/dV; no policy, no ragged form): attention whose keys carry weights, token merging on the bf16
+// data path, at inference and in training.  out_i = sum_j w_j exp(S_ij) v_j / sum_j w_j exp(S_ij), w = key_w [B, n] >= 1: the
 // tile's 32 weights travel through pol_s as a policy does, e_ij = 2^(s log2 e - m log2 e) * w_j (one more fp32 rounding) feeds both the
 // row sum and the bf16 P; no diagonal exception.  The running maximum stays the one over the raw scores (w >= 1 keeps e w >= e), so
 // lse_i = m_i + log(l_i) is the log of the weighted denominator, d2s_attn_keyw_fwd_f32's definition.  The weights travel in `policy`.
 // With unit weights the multiply is by 1.0: the bits of the plain kernel.
+//   backward:  P_ij = w_j exp(S_ij - lse_i) with that lse (one more fp32 rounding, before P meets dP - delta or the bf16 packing), then the
+//     plain rule dV = P^T dO, dS = P (dP - delta), dQ = scale dS K, dK = scale dS^T Q; the weights get no gradient.  The dQ kernel stages the
+//     tile's weights in pol_s as the forward does, the dK/dV kernel keeps its lane's key's weight in one register.  32-key tiles only.
 #include "d2s_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -595,17 +598,18 @@ __device__ __forceinline__ int varlen_rows(VarlenSeg v, int b, int max_n, int& r
 // launch picks the flagged instantiation at n = 1 only, so an image's rows stay the bits of the dense backward on that image alone and
 // every instantiation that runs at n > 1 keeps its code.  The POLICY kernels do not take it.
 // `tail` is the policy (const float*; read by the POLICY instantiations only; no __restrict__: with it the one on fp32 qkv re-schedules) or,
-// VARLEN, the segment table.
-template <typename QT, bool POLICY = false, bool VARLEN = false, bool ONE_KEY = false>
+// VARLEN, the segment table.  KEYW: the key weights [B, n] travel in `tail` as a policy does.
+template <typename QT, bool POLICY = false, bool VARLEN = false, bool ONE_KEY = false, bool KEYW = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
                                                                   std::conditional_t<VARLEN, VarlenSeg, const float*> tail) {
     static_assert(!(POLICY && (VARLEN || ONE_KEY)), "the ragged form has no policy, the policy kernels no one-key form");
+    static_assert(!(KEYW && (POLICY || VARLEN || ONE_KEY)), "key weights combine with neither the policy, the ragged nor the one-key form");
     __shared__ __attribute__((aligned(16))) __bf16 Ks[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Vs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Kt[DH * VP];
-    __shared__ __attribute__((aligned(16))) float pol_s[POLICY ? 32 : 1];
+    __shared__ __attribute__((aligned(16))) float pol_s[(POLICY || KEYW) ? 32 : 1];      // the tile's policy (KEYW: its key weights)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     int bx, by;
     xcd_remap_2d(bx, by);      // all blocks of one head on one XCD (shared K / V / Q / dO panels stay in its L2)
@@ -637,13 +641,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
     const int ntiles = (n + 31) / 32;
     f32x4 kr[2], vr[2];
     const float* polb = nullptr;
-    float pr = 0.f;                              // POLICY: policy of the staged tile's key tid & 31
+    float pr = 0.f;                              // POLICY: policy of the staged tile's key tid & 31; KEYW: its weight
     auto fetch_pol = [&](int row0) {
         const int kj = row0 + (tid & 31);
         const float p0 = polb[min(kj, n - 1)];
         pr = kj < n ? p0 : 0.f;
     };
-    if constexpr (POLICY) {
+    if constexpr (POLICY || KEYW) {
         polb = tail + (long)b * n;
         fetch_pol(0);
     }
@@ -654,12 +658,12 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
         put_rows(Ks, tid, kr, 1.0f);
         put_rows(Vs, tid, vr, 1.0f);
         put_rows_t(Kt, tid, kr);
-        if (POLICY && tid < 32) pol_s[tid] = pr;
+        if ((POLICY || KEYW) && tid < 32) pol_s[tid] = pr;
         __syncthreads();
         const int tn = min(t + 1, ntiles - 1) * 32;
         stage_rows(kb, ld, tn, n, tid, kr);
         stage_rows(vb, ld, tn, n, tid, vr);
-        if (POLICY) fetch_pol(tn);
+        if (POLICY || KEYW) fetch_pol(tn);
         if (!active) continue;
         f32x16 s = mma_rows(Ks, qf, l31, half);        // scaled scores^T [key][query]
         const f32x16 dp = mma_rows(Vs, dof, l31, half);  // dP^T[key][query] = sum_d V[key][d] dO[query][d]
@@ -673,6 +677,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
                     for (int j = 0; j < 4; ++j)
                         if (8 * g + 4 * half + j == l31) pg[j] = 1.f;
                 }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r = 4 * g + j;
+                    s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_i)) * pg[j] * (dp[r] - dl_i);
+                }
+            }
+        } else if constexpr (KEYW) {                   // dS^T = (P~^T w) (dP^T - delta): a key weighs the same for every query, no diagonal exception
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 pg = *reinterpret_cast<const f32x4*>(&pol_s[8 * g + 4 * half]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int r = 4 * g + j;
@@ -703,15 +717,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_bf16_kernel(const QT* __re
 // ---- backward, dK / dV: a lane owns one key; loop over query tiles ------------------------------------------------------------------
 // The policy arguments, read by the POLICY / DPOL instantiations only (dpol_part [B, H, n]: DPOL).  One struct: as three plain arguments the
 // DPOL instantiations load them in other groups, and the backward with dpolicy measured 0.3 us slower (118.8 -> 119.1 us at B 128, H 6, n 197).
-// VARLEN: the segment table takes the struct's place, as in the dQ kernel.
+// VARLEN: the segment table takes the struct's place, as in the dQ kernel.  KEYW: the key weights [B, n] travel in `policy`.
 struct AttnPolBwd { const float* policy; const float* cinv; float* dpol_part; };
-template <typename QT, bool POLICY = false, bool DPOL = false, bool VARLEN = false, bool ONE_KEY = false>
+template <typename QT, bool POLICY = false, bool DPOL = false, bool VARLEN = false, bool ONE_KEY = false, bool KEYW = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __restrict__ qkv, const float* __restrict__ dout,
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                                    float* __restrict__ dqkv, __bf16* __restrict__ dqkv16, int n, int H, float scale,
                                                                    std::conditional_t<VARLEN, VarlenSeg, AttnPolBwd> pol) {
     static_assert(!DPOL || POLICY, "the policy's gradient needs a policy");
     static_assert(!(POLICY && (VARLEN || ONE_KEY)), "the ragged form has no policy, the policy kernels no one-key form");
+    static_assert(!(KEYW && (POLICY || DPOL || VARLEN || ONE_KEY)), "key weights combine with neither the policy, the ragged nor the one-key form");
     __shared__ __attribute__((aligned(16))) __bf16 Qs[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Ds[32 * KP];
     __shared__ __attribute__((aligned(16))) __bf16 Qt[DH * VP];
@@ -754,6 +769,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
         ci_b = pol.cinv + ((long)b * H + h) * n;
         pol_key = kok ? pol.policy[(long)b * n + k0 + l31] : 0.f;
     }
+    [[maybe_unused]] float w_key = 0.f;                   // KEYW: this lane's key's weight
+    if constexpr (KEYW) w_key = kok ? pol.policy[(long)b * n + k0 + l31] : 0.f;
     auto fetch = [&](int row0) {
         stage_rows(qb, ld, row0, n, tid, qr);
         stage_rows(dob, ldo, row0, n, tid, dr);
@@ -792,7 +809,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const QT* __r
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int qi = mfma32_row(r, half);
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_s[qi]));
+            float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], L2E, -lse_s[qi]));
+            if constexpr (KEYW) p *= w_key;              // before p feeds dV and dS
             s[r] = p;
             dp[r] = p * (dp[r] - dl_s[qi]);
         }
@@ -925,6 +943,21 @@ static int attn_varlen_bwd_bf16_launch(const QT* qkv, const int* cu, const float
     return d2s_check_launch();
 }
 
+// the key-weighted backward: the dense backward's three launches with the KEYW dQ and dK/dV
+template <typename QT>
+static int attn_keyw_bwd_bf16_launch(const QT* qkv, const float* key_w, const float* out, const float* dout, const float* lse, float* dqkv,
+                                     void* dqkv_bf16, float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
+    const int rc = d2s_attn_delta(out, dout, delta_ws, B, n, H, stream);
+    if (rc != D2S_OK) return rc;
+    dim3 grid((n + 127) / 128, B * H), block(256);
+    __bf16* dqkv16 = static_cast<__bf16*>(dqkv_bf16);
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<QT, false, false, false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv, dqkv16, n, H,
+                       scale, key_w);
+    hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<QT, false, false, false, false, true>), grid, block, 0, stream, qkv, dout, lse, delta_ws, dqkv,
+                       dqkv16, n, H, scale, AttnPolBwd{key_w, nullptr, nullptr});
+    return d2s_check_launch();
+}
+
 extern "C" {
 
 // Same contract as d2s_attn_fwd_f32; Q, K, V rounded to bf16 for the two matrix products (bf16 arithmetic mode).
@@ -1031,6 +1064,19 @@ int d2s_attn_keyw_fwd_bf16(const void* qkv, int qkv_is_bf16, const float* key_w,
     if (!qkv || !key_w || (!out && !out_bf16) || !lse || B <= 0 || n < 2 || n > 8192 || H <= 0) return D2S_ERR_ARG;
     return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
         return attn_fwd_bf16_launch<false, false, true>(q, out, out_bf16, lse, nullptr, B, n, H, scale, stream, key_w);
+    });
+}
+
+// Backward of d2s_attn_keyw_fwd_bf16 (out its fp32 output, lse as it wrote it - the log of the weighted denominator; dout [B, n, H*64]):
+// dqkv (fp32) and / or dqkv_bf16, both [B, n, 3, H, 64], at least one, fully written; delta_ws: [B, H, n] floats of scratch.  The three
+// launches of d2s_attn_bwd_bf16_bf16out with P_ij = w_j exp(S_ij - lse_i); the weights get no gradient.  With unit weights and the plain
+// forward's out and lse: that entry's bits.  No atomics, two launches are bit-identical.  2 <= n <= 8192.
+int d2s_attn_keyw_bwd_bf16(const void* qkv, int qkv_is_bf16, const float* key_w, const float* out, const float* dout, const float* lse,
+                           float* dqkv, void* dqkv_bf16, float* delta_ws, int B, int n, int H, float scale, hipStream_t stream) {
+    if (!qkv || !key_w || !out || !dout || !lse || (!dqkv && !dqkv_bf16) || !delta_ws || B <= 0 || n < 2 || n > 8192 || H <= 0)
+        return D2S_ERR_ARG;
+    return with_qkv_type(qkv, qkv_is_bf16, [&](auto q) {
+        return attn_keyw_bwd_bf16_launch(q, key_w, out, dout, lse, dqkv, dqkv_bf16, delta_ws, B, n, H, scale, stream);
     });
 }
 

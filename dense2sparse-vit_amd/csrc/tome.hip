@@ -14,7 +14,9 @@
 //
 //   backward   (training through the merge; the plan and the sizes are constants, the match reads K under no gradient)  the merge is linear
 //              in x, so every INPUT row's gradient is one output row's, scaled: a merged row (a source, or a B row with sources) gets
-//              (size_t / size_out_row) dy_row, every other row its output row's gradient bit for bit.
+//              (size_t / size_out_row) dy_row, every other row its output row's gradient bit for bit.  On the bf16 data path
+//              (d2s_tome_merge_bwd_bf16out) the same pass also stores every row in bf16, the fp32 value rounded once, for the GEMMs
+//              that read the gradient behind the merge.
 //
 // No atomics, no memset, no scratch, nothing read back by the host: deterministic and legal inside a captured step.
 //
@@ -22,6 +24,7 @@
 // load converts each value to fp32 (exact) and everything after the load is the same fp32 code in the same order, so
 // d2s_tome_match_bf16(q16) is d2s_tome_match(float(q16)) bit for bit.
 #include "d2s_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -227,10 +230,22 @@ __device__ __forceinline__ int find_ascending(const int* __restrict__ v, int len
 // wave-uniform: a B row (odd token) scans dst_idx with ballots as the forward does, an A row (even token) looks itself up in src_idx and
 // then in unm_idx (both ascending: binary search).  An A row in neither list (not a plan) gets zeros; every index taken from the plan
 // is checked against the image before it is used.
+// BF16OUT: the row is written a second time in bf16 (dx16: the fp32 value rounded once), for the GEMMs of the bf16 data path that read the
+// gradient behind the merge; the pair of pointers takes the place of the last argument, the plain instantiation keeps its argument list.
+struct MergeDx { float* dx; __bf16* dx16; };
+typedef __bf16 bf16x4m __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void put4(MergeDx o, long row, int D, int c, const f32x4& v) {
+    reinterpret_cast<f32x4*>(o.dx + row * D)[c] = v;
+    bf16x4m hv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hv[j] = (__bf16)v[j];
+    reinterpret_cast<bf16x4m*>(o.dx16 + row * D)[c] = hv;
+}
+template <bool BF16OUT = false>
 __global__ __launch_bounds__(256) void tome_merge_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ size,
                                                              const float* __restrict__ size_out, const int* __restrict__ unm_idx,
                                                              const int* __restrict__ src_idx, const int* __restrict__ dst_idx, long rows_in,
-                                                             int n, int D, int r, float* __restrict__ dx) {
+                                                             int n, int D, int r, std::conditional_t<BF16OUT, MergeDx, float* __restrict__> dx) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (row >= rows_in) return;           // wave-uniform
@@ -259,18 +274,33 @@ __global__ __launch_bounds__(256) void tome_merge_bwd_kernel(const float* __rest
         }
     }
     const int D4 = D >> 2;
-    f32x4* xo = reinterpret_cast<f32x4*>(dx + row * D);
-    if (o < 0) {
-        for (int c = lane; c < D4; c += 64) xo[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        return;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BF16OUT) {      // spelled apart: the plain instantiation keeps its statements and with them its instructions
+        if (o < 0) {
+            for (int c = lane; c < D4; c += 64) put4(dx, row, D, c, zero);
+            return;
+        }
+        const f32x4* g = reinterpret_cast<const f32x4*>(dy + (b * no + o) * (long)D);
+        if (!scaled) {
+            for (int c = lane; c < D4; c += 64) put4(dx, row, D, c, g[c]);      // a copied row: no multiply, the bits of dy
+            return;
+        }
+        const float w = (size ? size[b * n + t] : 1.f) / size_out[b * no + o];
+        for (int c = lane; c < D4; c += 64) put4(dx, row, D, c, g[c] * w);
+    } else {
+        f32x4* xo = reinterpret_cast<f32x4*>(dx + row * D);
+        if (o < 0) {
+            for (int c = lane; c < D4; c += 64) xo[c] = zero;
+            return;
+        }
+        const f32x4* g = reinterpret_cast<const f32x4*>(dy + (b * no + o) * (long)D);
+        if (!scaled) {
+            for (int c = lane; c < D4; c += 64) xo[c] = g[c];
+            return;
+        }
+        const float w = (size ? size[b * n + t] : 1.f) / size_out[b * no + o];
+        for (int c = lane; c < D4; c += 64) xo[c] = g[c] * w;
     }
-    const f32x4* g = reinterpret_cast<const f32x4*>(dy + (b * no + o) * (long)D);
-    if (!scaled) {
-        for (int c = lane; c < D4; c += 64) xo[c] = g[c];
-        return;
-    }
-    const float w = (size ? size[b * n + t] : 1.f) / size_out[b * no + o];
-    for (int c = lane; c < D4; c += 64) xo[c] = g[c] * w;
 }
 
 }  // namespace
@@ -338,8 +368,23 @@ int d2s_tome_merge_bwd(const float* dy, const float* size, const float* size_out
         return D2S_ERR_ARG;
     const long rows = (long)B * n;
     if ((rows + 3) / 4 > 0x7fffffffL) return D2S_ERR_ARG;
-    hipLaunchKernelGGL(tome_merge_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dy, size, size_out, unm_idx, src_idx,
+    hipLaunchKernelGGL(tome_merge_bwd_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dy, size, size_out, unm_idx, src_idx,
                        dst_idx, rows, n, D, r, dx);
+    return d2s_check_launch();
+}
+
+// d2s_tome_merge_bwd that also writes the bf16 form of every row (the bf16 data path behind a merge): dx [B,n,D] fp32 - that entry's bits -
+// and dx_bf16 [B,n,D], the same values rounded once.  One pass, every row of both outputs written exactly once, no atomics; r = 0 is the
+// copy plus its rounding.  d2s_tome_merge_bwd's limits and refusals, plus a null dx_bf16.
+int d2s_tome_merge_bwd_bf16out(const float* dy, const float* size, const float* size_out, const int* unm_idx, const int* src_idx,
+                               const int* dst_idx, int B, int n, int D, int r, float* dx, void* dx_bf16, hipStream_t stream) {
+    if (!dy || !size_out || !unm_idx || !dx || !dx_bf16 || B <= 0 || n < 2 || n > TOME_MAX_N || D <= 0 || (D & 3) || r < 0 ||
+        r > (n - 1) / 2 || (r > 0 && (!src_idx || !dst_idx)))
+        return D2S_ERR_ARG;
+    const long rows = (long)B * n;
+    if ((rows + 3) / 4 > 0x7fffffffL) return D2S_ERR_ARG;
+    hipLaunchKernelGGL(tome_merge_bwd_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dy, size, size_out, unm_idx, src_idx,
+                       dst_idx, rows, n, D, r, MergeDx{dx, static_cast<__bf16*>(dx_bf16)});
     return d2s_check_launch();
 }
 

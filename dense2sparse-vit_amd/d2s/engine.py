@@ -727,6 +727,8 @@ class TrainStep:
             **{k: v for m in methods.METHODS if m.config_keys
                for k, v in zip(m.config_keys, m.config(s, self.args) if m is own else (None,) * len(m.config_keys))},
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
+            # recorded only when on: a config without the key - every other run, every older checkpoint - counts as off
+            **({"train_bf16": True} if getattr(s, "train_bf16", False) else {}),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -764,6 +766,8 @@ class TrainStep:
         for k in ours:
             if k not in theirs or theirs[k] != ours[k]:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")
+        if bool(theirs.get("train_bf16", False)) and not ours.get("train_bf16", False):      # the key exists only where it is on
+            raise lib.D2SError("checkpoint config mismatch: train_bf16: the checkpoint has True, this run has False")
         own = self.student.state_dict()
         _check_names_shapes("model", {k: tuple(v.shape) for k, v in own.items()}, {k: tuple(v.shape) for k, v in sd["model"].items()})
         self.opt.check_state_dict(sd["optimizer"])

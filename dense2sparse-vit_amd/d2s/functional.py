@@ -287,13 +287,16 @@ def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=No
                         n1b, qkvb, projb, n2b, fc1b, fc2b, aoh), cinv      # aoh: bf16 form of ao (bf16 attention only), proj's weight gradient
 
 
-def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, attn_bwd, mid_bwd=None):
+def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, attn_bwd, mid_bwd=None, mid_bwd_bf16=False):
     """The backward of block_forward_sequence (training; per-op, either data path).  gy: the gradient of y; x: the block's input as a
     [..., D] tensor; saved: what the forward sequence returned for this; wants: which of (x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b,
     fc1w, fc1b, fc2w, fc2b) take a gradient; s_attn / s_mlp: the forward's stochastic-depth row scales.
     attn_bwd(qkv, ao, dao, lse, io, dqkv16, want_f32) -> (dqkv or None, dpolicy or None) is attn_backward or a function of its shape.
     mid_bwd(g1) -> g1 on the rows of x, the backward of the forward's hook: the MLP half runs on the rows of gy, the attention half on the
     rows of x, and the first LayerNorm backward adds the gradient that left the hook.
+    mid_bwd_bf16: the hook also delivers the bf16 form of the gradient it returns, which lets it run on the bf16 data path: it is called
+    mid_bwd(g1, g1h) -> (g1, g1h) with the bf16 shadow of the MLP half's rows (LayerNorm-2's backward made it; it ends at the hook) and
+    hands back both forms on the rows of x - the bf16 one feeds proj's two gradient GEMMs.  A hook without it stays on the fp32 data path.
     -> (the 13 gradients in wants' order, gx shaped like x, None where not wanted; dpolicy)"""
     (n1w, qkvw, projw, n2w, fc1w, fc2w, mean1, rstd1, ln1, qkv, ao, lse, x1, mean2, rstd2, ln2, z, h,
      n1b, qkvb, projb, n2b, fc1b, fc2b, aoh) = saved
@@ -309,7 +312,8 @@ def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, 
     # bf16 data path: every gradient that feeds an input-gradient GEMM is also produced in bf16 by the kernel that computes it
     io = bf16_data_path(gy, D, z.shape[1])
     # behind a hook the bf16 shadow of g1 would have to be made again for the rows of x, and the row scales' groups differ between the halves
-    assert mid_bwd is None or (not io and s_attn is None and s_mlp is None), "a hook between the halves: fp32 data path, no stochastic depth"
+    assert mid_bwd is None or ((not io or mid_bwd_bf16) and s_attn is None and s_mlp is None), \
+        "a hook between the halves: fp32 data path, no stochastic depth"
     gyh = ops.shadow_take(gy) if io else None
     if gyh is not None:
         gyh = gyh.view(M2, D)
@@ -336,7 +340,7 @@ def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, 
                                                 torch.empty((M2, D), dtype=torch.float32, device=dev), M2, D, wants[7], wants[8],
                                                 add_src=g_res, dx16=g1h)
     if mid_bwd is not None:
-        g1 = mid_bwd(g1)
+        g1, g1h = mid_bwd(g1, g1h) if (io and mid_bwd_bf16) else (mid_bwd(g1), None)
     # ---- attention branch ----
     ga = g1
     if s_attn is not None:

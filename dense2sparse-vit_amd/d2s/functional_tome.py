@@ -8,16 +8,18 @@ stated here is what merging adds (_Merging): the hook between the halves, its ba
 match reads the keys of the qkv GEMM's output in place; the merge acts on x1 (after proj + residual), so the MLP half runs on n - r
 rows.  Attention is the plain kernel while every token still stands for one patch (size is None) and the key-weighted one afterwards
 (proportional attention).  The composite block call (ops.block_fwd) cannot serve here - the merge sits in the middle of the block: with
-r = 0 and no sizes the result is bit for bit the per-op dense block's.  The bf16 arithmetic mode is refused by tome_block_forward and
-ToMeBlockFn (the key-weighted attention they call is an fp32 kernel; the GEMM modes exact and split both run);
-tome_block_forward_bf16 is the same block on the bf16 data path, inference only: LayerNorm and the GEMMs hand bf16 to each other,
+r = 0 and no sizes the result is bit for bit the per-op dense block's.  The bf16 arithmetic mode is refused by tome_block_forward and by
+ToMeBlockFn without its bf16 input (the key-weighted attention they call is an fp32 kernel; the GEMM modes exact and split both run);
+tome_block_forward_bf16 is the same block on the bf16 data path at inference: LayerNorm and the GEMMs hand bf16 to each other,
 attention and the match read the bf16 qkv (ops.attn_keyw_fwd_bf16io, ops.tome_match_bf16), the residual stream and therefore the merge
-stay fp32.
+stay fp32.  ToMeBlockFn with bf16=True (tome_block_train(..., bf16=True)) trains on that data path.
 
 Training: the merge is a size-weighted average with a constant plan (the match reads K under no gradient, as the published
 bipartite_soft_matching does), so its backward is one scaled row copy per input row (ops.tome_merge_bwd); the attention backward takes
 the key weights where the forward did (ops.attn_keyw_bwd).  The MLP half's residual gradient lives on n - r rows, the attention half's
-on n.
+on n.  On the bf16 data path the attention backward is ops.attn_keyw_bwd_bf16io (the bf16 matrix cores, dqkv in bf16 for the qkv
+Linear's gradient GEMMs) and the merge backward also writes the bf16 form of the gradient it returns (ops.tome_merge_bwd with dx16), which
+proj's two gradient GEMMs read: block_backward_sequence's mid_bwd_bf16 convention.
 """
 import torch
 
@@ -26,6 +28,10 @@ from .functional import (attn_backward, attn_forward, bf16_data_path, block_back
                          wants_grad)
 from .lib import D2SError
 
+_BF16_MODE_NEEDED = ("ToMeBlockFn with bf16=True trains on the bf16 data path: it needs the bf16 arithmetic mode "
+                     "(ops.gemm_mode(ops.GEMM_BF16))")
+_BF16_PATH_NEEDED = ("ToMeBlockFn with bf16=True needs the bf16 data path: D2S_BF16_IO not 0, D and hidden multiples of 32 and device "
+                     "tensors")
 _BF16_REFUSAL = "token merging runs in the fp32 arithmetic modes (exact, split): the key-weighted attention has no bf16 kernel"
 
 
@@ -57,6 +63,8 @@ class _Merging:
         B, n, _ = self.geom
         if self.key_w is None:
             return attn_backward(qkv, ao, dao, lse, B, n, self.heads, self.scale, None, None, io, dqkv16, want_f32)
+        if io:
+            return ops.attn_keyw_bwd_bf16io(qkv, self.key_w, ao, dao, lse, B, n, self.heads, self.scale, dqkv16=dqkv16, want_f32=want_f32), None
         return ops.attn_keyw_bwd(qkv, self.key_w, ao, dao, lse, B, n, self.heads, self.scale), None
 
     def merge(self, qkv, x1):
@@ -74,6 +82,15 @@ class _Merging:
         if self.r == 0:
             return g1
         return ops.tome_merge_bwd(g1, self.size, self.size_out, *self.plan, *self.geom, self.r)
+
+    def merge_bwd_bf16(self, g1, g1h):
+        """the same hook on the bf16 data path (block_backward_sequence's mid_bwd_bf16): g1h, the bf16 shadow of the n - r rows, ends here;
+        the merge backward writes the bf16 form of the n rows it returns in the same launch.  r = 0: both forms pass through."""
+        if self.r == 0:
+            return g1, g1h
+        B, n, D = self.geom
+        g1h = ops.bf16_buffer(B * n, D, g1.device)
+        return ops.tome_merge_bwd(g1, self.size, self.size_out, *self.plan, B, n, D, self.r, dx16=g1h), g1h
 
 
 def _block_forward(x, size, params, B, n, heads, eps, scale, r, prop_attn, plan, io):
@@ -105,19 +122,29 @@ def tome_block_forward_bf16(x, size, params, B, n, heads, eps, scale, r, prop_at
 @mode_recorded
 class ToMeBlockFn(torch.autograd.Function):
     """tome_block_forward as a differentiable Function: x [B, n, D], size [B, n] or None, the 12 block parameters, heads, eps, scale, r,
-    prop_attn, plan (unm_idx, src_idx, dst_idx as three inputs, or three None to match here)
+    prop_attn, plan (unm_idx, src_idx, dst_idx as three inputs, or three None to match here), and optionally a trailing bf16 flag: with it
+    the block trains on the bf16 data path (the bf16 arithmetic mode is then required, and widths that keep the data path on)
     -> (y [B, n - r, D], size_out [B, n - r] or None, unm_idx, src_idx, dst_idx or None); only y is differentiable, in x and the parameters."""
 
     @staticmethod
     def forward(ctx, x, size, *rest):
-        if ops.get_gemm_mode() == ops.GEMM_BF16:
+        params, (heads, eps, scale, r, prop_attn, unm, src, dst), extra = rest[:12], rest[12:20], rest[20:]
+        ctx.nextra = len(extra)
+        io = bool(extra[0]) if extra else False          # optional 23rd input: train on the bf16 data path
+        if io:
+            if ops.get_gemm_mode() != ops.GEMM_BF16:
+                raise D2SError(_BF16_MODE_NEEDED)
+            if not bf16_data_path(x, x.shape[2], params[8].shape[0]):
+                raise D2SError(_BF16_PATH_NEEDED)
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        elif ops.get_gemm_mode() == ops.GEMM_BF16:
             raise D2SError(_BF16_REFUSAL)
-        params, (heads, eps, scale, r, prop_attn, unm, src, dst) = rest[:12], rest[12:]
         train = wants_grad(ctx)
         B, n, D = x.shape
         x = x.contiguous()
         m = _Merging(size, B, n, D, heads, scale, r, bool(prop_attn), None if unm is None else (unm, src, dst))
-        y, _, saved, _ = block_forward_sequence(x.view(B * n, D), params, eps, False, train, m.attn, (train,), mid=m.merge)
+        y, _, saved, _ = block_forward_sequence(x.view(B * n, D), params, eps, io, train, m.attn, (train,), mid=m.merge)
+        ctx.io = io
         if train:
             ctx.save_for_backward(x, *saved)
             ctx.merging = m
@@ -131,15 +158,20 @@ class ToMeBlockFn(torch.autograd.Function):
         m = ctx.merging
         # input slots: x 0, size 1, then n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> 2..13
         wants = [ctx.needs_input_grad[0]] + list(ctx.needs_input_grad[2:14])
-        grads, _ = block_backward_sequence(gy, x, saved, wants, None, None, 0, m.attn_bwd, m.merge_bwd)
-        return (grads[0], None) + tuple(grads[1:]) + (None,) * 8
+        if ctx.io:
+            grads, _ = block_backward_sequence(gy, x, saved, wants, None, None, 0, m.attn_bwd, m.merge_bwd_bf16, mid_bwd_bf16=True)
+        else:
+            grads, _ = block_backward_sequence(gy, x, saved, wants, None, None, 0, m.attn_bwd, m.merge_bwd)
+        return (grads[0], None) + tuple(grads[1:]) + (None,) * (8 + ctx.nextra)
 
 
-def tome_block_train(x, size, params, heads, eps, scale, r, prop_attn=True, plan=None):
-    """ToMeBlockFn with tome_block_forward's shape of a result: x [B, n, D] -> (y [B, n - r, D], size_out or None, plan or None)"""
+def tome_block_train(x, size, params, heads, eps, scale, r, prop_attn=True, plan=None, bf16=False):
+    """ToMeBlockFn with tome_block_forward's shape of a result: x [B, n, D] -> (y [B, n - r, D], size_out or None, plan or None).
+    bf16: train on the bf16 data path (the Function's trailing input; existing calls keep their argument list)."""
     if ops.tome_clip_r(r, x.shape[1]) == 0:
         plan = None
-    y, size_out, unm, src, dst = run(ToMeBlockFn, x, size, *params, heads, eps, scale, r, prop_attn, *(plan if plan is not None else (None,) * 3))
+    y, size_out, unm, src, dst = run(ToMeBlockFn, x, size, *params, heads, eps, scale, r, prop_attn, *(plan if plan is not None else (None,) * 3),
+                                     *((True,) if bf16 else ()))
     if ops.tome_clip_r(r, x.shape[1]) == 0:
         return y, size, None
     return y, size_out, (plan if plan is not None else (unm, src, dst))

@@ -2,7 +2,8 @@
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
 ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, include/d2s_hip_gemm_plan.h, the
-plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, and include/d2s_hip_ltp.h, learned token thresholds).
+plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, include/d2s_hip_ltp.h, learned token thresholds, and
+include/d2s_hip_tome_train_bf16.h, the backward pair of bf16 training through token merging).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -214,6 +215,12 @@ _SIGS_LTP = {
     "d2s_ltp_soft_mask_bwd": (I, [P, P, P, P, P, P, P, P, I, I, F, I, I]),
 }
 
+# the entries of include/d2s_hip_tome_train_bf16.h (training through token merging in the bf16 arithmetic mode), same form
+_SIGS_TOME_TRAIN_BF16 = {
+    "d2s_attn_keyw_bwd_bf16": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F]),
+    "d2s_tome_merge_bwd_bf16out": (I, [P, P, P, P, P, P, I, I, I, I, P, P]),
+}
+
 _lib = None
 
 
@@ -233,7 +240,7 @@ def load():
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
                               + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())
-                              + list(_SIGS_LTP.items())):
+                              + list(_SIGS_LTP.items()) + list(_SIGS_TOME_TRAIN_BF16.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -283,6 +290,10 @@ def ragged_bf16_symbols():
 
 def ltp_symbols():
     return sorted(_SIGS_LTP)
+
+
+def tome_train_bf16_symbols():
+    return sorted(_SIGS_TOME_TRAIN_BF16)
 
 
 def ptr(t):

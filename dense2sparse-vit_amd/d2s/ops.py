@@ -668,9 +668,10 @@ def tome_merge(x, size, unm, src, dst, B, n, D, r):
     return out, size_out
 
 
-def tome_merge_bwd(dy, size, size_out, unm, src, dst, B, n, D, r):
+def tome_merge_bwd(dy, size, size_out, unm, src, dst, B, n, D, r, dx16=None):
     """Backward of tome_merge in x: dy [B * (n - r), D], size [B, n] or None and the plan as the forward took them, size_out [B, n - r] as
-    it wrote them -> dx [B * n, D]"""
+    it wrote them -> dx [B * n, D].  dx16 (the bf16 data path behind a merge): a bf16 buffer [B * n, D] that receives dx rounded once, in
+    the same launch."""
     _f32(dy)
     _f32(size_out)
     B, n, D, r = int(B), int(n), int(D), int(r)
@@ -682,6 +683,11 @@ def tome_merge_bwd(dy, size, size_out, unm, src, dst, B, n, D, r):
         _f32(size)
         assert tuple(size.shape) == (B, n)
     dx = torch.empty((B * n, D), dtype=torch.float32, device=dy.device)
+    if dx16 is not None:
+        assert dx16.dtype == torch.bfloat16 and dx16.is_contiguous() and dx16.numel() == B * n * D and dx16.is_cuda
+        lib.call("d2s_tome_merge_bwd_bf16out", lib.ptr(dy), lib.ptr(size), lib.ptr(size_out), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
+                 lib.ptr(dst) if r > 0 else None, B, n, D, r, lib.ptr(dx), lib.ptr(dx16))
+        return dx
     lib.call("d2s_tome_merge_bwd", lib.ptr(dy), lib.ptr(size), lib.ptr(size_out), lib.ptr(unm), lib.ptr(src) if r > 0 else None,
              lib.ptr(dst) if r > 0 else None, B, n, D, r, lib.ptr(dx))
     return dx
@@ -918,7 +924,7 @@ def attn_fwd_bf16io(qkv, B, n, H, scale, want_cls=True, want_f32=True):
 
 def attn_keyw_fwd_bf16io(qkv, key_w, B, n, H, scale, want_f32=True):
     """Key-weighted attention forward (attn_keyw_fwd's definition) on the bf16 matrix cores and the bf16 data path: qkv fp32 or bf16 (the
-    qkv GEMM's c16); always writes the bf16 copy of its output for the projection GEMM.  Inference only.
+    qkv GEMM's c16); always writes the bf16 copy of its output for the projection GEMM.  Its backward: attn_keyw_bwd_bf16io.
     -> (out or None, lse [B,H,n], out16)"""
     assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
     _f32(key_w)
@@ -929,6 +935,22 @@ def attn_keyw_fwd_bf16io(qkv, key_w, B, n, H, scale, want_f32=True):
     lib.call("d2s_attn_keyw_fwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(key_w), lib.ptr(out), lib.ptr(out16),
              lib.ptr(lse), B, n, H, float(scale))
     return out, lse, out16
+
+
+def attn_keyw_bwd_bf16io(qkv, key_w, out, dout, lse, B, n, H, scale, dqkv16=None, want_f32=True):
+    """Backward of attn_keyw_fwd_bf16io (out its fp32 output, lse as it returned it) on the bf16 matrix cores, attn_bwd's shape in the bf16
+    mode: qkv fp32 or bf16; dqkv16: a bf16 buffer shaped like qkv that receives a copy of dqkv; want_f32=False (needs dqkv16): only that
+    form is written and None is returned.  The weights get no gradient."""
+    assert qkv.is_contiguous() and qkv.dtype in (torch.float32, torch.bfloat16)
+    _f32(key_w)
+    assert tuple(key_w.shape) == (B, n)
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device) if (want_f32 or dqkv16 is None) else None
+    if dqkv16 is not None:
+        assert dqkv16.dtype == torch.bfloat16 and dqkv16.is_contiguous() and dqkv16.numel() == qkv.numel()
+    delta = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_attn_keyw_bwd_bf16", lib.ptr(qkv), int(qkv.dtype == torch.bfloat16), lib.ptr(key_w), lib.ptr(out), lib.ptr(dout),
+             lib.ptr(lse), lib.ptr(dqkv), lib.ptr(dqkv16), lib.ptr(delta), B, n, H, float(scale))
+    return dqkv
 
 
 def attn_bwd(qkv, out, dout, lse, B, n, H, scale, dqkv16=None, want_f32=True):

@@ -26,6 +26,7 @@ are outside the path.
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --eval-only --tome-bf16 --student-checkpoint deit_small.pth
     python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --student-checkpoint deit_small.pth \
         --teacher-checkpoint deit_small.pth --epochs 30                   (fine-tune through the merges; --dist-weight 0: no teacher)
+    python dense2sparse-vit_amd/mask_predictor.py --method tome --tome-r 13 --arch deit_small --tome-train --tome-train-bf16 ...  (... in bf16)
     python dense2sparse-vit_amd/mask_predictor.py --method ats --pruning-locs 3 6 9 --ats-tokens 64 --arch deit_small --eval-only \
         --student-checkpoint deit_small.pth                               (adaptive token sampling: every image keeps its own count)
     python dense2sparse-vit_amd/mask_predictor.py --method avit --arch deit_small --student-checkpoint deit_small.pth --dist-weight 0
@@ -127,6 +128,16 @@ def check_supported(args):
             bad.append("--tome-bf16 with --tome-train (training through the merges is built in fp32 only)")
         if not args.eval_only:
             bad.append("--tome-bf16 without --eval-only (the bf16 merging trunk is built for inference)")
+    tome_train_bf16 = bool(getattr(args, "tome_train_bf16", False))
+    if tome_train_bf16:
+        # the flag, not the mode, selects the path (as --ragged-bf16): it sets the bf16 arithmetic mode itself, --gemm-mode bf16 stays refused below
+        if not tome_train:
+            bad.append("--tome-train-bf16 without --tome-train (it puts training through the merges into the bf16 arithmetic mode)")
+        if bool(getattr(args, "tome_bf16", False)):
+            bad.append("--tome-train-bf16 with --tome-bf16 (--tome-bf16 is the inference-only trunk; validation under --tome-train-bf16 "
+                       "runs on the bf16 data path already)")
+        if getattr(args, "gemm_mode", "exact") == "split":
+            bad.append("--tome-train-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
     if method == "tome":
         if not args.eval_only and not tome_train:
             bad.append("--method tome without --eval-only (token merging is built for inference: training through a merge needs the merge's "
@@ -214,6 +225,10 @@ def check_supported(args):
             print("Attention: --ragged-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the ragged attention "
                   "and its backward on the bf16 matrix cores, the residual stream, the selection and the row moves in fp32 (DESIGN.md "
                   "section 10.3)")
+    if tome_train_bf16 and tome_train and method == "tome":
+        print("Attention: --tome-train-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the (key-weighted) "
+              "attention and its backward on the bf16 matrix cores, the residual stream, the match and the merge in fp32; validation runs "
+              "the bf16 merging trunk (DESIGN.md section 22)")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:
@@ -385,7 +400,8 @@ def _trunk(name, args, *a, **kw):
 def build_tome(args):
     """--method tome: the dense DeiT trunk with token merging, weights from --student-checkpoint or the 'model' entry of a --resume file.  A
     dense-to-sparse student's checkpoint carries score predictors this model has no use for: they are ignored (strict=False)."""
-    return _trunk("tome", args, args.tome_r, train_merge=bool(getattr(args, "tome_train", False)), bf16=bool(getattr(args, "tome_bf16", False)))
+    return _trunk("tome", args, args.tome_r, train_merge=bool(getattr(args, "tome_train", False)), bf16=bool(getattr(args, "tome_bf16", False)),
+                  **({"train_bf16": True} if getattr(args, "tome_train_bf16", False) else {}))
 
 
 def load_trunk(args, model, method, why):
@@ -521,9 +537,10 @@ def main(argv=None):
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
-    # --ragged-bf16 sets the bf16 arithmetic mode itself, as --gemm-mode bf16 would (which stays refused with --ragged-train)
+    # --ragged-bf16 and --tome-train-bf16 set the bf16 arithmetic mode themselves, as --gemm-mode bf16 would (which stays refused with
+    # --ragged-train and with --method tome)
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[
-        "bf16" if getattr(args, "ragged_bf16", False) else args.gemm_mode])
+        "bf16" if (getattr(args, "ragged_bf16", False) or getattr(args, "tome_train_bf16", False)) else args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
     if (args.method == "ats" and not args.ats_train) or (args.method == "tome" and not args.tome_train):
         return eval_tome(args, rank, world, distributed)

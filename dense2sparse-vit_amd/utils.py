@@ -216,6 +216,11 @@ def parse_args(argv=None):
     p.add_argument('--tome-bf16', action='store_true', default=False,
                    help='with --method tome --eval-only: run the merging trunk on the bf16 data path (bf16 matrix cores for the GEMMs and the '
                         'key-weighted attention, the match on the bf16 qkv); --gemm-mode stays at exact or split')
+    # no attribute unless given (argparse.SUPPRESS): every reader asks getattr(args, "tome_train_bf16", False)
+    p.add_argument('--tome-train-bf16', action='store_true', default=argparse.SUPPRESS,
+                   help='with --method tome --tome-train: train through the merges in the bf16 arithmetic mode (bf16 matrix cores for the '
+                        'GEMMs, the key-weighted attention and its backward; the bf16 data path) - the flag sets that mode itself, '
+                        '--gemm-mode stays at exact (its default); validation runs the bf16 merging trunk')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

@@ -1,7 +1,8 @@
 """Token Merging baseline (ToMe, Bolya et al. 2023; DESIGN.md section 22 - no counterpart in the reference): an off-the-shelf DeiT trunk
 whose every block merges r tokens into their most similar partner between its attention branch and its MLP.  No predictor: the model has
 the teacher's parameters and state-dict keys and loads any DeiT checkpoint.  Off the shelf it is an inference model; train_merge=True opts
-into training through the merge (d2s.functional_tome.ToMeBlockFn), as the paper's fine-tuned numbers do."""
+into training through the merge (d2s.functional_tome.ToMeBlockFn), as the paper's fine-tuned numbers do; train_bf16=True puts that training
+on the bf16 data path when the process runs in the bf16 arithmetic mode."""
 import torch
 
 from d2s import functional as DF
@@ -21,9 +22,13 @@ class VisionTransformerToMe(VisionTransformerTeacher):
     train_merge: let the training-mode forward merge too - every block runs through ToMeBlockFn, gradients flow through the merge (a
     size-weighted average with a constant plan) and the key-weighted attention; off (the default), a merging model refuses to train.
     bf16: run the eval forward on the bf16 data path (TF.tome_block_forward_bf16) inside ops.gemm_mode(ops.GEMM_BF16), whatever the
-    ambient mode, which is restored afterwards; inference only, so it excludes train_merge."""
+    ambient mode, which is restored afterwards; inference only, so it excludes train_merge.
+    train_bf16 (needs train_merge): under the bf16 arithmetic mode the training-mode forward runs every block through ToMeBlockFn on the
+    bf16 data path - the GEMMs, the (key-weighted) attention and both their backwards on the bf16 matrix cores, the residual stream and the
+    merge in fp32 - and the eval forward takes the bf16=True route, so validation runs in the same process; under an fp32 mode it changes
+    nothing."""
 
-    def __init__(self, *args, tome_r=0, prop_attn=True, train_merge=False, bf16=False, **kwargs):
+    def __init__(self, *args, tome_r=0, prop_attn=True, train_merge=False, bf16=False, train_bf16=False, **kwargs):
         super().__init__(*args, **kwargs)
         depth = len(self.blocks)
         rs = [int(tome_r)] * depth if isinstance(tome_r, int) else [int(v) for v in tome_r]
@@ -35,6 +40,9 @@ class VisionTransformerToMe(VisionTransformerTeacher):
         self.bf16 = bool(bf16)
         if self.bf16 and self.train_merge:
             raise ValueError("bf16 with train_merge: training through a merge is built in fp32 only (the bf16 merging trunk is inference only)")
+        self.train_bf16 = bool(train_bf16)
+        if self.train_bf16 and not self.train_merge:
+            raise ValueError("train_bf16 without train_merge: it puts training through the merges on the bf16 data path (train_merge=True)")
         if self.train_merge and float(getattr(self, "drop_path_rate", 0.0)) > 0.0:
             raise ValueError("train_merge with drop_path_rate > 0: stochastic depth is not built for a merging block")
         self.grad_ready_hook = None          # set by a data-parallel TrainStep: called with i when block i's input gradient exists
@@ -54,7 +62,7 @@ class VisionTransformerToMe(VisionTransformerTeacher):
                 x = blk(x)
             self.tokens_per_block, self.tome_plans = [x.shape[1]] * len(self.blocks), [None] * len(self.blocks)
             return self._head(x)[0]
-        if self.bf16:
+        if self.bf16 or (self.train_bf16 and ops.get_gemm_mode() == ops.GEMM_BF16):
             with ops.gemm_mode(ops.GEMM_BF16):      # the context manager restores the ambient mode on return and on an exception
                 return self._forward_eval(x, plans, TF.tome_block_forward_bf16)
         return self._forward_eval(x, plans, TF.tome_block_forward)
@@ -79,12 +87,13 @@ class VisionTransformerToMe(VisionTransformerTeacher):
         """The eval forward's launches with everything a backward needs kept: one ToMeBlockFn per block, matching on the fly or replaying."""
         x = self._embed(x)
         size, counts, used = None, [], []
+        bf16 = self.train_bf16 and ops.get_gemm_mode() == ops.GEMM_BF16
         for i, blk in enumerate(self.blocks):
             if self.grad_ready_hook is not None and x.requires_grad:
                 x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
             a = blk.attn
             x, size, plan = TF.tome_block_train(x, size, blk._params(), a.num_heads, blk.norm1.eps, a.scale, self.tome_r[i], self.prop_attn,
-                                                None if plans is None else plans[i])
+                                                None if plans is None else plans[i], **({"bf16": True} if bf16 else {}))
             counts.append(x.shape[1])
             used.append(plan)
         self.tokens_per_block, self.tome_plans = counts, used

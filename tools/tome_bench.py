@@ -6,12 +6,14 @@ the table reports the median images/s with the lowest and highest round.  GPU bo
 
 --train: the same table for training through the merges (--tome-train): ms per d2s.engine.TrainStep call (forward, ToMeLoss without a
 teacher - dist_weight 0 -, backward, fused AdamW) of a train_merge student, hard labels, same alternating rounds; read every row against
-the r = 0 row of the same run.
+the r = 0 row of the same run.  --train --bf16: the steps of train_bf16 students under GEMM_BF16 (--tome-train-bf16); with --also-fp32
+the fp32 steps stay in the same run, each step called under its own arithmetic mode.
 
 --bf16: the same table with bf16=True models (--tome-bf16: the merging trunk on the bf16 data path) and the teacher row timed under
 GEMM_BF16; --bf16 --also-fp32 keeps the fp32 rows in the same run, so that each bf16 row is read against the fp32 row of equal r.
 
   python tools/tome_bench.py [--rounds 5] [--iters 10] [--r 0 8 13 16] [--train] [--bf16 [--also-fp32]]
+  python tools/tome_bench.py --train --bf16 --also-fp32      (training through the merges: bf16 rows against fp32 rows of equal r)
   rocprofv3 --kernel-trace --stats -d DIR -o tome -- python tools/tome_bench.py --no-teacher --r 13 --rounds 1      (kernel shares)
   rocprofv3 --kernel-trace --stats -d DIR -o tome -- python tools/tome_bench.py --bf16 --no-teacher --r 13 --rounds 1      (... on the bf16 data path)
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o tome -- python tools/tome_bench.py --train --r 13 --rounds 1     (... of a train step)
@@ -37,8 +39,6 @@ ap.add_argument("--train", action="store_true", help="time a TrainStep of a trai
 ap.add_argument("--bf16", action="store_true", help="bf16=True models (the bf16 data path); the teacher row runs under GEMM_BF16")
 ap.add_argument("--also-fp32", action="store_true", help="with --bf16: keep the fp32 rows in the same run")
 args = ap.parse_args()
-if args.bf16 and args.train:
-    raise SystemExit("--bf16 with --train: training through the merges is built in fp32 only")
 if args.also_fp32 and not args.bf16:
     raise SystemExit("--also-fp32 goes with --bf16")
 if not torch.cuda.is_available():
@@ -55,19 +55,25 @@ if args.train:
     from d2s.engine import TrainStep
     y = torch.randint(0, 1000, (B,), device=dev)
     steps = []
-    for r in args.r:
-        m = vit_models.tome_deit_small_patch16_224(r, train_merge=True)
-        m.load_state_dict(weights)
-        steps.append((f"tome r = {r}", TrainStep(m.to(dev), None, types.SimpleNamespace(mixup=0.0, cls_weight=1.0, dist_weight=0.0, step=0))))
+    for bf16 in ([False] if not args.bf16 else [False, True] if args.also_fp32 else [True]):      # fp32 rows first when both are timed
+        tag = " bf16" if bf16 else " fp32" if args.bf16 else ""
+        for r in args.r:
+            m = vit_models.tome_deit_small_patch16_224(r, train_merge=True, **({"train_bf16": True} if bf16 else {}))
+            m.load_state_dict(weights)
+            with ops.gemm_mode(ops.GEMM_BF16 if bf16 else ops.GEMM_EXACT):
+                step = TrainStep(m.to(dev), None, types.SimpleNamespace(mixup=0.0, cls_weight=1.0, dist_weight=0.0, step=0))
+            step.bench_mode = ops.GEMM_BF16 if bf16 else ops.GEMM_EXACT
+            steps.append((f"tome r = {r}{tag}", step))
     del teacher
 
     def train_window(step, iters):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(iters):
-            step(x, y)
-        e.record()
-        torch.cuda.synchronize()
+        with ops.gemm_mode(step.bench_mode):              # every step under its own arithmetic mode
+            s.record()
+            for _ in range(iters):
+                step(x, y)
+            e.record()
+            torch.cuda.synchronize()
         return s.elapsed_time(e) / iters
 
     for _, step in steps:
@@ -76,13 +82,14 @@ if args.train:
     for _ in range(args.rounds):
         for name, step in steps:
             ms[name].append(train_window(step, args.iters))
-    print(f"DeiT-S 224, B = {B}, fp32 exact GEMMs, TrainStep (no teacher, dist_weight 0), {args.rounds} rounds x {args.iters} steps per "
+    gemms = "fp32 exact GEMMs" if not args.bf16 else "bf16 data path and fp32 exact GEMMs" if args.also_fp32 else "bf16 data path"
+    print(f"DeiT-S 224, B = {B}, {gemms}, TrainStep (no teacher, dist_weight 0), {args.rounds} rounds x {args.iters} steps per "
           "configuration, rounds alternating")
-    print(f"{'configuration':16s} {'ms/step':>9s} {'min':>8s} {'max':>8s} {'images/s (median)':>18s} {'min':>8s} {'max':>8s}   tokens leaving each block")
+    print(f"{'configuration':21s} {'ms/step':>9s} {'min':>8s} {'max':>8s} {'images/s (median)':>18s} {'min':>8s} {'max':>8s}   tokens leaving each block")
     for name, step in steps:
         t = sorted(ms[name])
         rate = sorted(B / v * 1e3 for v in t)
-        print(f"{name:16s} {statistics.median(t):9.2f} {t[0]:8.2f} {t[-1]:8.2f} {statistics.median(rate):18.0f} {rate[0]:8.0f} {rate[-1]:8.0f}   "
+        print(f"{name:21s} {statistics.median(t):9.2f} {t[0]:8.2f} {t[-1]:8.2f} {statistics.median(rate):18.0f} {rate[0]:8.0f} {rate[-1]:8.0f}   "
               f"{' '.join(map(str, step.student.tokens_per_block))}", flush=True)
     sys.exit(0)
 
