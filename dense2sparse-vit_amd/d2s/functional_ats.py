@@ -20,7 +20,10 @@ The MLP half's residual gradient lives on the rows that left the stage, the atte
 
 Training in the bf16 arithmetic mode (_Ragged(..., bf16=True)): a block without a stage runs the same sequence
 on the bf16 data path, its attention and the backward on the bf16 matrix cores (ops.attn_varlen_fwd_lse_bf16io / attn_varlen_bwd_bf16io).
-The flag, not the mode, selects the path: without it the bf16 mode is refused as before."""
+The flag, not the mode, selects the path: without it the bf16 mode is refused as before.  A block WITH a stage joins it under
+_Ragged(..., bf16=True, stage_bf16=True): the selection reads the bf16 qkv, the re-pack moves the fp32 residual
+stream, and the hook's backward (sample_bwd_bf16: ops.ragged_repack_bwd with g16) writes the gradient of the rows that entered the stage
+in fp32 and in bf16 in one launch - block_backward_sequence's mid_bwd_bf16 convention."""
 import torch
 
 from . import functional as DF
@@ -31,6 +34,7 @@ _BF16_REFUSAL = "training through a ragged block runs in the fp32 arithmetic mod
 _BF16_STAGE_REFUSAL = (_BF16_REFUSAL + ".  A block with a sampling stage stays there with bf16=True too: behind the hook between the halves "
                        "(sample_bwd) the bf16 shadow of the gradient would have to be made again")
 _BF16_MODE_REFUSAL = "a ragged block with bf16=True runs in the bf16 arithmetic mode only (ops.gemm_mode(GEMM_BF16))"
+_STAGE_BF16_NEEDS_BF16 = "a ragged block with stage_bf16=True needs bf16=True too: stage_bf16 only lets a block with a stage onto the bf16 data path"
 
 
 class _Ragged:
@@ -39,11 +43,12 @@ class _Ragged:
     block without a stage; plan: (keep, counts) of an earlier forward on the same batch, replayed instead of selecting.  After a stage's
     forward: cu_new, row_src_new, plan, score / dense (None when replaying); max_n_out either way.
     bf16: train on the bf16 data path in the bf16 arithmetic mode (a block without a stage) - attn_train and attn_bwd then honour io,
-    dqkv16 and want_f32 as attn_forward / attn_backward do."""
+    dqkv16 and want_f32 as attn_forward / attn_backward do.
+    stage_bf16: with bf16, a block with a stage runs there too - the hook's backward is then sample_bwd_bf16."""
 
-    def __init__(self, cu, B, max_n, heads, scale, row_src=None, K=None, N=0, plan=None, bf16=False):
+    def __init__(self, cu, B, max_n, heads, scale, row_src=None, K=None, N=0, plan=None, bf16=False, stage_bf16=False):
         self.cu, self.B, self.max_n, self.heads, self.scale = cu, int(B), int(max_n), heads, float(scale)
-        self.bf16 = bool(bf16)
+        self.bf16, self.stage_bf16 = bool(bf16), bool(stage_bf16)
         self.row_src, self.K, self.N, self.plan = row_src, K, N, plan
         self.cu_new = self.row_src_new = self.score = self.dense = None
         self.max_n_out = self.max_n if K is None else min(self.max_n, int(K) + 1)
@@ -83,6 +88,12 @@ class _Ragged:
         """block_backward_sequence's hook: the gradient on the rows that left the stage -> on the rows that entered it"""
         return ops.ragged_repack_bwd(g1, self.plan[0], self.cu, self.cu_new, self.total_in, self.B)
 
+    def sample_bwd_bf16(self, g1, g1h):
+        """the same hook on the bf16 data path (block_backward_sequence's mid_bwd_bf16): g1h, the bf16 shadow of the rows that left the
+        stage, ends here; the row move writes both forms of the gradient on the rows that entered it, the bf16 one the fp32 one rounded once"""
+        g16 = ops.bf16_buffer(self.total_in, g1.shape[1], g1.device)
+        return ops.ragged_repack_bwd(g1, self.plan[0], self.cu, self.cu_new, self.total_in, self.B, g16=g16), g16
+
 
 def ats_block_forward(xp, cu, B, max_n, params, heads, eps, scale, K, N, row_src, plan=None):
     """xp [total, D] packed, cu [B+1], row_src [total] (original token index, 0 at CLS); at most K of an image's tokens survive.
@@ -106,10 +117,12 @@ class RaggedBlockFn(torch.autograd.Function):
     def forward(ctx, xp, *rest):
         params, (eps, r) = rest[:12], rest[12:]
         stage = r.K is not None
+        if r.stage_bf16 and not r.bf16:
+            raise D2SError(_STAGE_BF16_NEEDS_BF16)
         if ops.get_gemm_mode() == ops.GEMM_BF16:
             if not r.bf16:
                 raise D2SError(_BF16_REFUSAL)
-            if stage:
+            if stage and not r.stage_bf16:
                 raise D2SError(_BF16_STAGE_REFUSAL)
         elif r.bf16:
             raise D2SError(_BF16_MODE_REFUSAL)
@@ -137,8 +150,11 @@ class RaggedBlockFn(torch.autograd.Function):
         xp, *saved = ctx.saved_tensors
         r = ctx.ragged
         # input slots: xp 0, then n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> 1..12
-        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd,
-                                              r.sample_bwd if r.K is not None else None)
+        stage = r.K is not None
+        # a stage on the bf16 data path: the hook hands on both forms of the gradient
+        hook = None if not stage else r.sample_bwd_bf16 if r.bf16 else r.sample_bwd
+        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd, hook,
+                                              mid_bwd_bf16=stage and r.bf16)
         return tuple(grads) + (None, None)
 
 

@@ -9,7 +9,11 @@ finished: they live on the AViTRun the Functions of one forward share, so one ba
 the graph: the last block's Function returns the accumulator AND the per-layer partial sums, the penalty Function reads the latter, so
 its backward (which leaves the per-layer factors on the run) has run before any halting step's backward starts.
 
-One host read per block: the new offsets (B + 1 ints) size the next block's launches, as at an ATS stage."""
+One host read per block: the new offsets (B + 1 ints) size the next block's launches, as at an ATS stage.
+
+Training in the bf16 arithmetic mode (AViTRun(..., bf16=True)): the blocks are functional_ats._Ragged(bf16=True)
+ones, and a boundary's backward is ONE launch (ops.avit_halt_repack_bwd_bf16io: the re-pack's backward, the halting step's terms and the
+bf16 form of the result), parked as the gradient's shadow so that the block in front finds it and casts nothing."""
 import math
 
 import torch
@@ -31,8 +35,9 @@ class AViTRun:
     row).  After the forward: st["nh"] the halting layers [B, N], st["R"] the remainders, st["acc"] the accumulator; after the
     penalty's backward: gsc."""
 
-    def __init__(self, B, N, D, L, gamma, beta, eps_halt, device):
+    def __init__(self, B, N, D, L, gamma, beta, eps_halt, device, bf16=False):
         self.B, self.N, self.D, self.L = int(B), int(N), int(D), int(L)
+        self.bf16 = bool(bf16)               # the boundaries' backward hands on the bf16 form of the gradient too
         self.gamma, self.beta, self.eps_halt = float(gamma), float(beta), float(eps_halt)
         self.st = ops.avit_state(B, N, D, L, device)
         self.cu = ops.ragged_offsets(torch.full((B,), N - 1, dtype=torch.int32, device=device), extra=1)      # arange(B + 1) * N
@@ -71,13 +76,17 @@ class AViTHaltFn(torch.autograd.Function):
     def backward(ctx, g, gpart=None):
         run, layer = ctx.run, ctx.layer
         keep, cu, row_src, w, h, ycls, total = ctx.kept
-        if layer == run.L:
+        last = layer == run.L
+        if last:
             run.dacc = g.contiguous()
             if run.gsc is None:               # the penalties took no part in the loss
                 run.gsc = torch.zeros((run.L + 1,), dtype=torch.float32, device=g.device)
-            gin = None
-        else:
-            gin = ops.ragged_repack_bwd(g.contiguous(), keep, cu, ctx.cu_new, total, run.B)
+        if run.bf16:                          # one launch: the re-pack's backward (nothing arrives at the last layer), the step's terms, both forms
+            arrived = (None, None, None) if last else (g.contiguous(), keep, ctx.cu_new)
+            gy, gy16 = ops.avit_halt_repack_bwd_bf16io(*arrived, h, cu, row_src, run.st, w, run.dacc, ycls, run.gsc, layer, run.gamma)
+            ops.shadow_put(gy, gy16)          # the block in front takes it (ops.shadow_take): no cast of the [total, D] gradient
+            return gy, None, None
+        gin = None if last else ops.ragged_repack_bwd(g.contiguous(), keep, cu, ctx.cu_new, total, run.B)
         gy = ops.avit_halt_bwd(gin, h, cu, row_src, run.st, w, run.dacc, ycls, run.gsc, layer, run.gamma)
         return gy, None, None
 

@@ -2,8 +2,9 @@
 two entries, include/d2s_hip_squeeze.h, the entries of a squeezing stage, include/d2s_hip_ats.h, adaptive token sampling,
 include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/d2s_hip_ragged_threshold.h, training the dynamic keep
 ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, include/d2s_hip_gemm_plan.h, the
-plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, include/d2s_hip_ltp.h, learned token thresholds, and
-include/d2s_hip_tome_train_bf16.h, the backward pair of bf16 training through token merging).
+plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, include/d2s_hip_ltp.h, learned token thresholds,
+include/d2s_hip_tome_train_bf16.h, the backward pair of bf16 training through token merging, and include/d2s_hip_ragged_stage_bf16.h, the two
+backward row moves of bf16 training through ATS stages and A-ViT block boundaries).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -221,6 +222,12 @@ _SIGS_TOME_TRAIN_BF16 = {
     "d2s_tome_merge_bwd_bf16out": (I, [P, P, P, P, P, P, I, I, I, I, P, P]),
 }
 
+# the entries of include/d2s_hip_ragged_stage_bf16.h (training ATS and A-ViT in the bf16 arithmetic mode, DESIGN.md sections 24 and 25), same form
+_SIGS_RAGGED_STAGE_BF16 = {
+    "d2s_ragged_repack_bwd_bf16out": (I, [P, P, P, P, P, P, I, I]),
+    "d2s_avit_halt_repack_bwd_bf16out": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F]),
+}
+
 _lib = None
 
 
@@ -240,7 +247,8 @@ def load():
     for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_EXT.items()) + list(_SIGS_SQUEEZE.items()) + list(_SIGS_ATS.items())
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
                               + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())
-                              + list(_SIGS_LTP.items()) + list(_SIGS_TOME_TRAIN_BF16.items())):
+                              + list(_SIGS_LTP.items()) + list(_SIGS_TOME_TRAIN_BF16.items())
+                              + list(_SIGS_RAGGED_STAGE_BF16.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -294,6 +302,10 @@ def ltp_symbols():
 
 def tome_train_bf16_symbols():
     return sorted(_SIGS_TOME_TRAIN_BF16)
+
+
+def ragged_stage_bf16_symbols():
+    return sorted(_SIGS_RAGGED_STAGE_BF16)
 
 
 def ptr(t):

@@ -1330,11 +1330,18 @@ def attn_varlen_bwd(qkv, cu, out, dout, lse, B, total, max_n, H, scale):
     return dqkv
 
 
-def ragged_repack_bwd(g_new, keep, cu_old, cu_new, total_old, B):
-    """Backward of ragged_repack: g_new [total_new, D] -> g_old [total_old, D], a kept row takes the row it became, a dropped row zeros."""
+def ragged_repack_bwd(g_new, keep, cu_old, cu_new, total_old, B, g16=None):
+    """Backward of ragged_repack: g_new [total_new, D] -> g_old [total_old, D], a kept row takes the row it became, a dropped row zeros.
+    g16 (the bf16 data path behind a stage): a bf16 buffer [total_old, D] that receives g_old rounded once, in the same launch."""
     _f32(g_new), _f32(keep)
     D = g_new.shape[1]
     g_old = torch.empty((total_old, D), dtype=torch.float32, device=g_new.device)
+    if g16 is not None:
+        assert g16.dtype == torch.bfloat16 and g16.is_contiguous() and g16.numel() == int(total_old) * D and g16.is_cuda
+        assert keep.numel() == int(total_old) and cu_old.numel() == int(B) + 1 and cu_new.numel() == int(B) + 1
+        lib.call("d2s_ragged_repack_bwd_bf16out", lib.ptr(g_new), lib.ptr(keep), lib.ptr(cu_old), lib.ptr(cu_new), lib.ptr(g_old),
+                 lib.ptr(g16), int(B), D)
+        return g_old
     lib.call("d2s_ragged_repack_bwd", lib.ptr(g_new), lib.ptr(keep), lib.ptr(cu_old), lib.ptr(cu_new), lib.ptr(g_old), int(B), D)
     return g_old
 
@@ -1445,6 +1452,27 @@ def avit_halt_bwd(g, h, cu, row_src, st, w, dacc, ycls, gsc, layer, gamma):
     lib.call("d2s_avit_halt_bwd", lib.ptr(g), lib.ptr(h), lib.ptr(cu), lib.ptr(row_src), lib.ptr(st["nh"]), lib.ptr(w), lib.ptr(dacc),
              lib.ptr(ycls), lib.ptr(st["ysave"]), lib.ptr(gsc), B, N, D, total, int(layer), L, int(fresh), float(gamma))
     return g
+
+
+def avit_halt_repack_bwd_bf16io(g_new, keep, cu_new, h, cu, row_src, st, w, dacc, ycls, gsc, layer, gamma):
+    """The backward of an A-ViT block boundary on the bf16 data path, one launch: ragged_repack_bwd, avit_halt_bwd and the cast.  g_new
+    [total_new, D] with the keep / cu_new of the boundary's re-pack, or all three None (the last layer: nothing arrived).
+    -> (g [total, D] fp32 - the bits of the two ops chained - and g16, the same values rounded once to bf16)"""
+    B, N = st["c"].shape
+    total = h.numel()
+    D = dacc.shape[1]
+    L = gsc.numel() - 1
+    _f32(dacc), _f32(ycls), _f32(gsc), _f32(h)
+    if g_new is not None:
+        _f32(g_new), _f32(keep)
+        assert g_new.shape[1] == D and keep.numel() == total and cu_new.numel() == B + 1 and cu_new.dtype == torch.int32
+    assert cu.numel() == B + 1 and row_src.numel() == total
+    g = torch.empty((total, D), dtype=torch.float32, device=h.device)
+    g16 = bf16_buffer(total, D, h.device)
+    lib.call("d2s_avit_halt_repack_bwd_bf16out", lib.ptr(g_new), lib.ptr(keep), lib.ptr(cu_new), lib.ptr(h), lib.ptr(cu), lib.ptr(row_src),
+             lib.ptr(st["nh"]), lib.ptr(w), lib.ptr(dacc), lib.ptr(ycls), lib.ptr(st["ysave"]), lib.ptr(gsc), lib.ptr(g), lib.ptr(g16),
+             B, N, D, total, int(layer), L, float(gamma))
+    return g, g16
 
 
 def avit_penalty_fwd(part, tgt, N):

@@ -154,6 +154,21 @@ def check_supported(args):
         if args.eval_only:
             bad.append("--ats-train with --eval-only (evaluation runs the inference path: drop one of the two)")
         _training_refusals(methods.by_name("ats"), args, bad)
+    ats_train_bf16 = bool(getattr(args, "ats_train_bf16", False))
+    if ats_train_bf16:
+        # the flag, not the mode, selects the path (as --tome-train-bf16): it sets the bf16 arithmetic mode itself, --gemm-mode bf16 stays refused
+        if not ats_train:
+            bad.append("--ats-train-bf16 without --ats-train (it puts training through the sampling stages into the bf16 arithmetic mode)")
+        if getattr(args, "gemm_mode", "exact") == "split":
+            bad.append("--ats-train-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
+    avit_bf16 = bool(getattr(args, "avit_bf16", False))
+    if avit_bf16:
+        if method != "avit":
+            bad.append(f"--avit-bf16 with --method {method} (it puts training the A-ViT baseline into the bf16 arithmetic mode: --method avit)")
+        if args.eval_only:
+            bad.append("--avit-bf16 with --eval-only (--gemm-mode bf16 already evaluates the adaptive-depth trunk on the bf16 data path)")
+        if getattr(args, "gemm_mode", "exact") == "split":
+            bad.append("--avit-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
     if method == "ats":
         if not args.eval_only and not ats_train:
             bad.append("--method ats without --eval-only (adaptive token sampling is built for inference: a sampling stage has no backward)")
@@ -229,6 +244,14 @@ def check_supported(args):
         print("Attention: --tome-train-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the (key-weighted) "
               "attention and its backward on the bf16 matrix cores, the residual stream, the match and the merge in fp32; validation runs "
               "the bf16 merging trunk (DESIGN.md section 22)")
+    if ats_train_bf16 and ats_train and method == "ats":
+        print("Attention: --ats-train-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the ragged attention "
+              "and its backward on the bf16 matrix cores, the residual stream, the selection and the row moves in fp32, a stage's backward "
+              "handing on both forms of the gradient (DESIGN.md section 24)")
+    if avit_bf16 and method == "avit" and not args.eval_only:
+        print("Attention: --avit-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the ragged attention and "
+              "its backward on the bf16 matrix cores, the residual stream, the halting step and the row moves in fp32, every block "
+              "boundary's backward one launch that hands on both forms of the gradient (DESIGN.md section 25)")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:
@@ -353,7 +376,8 @@ def build_models(args):
     method = getattr(args, "method", "d2s")
     if method == "ats" and not getattr(args, "ats_train", False):
         return build_ats(args), None                 # inference only: no teacher
-    build = {"ats": lambda a: build_ats(a, train_sample=True), "avit": build_avit, "evo": build_evo, "ltp": build_ltp}.get(method)
+    ats_kw = {"train_bf16": True} if getattr(args, "ats_train_bf16", False) else {}
+    build = {"ats": lambda a: build_ats(a, train_sample=True, **ats_kw), "avit": build_avit, "evo": build_evo, "ltp": build_ltp}.get(method)
     if build is not None:
         # the family's student from --student-checkpoint; the dense teacher as for the other methods, unless --dist-weight 0
         teacher = _teacher(args)
@@ -425,7 +449,7 @@ def load_trunk(args, model, method, why):
 
 def build_ats(args, **kw):
     """--method ats: the dense DeiT trunk with a sampling stage in every block of --pruning-locs, at most --ats-tokens tokens each.
-    kw: train_sample=True under --ats-train, nothing otherwise."""
+    kw: train_sample=True under --ats-train (and train_bf16=True under --ats-train-bf16), nothing otherwise."""
     toks = getattr(args, "ats_tokens", None)
     if toks is not None and len(toks) == 1:
         toks = int(toks[0])
@@ -435,7 +459,8 @@ def build_ats(args, **kw):
 def build_avit(args):
     """--method avit: the dense DeiT trunk with per-token adaptive depth; the gate constants and the prior's target depth from --avit-*."""
     v = methods.flag_values(methods.by_name("avit"), args)
-    return _trunk("avit", args, gate_scale=v["avit_gate_scale"], gate_center=v["avit_gate_center"], target_depth=v["avit_target_depth"])
+    return _trunk("avit", args, gate_scale=v["avit_gate_scale"], gate_center=v["avit_gate_center"], target_depth=v["avit_target_depth"],
+                  **({"train_bf16": True} if getattr(args, "avit_bf16", False) else {}))
 
 
 def build_evo(args):
@@ -537,10 +562,10 @@ def main(argv=None):
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
-    # --ragged-bf16 and --tome-train-bf16 set the bf16 arithmetic mode themselves, as --gemm-mode bf16 would (which stays refused with
-    # --ragged-train and with --method tome)
-    ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}[
-        "bf16" if (getattr(args, "ragged_bf16", False) or getattr(args, "tome_train_bf16", False)) else args.gemm_mode])
+    # --ragged-bf16, --tome-train-bf16, --ats-train-bf16 and --avit-bf16 set the bf16 arithmetic mode themselves, as --gemm-mode bf16 would
+    # (which stays refused with --ragged-train, with --method tome, with --ats-train and with training --method avit)
+    own_bf16 = any(getattr(args, f, False) for f in ("ragged_bf16", "tome_train_bf16", "ats_train_bf16", "avit_bf16"))
+    ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}["bf16" if own_bf16 else args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
     if (args.method == "ats" and not args.ats_train) or (args.method == "tome" and not args.tome_train):
         return eval_tome(args, rank, world, distributed)

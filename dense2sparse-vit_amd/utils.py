@@ -221,6 +221,14 @@ def parse_args(argv=None):
                    help='with --method tome --tome-train: train through the merges in the bf16 arithmetic mode (bf16 matrix cores for the '
                         'GEMMs, the key-weighted attention and its backward; the bf16 data path) - the flag sets that mode itself, '
                         '--gemm-mode stays at exact (its default); validation runs the bf16 merging trunk')
+    p.add_argument('--ats-train-bf16', action='store_true', default=argparse.SUPPRESS,
+                   help='with --method ats --ats-train: train through the sampling stages in the bf16 arithmetic mode (bf16 matrix cores for '
+                        'the GEMMs, the ragged attention and its backward; the bf16 data path) - the flag sets that mode itself, --gemm-mode '
+                        'stays at exact (its default)')
+    p.add_argument('--avit-bf16', action='store_true', default=argparse.SUPPRESS,
+                   help='with --method avit: train in the bf16 arithmetic mode (bf16 matrix cores for the GEMMs, the ragged attention and its '
+                        'backward; the bf16 data path, every block boundary handing on the bf16 form of its gradient) - the flag sets that '
+                        'mode itself, --gemm-mode stays at exact (its default); with --eval-only use --gemm-mode bf16')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

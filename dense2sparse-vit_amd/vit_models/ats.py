@@ -24,9 +24,12 @@ class VisionTransformerATS(VisionTransformerTeacher):
     train_sample: let the training-mode forward sample too - the blocks before the first stage are the dense differentiable ones, every
     block from the first stage on runs through RaggedBlockFn on the packed batch, the head reads the gathered CLS rows; the selection is
     the inference one and a constant of the backward (no gradient through score, keep or counts), the records above are filled as in eval
-    mode and plans= replays.  fp32 data path only.  Off (the default), a model with a stage refuses to train."""
+    mode and plans= replays.  fp32 data path unless train_bf16.  Off (the default), a model with a stage refuses to train.
+    train_bf16: with train_sample, the training-mode forward also runs in the bf16 arithmetic mode - the ragged blocks on the bf16 data
+    path (_Ragged(bf16=True), stage_bf16=True at a stage), the dense blocks in front as they run there anyway.  Under an fp32 mode the
+    keyword changes nothing; without it the bf16 mode is refused as before."""
 
-    def __init__(self, *args, ats_locs=(), ats_tokens=None, train_sample=False, **kwargs):
+    def __init__(self, *args, ats_locs=(), ats_tokens=None, train_sample=False, train_bf16=False, **kwargs):
         super().__init__(*args, **kwargs)
         depth = len(self.blocks)
         locs = [int(v) for v in ats_locs]
@@ -43,6 +46,9 @@ class VisionTransformerATS(VisionTransformerTeacher):
             raise ValueError(f"ats_tokens: None, one int >= 1 or a list of {len(locs)} of them (one per stage), got {ats_tokens!r}")
         self.ats_locs, self.ats_tokens = locs, toks
         self.train_sample = bool(train_sample)
+        self.train_bf16 = bool(train_bf16)
+        if self.train_bf16 and not self.train_sample:
+            raise ValueError("train_bf16 without train_sample: it puts training through the sampling stages into the bf16 arithmetic mode")
         if self.train_sample and float(getattr(self, "drop_path_rate", 0.0)) > 0.0:
             raise ValueError("train_sample with drop_path_rate > 0: stochastic depth is not built for a ragged block")
         self.grad_ready_hook = None          # set by a data-parallel TrainStep: called with i when block i's input gradient exists
@@ -110,7 +116,8 @@ class VisionTransformerATS(VisionTransformerTeacher):
         one RaggedBlockFn per block from there on, the CLS rows gathered in front of the final LayerNorm (row-wise, so the same function
         as normalising every row first) and HeadFn on them."""
         self._check_plans(plans)
-        if ops.get_gemm_mode() == ops.GEMM_BF16:
+        bf16 = ops.get_gemm_mode() == ops.GEMM_BF16
+        if bf16 and not self.train_bf16:
             raise NotImplementedError("train_sample in the bf16 arithmetic mode: training through a sampling stage is built on the fp32 data "
                                       "path only (gemm modes exact and split)")
         x = self._embed(x)
@@ -131,9 +138,10 @@ class VisionTransformerATS(VisionTransformerTeacher):
                 row_src = torch.arange(n, dtype=torch.int32, device=x.device).repeat(B)
             a = blk.attn
             if here:
-                r = AF._Ragged(cu, B, n, a.num_heads, a.scale, row_src, self.ats_tokens[stage], N, None if plans is None else plans[stage])
+                r = AF._Ragged(cu, B, n, a.num_heads, a.scale, row_src, self.ats_tokens[stage], N, None if plans is None else plans[stage],
+                               **(dict(bf16=True, stage_bf16=True) if bf16 else {}))
             else:
-                r = AF._Ragged(cu, B, n, a.num_heads, a.scale)
+                r = AF._Ragged(cu, B, n, a.num_heads, a.scale, **(dict(bf16=True) if bf16 else {}))
             x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, r)
             if here:
                 cu, row_src, n = r.cu_new, r.row_src_new, r.max_n_out

@@ -7,6 +7,7 @@ import torch
 
 from d2s import functional_ats as AF
 from d2s import functional_avit as VF
+from d2s import ops
 from .dynamic_vit import VisionTransformerTeacher, _GEOM, _load_local
 
 
@@ -15,12 +16,16 @@ class VisionTransformerAViT(VisionTransformerTeacher):
     Afterwards: tokens_per_layer - [L] ints, the rows of the packed batch block l ran on; tokens_per_layer_counts - [L, B] int32 (host),
     the same per image (a finished image goes on as its dead CLS row and counts 1); halt_layer - [B, N] int32 on the device, the layer
     every token halted at (N counts CLS); avg_depth - 0-d device tensor, the mean of halt_layer; ponder_loss, prior_loss - the two penalty
-    terms of AViTLoss (0-d, differentiable in training), which target_depth shapes; avit_run - the d2s.functional_avit.AViTRun."""
+    terms of AViTLoss (0-d, differentiable in training), which target_depth shapes; avit_run - the d2s.functional_avit.AViTRun.
+    train_bf16: the training forward also runs in the bf16 arithmetic mode - every block on the bf16 data path (_Ragged(bf16=True)), every
+    boundary's backward handing on the bf16 form of its gradient (AViTRun(bf16=True)).  Under an fp32 mode the keyword changes nothing;
+    without it the bf16 mode is refused by the ragged block as before."""
 
-    def __init__(self, *args, gate_scale=10.0, gate_center=30.0, eps_halt=0.01, target_depth=7.0, **kwargs):
+    def __init__(self, *args, gate_scale=10.0, gate_center=30.0, eps_halt=0.01, target_depth=7.0, train_bf16=False, **kwargs):
         super().__init__(*args, **kwargs)
         self.gate_scale, self.gate_center, self.eps_halt = float(gate_scale), float(gate_center), float(eps_halt)
         self.target_depth = float(target_depth)
+        self.train_bf16 = bool(train_bf16)
         if not 0.0 < self.eps_halt < 1.0:
             raise ValueError(f"eps_halt: a value in (0, 1), got {eps_halt!r}")
         if len(self.blocks) > 64:
@@ -47,14 +52,16 @@ class VisionTransformerAViT(VisionTransformerTeacher):
         x = self._embed(x)
         B, n, D = x.shape
         L = len(self.blocks)
-        run = VF.AViTRun(B, n, D, L, self.gate_scale, self.gate_center, self.eps_halt, x.device)
+        bf16 = train and self.train_bf16 and ops.get_gemm_mode() == ops.GEMM_BF16
+        run = VF.AViTRun(B, n, D, L, self.gate_scale, self.gate_center, self.eps_halt, x.device, **(dict(bf16=True) if bf16 else {}))
         x = x.contiguous().view(B * n, D)
         for i, blk in enumerate(self.blocks):
             a = blk.attn
             if train:
                 if self.grad_ready_hook is not None and x.requires_grad:
                     x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
-                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(run.cu, B, run.max_n, a.num_heads, a.scale))
+                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps,
+                                          AF._Ragged(run.cu, B, run.max_n, a.num_heads, a.scale, **(dict(bf16=True) if bf16 else {})))
             else:
                 x = blk.forward_ragged(x, run.cu, B, run.max_n)
             x = VF.halt(x, run, i + 1)

@@ -5,13 +5,17 @@ given.  The no-stage trunk is the same DeiT-S through the same route (VisionTran
 BlockFn's composite blocks - what VisionTransformerATS(ats_locs=()) runs in training mode).  The models alternate in one process for
 --rounds rounds of 10 steps each; prints ms per step (mean over the rounds, with the spread between them), images/s and, for ATS, the mean
 number of tokens (CLS not counted) that leave every stage in the last step - the figure means nothing without it.  GPU box only.
+--bf16: the same rows as train_bf16 students under GEMM_BF16 (--ats-train-bf16; the dense trunk: the bf16 step of the r = 0 merging
+student); with --also-fp32 the fp32 rows stay in the same run, alternating with them, and every row prints the median of its rounds.
 
   python tools/ats_train_bench.py [--gemm-mode exact|split] [--ats-tokens 196 98 49] [--student-checkpoint deit_small.pth]
+  python tools/ats_train_bench.py --bf16 [--also-fp32]
   python tools/ats_train_bench.py --kernels        (under rocprofv3 --kernel-trace --stats: the three varlen attention-backward launches on
                                                     128 images of 197 rows next to d2s_attn_bwd_f32 on the same data, alternating)
 """
 import argparse
 import os
+import statistics
 import sys
 import types
 
@@ -30,7 +34,11 @@ ap.add_argument("--ats-tokens", type=int, nargs="+", default=[196, 98, 49], help
 ap.add_argument("--student-checkpoint", default=None, help="DeiT-S weights for every model (default: seeded random weights)")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--kernels", action="store_true", help="only the attention-backward kernels, varlen next to dense at equal length")
+ap.add_argument("--bf16", action="store_true", help="time the train_bf16 students under GEMM_BF16 (--ats-train-bf16)")
+ap.add_argument("--also-fp32", action="store_true", help="with --bf16: keep the fp32 rows in the same run")
 args = ap.parse_args()
+if args.also_fp32 and not args.bf16:
+    raise SystemExit("--also-fp32 goes with --bf16")
 
 dev = torch.device("cuda:0")
 B, WARMUP, TIMED = 128, 2, 10
@@ -56,12 +64,21 @@ mode, mname = MODES[args.gemm_mode]
 ops.set_gemm_mode(mode)
 
 
-def step_of(model):
+def step_of(model, bf16=False):
+    """the step and the arithmetic mode it is built and called in (a train_bf16 student under GEMM_BF16)"""
     a = types.SimpleNamespace(mixup=0.0, cls_weight=1.0, dist_weight=0.0, step=0)
-    return TrainStep(model.to(dev).train(), None, a, lr=1e-5, graph=False)
+    m = ops.GEMM_BF16 if bf16 else mode
+    with ops.gemm_mode(m):
+        return TrainStep(model.to(dev).train(), None, a, lr=1e-5, graph=False), m
 
 
-def timed(ts, warm):
+def timed(step, warm):
+    ts, m = step
+    with ops.gemm_mode(m):
+        return _timed(ts, warm)
+
+
+def _timed(ts, warm):
     for _ in range(WARMUP if warm else 0):
         ts(x, y)
     torch.cuda.synchronize()
@@ -74,20 +91,26 @@ def timed(ts, warm):
     return s.elapsed_time(e) / TIMED
 
 
-torch.manual_seed(0)
-steps = [("no stage (dense trunk)", step_of(vit_models.tome_deit_small_patch16_224(0, checkpoint_path=args.student_checkpoint)))]
-for K in args.ats_tokens:
+steps = []
+for bf16 in ([False] if not args.bf16 else [False, True] if args.also_fp32 else [True]):      # fp32 rows first when both are timed
+    tag = " bf16" if bf16 else " fp32" if args.bf16 else ""
+    kw = {"train_bf16": True} if bf16 else {}
     torch.manual_seed(0)
-    steps.append((f"ats @ blocks {args.ats_locs[0]}-{args.ats_locs[-1]} K = {K:3d}",
-                  step_of(vit_models.ats_deit_small_patch16_224(ats_locs=args.ats_locs, ats_tokens=K, train_sample=True,
-                                                                checkpoint_path=args.student_checkpoint))))
+    steps.append(("no stage (dense trunk)" + tag,
+                  step_of(vit_models.tome_deit_small_patch16_224(0, checkpoint_path=args.student_checkpoint,
+                                                                 **({"train_merge": True, "train_bf16": True} if bf16 else {})), bf16)))
+    for K in args.ats_tokens:
+        torch.manual_seed(0)
+        steps.append((f"ats @ blocks {args.ats_locs[0]}-{args.ats_locs[-1]} K = {K:3d}" + tag,
+                      step_of(vit_models.ats_deit_small_patch16_224(ats_locs=args.ats_locs, ats_tokens=K, train_sample=True,
+                                                                    checkpoint_path=args.student_checkpoint, **kw), bf16)))
 times = [[] for _ in steps]
 for r in range(args.rounds):
-    for i, (_, ts) in enumerate(steps):
-        times[i].append(timed(ts, r == 0))
-for (name, ts), t in zip(steps, times):
-    ms, spread = sum(t) / len(t), max(t) - min(t)
-    line = f"{mname:12s} {name:30s} {ms:7.2f} ms/step (spread {spread:.2f})  {B / ms * 1e3:8.0f} images/s"
+    for i, (_, step) in enumerate(steps):
+        times[i].append(timed(step, r == 0))
+for (name, (ts, _)), t in zip(steps, times):
+    ms, spread = statistics.median(t) if args.bf16 else sum(t) / len(t), max(t) - min(t)      # --bf16: the median of the rounds
+    line = f"{mname if not args.bf16 else '':12s} {name:35s} {ms:7.2f} ms/step (spread {spread:.2f})  {B / ms * 1e3:8.0f} images/s"
     if ts.method.name == "ats":
         per = [c.float() for c in ts.student.tokens_per_stage]
         line += f"   tokens per stage: mean {[round(float(c.mean()), 1) for c in per]} min {[int(c.min()) for c in per]} max {[int(c.max()) for c in per]}"
