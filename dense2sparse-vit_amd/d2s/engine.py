@@ -545,7 +545,7 @@ class TrainStep:
                 raise lib.D2SError(f"TrainStep with {m.opt_in[2]}")
             if float(getattr(student, "drop_path_rate", 0.0)) > 0.:
                 raise lib.D2SError(f"TrainStep with {m.student} and drop_path_rate > 0: stochastic depth is not built for {m.block}")
-            if m.bf16_refusal and ops.get_gemm_mode() == ops.GEMM_BF16:
+            if m.bf16_refusal and ops.get_gemm_mode() == ops.GEMM_BF16 and not getattr(student, "train_bf16", False):
                 raise lib.D2SError(f"TrainStep with {m.student} in the bf16 arithmetic mode: " + m.bf16_refusal())
             if m.no_graph:
                 graph = False

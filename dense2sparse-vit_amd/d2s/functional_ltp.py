@@ -11,7 +11,12 @@ the thresholds receive no gradient in this phase.
 Soft phase (training with ltp_phase == "soft"): the batch stays dense and the soft mask acts where removal acts - on the token as a KEY
 of every later block, through policy attention (LTPSoftBlockFn: block_forward_sequence with attn_forward(..., policy), the score launched
 next to it as a non-differentiable side output; the backward asks attn_backward for dpolicy).  LTPSoftMaskFn is the mask of one stage,
-M = sigmoid((score - theta_k) / tau), m <- m * M; the score carries no gradient, the threshold learns through M."""
+M = sigmoid((score - theta_k) / tau), m <- m * M; the score carries no gradient, the threshold learns through M.
+
+The bf16 arithmetic mode is refused (BF16_REFUSAL) unless asked for: _RaggedLTP(..., bf16=True) and soft_block(..., bf16=True) put a stage
+block and a soft block on the bf16 data path - the ragged and the policy attention and their backwards on the bf16 matrix cores, the hook's
+backward handing on both forms of the gradient (functional_ats._Ragged.sample_bwd_bf16) - and the score is then rebuilt from the bf16 qkv
+and the log-sum-exp those kernels wrote (ops.ltp_score dispatches on qkv's dtype; csrc/ltp_bf16.hip).  The soft mask stays fp32."""
 import torch
 
 from . import functional as DF
@@ -35,13 +40,21 @@ class _RaggedLTP(AF._Ragged):
     deciding.  After the forward: cu_new, row_src_new, plan, rows (the new row count of every image, CLS included), max_n_out, and -
     unless replaying - score [total] and dense [B, T], the stage's kept patches in original coordinates."""
 
-    def __init__(self, cu, B, max_n, heads, scale, row_src, theta, T, plan=None):
-        super().__init__(cu, B, max_n, heads, scale, row_src, K=int(T), N=int(T), plan=plan)      # K: a stage without a token limit
+    def __init__(self, cu, B, max_n, heads, scale, row_src, theta, T, plan=None, bf16=False):
+        # K: a stage without a token limit.  bf16: the stage on the bf16 data path in the bf16 arithmetic mode (stage_bf16: the hook's
+        # backward hands on both forms of the gradient)
+        super().__init__(cu, B, max_n, heads, scale, row_src, K=int(T), N=int(T), plan=plan, **(dict(bf16=True, stage_bf16=True) if bf16 else {}))
         self.theta, self.T, self.rows = theta, int(T), None
 
     def attn_train(self, qkv, io, want_f32):
         """The LSE form in training and in eval: the score is the column mean of the probabilities this very log-sum-exp normalises"""
         total = qkv.shape[0]
+        if self.bf16 and io:
+            # the bf16 kernels' log-sum-exp, of the bf16-rounded operands: the score is rebuilt from those (ops.ltp_score on the bf16 qkv)
+            out, lse, _, out16 = ops.attn_varlen_fwd_lse_bf16io(qkv, self.cu, self.B, total, self.max_n, self.heads, self.scale, want_f32=want_f32)
+            if self.plan is None:
+                self.score = ops.ltp_score(qkv, lse, self.B, self.max_n, self.heads, self.scale, cu=self.cu, total=total)
+            return out, lse, None, None, out16
         out, lse, _ = ops.attn_varlen_fwd_lse(qkv, self.cu, self.B, total, self.max_n, self.heads, self.scale)
         if self.plan is None:
             self.score = ops.ltp_score(qkv, lse, self.B, self.max_n, self.heads, self.scale, cu=self.cu, total=total)
@@ -69,10 +82,20 @@ class LTPStageBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xp, *rest):
         params, (eps, r) = rest[:12], rest[12:]
-        refuse_bf16()
+        if r.bf16:
+            if ops.get_gemm_mode() != ops.GEMM_BF16:
+                raise D2SError(AF._BF16_MODE_REFUSAL)
+        else:
+            refuse_bf16()
         train = DF.wants_grad(ctx)
         xp = xp.contiguous()
-        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, False, train, r.attn_train, (), mid=r.sample, mid_cls=True)
+        # bf16=True: the bf16 data path, as functional_ats.RaggedBlockFn runs a block with a stage there
+        io = r.bf16 and DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
+        if r.bf16:
+            if not io:
+                raise D2SError("a ragged block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, io, train, r.attn_train, (), mid=r.sample, mid_cls=True)
         if train:
             ctx.save_for_backward(xp, *saved)
             ctx.ragged = r
@@ -82,7 +105,8 @@ class LTPStageBlockFn(torch.autograd.Function):
     def backward(ctx, gy):
         xp, *saved = ctx.saved_tensors
         r = ctx.ragged
-        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd, r.sample_bwd)
+        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd,
+                                              r.sample_bwd_bf16 if r.bf16 else r.sample_bwd, mid_bwd_bf16=r.bf16)
         return tuple(grads) + (None, None)
 
 
@@ -95,18 +119,28 @@ def stage_block(xp, params, eps, r):
 @DF.mode_recorded
 class LTPSoftBlockFn(torch.autograd.Function):
     """One dense block of the soft phase: x [B, n, D], the 12 block parameters, heads, eps, scale, policy ([B, n] fp32 or None: no stage
-    passed yet, the plain softmax), want_score -> (y [B, n, D], score [B, n] or an empty tensor).  Differentiable in x, the parameters
+    passed yet, the plain softmax), want_score[, bf16] -> (y [B, n, D], score [B, n] or an empty tensor).  Differentiable in x, the parameters
     and the policy; the score is a side output without a gradient."""
 
     @staticmethod
     def forward(ctx, x, *rest):
-        params, (heads, eps, scale, policy, want_score) = rest[:12], rest[12:]
-        refuse_bf16()
+        params, (heads, eps, scale, policy, want_score) = rest[:12], rest[12:17]
+        bf16 = len(rest) > 17 and bool(rest[17])          # optional trailing input: the block may run in the bf16 arithmetic mode
+        if not bf16:
+            refuse_bf16()
         train = DF.wants_grad(ctx)
         B, n, D = x.shape
         x = x.contiguous()
         scale = float(scale)
         side = {}
+        # bf16 and the bf16 mode on: the bf16 data path, policy attention on the bf16 matrix cores (d2s_attn_policy_fwd_bf16 / _bwd_bf16);
+        # under an fp32 mode the keyword changes nothing
+        io = bf16 and DF.bf16_data_path(x, D, params[8].shape[0])
+        if bf16 and ops.get_gemm_mode() == ops.GEMM_BF16:
+            if not io:      # the fp32 score kernel would meet a log-sum-exp of bf16-rounded operands
+                raise D2SError("an LTP soft block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        ctx.nbf16 = len(rest) - 17
 
         def attn(qkv, io, want_f32):
             out = DF.attn_forward(qkv, B, n, heads, scale, False, policy, io)
@@ -114,7 +148,7 @@ class LTPSoftBlockFn(torch.autograd.Function):
                 side["score"] = ops.ltp_score(qkv, out[1], B, n, heads, scale, policy=policy, cinv=out[2]).view(B, n)
             return out
 
-        y, _, saved, cinv = DF.block_forward_sequence(x.view(B * n, D), params, eps, False, train, attn, ())
+        y, _, saved, cinv = DF.block_forward_sequence(x.view(B * n, D), params, eps, io, train, attn, ())
         if train:
             ctx.save_for_backward(x, *saved)
             ctx.policy = (policy, cinv)
@@ -136,12 +170,12 @@ class LTPSoftBlockFn(torch.autograd.Function):
             gy, x, saved, list(ctx.needs_input_grad[:13]), None, None, 0,
             lambda qkv, ao, dao, lse, io, dqkvh, want_f32: DF.attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh,
                                                                             want_f32, want_dpolicy))
-        return tuple(grads) + (None, None, None, dpolicy, None)
+        return tuple(grads) + (None, None, None, dpolicy, None) + (None,) * ctx.nbf16
 
 
-def soft_block(x, params, heads, eps, scale, policy, want_score):
-    """-> (y, score [B, n] or None)"""
-    y, score = DF.run(LTPSoftBlockFn, x, *params, heads, eps, scale, policy, bool(want_score))
+def soft_block(x, params, heads, eps, scale, policy, want_score, bf16=False):
+    """-> (y, score [B, n] or None).  bf16: the block follows the bf16 arithmetic mode onto the bf16 data path instead of refusing it"""
+    y, score = DF.run(LTPSoftBlockFn, x, *params, heads, eps, scale, policy, bool(want_score), *((True,) if bf16 else ()))
     return y, (score if want_score else None)
 
 

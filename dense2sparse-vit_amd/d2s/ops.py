@@ -1500,7 +1500,11 @@ def avit_penalty_bwd(hbar, cnt, tgt, dponder, dprior, B, N):
 def ltp_score(qkv, lse, B, n, H, scale, policy=None, cinv=None, cu=None, total=None):
     """The attention every token receives in one block: qkv [rows, 3 * H * 64] and the lse (and cinv) that block's attention forward wrote.
     Plain: lse [B, H, n]; policy: policy [B, n], cinv [B, H, n] as attn_policy_fwd returned them; varlen: cu [B + 1] int32, lse [H, total],
-    n = max_n (any upper bound).  -> score [rows] fp32, each image's entries summing to 1."""
+    n = max_n (any upper bound).  -> score [rows] fp32, each image's entries summing to 1.
+    qkv in bf16 (the bf16 data path): lse and cinv as the bf16 attention forward wrote them, the score rebuilt on the bf16 matrix cores
+    (csrc/ltp_bf16.hip)."""
+    if qkv.dtype == torch.bfloat16:
+        return _ltp_score_bf16(qkv, lse, B, n, H, scale, policy, cinv, cu, total)
     assert qkv.dtype == torch.float32 and qkv.is_contiguous()
     _f32(lse)
     rows = int(total) if cu is not None else B * n
@@ -1514,6 +1518,24 @@ def ltp_score(qkv, lse, B, n, H, scale, policy=None, cinv=None, cu=None, total=N
     need = lib.query("d2s_ltp_score_workspace_bytes", rows, int(H))
     ws = torch.empty((need // 4,), dtype=torch.float32, device=qkv.device)
     lib.call("d2s_ltp_score_f32", lib.ptr(qkv), lib.ptr(lse), lib.ptr(policy), lib.ptr(cinv), lib.ptr(cu), lib.ptr(score), lib.ptr(ws), need,
+             int(B), int(n), rows, int(H), float(scale))
+    return score
+
+
+def _ltp_score_bf16(qkv, lse, B, n, H, scale, policy, cinv, cu, total):
+    assert qkv.is_contiguous()
+    _f32(lse)
+    rows = int(total) if cu is not None else B * n
+    assert qkv.numel() == rows * 3 * H * 64 and lse.numel() == rows * H, (tuple(qkv.shape), tuple(lse.shape), rows, H)
+    if policy is not None:
+        assert cu is None and cinv is not None and policy.numel() == rows and cinv.numel() == rows * H
+        _f32(policy), _f32(cinv)
+    if cu is not None:
+        assert cu.dtype == torch.int32 and cu.numel() == B + 1 and cu.is_contiguous()
+    score = torch.empty((rows,), dtype=torch.float32, device=qkv.device)
+    need = lib.query("d2s_ltp_score_bf16_workspace_bytes", rows, int(H))
+    ws = torch.empty((need // 4,), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_ltp_score_bf16", lib.ptr(qkv), lib.ptr(lse), lib.ptr(policy), lib.ptr(cinv), lib.ptr(cu), lib.ptr(score), lib.ptr(ws), need,
              int(B), int(n), rows, int(H), float(scale))
     return score
 

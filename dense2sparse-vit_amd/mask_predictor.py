@@ -169,6 +169,13 @@ def check_supported(args):
             bad.append("--avit-bf16 with --eval-only (--gemm-mode bf16 already evaluates the adaptive-depth trunk on the bf16 data path)")
         if getattr(args, "gemm_mode", "exact") == "split":
             bad.append("--avit-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
+    ltp_bf16 = bool(getattr(args, "ltp_bf16", False))
+    if ltp_bf16:
+        # the flag, not the mode, selects the path (as --avit-bf16): it sets the bf16 arithmetic mode itself, --gemm-mode bf16 stays refused
+        if method != "ltp":
+            bad.append(f"--ltp-bf16 with --method {method} (it puts the LTP baseline into the bf16 arithmetic mode: --method ltp)")
+        if getattr(args, "gemm_mode", "exact") == "split":
+            bad.append("--ltp-bf16 with --gemm-mode split (the flag sets the bf16 arithmetic mode itself: leave --gemm-mode at exact)")
     if method == "ats":
         if not args.eval_only and not ats_train:
             bad.append("--method ats without --eval-only (adaptive token sampling is built for inference: a sampling stage has no backward)")
@@ -252,6 +259,11 @@ def check_supported(args):
         print("Attention: --avit-bf16: the step runs in the bf16 arithmetic mode on the bf16 data path - GEMMs, the ragged attention and "
               "its backward on the bf16 matrix cores, the residual stream, the halting step and the row moves in fp32, every block "
               "boundary's backward one launch that hands on both forms of the gradient (DESIGN.md section 25)")
+    if ltp_bf16 and method == "ltp":
+        print("Attention: --ltp-bf16: every phase and the evaluation run in the bf16 arithmetic mode on the bf16 data path - GEMMs, the "
+              "ragged and the policy attention and their backwards on the bf16 matrix cores, the score rebuilt there from the bf16 qkv and "
+              "the bf16 kernels' log-sum-exp; the residual stream, the thresholds' comparison, the soft mask and the row moves in fp32 "
+              "(DESIGN.md section 27)")
     if args.early_exit:
         print("Attention: --early-exit creates the extra head but, as in the reference, nothing calls it (dynamic_vit.py:752-758)")
     if args.random_drop:
@@ -474,7 +486,8 @@ def build_ltp(args):
     earlier LTP run (the soft phase's best.pt) brings its own."""
     v = methods.flag_values(methods.by_name("ltp"), args)
     return _trunk("ltp", args, pruning_loc=list(args.pruning_locs), ltp_temperature=v["ltp_temperature"],
-                  ltp_init_threshold=v["ltp_init_threshold"], ltp_phase=v["ltp_phase"])
+                  ltp_init_threshold=v["ltp_init_threshold"], ltp_phase=v["ltp_phase"],
+                  **({"train_bf16": True} if getattr(args, "ltp_bf16", False) else {}))
 
 
 def folder_loaders(args, samples, split, epoch, rank, world):
@@ -564,7 +577,7 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)          # RCCL
     # --ragged-bf16, --tome-train-bf16, --ats-train-bf16 and --avit-bf16 set the bf16 arithmetic mode themselves, as --gemm-mode bf16 would
     # (which stays refused with --ragged-train, with --method tome, with --ats-train and with training --method avit)
-    own_bf16 = any(getattr(args, f, False) for f in ("ragged_bf16", "tome_train_bf16", "ats_train_bf16", "avit_bf16"))
+    own_bf16 = any(getattr(args, f, False) for f in ("ragged_bf16", "tome_train_bf16", "ats_train_bf16", "avit_bf16", "ltp_bf16"))
     ops.set_gemm_mode({"exact": ops.GEMM_EXACT, "split": ops.GEMM_SPLIT, "bf16": ops.GEMM_BF16}["bf16" if own_bf16 else args.gemm_mode])
     torch.manual_seed(42)                                                     # mask_predictor.py:43-44
     if (args.method == "ats" and not args.ats_train) or (args.method == "tome" and not args.tome_train):

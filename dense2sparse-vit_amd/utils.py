@@ -229,6 +229,10 @@ def parse_args(argv=None):
                    help='with --method avit: train in the bf16 arithmetic mode (bf16 matrix cores for the GEMMs, the ragged attention and its '
                         'backward; the bf16 data path, every block boundary handing on the bf16 form of its gradient) - the flag sets that '
                         'mode itself, --gemm-mode stays at exact (its default); with --eval-only use --gemm-mode bf16')
+    p.add_argument('--ltp-bf16', action='store_true', default=argparse.SUPPRESS,
+                   help='with --method ltp: run both phases and the evaluation in the bf16 arithmetic mode (bf16 matrix cores for the GEMMs, '
+                        'the ragged and the policy attention, their backwards and the score; the bf16 data path) - the flag sets that mode '
+                        'itself, --gemm-mode stays at exact (its default)')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

@@ -27,9 +27,13 @@ class VisionTransformerLTP(VisionTransformerTeacher):
     (host), the same per image, CLS included; avg_tokens - their mean per image and block; ltp_kept - per stage a [B, T] 0/1 mask of the
     patches that went on, in original patch coordinates (soft: M >= 1/2; None when replaying); ltp_plans - per stage (keep, counts)
     (hard); ltp_scores - per stage the scores of the rows that entered it; ltp_reg - the regulariser R (0-d; differentiable in the
-    soft phase, the kept fraction of the patches per stage in the hard one)."""
+    soft phase, the kept fraction of the patches per stage in the hard one).
+    train_bf16: every forward - soft, hard and eval() - also runs in the bf16 arithmetic mode, on the bf16 data path: the stage blocks as
+    _RaggedLTP(bf16=True) with the score rebuilt on the bf16 matrix cores (ops.ltp_score on the bf16 qkv), the other ragged blocks as
+    _Ragged(bf16=True), the soft blocks through the bf16 policy attention; the soft mask stays fp32.  Under an fp32 mode the keyword changes
+    nothing; without it the bf16 mode is refused as before."""
 
-    def __init__(self, *args, pruning_loc=(), ltp_temperature=1e-3, ltp_init_threshold=0.005, ltp_phase="soft", **kwargs):
+    def __init__(self, *args, pruning_loc=(), ltp_temperature=1e-3, ltp_init_threshold=0.005, ltp_phase="soft", train_bf16=False, **kwargs):
         super().__init__(*args, **kwargs)
         depth = len(self.blocks)
         locs = [int(v) for v in pruning_loc]
@@ -43,6 +47,7 @@ class VisionTransformerLTP(VisionTransformerTeacher):
             raise ValueError("drop_path_rate > 0: stochastic depth is not built for a ragged block or a block with a learnt policy")
         self.pruning_loc = locs
         self.ltp_temperature, self.ltp_init_threshold = float(ltp_temperature), float(ltp_init_threshold)
+        self.train_bf16 = bool(train_bf16)
         S = len(locs)
         self.ltp_threshold = nn.Parameter(torch.tensor([self.ltp_init_threshold * (k + 1) / S for k in range(S)], dtype=torch.float32))
         self.set_phase(ltp_phase)
@@ -71,7 +76,8 @@ class VisionTransformerLTP(VisionTransformerTeacher):
 
     def forward(self, x, plans=None):
         self._reset_records()
-        LF.refuse_bf16()
+        if not self.train_bf16:
+            LF.refuse_bf16()
         if plans is not None and len(plans) != len(self.pruning_loc):
             raise ValueError(f"plans: one (keep, counts) per stage, {len(self.pruning_loc)} of them, got {len(plans)}")
         if self.training and self.ltp_phase == "soft":
@@ -91,6 +97,7 @@ class VisionTransformerLTP(VisionTransformerTeacher):
         cu = ops.ragged_offsets(torch.full((B,), T, dtype=torch.int32, device=x.device), extra=1)      # arange(B + 1) * N
         row_src = torch.arange(n, dtype=torch.int32, device=x.device).repeat(B)
         rows, per_block, stage = [n] * B, [], 0
+        bf16 = dict(bf16=True) if (self.train_bf16 and ops.get_gemm_mode() == ops.GEMM_BF16) else {}
         for i, blk in enumerate(self.blocks):
             if train and self.grad_ready_hook is not None and x.requires_grad:
                 x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
@@ -98,7 +105,7 @@ class VisionTransformerLTP(VisionTransformerTeacher):
             a = blk.attn
             if stage < len(self.pruning_loc) and i == self.pruning_loc[stage]:
                 r = LF._RaggedLTP(cu, B, n, a.num_heads, a.scale, row_src, self.ltp_threshold.detach()[stage:stage + 1], T,
-                                  None if plans is None else plans[stage])
+                                  None if plans is None else plans[stage], **bf16)
                 x = LF.stage_block(x, blk._params(), blk.norm1.eps, r)
                 cu, row_src, n, rows = r.cu_new, r.row_src_new, r.max_n_out, r.rows
                 self.ltp_plans.append(r.plan)
@@ -106,7 +113,7 @@ class VisionTransformerLTP(VisionTransformerTeacher):
                 self.ltp_kept.append(r.dense)
                 stage += 1
             elif train:
-                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(cu, B, n, a.num_heads, a.scale))
+                x = AF.ragged_block_train(x, blk._params(), blk.norm1.eps, AF._Ragged(cu, B, n, a.num_heads, a.scale, **bf16))
             else:
                 x = blk.forward_ragged(x, cu, B, n)
         self._record_counts(per_block)
@@ -120,12 +127,13 @@ class VisionTransformerLTP(VisionTransformerTeacher):
         B, n, D = x.shape
         T, S = n - 1, len(self.pruning_loc)
         m, msums, stage = None, [], 0
+        bf16 = dict(bf16=True) if self.train_bf16 else {}
         for i, blk in enumerate(self.blocks):
             if self.grad_ready_hook is not None and x.requires_grad:
                 x.register_hook(lambda g, i=i, cb=self.grad_ready_hook: (cb(i), None)[1])
             here = stage < S and i == self.pruning_loc[stage]
             a = blk.attn
-            x, score = LF.soft_block(x, blk._params(), a.num_heads, blk.norm1.eps, a.scale, m, here)
+            x, score = LF.soft_block(x, blk._params(), a.num_heads, blk.norm1.eps, a.scale, m, here, **bf16)
             if here:
                 m_new, msum, M = LF.soft_mask(score, m, self.ltp_threshold, stage, self.ltp_temperature)
                 self.ltp_kept.append((M[:, 1:] >= 0.5).float())
