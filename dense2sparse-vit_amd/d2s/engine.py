@@ -309,6 +309,12 @@ def checkpoint_config(config):
     return theirs
 
 
+def graph_rank_iters(config):
+    """The PageRank iterations of a checkpoint's (or a run's) 'config': the key is recorded only when positive, so a
+    config without it - every other run, every checkpoint written before graph ranking existed - reads as 0"""
+    return int(config.get("graph_rank_iters", 0))
+
+
 def adjust_learning_rate(optimizer, model, step, epochs, lr, min_lr, warmup_steps, frozen=()):
     """utils.adjust_learning_rate (utils.py:93-147): cosine schedule, backbone frozen for the first `warmup_steps`
     epochs (requires_grad toggled exactly like the reference), backbone lr = min(0.01 lr, cos) afterwards."""
@@ -530,6 +536,10 @@ class TrainStep:
                                  "predictors only (train.py:50-53), and attention selection has none to train - pass warmup_steps=0")
             for p in student.score_predictor.parameters():
                 p.requires_grad_(False)       # listed in self.frozen below: the epoch schedule leaves them alone, AdamW marks their chunks idle
+            # ... and one that ranks by PageRank over the attention graph needs the block's fp32 qkv
+            if int(getattr(student, "graph_rank_iters", 0)) > 0 and ops.get_gemm_mode() == ops.GEMM_BF16:
+                from .functional_graph_rank import GRAPH_RANK_BF16_ERROR
+                raise lib.D2SError(GRAPH_RANK_BF16_ERROR)
         # the logits-only families (methods.py; DESIGN.md sections 22 and 24 to 27) return logits alone and train with one objective of their
         # own; the teacher is optional (None: no teacher forward, no side stream).  Every refusal comes before anything touches the device.
         # A step is captured only where no block reads a row count on the host and the captured step is built: the Evo-ViT baseline's.
@@ -729,6 +739,7 @@ class TrainStep:
             "squeeze_dropped": bool(getattr(s, "squeeze_dropped", False)),
             # recorded only when on: a config without the key - every other run, every older checkpoint - counts as off
             **({"train_bf16": True} if getattr(s, "train_bf16", False) else {}),
+            **({"graph_rank_iters": int(s.graph_rank_iters)} if int(getattr(s, "graph_rank_iters", 0)) > 0 else {}),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -768,6 +779,9 @@ class TrainStep:
                 raise lib.D2SError(f"checkpoint config mismatch: {k}: the checkpoint has {theirs.get(k)!r}, this run has {ours[k]!r}")
         if bool(theirs.get("train_bf16", False)) and not ours.get("train_bf16", False):      # the key exists only where it is on
             raise lib.D2SError("checkpoint config mismatch: train_bf16: the checkpoint has True, this run has False")
+        if graph_rank_iters(theirs) != graph_rank_iters(ours):                               # likewise; a config without the key ranks by the CLS row
+            raise lib.D2SError(f"checkpoint config mismatch: graph_rank_iters: the checkpoint has {graph_rank_iters(theirs)}, this run has "
+                               f"{graph_rank_iters(ours)}")
         own = self.student.state_dict()
         _check_names_shapes("model", {k: tuple(v.shape) for k, v in own.items()}, {k: tuple(v.shape) for k, v in sd["model"].items()})
         self.opt.check_state_dict(sd["optimizer"])

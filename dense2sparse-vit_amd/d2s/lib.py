@@ -4,8 +4,8 @@ include/d2s_hip_ragged_train.h, training through a ragged packed batch, include/
 ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_evo.h, the slow-fast token update, include/d2s_hip_gemm_plan.h, the
 plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, include/d2s_hip_ltp.h, learned token thresholds,
 include/d2s_hip_tome_train_bf16.h, the backward pair of bf16 training through token merging, include/d2s_hip_ragged_stage_bf16.h, the two
-backward row moves of bf16 training through ATS stages and A-ViT block boundaries, and include/d2s_hip_ltp_bf16.h, the LTP score on the
-bf16 data path).
+backward row moves of bf16 training through ATS stages and A-ViT block boundaries, include/d2s_hip_ltp_bf16.h, the LTP score on the
+bf16 data path, and include/d2s_hip_graph_rank.h, the PageRank iteration over a block's attention graph).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -236,6 +236,11 @@ _SIGS_LTP_BF16 = {
     "d2s_ltp_score_bf16": (I, [P, P, P, P, P, P, P, Z, I, I, I, I, F]),
 }
 
+# the entry of include/d2s_hip_graph_rank.h (token selection by PageRank over the block's attention), same form
+_SIGS_GRAPH_RANK = {
+    "d2s_graph_rank_f32": (I, [P, P, P, P, P, I, I, I, F, I]),
+}
+
 _lib = None
 
 
@@ -256,7 +261,8 @@ def load():
                               + list(_SIGS_RAGGED_TRAIN.items()) + list(_SIGS_RAGGED_THRESHOLD.items()) + list(_SIGS_AVIT.items())
                               + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())
                               + list(_SIGS_LTP.items()) + list(_SIGS_TOME_TRAIN_BF16.items())
-                              + list(_SIGS_RAGGED_STAGE_BF16.items()) + list(_SIGS_LTP_BF16.items())):
+                              + list(_SIGS_RAGGED_STAGE_BF16.items()) + list(_SIGS_LTP_BF16.items())
+                              + list(_SIGS_GRAPH_RANK.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -318,6 +324,10 @@ def ragged_stage_bf16_symbols():
 
 def ltp_bf16_symbols():
     return sorted(_SIGS_LTP_BF16)
+
+
+def graph_rank_symbols():
+    return sorted(_SIGS_GRAPH_RANK)
 
 
 def ptr(t):

@@ -1586,6 +1586,23 @@ def ltp_soft_mask_bwd(g_out, M, m_in, tau, dtheta, greg=None, gm_in=None, want_g
     return gM, gm_in
 
 
+# ---- graph ranking: PageRank over a block's attention (csrc/graph_rank.hip) ----
+def graph_rank(qkv, lse, B, n, H, scale, iters, w0=None):
+    """`iters` steps of s <- s P per image and head, P = exp(scale q k^T - lse) recomputed from the block's fp32 qkv [B * n, 3 * H * 64]
+    and the lse [B, H, n] its attention forward wrote; the start is w0 [B, H, n] or 1 / n.  -> rank [B, H, n] fp32, the layout of a CLS
+    row; every (image, head) keeps the mass of its start (1 without w0).  The ping-pong buffer of iters >= 2 is allocated here."""
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous()
+    _f32(lse)
+    B, n, H, iters = int(B), int(n), int(H), int(iters)
+    assert qkv.numel() == B * n * 3 * H * 64 and lse.numel() == B * n * H, (tuple(qkv.shape), tuple(lse.shape), B, n, H)
+    if w0 is not None:
+        assert _f32(w0).numel() == B * H * n
+    rank = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device)
+    ws = torch.empty((B, H, n), dtype=torch.float32, device=qkv.device) if iters >= 2 else None
+    lib.call("d2s_graph_rank_f32", lib.ptr(qkv), lib.ptr(lse), lib.ptr(w0), lib.ptr(rank), lib.ptr(ws), B, n, H, float(scale), iters)
+    return rank
+
+
 # ---- the Evo-ViT baseline: slow-fast token update (csrc/evo.hip; DESIGN.md section 26) ----
 def _evo_shapes(X, kept, dropped):
     B, n, D = X.shape

@@ -312,6 +312,16 @@ def check_supported(args):
             bad.append("--attn-selection with --diff-topk (the perturbed top-k trains the score predictor, which attention selection never calls)")
         if 0 in list(args.pruning_locs or []):
             bad.append("--attn-selection with a pruning location of 0 (a stage is scored by the CLS attention of the block before it)")
+    graph_rank = getattr(args, "graph_rank", 0)          # no attribute unless given
+    if hasattr(args, "graph_rank"):
+        if graph_rank < 1:
+            bad.append(f"--graph-rank {graph_rank} (at least 1 PageRank iteration)")
+        if method != "d2s":
+            bad.append(f"--graph-rank with --method {method} (graph ranking is a rule of the dense-to-sparse student's attention selection)")
+        elif not getattr(args, "attn_selection", False):
+            bad.append("--graph-rank without --attn-selection (it replaces the CLS attention row that attention selection ranks)")
+        if getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--graph-rank with --gemm-mode bf16 (the rank is recomputed from the block's fp32 qkv; exact and split run)")
     if getattr(args, "accum_steps", 1) < 1:
         bad.append(f"--accum-steps {args.accum_steps} (at least 1)")
     if getattr(args, "clip_grad", None) is not None and not args.clip_grad > 0:
@@ -370,6 +380,10 @@ def check_supported(args):
               "predictor warm-up has no meaning (mask_predictor.py:300): --warmup-steps is set to 0"
               + (" (--mean-heads: mean over heads instead of max)" if args.mean_heads else ""))
         args.warmup_steps = 0
+        if graph_rank > 0:
+            print(f"Attention: --graph-rank {graph_rank} ranks every stage's tokens by {graph_rank} PageRank iteration"
+                  f"{'s' if graph_rank > 1 else ''} over the attention graph of the block before it instead of by that block's CLS row "
+                  "(the importance stage of Zero-TPrune; DESIGN.md section 29)")
     elif args.mean_heads:
         print("Attention: --mean-heads has no effect without --attn-selection (it chooses how attention selection aggregates the heads, "
               "losses.py:126)")
@@ -413,7 +427,8 @@ def build_models(args):
                                                    attn_selection=getattr(args, "attn_selection", False),
                                                    checkpoint_path=args.student_checkpoint,
                                                    **({"ragged_train": True} if getattr(args, "ragged_train", False) else {}),
-                                                   **({"ragged_bf16": True} if getattr(args, "ragged_bf16", False) else {}))
+                                                   **({"ragged_bf16": True} if getattr(args, "ragged_bf16", False) else {}),
+                                                   **({"graph_rank_iters": int(args.graph_rank)} if getattr(args, "graph_rank", 0) else {}))
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
 

@@ -233,6 +233,10 @@ def parse_args(argv=None):
                    help='with --method ltp: run both phases and the evaluation in the bf16 arithmetic mode (bf16 matrix cores for the GEMMs, '
                         'the ragged and the policy attention, their backwards and the score; the bf16 data path) - the flag sets that mode '
                         'itself, --gemm-mode stays at exact (its default)')
+    p.add_argument('--graph-rank', type=int, default=argparse.SUPPRESS, metavar='T',
+                   help='with --topk-selection --attn-selection: rank the tokens of every stage by T iterations of PageRank over the whole '
+                        'attention graph of the block before it (s <- s P from s = 1/n per head; the importance stage of Zero-TPrune) instead '
+                        'of by that block\'s CLS row; T = 1 is the mean attention a token receives; --gemm-mode exact or split')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

@@ -97,6 +97,9 @@ ATTN_SELECTION_DIFF_TOPK_ERROR = ("attn_selection cannot be combined with diff_t
                                   "attention selection never calls")
 ATTN_SELECTION_BLOCK0_ERROR = ("attn_selection cannot prune at block 0: a stage is scored by the CLS attention of the block before it, and "
                                "there is no attention before block 0")
+GRAPH_RANK_NEGATIVE_ERROR = "graph_rank_iters counts PageRank iterations over the block's attention graph: it cannot be negative"
+GRAPH_RANK_ATTN_SELECTION_ERROR = ("graph_rank_iters > 0 needs attn_selection=True: graph ranking replaces the CLS attention row that "
+                                   "attention selection ranks, and the score predictor has no use for it")
 
 
 class DropPath(nn.Module):
@@ -273,6 +276,15 @@ class Block(nn.Module):
             extra = (extra[0] if extra else None,) + rows
         y, cls_row = DF.run(DF.BlockFn, x, *self._params(), a.num_heads, self.norm1.eps, bool(return_cls_attn), a.scale, *extra)
         return (y, cls_row) if return_cls_attn else y
+
+    def forward_ranked(self, x, iters, drop_path_rows=None):
+        """The block before a graph-ranked stage: forward(x, return_cls_attn=True) through the per-op launch
+        sequence, which also ranks the block's n tokens by `iters` PageRank steps over its attention graph.
+        -> (y, cls_row, rank [B, H, n] without a gradient)"""
+        from d2s import functional_graph_rank as GF
+        a = self.attn
+        return GF.rank_block(x, self._params(), a.num_heads, self.norm1.eps, a.scale, iters, want_cls=True,
+                             drop_path_rows=block_drop_path_rows(self, x, drop_path_rows))
 
     def forward_ragged(self, xp, cu_seqlens, B, max_n, return_cls_attn=False):
         """The block on a ragged packed batch [total, D] (inference with a dynamic keep ratio, :935-949).  Forward only."""
@@ -465,6 +477,11 @@ class VisionTransformerDiffPruning(_ViTBase):
     and checkpoints are unchanged) and never called; `pred_logits` then holds each stage's attention PROBABILITIES [B, T], detached (not
     logits: there is no predictor output), and no gradient reaches the attention row through the selection or the fused package token.
 
+    graph_rank_iters=T > 0 (with attn_selection; the importance stage of Zero-TPrune, the build's own definition):
+    the stage ranks by T steps of PageRank over the whole attention graph of block i - 1, s <- s P from s = 1 / n per head, instead of by
+    that block's CLS row; the rank has the CLS row's layout and goes through the same reduction, renormalisation and top-k.
+    `graph_ranks` holds each stage's rank [B, H, n] after a forward, detached.  T = 1 is the mean attention a token receives.
+
     squeeze_dropped=True (pruning and squeezing, the build's own definition): a stage keeps the k tokens its selector
     chose and folds every token it drops into the kept token with the highest cosine, so the sequence lengths are those of plain pruning;
     `squeeze_plans` holds each stage's (dst, sim) after a forward."""
@@ -475,8 +492,12 @@ class VisionTransformerDiffPruning(_ViTBase):
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
                  predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, squeeze_dropped=False,
-                 ragged_train=False, ragged_bf16=False, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
+                 ragged_train=False, ragged_bf16=False, graph_rank_iters=0, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
         super().__init__()
+        if int(graph_rank_iters) < 0:
+            raise ValueError(GRAPH_RANK_NEGATIVE_ERROR)
+        if int(graph_rank_iters) > 0 and not attn_selection:
+            raise ValueError(GRAPH_RANK_ATTN_SELECTION_ERROR)
         if ragged_bf16 and not ragged_train:
             raise ValueError(RAGGED_BF16_ERROR)
         if ragged_train and patch_score_threshold is None:
@@ -531,6 +552,10 @@ class VisionTransformerDiffPruning(_ViTBase):
             self.current_sigma = 0.05
         self.mean_heads, self.random_drop, self.current_score, self.early_exit = mean_heads, random_drop, None, early_exit
         self.cls_attns = []
+        # graph ranking: PageRank iterations over the attention graph of the block before each stage (0: the CLS row ranks, as ever);
+        # graph_ranks[s] = stage s's rank [B, H, n] after a forward, detached
+        self.graph_rank_iters = int(graph_rank_iters)
+        self.graph_ranks = []
         self.kept_token_indices = None
         self.dropped_token_indices = None
         self.pred_logits = []
@@ -608,6 +633,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.num_kept_tokens, self.cls_attns, self.pred_logits = [], [], []
         self.kept_token_indices, self.dropped_token_indices = [], []
         self.squeeze_plans = []
+        self.graph_ranks = []
         p_count = 0
         for i, blk in enumerate(self.blocks):
             if self.grad_ready_hook is not None and x.requires_grad:
@@ -617,7 +643,11 @@ class VisionTransformerDiffPruning(_ViTBase):
                 carried = p_count if self.fuse_dropped else 0                 # trailing package rows of earlier stages: never scored
                 n_scored = x.shape[1] - 1 - carried
                 if self.attn_selection:      # the CLS row block i - 1 just returned: reduce over heads, renormalise, rank - one launch
-                    pred_logits, kept, dropped = DF.ops.select_cls_attn(prev_cls_row.detach().contiguous(), 1, n_scored, num_keep_node,
+                    row = prev_cls_row
+                    if self.graph_rank_iters > 0:      # ... or its tokens' PageRank over that block's attention graph, in the row's layout
+                        row = prev_rank
+                        self.graph_ranks.append(prev_rank)
+                    pred_logits, kept, dropped = DF.ops.select_cls_attn(row.detach().contiguous(), 1, n_scored, num_keep_node,
                                                                         self.mean_heads)
                 else:
                     scored = x[:, :x.shape[1] - carried].contiguous() if carried else x
@@ -647,7 +677,11 @@ class VisionTransformerDiffPruning(_ViTBase):
                 else:
                     x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
-            x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
+            if self.graph_rank_iters > 0 and (i + 1) in self.pruning_loc:      # the block before a ranked stage also ranks its tokens
+                x, cls_attn, prev_rank = blk.forward_ranked(x, self.graph_rank_iters, drop_path_rows=self._drop_path.rows(dp, i))
+                prev_rank = prev_rank.detach()
+            else:
+                x, cls_attn = blk(x, return_cls_attn=True, drop_path_rows=self._drop_path.rows(dp, i))   # :924 / :985
             prev_cls_row = cls_attn
             self.cls_attns.append(cls_attn[:, :, 1:])
         logits, features = self._head(x, tail=p_count if self.fuse_dropped else 0)   # :993-1006
