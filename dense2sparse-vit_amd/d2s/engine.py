@@ -315,6 +315,12 @@ def graph_rank_iters(config):
     return int(config.get("graph_rank_iters", 0))
 
 
+def sim_prune(config):
+    """The similarity-pruning count of a checkpoint's (or a run's) 'config': the key is recorded only when positive (DESIGN.md section
+    30), so a config without it - every other run, every checkpoint written before the similarity stage existed - reads as 0"""
+    return int(config.get("sim_prune", 0))
+
+
 def adjust_learning_rate(optimizer, model, step, epochs, lr, min_lr, warmup_steps, frozen=()):
     """utils.adjust_learning_rate (utils.py:93-147): cosine schedule, backbone frozen for the first `warmup_steps`
     epochs (requires_grad toggled exactly like the reference), backbone lr = min(0.01 lr, cos) afterwards."""
@@ -540,6 +546,10 @@ class TrainStep:
             if int(getattr(student, "graph_rank_iters", 0)) > 0 and ops.get_gemm_mode() == ops.GEMM_BF16:
                 from .functional_graph_rank import GRAPH_RANK_BF16_ERROR
                 raise lib.D2SError(GRAPH_RANK_BF16_ERROR)
+            # ... and so does one that prunes similar candidates: the key metric is computed from it
+            if int(getattr(student, "sim_prune", 0)) > 0 and ops.get_gemm_mode() == ops.GEMM_BF16:
+                from .functional_sim_prune import SIM_PRUNE_BF16_ERROR
+                raise lib.D2SError(SIM_PRUNE_BF16_ERROR)
         # the logits-only families (methods.py; DESIGN.md sections 22 and 24 to 27) return logits alone and train with one objective of their
         # own; the teacher is optional (None: no teacher forward, no side stream).  Every refusal comes before anything touches the device.
         # A step is captured only where no block reads a row count on the host and the captured step is built: the Evo-ViT baseline's.
@@ -740,6 +750,7 @@ class TrainStep:
             # recorded only when on: a config without the key - every other run, every older checkpoint - counts as off
             **({"train_bf16": True} if getattr(s, "train_bf16", False) else {}),
             **({"graph_rank_iters": int(s.graph_rank_iters)} if int(getattr(s, "graph_rank_iters", 0)) > 0 else {}),
+            **({"sim_prune": int(s.sim_prune)} if int(getattr(s, "sim_prune", 0)) > 0 else {}),
         }
 
     def state_dict(self, best_acc=0.0, epoch=None):
@@ -782,6 +793,8 @@ class TrainStep:
         if graph_rank_iters(theirs) != graph_rank_iters(ours):                               # likewise; a config without the key ranks by the CLS row
             raise lib.D2SError(f"checkpoint config mismatch: graph_rank_iters: the checkpoint has {graph_rank_iters(theirs)}, this run has "
                                f"{graph_rank_iters(ours)}")
+        if sim_prune(theirs) != sim_prune(ours):                                             # likewise; a config without the key prunes by importance alone
+            raise lib.D2SError(f"checkpoint config mismatch: sim_prune: the checkpoint has {sim_prune(theirs)}, this run has {sim_prune(ours)}")
         own = self.student.state_dict()
         _check_names_shapes("model", {k: tuple(v.shape) for k, v in own.items()}, {k: tuple(v.shape) for k, v in sd["model"].items()})
         self.opt.check_state_dict(sd["optimizer"])

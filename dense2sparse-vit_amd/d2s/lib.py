@@ -5,7 +5,8 @@ ratio on it, include/d2s_hip_avit.h, per-token adaptive depth, include/d2s_hip_e
 plan query of the exact fp32 GEMM, include/d2s_hip_ragged_bf16.h, the ragged attention pair of bf16 training, include/d2s_hip_ltp.h, learned token thresholds,
 include/d2s_hip_tome_train_bf16.h, the backward pair of bf16 training through token merging, include/d2s_hip_ragged_stage_bf16.h, the two
 backward row moves of bf16 training through ATS stages and A-ViT block boundaries, include/d2s_hip_ltp_bf16.h, the LTP score on the
-bf16 data path, and include/d2s_hip_graph_rank.h, the PageRank iteration over a block's attention graph).
+bf16 data path, include/d2s_hip_graph_rank.h, the PageRank iteration over a block's attention graph, and include/d2s_hip_sim_prune.h, the
+similarity stage of an attention-selecting student).
 
 There is no fallback: if the shared object is missing or a symbol cannot be resolved this raises, and every op
 raises on a non-zero return code.  Tensors are passed as raw device pointers; the caller keeps them alive and all
@@ -241,6 +242,12 @@ _SIGS_GRAPH_RANK = {
     "d2s_graph_rank_f32": (I, [P, P, P, P, P, I, I, I, F, I]),
 }
 
+# the entries of include/d2s_hip_sim_prune.h (the similarity stage after attention ranking), same form
+_SIGS_SIM_PRUNE = {
+    "d2s_key_metric_f32": (I, [P, I, I, I, P]),
+    "d2s_sim_prune_f32": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -262,7 +269,7 @@ def load():
                               + list(_SIGS_EVO.items()) + list(_SIGS_GEMM_PLAN.items()) + list(_SIGS_RAGGED_BF16.items())
                               + list(_SIGS_LTP.items()) + list(_SIGS_TOME_TRAIN_BF16.items())
                               + list(_SIGS_RAGGED_STAGE_BF16.items()) + list(_SIGS_LTP_BF16.items())
-                              + list(_SIGS_GRAPH_RANK.items())):
+                              + list(_SIGS_GRAPH_RANK.items()) + list(_SIGS_SIM_PRUNE.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = [] if args is None else list(args) + ([P] if res is I else [])
@@ -328,6 +335,10 @@ def ltp_bf16_symbols():
 
 def graph_rank_symbols():
     return sorted(_SIGS_GRAPH_RANK)
+
+
+def sim_prune_symbols():
+    return sorted(_SIGS_SIM_PRUNE)
 
 
 def ptr(t):

@@ -1603,6 +1603,45 @@ def graph_rank(qkv, lse, B, n, H, scale, iters, w0=None):
     return rank
 
 
+# ---- the similarity stage after attention ranking (csrc/sim_prune.hip) ----
+def key_metric(qkv, B, n, H):
+    """The key metric of a block's tokens from its fp32 qkv [B * n, 3 * H * 64], read in place (the K third only): -> metric [B, n, 64],
+    row t = the mean of token t's keys over the heads divided by its L2 norm (tome_match's metric; a zero row gives NaN)"""
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous()
+    B, n, H = int(B), int(n), int(H)
+    assert qkv.numel() == B * n * 3 * H * 64, (tuple(qkv.shape), B, n, H)
+    metric = torch.empty((B, n, 64), dtype=torch.float32, device=qkv.device)
+    lib.call("d2s_key_metric_f32", lib.ptr(qkv), B, n, H, lib.ptr(metric))
+    return metric
+
+
+def sim_prune_clip_r(R, k, T):
+    """A stage's own similarity-pruning count: at most k (so that r <= half of the k + r candidates) and at most the T - k tokens that
+    the importance ranking would drop anyway"""
+    return max(0, min(int(R), int(k), int(T) - int(k)))
+
+
+def sim_prune(metric, probs, cand, lead, r):
+    """metric [B, n, 64] (key_metric), probs [B, T] and cand [B, c] as select_cls_attn returned them for c candidates, r the effective
+    count (sim_prune_clip_r, 0 <= r <= c // 2): the c // 2 least important candidates are matched against the others by the cosine of
+    their metrics and the r with the closest partner are pruned.
+    -> (kept [B, c - r], dropped [B, T - c + r], pruned [B, r], partner [B, r], sim [B, r]); ids int64 ascending, the plan in pruned order"""
+    _f32(metric), _f32(probs)
+    assert cand.dtype == torch.int64 and cand.is_contiguous()
+    B, n, _ = metric.shape
+    T, c, r = int(probs.shape[1]), int(cand.shape[1]), int(r)
+    assert metric.shape[2] == 64 and tuple(probs.shape) == (B, T) and tuple(cand.shape) == (B, c), (tuple(metric.shape), tuple(probs.shape),
+                                                                                                   tuple(cand.shape))
+    i64 = dict(dtype=torch.int64, device=metric.device)
+    k = max(c - r, 0)
+    kept, dropped = torch.empty((B, k), **i64), torch.empty((B, max(T - k, 0)), **i64)
+    pruned, partner = torch.empty((B, max(r, 0)), **i64), torch.empty((B, max(r, 0)), **i64)
+    sim = torch.empty((B, max(r, 0)), dtype=torch.float32, device=metric.device)
+    lib.call("d2s_sim_prune_f32", lib.ptr(metric), lib.ptr(probs), lib.ptr(cand), B, n, int(lead), T, c, r, lib.ptr(kept),
+             lib.ptr(dropped) if T - k > 0 else None, *((lib.ptr(pruned), lib.ptr(partner), lib.ptr(sim)) if r > 0 else (None, None, None)))
+    return kept, dropped, pruned, partner, sim
+
+
 # ---- the Evo-ViT baseline: slow-fast token update (csrc/evo.hip; DESIGN.md section 26) ----
 def _evo_shapes(X, kept, dropped):
     B, n, D = X.shape

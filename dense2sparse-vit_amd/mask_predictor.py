@@ -322,6 +322,16 @@ def check_supported(args):
             bad.append("--graph-rank without --attn-selection (it replaces the CLS attention row that attention selection ranks)")
         if getattr(args, "gemm_mode", "exact") == "bf16":
             bad.append("--graph-rank with --gemm-mode bf16 (the rank is recomputed from the block's fp32 qkv; exact and split run)")
+    sim_prune = getattr(args, "sim_prune", 0)            # no attribute unless given
+    if hasattr(args, "sim_prune"):
+        if sim_prune < 1:
+            bad.append(f"--sim-prune {sim_prune} (at least 1 candidate pruned by similarity)")
+        if method != "d2s":
+            bad.append(f"--sim-prune with --method {method} (the similarity stage is a rule of the dense-to-sparse student's attention selection)")
+        elif not getattr(args, "attn_selection", False):
+            bad.append("--sim-prune without --attn-selection (it prunes among the candidates that attention selection ranks by importance)")
+        if getattr(args, "gemm_mode", "exact") == "bf16":
+            bad.append("--sim-prune with --gemm-mode bf16 (the key metric is computed from the block's fp32 qkv; exact and split run)")
     if getattr(args, "accum_steps", 1) < 1:
         bad.append(f"--accum-steps {args.accum_steps} (at least 1)")
     if getattr(args, "clip_grad", None) is not None and not args.clip_grad > 0:
@@ -384,6 +394,10 @@ def check_supported(args):
             print(f"Attention: --graph-rank {graph_rank} ranks every stage's tokens by {graph_rank} PageRank iteration"
                   f"{'s' if graph_rank > 1 else ''} over the attention graph of the block before it instead of by that block's CLS row "
                   "(the importance stage of Zero-TPrune; DESIGN.md section 29)")
+        if sim_prune > 0:
+            print(f"Attention: --sim-prune {sim_prune} lets every stage rank {sim_prune} candidate{'s' if sim_prune > 1 else ''} more than it "
+                  f"keeps and prunes, from the less important half, the {sim_prune} whose keys resemble a more important candidate most "
+                  "(the similarity stage of Zero-TPrune; a stage clips the count to its k and to T - k; DESIGN.md section 30)")
     elif args.mean_heads:
         print("Attention: --mean-heads has no effect without --attn-selection (it chooses how attention selection aggregates the heads, "
               "losses.py:126)")
@@ -428,7 +442,8 @@ def build_models(args):
                                                    checkpoint_path=args.student_checkpoint,
                                                    **({"ragged_train": True} if getattr(args, "ragged_train", False) else {}),
                                                    **({"ragged_bf16": True} if getattr(args, "ragged_bf16", False) else {}),
-                                                   **({"graph_rank_iters": int(args.graph_rank)} if getattr(args, "graph_rank", 0) else {}))
+                                                   **({"graph_rank_iters": int(args.graph_rank)} if getattr(args, "graph_rank", 0) else {}),
+                                                   **({"sim_prune": int(args.sim_prune)} if getattr(args, "sim_prune", 0) else {}))
     teacher = getattr(vit_models, _TEACHERS[arch])(checkpoint_path=args.teacher_checkpoint)
     return student.to(args.device), teacher.to(args.device)
 

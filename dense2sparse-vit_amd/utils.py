@@ -237,6 +237,11 @@ def parse_args(argv=None):
                    help='with --topk-selection --attn-selection: rank the tokens of every stage by T iterations of PageRank over the whole '
                         'attention graph of the block before it (s <- s P from s = 1/n per head; the importance stage of Zero-TPrune) instead '
                         'of by that block\'s CLS row; T = 1 is the mean attention a token receives; --gemm-mode exact or split')
+    p.add_argument('--sim-prune', type=int, default=argparse.SUPPRESS, metavar='R',
+                   help='with --topk-selection --attn-selection: every stage ranks R candidates more than it keeps, matches the less '
+                        'important half of them against the more important half by the cosine of the previous block\'s keys and prunes the '
+                        'R with the closest partner (the similarity stage of Zero-TPrune), so the kept tokens are not near-duplicates; '
+                        'combines with --graph-rank; --gemm-mode exact or split')
     p.add_argument('--tome-r', type=int, default=0, metavar='R',
                    help='with --method tome: tokens merged away in every block (each block clips it to half of its non-CLS tokens)')
     p.add_argument('--diff-topk', action='store_true', default=False,

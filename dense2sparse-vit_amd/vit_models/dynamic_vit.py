@@ -100,6 +100,9 @@ ATTN_SELECTION_BLOCK0_ERROR = ("attn_selection cannot prune at block 0: a stage 
 GRAPH_RANK_NEGATIVE_ERROR = "graph_rank_iters counts PageRank iterations over the block's attention graph: it cannot be negative"
 GRAPH_RANK_ATTN_SELECTION_ERROR = ("graph_rank_iters > 0 needs attn_selection=True: graph ranking replaces the CLS attention row that "
                                    "attention selection ranks, and the score predictor has no use for it")
+SIM_PRUNE_NEGATIVE_ERROR = "sim_prune counts the candidates a stage prunes for resembling a more important one: it cannot be negative"
+SIM_PRUNE_ATTN_SELECTION_ERROR = ("sim_prune > 0 needs attn_selection=True: the similarity stage prunes among the candidates that attention "
+                                  "selection ranks by importance, and the score predictor's stages have no such ranking to refine")
 
 
 class DropPath(nn.Module):
@@ -285,6 +288,15 @@ class Block(nn.Module):
         a = self.attn
         return GF.rank_block(x, self._params(), a.num_heads, self.norm1.eps, a.scale, iters, want_cls=True,
                              drop_path_rows=block_drop_path_rows(self, x, drop_path_rows))
+
+    def forward_with_metric(self, x, iters=0, drop_path_rows=None):
+        """The block before a stage with similarity pruning: forward(x, return_cls_attn=True) through the per-op
+        launch sequence, which also emits the key metric of the block's n tokens and, with `iters` > 0, their PageRank as
+        forward_ranked does.  -> (y, cls_row, metric [B, n, 64], rank [B, H, n] or None), the side outputs without a gradient"""
+        from d2s import functional_sim_prune as SF
+        a = self.attn
+        return SF.metric_block(x, self._params(), a.num_heads, self.norm1.eps, a.scale, iters, want_cls=True,
+                               drop_path_rows=block_drop_path_rows(self, x, drop_path_rows))
 
     def forward_ragged(self, xp, cu_seqlens, B, max_n, return_cls_attn=False):
         """The block on a ragged packed batch [total, D] (inference with a dynamic keep ratio, :935-949).  Forward only."""
@@ -482,6 +494,12 @@ class VisionTransformerDiffPruning(_ViTBase):
     that block's CLS row; the rank has the CLS row's layout and goes through the same reduction, renormalisation and top-k.
     `graph_ranks` holds each stage's rank [B, H, n] after a forward, detached.  T = 1 is the mean attention a token receives.
 
+    sim_prune=R > 0 (with attn_selection; the similarity stage of Zero-TPrune, the build's own definition): the
+    stage takes k + r candidates by importance (the CLS row, or the graph rank), r = min(R, k, T - k), and prunes the r of the less
+    important half that have the highest cosine, between the key metrics of block i - 1, to a candidate of the more important half; it
+    still keeps k tokens.  `sim_plans` holds each stage's (pruned, partner, sim) [B, r] after a forward, detached, and
+    `sim_prune_counts` each stage's r.
+
     squeeze_dropped=True (pruning and squeezing, the build's own definition): a stage keeps the k tokens its selector
     chose and folds every token it drops into the kept token with the highest cosine, so the sequence lengths are those of plain pruning;
     `squeeze_plans` holds each stage's (dst, sim) after a forward."""
@@ -492,8 +510,13 @@ class VisionTransformerDiffPruning(_ViTBase):
                  pruning_loc=None, token_ratio=None, distill=False, attn_selection=False, attn_selection_threshold=0.0,
                  topk_selection=False, early_exit=False, mean_heads=False, random_drop=False, small_predictor=False,
                  predictor_loss_type=False, predictor_bn=False, patch_score_threshold=None, fuse_dropped=False, squeeze_dropped=False,
-                 ragged_train=False, ragged_bf16=False, graph_rank_iters=0, init_n=14 * 14, diff_topk=False, topk_num_samples=500):
+                 ragged_train=False, ragged_bf16=False, graph_rank_iters=0, sim_prune=0, init_n=14 * 14, diff_topk=False,
+                 topk_num_samples=500):
         super().__init__()
+        if int(sim_prune) < 0:
+            raise ValueError(SIM_PRUNE_NEGATIVE_ERROR)
+        if int(sim_prune) > 0 and not attn_selection:
+            raise ValueError(SIM_PRUNE_ATTN_SELECTION_ERROR)
         if int(graph_rank_iters) < 0:
             raise ValueError(GRAPH_RANK_NEGATIVE_ERROR)
         if int(graph_rank_iters) > 0 and not attn_selection:
@@ -556,6 +579,10 @@ class VisionTransformerDiffPruning(_ViTBase):
         # graph_ranks[s] = stage s's rank [B, H, n] after a forward, detached
         self.graph_rank_iters = int(graph_rank_iters)
         self.graph_ranks = []
+        # similarity pruning: candidates a stage prunes for resembling a more important one (0: the importance ranking alone decides, as
+        # ever); after a forward sim_plans[s] = stage s's (pruned, partner, sim) [B, r], detached, and sim_prune_counts[s] its r
+        self.sim_prune = int(sim_prune)
+        self.sim_plans, self.sim_prune_counts = [], []
         self.kept_token_indices = None
         self.dropped_token_indices = None
         self.pred_logits = []
@@ -634,6 +661,7 @@ class VisionTransformerDiffPruning(_ViTBase):
         self.kept_token_indices, self.dropped_token_indices = [], []
         self.squeeze_plans = []
         self.graph_ranks = []
+        self.sim_plans, self.sim_prune_counts = [], []
         p_count = 0
         for i, blk in enumerate(self.blocks):
             if self.grad_ready_hook is not None and x.requires_grad:
@@ -647,8 +675,18 @@ class VisionTransformerDiffPruning(_ViTBase):
                     if self.graph_rank_iters > 0:      # ... or its tokens' PageRank over that block's attention graph, in the row's layout
                         row = prev_rank
                         self.graph_ranks.append(prev_rank)
-                    pred_logits, kept, dropped = DF.ops.select_cls_attn(row.detach().contiguous(), 1, n_scored, num_keep_node,
+                    # similarity pruning: r candidates more, of which the stage prunes the r that resemble a more important one most
+                    sim_r = DF.ops.sim_prune_clip_r(self.sim_prune, num_keep_node, n_scored) if self.sim_prune > 0 else 0
+                    pred_logits, kept, dropped = DF.ops.select_cls_attn(row.detach().contiguous(), 1, n_scored, num_keep_node + sim_r,
                                                                         self.mean_heads)
+                    if self.sim_prune > 0:
+                        self.sim_prune_counts.append(sim_r)
+                    if sim_r > 0:
+                        kept, dropped, *plan = DF.ops.sim_prune(prev_metric, pred_logits, kept, 1, sim_r)
+                        self.sim_plans.append(tuple(t.detach() for t in plan))
+                    elif self.sim_prune > 0:
+                        self.sim_plans.append(tuple(torch.empty((x.shape[0], 0), dtype=dt, device=x.device)
+                                                    for dt in (torch.int64, torch.int64, torch.float32)))
                 else:
                     scored = x[:, :x.shape[1] - carried].contiguous() if carried else x
                     pred_logits, pred_score = _scores(self.score_predictor[p_count], scored)   # :855
@@ -677,7 +715,12 @@ class VisionTransformerDiffPruning(_ViTBase):
                 else:
                     x = DF.GatherFn.apply(x, kept)                           # :907-912 / :954-960
                 p_count += 1
-            if self.graph_rank_iters > 0 and (i + 1) in self.pruning_loc:      # the block before a ranked stage also ranks its tokens
+            if self.sim_prune > 0 and (i + 1) in self.pruning_loc:      # the block before a similarity stage also emits its key metric
+                x, cls_attn, prev_metric, prev_rank = blk.forward_with_metric(x, self.graph_rank_iters,
+                                                                              drop_path_rows=self._drop_path.rows(dp, i))
+                prev_metric = prev_metric.detach()
+                prev_rank = prev_rank.detach() if prev_rank is not None else None
+            elif self.graph_rank_iters > 0 and (i + 1) in self.pruning_loc:      # the block before a ranked stage also ranks its tokens
                 x, cls_attn, prev_rank = blk.forward_ranked(x, self.graph_rank_iters, drop_path_rows=self._drop_path.rows(dp, i))
                 prev_rank = prev_rank.detach()
             else:
