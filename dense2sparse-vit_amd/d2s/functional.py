@@ -2,11 +2,15 @@
 sequences of C-ABI calls (d2s.ops); torch only owns the tensors and the graph.  No torch arithmetic runs here.
 
 The transformer block's seven launches (LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm, fc1 + GELU, fc2 + residual) are
-written once, in block_forward_sequence, and their backward once, in block_backward_sequence.  The forward's callers: BlockFn.forward
-without a backward to serve (the frozen teacher, eval), BlockFn.forward in training, ragged_block_forward, and the token-merging block of
-functional_tome (forward only on either data path, and training), which hooks its match and merge in between the two halves; the
-backward's callers: BlockFn.backward and ToMeBlockFn.backward.  In front of both BlockFn keeps the composite path (ops.block_fwd /
-block_bwd: one C-ABI call for the same launches on the fp32 data path).  Which attention entry runs is decided in attn_forward /
+written once, in block_forward_sequence, and their backward once, in block_backward_sequence.  What a block adds around them - its
+refusals, its attention of either direction, taps behind the attention forward, a hook between the halves, stochastic-depth rows, side
+outputs - is a BlockRoute: DenseRoute here, functional_ats._Ragged (and functional_ltp._RaggedLTP) for a ragged packed batch,
+functional_tome._Merging for token merging.  The autograd glue around the sequences is written once too: route_forward / route_backward,
+behind RouteBlockFn (any route: the graph-rank, similarity-pruning and LTP soft blocks, ragged and LTP stage blocks, the token-merging
+block) and behind BlockFn's per-op branch (a DenseRoute without a tap).  The forward sequence's callers: route_forward and the forward-only
+helpers ragged_block_forward, functional_ats.ats_block_forward and functional_tome._block_forward; the backward sequence's one caller:
+route_backward.  In front of both BlockFn keeps the composite path (ops.block_fwd / block_bwd: one C-ABI call for the same launches on
+the fp32 data path).  Which attention entry runs is decided in attn_forward /
 attn_backward, for BlockFn and AttnCoreFn alike; xarg, cls_or_empty and layernorm_backward are the small shared pieces (the latter also
 serves the predictor and Tokens-to-Token Functions of the neighbouring modules).
 
@@ -248,7 +252,8 @@ def _norm_linear(x, cmap, nw, nb, w, b, eps, io, train, epi=None, aux_out=None):
 
 def block_forward_sequence(x, params, eps, io, train, attn, attn_args, s_attn=None, s_mlp=None, rows_per_group=0, mid=None, mid_cls=False):
     """THE launch sequence of a pre-norm transformer block on [rows, D] tokens: LayerNorm, qkv GEMM, attention, proj + residual, LayerNorm,
-    fc1 + GELU, fc2 + residual.  Callers: BlockFn.forward (forward only and training), ragged_block_forward, functional_tome, functional_ats.
+    fc1 + GELU, fc2 + residual.  Callers: route_forward (BlockFn's per-op branch and RouteBlockFn, forward only and training) and the
+    forward-only ragged_block_forward, functional_ats.ats_block_forward and functional_tome._block_forward.
     io: bf16 data path - every GEMM input exists in bf16 only, the residual stream stays fp32.
     train: keep the LayerNorm statistics, the GELU pre-activation and every layer input for block_backward_sequence; otherwise (the frozen
     teacher, eval) nothing is kept and each intermediate dies before the next allocation (the pre-activation alone is 155 MB per block at
@@ -367,6 +372,112 @@ def block_backward_sequence(gy, x, saved, wants, s_attn, s_mlp, rows_per_group, 
     return grads, dpolicy
 
 
+class BlockRoute:
+    """What one block puts into the launch sequence around the seven launches, and the constants of its backward (no gradient reaches
+    them).  RouteBlockFn runs any route, BlockFn a DenseRoute on its per-op branch; functional_ats._Ragged and functional_tome._Merging
+    are the routes with a hook between the halves.  A route answers, and nothing more:
+    begin(x, params) -> io: raises the refusals of the current arithmetic mode, in the route's own order; says whether the block runs on
+    the bf16 data path; clears the gradient shadows where the route's backward may make new ones.
+    attn(qkv, keep, io, want_f32): attn_forward's shape.  keep: this forward keeps something for a backward (a route may take a kernel
+    without the log-sum-exp otherwise).  Taps - launches that read qkv and the log-sum-exp - follow the attention in here: in eval both
+    exist nowhere later.
+    attn_bwd(qkv, ao, dao, lse, io, dqkv16, want_f32): attn_backward's shape; want_dpolicy is set on the route before it is called.
+    hook() -> (mid, mid_cls) and hook_bwd() -> (mid_bwd, mid_bwd_bf16): the hook between the halves and its backward, as
+    block_forward_sequence and block_backward_sequence take them.
+    drop_path, rows_per_group: the stochastic-depth rows (s_attn, s_mlp) and how many rows share one; only a forward that keeps something
+    for a backward applies them, and a route with a hook has none (the sequence asserts it).
+    side(cls_row) -> the non-differentiable outputs that follow y (a slot may be None)."""
+    drop_path, rows_per_group, want_dpolicy = (None, None), 0, False
+
+    def hook(self):
+        return None, False
+
+    def hook_bwd(self):
+        return None, False
+
+    def side(self, cls_row):
+        return ()
+
+
+class DenseRoute(BlockRoute):
+    """A dense block on [B, n, D] tokens: plain attention or (policy [B, n]) softmax_with_policy, no hook, stochastic depth.
+    taps: callables tap(route, qkv, lse, cinv) -> tensor, launched in this order right after the attention forward; their results follow
+    the CLS row in side().  refuse: called first, raises where the arithmetic mode cannot run the block (a tap built for fp32 qkv), or None.
+    always_f32: the fp32 form of the attention output is written on the bf16 data path in eval too."""
+    always_f32 = False
+
+    def __init__(self, B, n, heads, scale, want_cls=False, policy=None, taps=(), drop_path=(None, None), refuse=None):
+        # Attention.scale = qk_scale or head_dim ** -0.5 (:188)
+        self.geom = (B, n, heads, float(_DH) ** -0.5 if scale is None else float(scale))
+        self.want_cls, self.policy, self.taps, self.drop_path, self.rows_per_group, self.refuse = want_cls, policy, taps, drop_path, n, refuse
+        self.cinv, self.tapped = None, ()
+
+    def begin(self, x, params):
+        if self.refuse is not None:
+            self.refuse()
+        ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        return bf16_data_path(x, x.shape[-1], params[8].shape[0])
+
+    def attn(self, qkv, keep, io, want_f32):
+        out = attn_forward(qkv, *self.geom, self.want_cls, self.policy, io, want_f32 or self.always_f32)
+        self.tapped = tuple(tap(self, qkv, out[1], out[2]) for tap in self.taps)
+        if keep:
+            self.cinv = out[2]
+        return out
+
+    def attn_bwd(self, qkv, ao, dao, lse, io, dqkv16, want_f32):
+        return attn_backward(qkv, ao, dao, lse, *self.geom, self.policy, self.cinv, io, dqkv16, want_f32, self.want_dpolicy)
+
+    def side(self, cls_row):
+        tapped, self.tapped = self.tapped, ()
+        return (cls_row, *tapped)
+
+
+def route_forward(ctx, x, params, eps, route, io):
+    """The forward of a Function that runs `route` on x [..., D]: block_forward_sequence over all rows, and what the backward needs kept on
+    ctx when there is one to serve.  -> (y [rows', D], the route's side outputs)"""
+    train = wants_grad(ctx)
+    x = x.contiguous()
+    s_attn, s_mlp = route.drop_path if train else (None, None)
+    y, cls_row, saved, _ = block_forward_sequence(x if x.dim() == 2 else x.view(-1, x.shape[-1]), params, eps, io, train, route.attn, (train,),
+                                                  s_attn, s_mlp, route.rows_per_group, *route.hook())
+    if train:
+        ctx.save_for_backward(x, *saved)
+        ctx.route = route
+    return y, route.side(cls_row)
+
+
+def route_backward(ctx, gy, policy_slot):
+    """The backward of route_forward.  -> one gradient per input of the Function: x and the 12 parameters in slots 0..12, the policy in
+    policy_slot if the call had that many inputs and it takes one, None everywhere else"""
+    x, *saved = ctx.saved_tensors
+    r, need = ctx.route, ctx.needs_input_grad
+    r.want_dpolicy = len(need) > policy_slot and need[policy_slot]
+    grads, dpolicy = block_backward_sequence(gy, x, saved, list(need[:13]), *r.drop_path, r.rows_per_group, r.attn_bwd, *r.hook_bwd())
+    grads += [None] * (len(need) - 13)
+    if r.want_dpolicy:
+        grads[policy_slot] = dpolicy
+    return tuple(grads)
+
+
+@mode_recorded
+class RouteBlockFn(torch.autograd.Function):
+    """One transformer block run by a route: x [..., D], the 12 block parameters, eps, the BlockRoute, the policy (the route's own, a
+    tensor input only to receive its gradient; None otherwise) -> (y [total', D] of packed rows or [B, n', D], *route.side(...)).  Differentiable in x, the
+    parameters and the policy; the side outputs carry no gradient.  What a stage or a merge decided is left on the route."""
+
+    @staticmethod
+    def forward(ctx, x, *rest):
+        params, (eps, route, _policy) = rest[:12], rest[12:]
+        y, side = route_forward(ctx, x, params, eps, route, route.begin(x, params))
+        ctx.mark_non_differentiable(*(t for t in side if t is not None))
+        return (y if x.dim() == 2 else y.view(x.shape[0], -1, x.shape[-1]), *side)
+
+    @staticmethod
+    def backward(ctx, gy, *_gside):
+        return route_backward(ctx, gy, 15)
+
+
 @mode_recorded
 class BlockFn(torch.autograd.Function):
     """One pre-norm transformer block on a packed [B, n, D] token tensor; also returns the CLS row of the softmax."""
@@ -393,17 +504,14 @@ class BlockFn(torch.autograd.Function):
         if ctx.composite:
             # fp32 data path: the whole block is ONE C-ABI call (csrc/block.hip issues the same seven launches)
             y, cls_row, slab = ops.block_fwd(x, params, B, n, D, heads, hidden, eps, scale, want_cls, train, s_attn, s_mlp)
-            saved = (slab,) + params
             ctx.hidden = hidden
+            if train:
+                ctx.save_for_backward(x, slab, *params)
+                ctx.drop_path = (s_attn, s_mlp)
+                ctx.dims = (B, n, D, heads, scale)
         else:
-            y, cls_row, saved, cinv = block_forward_sequence(x.view(B * n, D), params, eps, io, train, attn_forward,
-                                                             (B, n, heads, scale, want_cls, policy), s_attn, s_mlp, n)
+            y, (cls_row,) = route_forward(ctx, x, params, eps, DenseRoute(B, n, heads, scale, want_cls, policy, drop_path=(s_attn, s_mlp)), io)
             y = y.view(B, n, D)
-            ctx.policy = (policy, cinv)
-        if train:
-            ctx.save_for_backward(x, *saved)
-            ctx.drop_path = (s_attn, s_mlp)
-            ctx.dims = (B, n, D, heads, scale)
         cls_row = cls_or_empty(cls_row, x.device)
         ctx.mark_non_differentiable(cls_row)
         return y, cls_row
@@ -426,18 +534,8 @@ class BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gcls):
-        if ctx.composite:
-            return BlockFn._backward_composite(ctx, gy)
-        x, *saved = ctx.saved_tensors
-        B, n, D, heads, scale = ctx.dims
-        policy, cinv = ctx.policy
-        want_dpolicy = policy is not None and ctx.needs_input_grad[17]
-        # parameter order: n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> input slots 1..12
-        grads, dpolicy = block_backward_sequence(
-            gy, x, saved, [_need(ctx, i) for i in range(13)], *ctx.drop_path, n,
-            lambda qkv, ao, dao, lse, io, dqkvh, want_f32: attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh,
-                                                                         want_f32, want_dpolicy))
-        return tuple(grads) + (None, None, None, None) + ((dpolicy,) + (None,) * (ctx.nextra - 1) if ctx.nextra else ())
+        # the policy: input slot 17
+        return BlockFn._backward_composite(ctx, gy) if ctx.composite else route_backward(ctx, gy, 17)
 
 
 class PredictorRows:

@@ -1,6 +1,6 @@
 """Adaptive Token Sampling (ATS, Fayyaz et al. 2022; DESIGN.md section 24 - the build's own definition, PARITY UNPINNED): a block with a
-sampling stage between its attention half and its MLP half, on a ragged packed batch - ats_block_forward for inference, RaggedBlockFn to
-train through the stages.
+sampling stage between its attention half and its MLP half, on a ragged packed batch - ats_block_forward for inference, RaggedBlockFn
+(functional.RouteBlockFn run on a _Ragged) to train through the stages.
 
 The block attends over every token it received; after the projection and the residual add only the sampled rows and CLS go on into the
 MLP half and the later blocks (rows are independent after attention, so this equals attention for the sampled queries only).  The score
@@ -8,9 +8,9 @@ is the CLS softmax row the varlen attention already emits times the norm of the 
 out of the image (d2s_ats_select), so every image keeps its own number of tokens and the batch stays ragged.
 
 The seven block launches are functional.block_forward_sequence's and their backward is functional.block_backward_sequence's; what is
-stated here is what a ragged block adds (_Ragged): the attention of either direction on the packed batch, and the hook between the
-halves with its backward - select (or replay a plan), the new offsets, ONE host read of the new row total (it sizes every later launch,
-as at a threshold stage), the re-pack of the residual stream.  Inference runs on both data paths: fp32, and the bf16 path, where qkv
+stated here is what a ragged block adds (_Ragged, a functional.BlockRoute): its refusals, the attention of either direction on the
+packed batch, and the hook between the halves with its backward - select (or replay a plan), the new offsets, ONE host read of the
+new row total (it sizes every later launch, as at a threshold stage), the re-pack of the residual stream.  Inference runs on both data paths: fp32, and the bf16 path, where qkv
 exists in bf16 only and the kernel reads that; the residual stream and the re-pack are fp32.
 
 Training (RaggedBlockFn, fp32 data path): the selection is a constant of the backward - score, keep and counts carry no gradient - so the
@@ -37,12 +37,13 @@ _BF16_MODE_REFUSAL = "a ragged block with bf16=True runs in the bf16 arithmetic 
 _STAGE_BF16_NEEDS_BF16 = "a ragged block with stage_bf16=True needs bf16=True too: stage_bf16 only lets a block with a stage onto the bf16 data path"
 
 
-class _Ragged:
-    """What a ragged packed batch puts into one block's launch sequence, and the constants of its backward (no gradient reaches them).
+class _Ragged(DF.BlockRoute):
+    """What a ragged packed batch puts into one block's launch sequence, and the constants of its backward (no gradient reaches them):
+    a functional.BlockRoute.
     cu [B+1], row_src [total] (original token index, 0 at CLS), max_n the longest image.  K: the stage's token limit, or None for a
     block without a stage; plan: (keep, counts) of an earlier forward on the same batch, replayed instead of selecting.  After a stage's
     forward: cu_new, row_src_new, plan, score / dense (None when replaying); max_n_out either way.
-    bf16: train on the bf16 data path in the bf16 arithmetic mode (a block without a stage) - attn_train and attn_bwd then honour io,
+    bf16: train on the bf16 data path in the bf16 arithmetic mode (a block without a stage) - attn and attn_bwd then honour io,
     dqkv16 and want_f32 as attn_forward / attn_backward do.
     stage_bf16: with bf16, a block with a stage runs there too - the hook's backward is then sample_bwd_bf16."""
 
@@ -53,8 +54,32 @@ class _Ragged:
         self.cu_new = self.row_src_new = self.score = self.dense = None
         self.max_n_out = self.max_n if K is None else min(self.max_n, int(K) + 1)
 
-    def attn_train(self, qkv, io, want_f32):
-        """attn_forward's shape, keeping the log-sum-exp for attn_bwd: the fp32 kernel, or (bf16, on the bf16 data path) the bf16 one"""
+    def begin(self, xp, params):
+        if self.stage_bf16 and not self.bf16:
+            raise D2SError(_STAGE_BF16_NEEDS_BF16)
+        if ops.get_gemm_mode() == ops.GEMM_BF16:
+            if not self.bf16:
+                raise D2SError(_BF16_REFUSAL)
+            if self.K is not None and not self.stage_bf16:
+                raise D2SError(_BF16_STAGE_REFUSAL)
+        elif self.bf16:
+            raise D2SError(_BF16_MODE_REFUSAL)
+        return self.data_path(xp, params)
+
+    def data_path(self, xp, params):
+        """bf16=True: the bf16 data path (every GEMM input in bf16 only, the residual stream fp32), as BlockFn runs a dense block in that mode"""
+        io = self.bf16 and DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
+        if self.bf16:
+            if not io:
+                raise D2SError("a ragged block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        return io
+
+    def attn(self, qkv, keep, io, want_f32):
+        """attn_forward's shape.  keep: the log-sum-exp is kept for attn_bwd - the fp32 kernel, or (bf16, on the bf16 data path) the bf16
+        one; a forward that keeps nothing takes the varlen kernel without it."""
+        if not keep:
+            return DF._varlen_attn_forward(qkv, self.cu, self.B, self.max_n, self.heads, self.scale, self.K is not None, io, want_f32)
         if self.bf16 and io:
             out, lse, cls_rows, out16 = ops.attn_varlen_fwd_lse_bf16io(qkv, self.cu, self.B, qkv.shape[0], self.max_n, self.heads, self.scale,
                                                                        want_cls=self.K is not None, want_f32=want_f32)
@@ -95,6 +120,16 @@ class _Ragged:
         return ops.ragged_repack_bwd(g1, self.plan[0], self.cu, self.cu_new, self.total_in, self.B, g16=g16), g16
 
 
+    def hook(self):
+        return (self.sample, True) if self.K is not None else (None, False)
+
+    def hook_bwd(self):
+        """a stage on the bf16 data path: the hook hands on both forms of the gradient"""
+        if self.K is None:
+            return None, False
+        return (self.sample_bwd_bf16, True) if self.bf16 else (self.sample_bwd, False)
+
+
 def ats_block_forward(xp, cu, B, max_n, params, heads, eps, scale, K, N, row_src, plan=None):
     """xp [total, D] packed, cu [B+1], row_src [total] (original token index, 0 at CLS); at most K of an image's tokens survive.
     plan: (keep [total] float 0/1, counts [B] int32) of an earlier forward on the same batch, replayed instead of selecting.
@@ -102,65 +137,18 @@ def ats_block_forward(xp, cu, B, max_n, params, heads, eps, scale, K, N, row_src
     dense_mask [B, N] or None when replaying).  Forward only."""
     io = DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
     r = _Ragged(cu, B, max_n, heads, scale, row_src, K, N, plan)
-    y, _, _, _ = DF.block_forward_sequence(xp, params, eps, io, False, DF._varlen_attn_forward, (cu, B, max_n, heads, scale, True),
-                                           mid=r.sample, mid_cls=True)
+    y, _, _, _ = DF.block_forward_sequence(xp, params, eps, io, False, r.attn, (False,), mid=r.sample, mid_cls=True)
     return y, r.cu_new, r.row_src_new, r.max_n_out, r.plan, r.score, r.dense
 
 
-@DF.mode_recorded
-class RaggedBlockFn(torch.autograd.Function):
-    """One transformer block on a ragged packed batch as a differentiable Function, with or without a sampling stage: xp [total, D], the 12
-    block parameters, eps, the block's _Ragged -> y [total', D] (total' = total without a stage), differentiable in xp and the parameters.
-    What the stage decided is left on the _Ragged."""
-
-    @staticmethod
-    def forward(ctx, xp, *rest):
-        params, (eps, r) = rest[:12], rest[12:]
-        stage = r.K is not None
-        if r.stage_bf16 and not r.bf16:
-            raise D2SError(_STAGE_BF16_NEEDS_BF16)
-        if ops.get_gemm_mode() == ops.GEMM_BF16:
-            if not r.bf16:
-                raise D2SError(_BF16_REFUSAL)
-            if stage and not r.stage_bf16:
-                raise D2SError(_BF16_STAGE_REFUSAL)
-        elif r.bf16:
-            raise D2SError(_BF16_MODE_REFUSAL)
-        train = DF.wants_grad(ctx)
-        xp = xp.contiguous()
-        # bf16=True: the bf16 data path (every GEMM input in bf16 only, the residual stream fp32), as BlockFn runs a dense block in that mode
-        io = r.bf16 and DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
-        if r.bf16:
-            if not io:
-                raise D2SError("a ragged block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
-            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
-        if train:
-            attn, attn_args = r.attn_train, ()
-        else:
-            attn, attn_args = DF._varlen_attn_forward, (r.cu, r.B, r.max_n, r.heads, r.scale, stage)
-        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, io, train, attn, attn_args, mid=r.sample if stage else None,
-                                                   mid_cls=stage)
-        if train:
-            ctx.save_for_backward(xp, *saved)
-            ctx.ragged = r
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xp, *saved = ctx.saved_tensors
-        r = ctx.ragged
-        # input slots: xp 0, then n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> 1..12
-        stage = r.K is not None
-        # a stage on the bf16 data path: the hook hands on both forms of the gradient
-        hook = None if not stage else r.sample_bwd_bf16 if r.bf16 else r.sample_bwd
-        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd, hook,
-                                              mid_bwd_bf16=stage and r.bf16)
-        return tuple(grads) + (None, None)
+# One transformer block on a ragged packed batch as a differentiable Function, with or without a sampling stage: xp [total, D], the 12
+# block parameters, eps, the block's _Ragged, None -> (y [total', D],) (total' = total without a stage)
+RaggedBlockFn = DF.RouteBlockFn
 
 
 def ragged_block_train(xp, params, eps, r):
     """RaggedBlockFn on the block described by r (a _Ragged) -> y; afterwards r holds cu_new / row_src_new / plan / score / dense of a stage"""
-    return DF.run(RaggedBlockFn, xp, *params, eps, r)
+    return DF.run(RaggedBlockFn, xp, *params, eps, r, None)[0]
 
 
 class ClsGatherFn(torch.autograd.Function):

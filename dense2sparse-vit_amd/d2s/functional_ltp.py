@@ -3,14 +3,14 @@ is the attention it receives in a block (ops.ltp_score, from that block's qkv an
 block owns one learnable threshold.
 
 Hard phase (eval always, training with ltp_phase == "hard"): the ragged packed batch of functional_ats.  A stage block is a ragged block
-with a hook between its halves (_RaggedLTP): its attention always keeps the log-sum-exp, in eval as well, because the score needs it; the
-hook compares the score with the threshold on the device (ops.ltp_select), reads the new offsets once on the host and re-packs the residual
-stream.  The selection is a constant of the backward, as at an ATS stage: the hook's backward is functional_ats._Ragged.sample_bwd, and
+with a hook between its halves (_RaggedLTP, run like every route by functional.RouteBlockFn): its attention always keeps the
+log-sum-exp, in eval as well, because the score needs it; the hook compares the score with the threshold on the device
+(ops.ltp_select), reads the new offsets once on the host and re-packs the residual stream.  The selection is a constant of the backward, as at an ATS stage: the hook's backward is functional_ats._Ragged.sample_bwd, and
 the thresholds receive no gradient in this phase.
 
 Soft phase (training with ltp_phase == "soft"): the batch stays dense and the soft mask acts where removal acts - on the token as a KEY
-of every later block, through policy attention (LTPSoftBlockFn: block_forward_sequence with attn_forward(..., policy), the score launched
-next to it as a non-differentiable side output; the backward asks attn_backward for dpolicy).  LTPSoftMaskFn is the mask of one stage,
+of every later block, through policy attention (_Soft: a functional.DenseRoute with attn_forward(..., policy), the score a tap launched
+next to it, a non-differentiable side output; the backward asks attn_backward for dpolicy).  LTPSoftMaskFn is the mask of one stage,
 M = sigmoid((score - theta_k) / tau), m <- m * M; the score carries no gradient, the threshold learns through M.
 
 The bf16 arithmetic mode is refused (BF16_REFUSAL) unless asked for: _RaggedLTP(..., bf16=True) and soft_block(..., bf16=True) put a stage
@@ -46,7 +46,15 @@ class _RaggedLTP(AF._Ragged):
         super().__init__(cu, B, max_n, heads, scale, row_src, K=int(T), N=int(T), plan=plan, **(dict(bf16=True, stage_bf16=True) if bf16 else {}))
         self.theta, self.T, self.rows = theta, int(T), None
 
-    def attn_train(self, qkv, io, want_f32):
+    def begin(self, xp, params):
+        if self.bf16:
+            if ops.get_gemm_mode() != ops.GEMM_BF16:
+                raise D2SError(AF._BF16_MODE_REFUSAL)
+        else:
+            refuse_bf16()
+        return self.data_path(xp, params)
+
+    def attn(self, qkv, keep, io, want_f32):
         """The LSE form in training and in eval: the score is the column mean of the probabilities this very log-sum-exp normalises"""
         total = qkv.shape[0]
         if self.bf16 and io:
@@ -74,109 +82,47 @@ class _RaggedLTP(AF._Ragged):
         return x1
 
 
-@DF.mode_recorded
-class LTPStageBlockFn(torch.autograd.Function):
-    """A stage block of the hard phase: xp [total, D], the 12 block parameters, eps, the block's _RaggedLTP -> y [total', D].
-    functional_ats.RaggedBlockFn with the attention of the LSE form whether or not a backward follows."""
-
-    @staticmethod
-    def forward(ctx, xp, *rest):
-        params, (eps, r) = rest[:12], rest[12:]
-        if r.bf16:
-            if ops.get_gemm_mode() != ops.GEMM_BF16:
-                raise D2SError(AF._BF16_MODE_REFUSAL)
-        else:
-            refuse_bf16()
-        train = DF.wants_grad(ctx)
-        xp = xp.contiguous()
-        # bf16=True: the bf16 data path, as functional_ats.RaggedBlockFn runs a block with a stage there
-        io = r.bf16 and DF.bf16_data_path(xp, xp.shape[1], params[8].shape[0])
-        if r.bf16:
-            if not io:
-                raise D2SError("a ragged block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
-            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
-        y, _, saved, _ = DF.block_forward_sequence(xp, params, eps, io, train, r.attn_train, (), mid=r.sample, mid_cls=True)
-        if train:
-            ctx.save_for_backward(xp, *saved)
-            ctx.ragged = r
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xp, *saved = ctx.saved_tensors
-        r = ctx.ragged
-        grads, _ = DF.block_backward_sequence(gy, xp, saved, list(ctx.needs_input_grad[:13]), None, None, 0, r.attn_bwd,
-                                              r.sample_bwd_bf16 if r.bf16 else r.sample_bwd, mid_bwd_bf16=r.bf16)
-        return tuple(grads) + (None, None)
-
-
 def stage_block(xp, params, eps, r):
-    """LTPStageBlockFn on the block described by r (a _RaggedLTP) -> y; afterwards r holds what the stage decided"""
-    return DF.run(LTPStageBlockFn, xp, *params, eps, r)
+    """A stage block of the hard phase, described by r (a _RaggedLTP): xp [total, D] -> y [total', D], differentiable in xp and the
+    parameters; afterwards r holds what the stage decided"""
+    return DF.run(DF.RouteBlockFn, xp, *params, eps, r, None)[0]
 
 
 # ---- soft phase ----
-@DF.mode_recorded
-class LTPSoftBlockFn(torch.autograd.Function):
-    """One dense block of the soft phase: x [B, n, D], the 12 block parameters, heads, eps, scale, policy ([B, n] fp32 or None: no stage
-    passed yet, the plain softmax), want_score[, bf16] -> (y [B, n, D], score [B, n] or an empty tensor).  Differentiable in x, the parameters
-    and the policy; the score is a side output without a gradient."""
+def _score(route, qkv, lse, cinv):
+    """DenseRoute's tap: the attention every token receives, under the block's policy"""
+    B, n = route.geom[:2]
+    return ops.ltp_score(qkv, lse, *route.geom, policy=route.policy, cinv=cinv).view(B, n)
 
-    @staticmethod
-    def forward(ctx, x, *rest):
-        params, (heads, eps, scale, policy, want_score) = rest[:12], rest[12:17]
-        bf16 = len(rest) > 17 and bool(rest[17])          # optional trailing input: the block may run in the bf16 arithmetic mode
-        if not bf16:
+
+class _Soft(DF.DenseRoute):
+    """One dense block of the soft phase: policy attention under the mask so far ([B, n] fp32, or None: no stage passed yet, the plain
+    softmax), the score a tap.  bf16: the block follows the bf16 arithmetic mode onto the bf16 data path - policy attention on the bf16
+    matrix cores (d2s_attn_policy_fwd_bf16 / _bwd_bf16) - instead of refusing it; under an fp32 mode the keyword changes nothing."""
+    always_f32 = True
+
+    def __init__(self, B, n, heads, scale, policy, want_score, bf16):
+        super().__init__(B, n, heads, float(scale), False, policy, (_score,) if want_score else ())
+        self.bf16 = bool(bf16)
+
+    def begin(self, x, params):
+        if not self.bf16:
             refuse_bf16()
-        train = DF.wants_grad(ctx)
-        B, n, D = x.shape
-        x = x.contiguous()
-        scale = float(scale)
-        side = {}
-        # bf16 and the bf16 mode on: the bf16 data path, policy attention on the bf16 matrix cores (d2s_attn_policy_fwd_bf16 / _bwd_bf16);
-        # under an fp32 mode the keyword changes nothing
-        io = bf16 and DF.bf16_data_path(x, D, params[8].shape[0])
-        if bf16 and ops.get_gemm_mode() == ops.GEMM_BF16:
+            return False
+        io = DF.bf16_data_path(x, x.shape[-1], params[8].shape[0])
+        if ops.get_gemm_mode() == ops.GEMM_BF16:
             if not io:      # the fp32 score kernel would meet a log-sum-exp of bf16-rounded operands
                 raise D2SError("an LTP soft block with bf16=True needs the bf16 data path: widths that are multiples of 32, D2S_BF16_IO not 0")
             ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
-        ctx.nbf16 = len(rest) - 17
-
-        def attn(qkv, io, want_f32):
-            out = DF.attn_forward(qkv, B, n, heads, scale, False, policy, io)
-            if want_score:
-                side["score"] = ops.ltp_score(qkv, out[1], B, n, heads, scale, policy=policy, cinv=out[2]).view(B, n)
-            return out
-
-        y, _, saved, cinv = DF.block_forward_sequence(x.view(B * n, D), params, eps, io, train, attn, ())
-        if train:
-            ctx.save_for_backward(x, *saved)
-            ctx.policy = (policy, cinv)
-            ctx.dims = (B, n, heads, scale)
-        score = side.get("score")
-        if score is None:
-            score = torch.empty(0, device=x.device)
-        ctx.mark_non_differentiable(score)
-        return y.view(B, n, D), score
-
-    @staticmethod
-    def backward(ctx, gy, _gscore):
-        x, *saved = ctx.saved_tensors
-        B, n, heads, scale = ctx.dims
-        policy, cinv = ctx.policy
-        want_dpolicy = policy is not None and ctx.needs_input_grad[16]
-        # input slots: x 0, the 12 parameters 1..12, heads eps scale 13..15, policy 16, want_score 17
-        grads, dpolicy = DF.block_backward_sequence(
-            gy, x, saved, list(ctx.needs_input_grad[:13]), None, None, 0,
-            lambda qkv, ao, dao, lse, io, dqkvh, want_f32: DF.attn_backward(qkv, ao, dao, lse, B, n, heads, scale, policy, cinv, io, dqkvh,
-                                                                            want_f32, want_dpolicy))
-        return tuple(grads) + (None, None, None, dpolicy, None) + (None,) * ctx.nbf16
+        return io
 
 
 def soft_block(x, params, heads, eps, scale, policy, want_score, bf16=False):
-    """-> (y, score [B, n] or None).  bf16: the block follows the bf16 arithmetic mode onto the bf16 data path instead of refusing it"""
-    y, score = DF.run(LTPSoftBlockFn, x, *params, heads, eps, scale, policy, bool(want_score), *((True,) if bf16 else ()))
-    return y, (score if want_score else None)
+    """x [B, n, D] -> (y [B, n, D], score [B, n] or None), differentiable in x, the parameters and the policy; the score is a side output
+    without a gradient"""
+    B, n, _ = x.shape
+    y, _, *score = DF.run(DF.RouteBlockFn, x, *params, eps, _Soft(B, n, heads, scale, policy, want_score, bf16), policy)
+    return y, (score[0] if want_score else None)
 
 
 class LTPSoftMaskFn(torch.autograd.Function):

@@ -1,15 +1,17 @@
 """Token Merging (ToMe, Bolya et al. 2023): one transformer block that merges r tokens between its attention
-branch and its MLP - tome_block_forward / tome_block_forward_bf16 for inference, ToMeBlockFn to train through the merge.
+branch and its MLP - tome_block_forward / tome_block_forward_bf16 for inference, ToMeBlockFn (functional.RouteBlockFn run on a
+_Merging) to train through the merge.
 
     LayerNorm -> qkv GEMM -> attention -> proj + residual -> match -> merge -> LayerNorm -> fc1 + GELU -> fc2 + residual
 
 The seven block launches are functional.block_forward_sequence's and their backward is functional.block_backward_sequence's; what is
-stated here is what merging adds (_Merging): the hook between the halves, its backward, and the attention of either direction.  The
+stated here is what merging adds (_Merging, a functional.BlockRoute): its refusals, the hook between the halves, its backward, and the
+attention of either direction.  The
 match reads the keys of the qkv GEMM's output in place; the merge acts on x1 (after proj + residual), so the MLP half runs on n - r
 rows.  Attention is the plain kernel while every token still stands for one patch (size is None) and the key-weighted one afterwards
 (proportional attention).  The composite block call (ops.block_fwd) cannot serve here - the merge sits in the middle of the block: with
 r = 0 and no sizes the result is bit for bit the per-op dense block's.  The bf16 arithmetic mode is refused by tome_block_forward and by
-ToMeBlockFn without its bf16 input (the key-weighted attention they call is an fp32 kernel; the GEMM modes exact and split both run);
+ToMeBlockFn without bf16 on its route (the key-weighted attention they call is an fp32 kernel; the GEMM modes exact and split both run);
 tome_block_forward_bf16 is the same block on the bf16 data path at inference: LayerNorm and the GEMMs hand bf16 to each other,
 attention and the match read the bf16 qkv (ops.attn_keyw_fwd_bf16io, ops.tome_match_bf16), the residual stream and therefore the merge
 stay fp32.  ToMeBlockFn with bf16=True (tome_block_train(..., bf16=True)) trains on that data path.
@@ -24,8 +26,7 @@ proj's two gradient GEMMs read: block_backward_sequence's mid_bwd_bf16 conventio
 import torch
 
 from . import ops
-from .functional import (attn_backward, attn_forward, bf16_data_path, block_backward_sequence, block_forward_sequence, mode_recorded, run,
-                         wants_grad)
+from .functional import BlockRoute, RouteBlockFn, attn_backward, attn_forward, bf16_data_path, block_forward_sequence, run
 from .lib import D2SError
 
 _BF16_MODE_NEEDED = ("ToMeBlockFn with bf16=True trains on the bf16 data path: it needs the bf16 arithmetic mode "
@@ -35,17 +36,30 @@ _BF16_PATH_NEEDED = ("ToMeBlockFn with bf16=True needs the bf16 data path: D2S_B
 _BF16_REFUSAL = "token merging runs in the fp32 arithmetic modes (exact, split): the key-weighted attention has no bf16 kernel"
 
 
-class _Merging:
-    """What token merging puts into one block's launch sequence, and the constants of its backward (no gradient reaches them).
+class _Merging(BlockRoute):
+    """What token merging puts into one block's launch sequence, and the constants of its backward (no gradient reaches them): a
+    functional.BlockRoute.
     size [B, n] patches per token or None (all ones), r the merge count asked for (clipped here to (n - 1) // 2), plan (unm_idx, src_idx,
-    dst_idx) to merge by instead of matching (a replay) or None.  Afterwards: size_out [B, n - r] (size itself at r = 0), plan (None at
-    r = 0), matched (the plan was made here)."""
+    dst_idx) to merge by instead of matching (a replay) or None, bf16: train on the bf16 data path (the bf16 arithmetic mode is then
+    required, and widths that keep the data path on).  Afterwards: size_out [B, n - r] (size itself at r = 0), plan (None at r = 0),
+    matched (the plan was made here)."""
 
-    def __init__(self, size, B, n, D, heads, scale, r, prop_attn, plan):
-        self.size, self.geom, self.heads, self.scale = size, (B, n, D), heads, float(scale)
+    def __init__(self, size, B, n, D, heads, scale, r, prop_attn, plan, bf16=False):
+        self.size, self.geom, self.heads, self.scale, self.bf16 = size, (B, n, D), heads, float(scale), bool(bf16)
         self.key_w = size if prop_attn else None
         self.r = ops.tome_clip_r(r, n)
         self.size_out, self.plan, self.matched = size, (plan if self.r > 0 else None), False
+
+    def begin(self, x, params):
+        if self.bf16:
+            if ops.get_gemm_mode() != ops.GEMM_BF16:
+                raise D2SError(_BF16_MODE_NEEDED)
+            if not bf16_data_path(x, x.shape[2], params[8].shape[0]):
+                raise D2SError(_BF16_PATH_NEEDED)
+            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
+        elif ops.get_gemm_mode() == ops.GEMM_BF16:
+            raise D2SError(_BF16_REFUSAL)
+        return self.bf16
 
     def attn(self, qkv, want_lse, io, want_f32):
         """attn_forward's shape: plain attention, or key-weighted once sizes exist and prop_attn is set"""
@@ -93,6 +107,17 @@ class _Merging:
         return ops.tome_merge_bwd(g1, self.size, self.size_out, *self.plan, B, n, D, self.r, dx16=g1h), g1h
 
 
+    def hook(self):
+        return self.merge, False
+
+    def hook_bwd(self):
+        return (self.merge_bwd_bf16, True) if self.bf16 else (self.merge_bwd, False)
+
+    def side(self, cls_row):
+        """(size_out or None while nothing has merged, unm_idx, src_idx, dst_idx of a plan matched here or None)"""
+        return (self.size_out if self.r > 0 else None,) + (self.plan if self.matched else (None, None, None))
+
+
 def _block_forward(x, size, params, B, n, heads, eps, scale, r, prop_attn, plan, io):
     rows, D = x.shape
     assert rows == B * n
@@ -119,59 +144,17 @@ def tome_block_forward_bf16(x, size, params, B, n, heads, eps, scale, r, prop_at
     return _block_forward(x, size, params, B, n, heads, eps, scale, r, prop_attn, plan, True)
 
 
-@mode_recorded
-class ToMeBlockFn(torch.autograd.Function):
-    """tome_block_forward as a differentiable Function: x [B, n, D], size [B, n] or None, the 12 block parameters, heads, eps, scale, r,
-    prop_attn, plan (unm_idx, src_idx, dst_idx as three inputs, or three None to match here), and optionally a trailing bf16 flag: with it
-    the block trains on the bf16 data path (the bf16 arithmetic mode is then required, and widths that keep the data path on)
-    -> (y [B, n - r, D], size_out [B, n - r] or None, unm_idx, src_idx, dst_idx or None); only y is differentiable, in x and the parameters."""
-
-    @staticmethod
-    def forward(ctx, x, size, *rest):
-        params, (heads, eps, scale, r, prop_attn, unm, src, dst), extra = rest[:12], rest[12:20], rest[20:]
-        ctx.nextra = len(extra)
-        io = bool(extra[0]) if extra else False          # optional 23rd input: train on the bf16 data path
-        if io:
-            if ops.get_gemm_mode() != ops.GEMM_BF16:
-                raise D2SError(_BF16_MODE_NEEDED)
-            if not bf16_data_path(x, x.shape[2], params[8].shape[0]):
-                raise D2SError(_BF16_PATH_NEEDED)
-            ops._SHADOW.clear()          # gradient shadows never outlive the backward pass that made them
-        elif ops.get_gemm_mode() == ops.GEMM_BF16:
-            raise D2SError(_BF16_REFUSAL)
-        train = wants_grad(ctx)
-        B, n, D = x.shape
-        x = x.contiguous()
-        m = _Merging(size, B, n, D, heads, scale, r, bool(prop_attn), None if unm is None else (unm, src, dst))
-        y, _, saved, _ = block_forward_sequence(x.view(B * n, D), params, eps, io, train, m.attn, (train,), mid=m.merge)
-        ctx.io = io
-        if train:
-            ctx.save_for_backward(x, *saved)
-            ctx.merging = m
-        outs = (m.size_out if m.r > 0 else None,) + (m.plan if m.matched else (None, None, None))
-        ctx.mark_non_differentiable(*[t for t in outs if t is not None])
-        return (y.view(B, n - m.r, D),) + outs
-
-    @staticmethod
-    def backward(ctx, gy, *_unused):
-        x, *saved = ctx.saved_tensors
-        m = ctx.merging
-        # input slots: x 0, size 1, then n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b -> 2..13
-        wants = [ctx.needs_input_grad[0]] + list(ctx.needs_input_grad[2:14])
-        if ctx.io:
-            grads, _ = block_backward_sequence(gy, x, saved, wants, None, None, 0, m.attn_bwd, m.merge_bwd_bf16, mid_bwd_bf16=True)
-        else:
-            grads, _ = block_backward_sequence(gy, x, saved, wants, None, None, 0, m.attn_bwd, m.merge_bwd)
-        return (grads[0], None) + tuple(grads[1:]) + (None,) * (8 + ctx.nextra)
+# tome_block_forward as a differentiable Function: x [B, n, D], the 12 block parameters, eps, the block's _Merging, None
+# -> (y [B, n - r, D], *_Merging.side(...)); only y is differentiable, in x and the parameters
+ToMeBlockFn = RouteBlockFn
 
 
 def tome_block_train(x, size, params, heads, eps, scale, r, prop_attn=True, plan=None, bf16=False):
     """ToMeBlockFn with tome_block_forward's shape of a result: x [B, n, D] -> (y [B, n - r, D], size_out or None, plan or None).
-    bf16: train on the bf16 data path (the Function's trailing input; existing calls keep their argument list)."""
-    if ops.tome_clip_r(r, x.shape[1]) == 0:
-        plan = None
-    y, size_out, unm, src, dst = run(ToMeBlockFn, x, size, *params, heads, eps, scale, r, prop_attn, *(plan if plan is not None else (None,) * 3),
-                                     *((True,) if bf16 else ()))
-    if ops.tome_clip_r(r, x.shape[1]) == 0:
+    bf16: train on the bf16 data path."""
+    B, n, D = x.shape
+    m = _Merging(size, B, n, D, heads, scale, r, bool(prop_attn), plan, bf16)
+    y, size_out, unm, src, dst = run(ToMeBlockFn, x, *params, eps, m, None)
+    if m.r == 0:
         return y, size, None
     return y, size_out, (plan if plan is not None else (unm, src, dst))

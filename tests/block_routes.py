@@ -1,6 +1,7 @@
 """What the transformer block's host code does, per configuration, through the public entry points only (DF.run(DF.BlockFn, ...),
-DF.ragged_block_forward, DF.AttnCoreFn.apply, and the token-merging block's TF.tome_block_forward, TF.tome_block_forward_bf16 and
-TF.tome_block_train): the C-ABI entries it issues (forward, backward), the bytes it saves for the backward and its peak of allocated
+DF.ragged_block_forward, DF.AttnCoreFn.apply, the token-merging block's TF.tome_block_forward, TF.tome_block_forward_bf16 and
+TF.tome_block_train, AF.ragged_block_train, and the blocks with a tap or a stage: GF.rank_block, SF.metric_block, LF.soft_block,
+LF.stage_block): the C-ABI entries it issues (forward, backward), the bytes it saves for the backward and its peak of allocated
 memory.  Shared by tools/gen_block_routes.py, which records tests/golden/block_routes.json, and
 tests/test_block_routes_gpu.py, which compares a fresh recording with it.
 
@@ -8,7 +9,8 @@ Geometry: the block of tests/test_ragged_bf16_gpu.py (D 128, 2 heads, hidden 512
 the ragged case packs the lengths (5, 33); the token-merging block merges r = 5 of the 33 tokens away (28 rows per image in its MLP
 half) or none, with every token one patch (size None) or the fixed patch counts of _size().  The attention configurations appended
 last run longer sequences: n = 70 (two full key tiles plus a 6-row remainder; the dense bf16 forward takes its 32-key-tile kernel there)
-and n = 161 (a second workgroup, of 33 queries), and the packed lengths (70, 161)."""
+and n = 161 (a second workgroup, of 33 queries), and the packed lengths (70, 161).  The tap and stage configurations behind them are
+back at B = 2, n = 33 and the packed lengths (5, 33); their stages leave the 5-row image whole and shorten the 33-row one."""
 import torch
 
 from tests.test_ragged_bf16_gpu import BLOCK_D, BLOCK_H, SCALE, _block_params, _cu, _t
@@ -46,7 +48,7 @@ def configurations():
         for policy in ("none", "const", "grad"):
             out.append((f"attn/{mode}/policy_{policy}", dict(kind="attn", mode=mode, policy=policy)))
     # appended: the caching allocator rounds for the ones above as it did at their recording
-    return out + _tome_configurations() + _attention_configurations()
+    return out + _tome_configurations() + _attention_configurations() + _tap_and_stage_configurations()
 
 
 def _tome_configurations():
@@ -91,6 +93,37 @@ def _attention_configurations():
     for mode in ("bf16", "bf16_noio"):          # the dense bf16 kernels on bf16 and on fp32 qkv, the forward on 32-key tiles
         out.append((f"block/{mode}/train/policy_none/nodp/n70",
                     dict(kind="block", mode=mode, train=True, policy="none", dp=False, composite=True, grads="all", n=70)))
+    return out
+
+
+def _tap_and_stage_configurations():
+    """the per-op routes with a tap behind the attention forward (graph rank, key metric, the LTP score) and the ragged blocks with a stage
+    between their halves (an LTP threshold, ATS sampling), through GF.rank_block, SF.metric_block, LF.soft_block, LF.stage_block and
+    AF.ragged_block_train"""
+    out = []
+    tg = lambda train: "train" if train else "nograd"
+    for mode in ("exact", "split"):
+        for train in (False, True):
+            for dp in (False, True):
+                out.append((f"rank/{mode}/{tg(train)}/{'dp' if dp else 'nodp'}", dict(kind="rank", mode=mode, train=train, dp=dp, iters=3)))
+    for iters in (0, 3):
+        for train in (False, True):
+            for dp in (False, True):
+                out.append((f"metric/exact/iters{iters}/{tg(train)}/{'dp' if dp else 'nodp'}",
+                            dict(kind="metric", mode="exact", train=train, dp=dp, iters=iters)))
+    for mode, bf16 in (("exact", False), ("split", False), ("exact", True), ("bf16", True)):
+        for policy in ("none", "const", "grad"):
+            for score in (True, False):
+                for train in (False, True):
+                    out.append((f"ltp_soft/{mode}{'/bf16flag' if bf16 else ''}/{tg(train)}/policy_{policy}/{'score' if score else 'noscore'}",
+                                dict(kind="ltp_soft", mode=mode, bf16=bf16, policy=policy, score=score, train=train)))
+    for kind in ("ltp_stage", "ragged_stage"):          # ragged_stage: an ATS stage of K = 8, 33 -> 9 rows and 5 stays 5
+        for mode in ("exact", "bf16"):
+            for train, replay in ((False, False), (True, False), (True, True)):
+                out.append((f"{kind}/{mode}/{tg(train)}" + ("/replay" if replay else ""),
+                            dict(kind=kind, mode=mode, bf16=mode == "bf16", train=train, replay=replay)))
+    for train in (False, True):          # the stage-less ragged block on the bf16 data path
+        out.append((f"ragged_train/bf16/{tg(train)}", dict(kind="ragged_stage", mode="bf16", bf16=True, train=train, replay=False, stage=False)))
     return out
 
 
@@ -155,6 +188,81 @@ def _make_tome_call(cfg):
     return call, leaves
 
 
+def _ltp_theta():
+    """The threshold of the ltp_stage configurations, from the float64 restatement (tests/ltp_ref.py) on the synthetic packed input: the
+    middle of the widest gap between two neighbouring patch scores of the 33-row image, so that image drops some of its patches and keeps
+    the others in every arithmetic mode.  One threshold cannot also split the 5-row image: an image's scores sum to 1, its four patches
+    score about 1 / 5 each, above every patch of the longer image - it keeps them all."""
+    if "theta" not in _HOST:
+        import torch.nn.functional as F
+        from tests import ltp_ref
+        p = [t.double() for t in _block_params()]
+        x = _synth("xr", (sum(RAGGED_LENGTHS), BLOCK_D)).cpu().double()          # the input of _make_stage_call
+        qkv = F.linear(F.layer_norm(x, (BLOCK_D,), p[0], p[1], EPS), p[2], p[3])
+        s = ltp_ref.score_varlen(qkv, RAGGED_LENGTHS, BLOCK_H, SCALE)[RAGGED_LENGTHS[0] + 1:].sort().values
+        i = int((s[1:] - s[:-1]).argmax())
+        _HOST["theta"] = float(s[i] + s[i + 1]) / 2
+    return torch.full((1,), _HOST["theta"], device=DEV)
+
+
+def _make_tap_call(cfg):
+    """rank_block, metric_block and soft_block on the dense [B, N, D] input"""
+    from d2s import functional_graph_rank as GF, functional_ltp as LF, functional_sim_prune as SF
+    x = _synth("x", (B, N, BLOCK_D)).requires_grad_(True)
+    p = [t.requires_grad_(True) for t in _params()]
+    leaves = dict(dx=x, **{f"dp{i}": t for i, t in enumerate(p)})
+    if cfg["kind"] == "ltp_soft":
+        policy = _policy(cfg["policy"])
+        if policy is not None and policy.requires_grad:
+            leaves["dpolicy"] = policy
+    else:
+        rows = (torch.tensor([1.25, 0.0], device=DEV), torch.tensor([0.0, 1.25], device=DEV)) if cfg["dp"] else None
+
+    def call():
+        with torch.enable_grad() if cfg["train"] else torch.no_grad():
+            if cfg["kind"] == "rank":
+                y, cls_row, rank = GF.rank_block(x, p, BLOCK_H, EPS, SCALE, cfg["iters"], drop_path_rows=rows)
+                outs = dict(y=y, cls=cls_row, rank=rank)
+            elif cfg["kind"] == "metric":
+                y, cls_row, metric, rank = SF.metric_block(x, p, BLOCK_H, EPS, SCALE, cfg["iters"], drop_path_rows=rows)
+                outs = dict(y=y, cls=cls_row, metric=metric, rank=rank)
+            else:
+                y, score = LF.soft_block(x, p, BLOCK_H, EPS, SCALE, policy, cfg["score"], bf16=cfg["bf16"])
+                outs = dict(y=y, score=score)
+        return outs, (y if cfg["train"] else None)
+    return call, leaves
+
+
+def _make_stage_call(cfg):
+    """stage_block and ragged_block_train on the packed lengths (5, 33); a replaying configuration replays, in its measured call, the plan
+    its warm-up call decided"""
+    from d2s import functional_ats as AF, functional_ltp as LF
+    lengths, plans = RAGGED_LENGTHS, []
+    xp, cu = _synth("xr", (sum(lengths), BLOCK_D)).requires_grad_(True), _cu(lengths).to(DEV)
+    p = [t.requires_grad_(True) for t in _params()]
+    row_src = torch.cat([torch.arange(n, dtype=torch.int32) for n in lengths]).to(DEV)
+    theta = _ltp_theta() if cfg["kind"] == "ltp_stage" else None
+    geom = (cu, len(lengths), max(lengths), BLOCK_H, SCALE)
+
+    def call():
+        plan = plans[0] if (cfg["replay"] and plans) else None
+        with torch.enable_grad() if cfg["train"] else torch.no_grad():
+            if cfg["kind"] == "ltp_stage":
+                r = LF._RaggedLTP(*geom, row_src, theta, max(lengths) - 1, plan, bf16=cfg["bf16"])
+                y = LF.stage_block(xp, p, EPS, r)
+            elif cfg.get("stage", True):
+                r = AF._Ragged(*geom, row_src, 8, max(lengths) - 1, plan, bf16=cfg["bf16"], stage_bf16=cfg["bf16"])
+                y = AF.ragged_block_train(xp, p, EPS, r)
+            else:
+                r = AF._Ragged(*geom, bf16=cfg["bf16"])
+                y = AF.ragged_block_train(xp, p, EPS, r)
+        plans.append(r.plan)
+        keep, counts = r.plan if r.plan is not None else (None, None)
+        return dict(y=y, cu_new=r.cu_new, row_src_new=r.row_src_new, keep=keep, counts=counts, score=r.score, dense=r.dense), \
+            (y if cfg["train"] else None)
+    return call, dict(dx=xp, **{f"dp{i}": t for i, t in enumerate(p)})
+
+
 def _make_call(cfg):
     """-> (call, leaves): call() runs the forward and returns (outputs, the output to run the backward from or None); leaves: the named
     tensors whose .grad the backward fills"""
@@ -162,6 +270,10 @@ def _make_call(cfg):
     leaves = {}
     if cfg["kind"] == "tome":
         return _make_tome_call(cfg)
+    if cfg["kind"] in ("rank", "metric", "ltp_soft"):
+        return _make_tap_call(cfg)
+    if cfg["kind"] in ("ltp_stage", "ragged_stage"):
+        return _make_stage_call(cfg)
     if cfg["kind"] in ("ragged", "ragged_train"):
         p = _params()
         lengths = cfg.get("lengths", RAGGED_LENGTHS)
@@ -231,7 +343,8 @@ def _run(call, leaves, gy, names, distinct=False):
         if root.grad_fn is None:
             saved[0] = 0
         else:
-            torch.autograd.backward([root], [gy])
+            # behind a stage the output has fewer rows than went in: how many is known only here
+            torch.autograd.backward([root], [gy if gy.shape[0] == root.shape[0] else gy[:root.shape[0]]])
     else:
         saved[0] = 0
     bwd = [s for s in names if s != "d2s_convert_bf16"]
@@ -248,9 +361,11 @@ def record(cfg):
             gy = _synth("gy", (B * (N - cfg["r"]), BLOCK_D)).view(B, N - cfg["r"], BLOCK_D)
         elif cfg["kind"] == "ragged_train":
             gy = _synth("gy", (sum(cfg["lengths"]), BLOCK_D))
+        elif cfg["kind"] in ("ltp_stage", "ragged_stage"):          # the rows that entered; _run takes as many as left the stage
+            gy = _synth("gy", (sum(RAGGED_LENGTHS), BLOCK_D))
         else:
             n = cfg.get("n", N)
-            gy = _synth("gy", (B * n, BLOCK_D)).view(B, n, BLOCK_D) if cfg["kind"] == "block" else _synth("gy", (B * n, BLOCK_D))
+            gy = _synth("gy", (B * n, BLOCK_D)) if cfg["kind"] == "attn" else _synth("gy", (B * n, BLOCK_D)).view(B, n, BLOCK_D)
         return call, leaves, gy
     return record_call(make, cfg["mode"], cfg.get("composite", True))
 

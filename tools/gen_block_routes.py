@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Record tests/golden/block_routes.json: for every configuration of tests/block_routes.py (BlockFn, ragged_block_forward, AttnCoreFn
-across arithmetic modes, grad modes, policies, stochastic depth; the token-merging block across merge counts, sizes and replays) the
+across arithmetic modes, grad modes, policies, stochastic depth; the token-merging block across merge counts, sizes and replays; the
+graph-rank, key-metric and LTP soft blocks; ragged blocks with an LTP or an ATS stage) the
 C-ABI entries issued by the forward and by the backward, the bytes saved for the backward and the peak of allocated memory.  Needs the
 GPU.  It goes through the public entry points only, so the same file runs on any commit: record on the commit whose host-side behaviour
 is to be kept, change the code, let tests/test_block_routes_gpu.py compare.
