@@ -14,6 +14,7 @@
 // once, so results are bit-identical run to run.  A bf16 qkv is widened to fp32 at the load (exact) and every lane sums the same eight
 // columns in the same order for either element type: d2s_ats_select on a bf16 qkv is d2s_ats_select on its fp32 copy bit for bit.
 #include "d2s_common.h"
+#include "d2s_hip_ats.h"
 
 namespace {
 

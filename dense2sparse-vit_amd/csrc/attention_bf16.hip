@@ -45,6 +45,9 @@
 //     plain rule dV = P^T dO, dS = P (dP - delta), dQ = scale dS K, dK = scale dS^T Q; the weights get no gradient.  The dQ kernel stages the
 //     tile's weights in pol_s as the forward does, the dK/dV kernel keeps its lane's key's weight in one register.  32-key tiles only.
 #include "d2s_common.h"
+#include "d2s_hip_ext.h"
+#include "d2s_hip_ragged_bf16.h"
+#include "d2s_hip_tome_train_bf16.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -852,7 +855,6 @@ __global__ __launch_bounds__(256) void attn_dpol_fold_bf16_kernel(const float* _
 
 }  // namespace
 
-extern "C" int d2s_attn_delta(const float* out, const float* dout, float* delta, int B, int n, int H, hipStream_t stream);
 // D2S_ATTN_BF16_T64 [1]: 1 = the 64-key-tile forward with transposed V reads for long sequences (n >= 384, or where 64-key tiles pad no more
 // than 32-key tiles), 2 = always, 0 = never (the 32-key-tile kernel).  Same-call A/B: n = 577 182.4 -> 179.3 us, config 5 +0.9 %; n = 197 36.8 ->
 // 39.4 us (256 instead of 224 padded keys), hence the rule.

@@ -16,6 +16,7 @@
 // col l&31.  The 64-long d reduction is walked as 32 steps; step s = 4t+j uses d = 8t + 4*half + j, so each lane
 // fetches its operand as 8 float4 (t = 0..7).
 #include "d2s_common.h"
+#include "d2s_hip_ragged_train.h"
 
 namespace {
 

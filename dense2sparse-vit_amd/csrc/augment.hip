@@ -348,9 +348,6 @@ __global__ __launch_bounds__(256) void augment_labels_kernel(const int* __restri
 
 extern "C" {
 
-size_t d2s_randaug_scratch_bytes(int B, int S);                                  // csrc/randaug.hip
-int d2s_randaug_apply(const uint8_t* in, const int* table, int B, int S, uint8_t* scratch, uint8_t* out, hipStream_t stream);
-
 int d2s_augment_desc_ints(void) { return DESC; }
 
 // Dynamic LDS of the horizontal pass for one staged row count, and the row count used for a batch (as many as fit, at most HROWS).

@@ -11,6 +11,7 @@
 // load of its channel 0.  No atomics; every sum has a fixed order (lane-strided partials, wave butterfly, waves as (0+1)+(2+3); the
 // penalty kernels sum sequentially), so two launches give the same bits.
 #include "d2s_common.h"
+#include "d2s_hip_avit.h"
 
 namespace {
 

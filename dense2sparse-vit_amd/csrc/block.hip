@@ -13,34 +13,6 @@
 
 #include <mutex>
 
-extern "C" {
-size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode);
-int d2s_gemm_f32(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K, int epilogue,
-                 const float* bias, const float* aux, long ldaux, float* aux_out, int aux_rows, int remap_rows_per_img, int remap_skip,
-                 int accumulate, int mode, void* workspace, size_t workspace_bytes, hipStream_t stream);
-size_t d2s_linear_wgrad_workspace_bytes(int tokens, int n_out, int n_in, int mode);
-int d2s_linear_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, float* dW, long lddw, float* db, int tokens, int n_out,
-                         int n_in, int accumulate, int mode, void* workspace, size_t workspace_bytes, hipStream_t stream);
-int d2s_colsum_f32(const float* X, long ldx, int M, int N, float* out, int accumulate, void* workspace, size_t workspace_bytes,
-                   hipStream_t stream);
-size_t d2s_colsum_workspace_bytes(int M, int N);
-int d2s_layernorm_fwd(const float* x, long rows_per_group, long group_stride, long row_stride, long offset, const float* w, const float* b,
-                      float* y, float* mean, float* rstd, long rows, int D, float eps, hipStream_t stream);
-size_t d2s_layernorm_bwd_workspace_bytes(long rows, int D);
-int d2s_layernorm_bwd(const float* x, long rows_per_group, long group_stride, long row_stride, long offset, const float* dy, const float* w,
-                      const float* mean, const float* rstd, float* dx, const float* add_src, float* dweight, float* dbias, int accumulate_wb,
-                      int relu_mask, long rows, int D, void* workspace, size_t workspace_bytes, hipStream_t stream);
-int d2s_attn_fwd_f32(const float* qkv, float* out, float* lse, float* cls_row, int B, int n, int H, float scale, hipStream_t stream);
-int d2s_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta_ws, int B, int n,
-                     int H, float scale, hipStream_t stream);
-int d2s_half_mean_concat(const float* x, const float* relu_mask_src, float* out, int B, int T, int C, hipStream_t stream);
-int d2s_softmax_rows(const float* scores, float* probs, int rows, int T, hipStream_t stream);
-int d2s_gemm_f32_rowscale(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K,
-                          const float* bias, const float* aux, long ldaux, const float* rowscale, int rows_per_group, int mode,
-                          const void* a_bf16, const void* b_bf16, void* c_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream);
-int d2s_scale_rows(const float* g, const float* rowscale, float* out, long M, int D, int rows_per_group, hipStream_t stream);
-}
-
 namespace {
 
 enum { NT = 0, NN = 1 };

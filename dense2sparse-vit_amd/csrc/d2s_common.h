@@ -3,10 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define D2S_OK 0
-#define D2S_ERR_ARG (-1)       // bad shape / null pointer / unsupported size
-#define D2S_ERR_WORKSPACE (-2) // workspace too small
-#define D2S_ERR_LAUNCH (-3)    // hipGetLastError() after launch
+// The core of the C ABI and D2S_OK / D2S_ERR_*: ARG = bad shape / null pointer / unsupported size, WORKSPACE = workspace too small,
+// LAUNCH = hipGetLastError() after a launch.  Every source sees these declarations, so a definition that drifts from its header does
+// not compile; a source that defines or calls an entry of another include/d2s_hip_*.h includes that header beside this one.
+#include "d2s_hip.h"
 
 #define D2S_WAVE 64
 

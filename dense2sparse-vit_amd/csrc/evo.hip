@@ -13,6 +13,7 @@
 // written exactly once: results are bit-identical run to run and the launches are legal inside a captured step.  fp32 in every
 // arithmetic mode (the residual stream).
 #include "d2s_common.h"
+#include "d2s_hip_evo.h"
 
 namespace {
 

@@ -15,6 +15,7 @@
 // transposing ds_write_b32 of k-contiguous operands and the ds_read_b32 fragment reads conflict-free.
 // Global->register prefetch of tile t+1 is issued before the 32 MFMAs of tile t; one barrier per K-step.
 #include "gemm_common.h"
+#include "d2s_hip_gemm_plan.h"
 
 namespace {
 using namespace d2s_gemm;
@@ -700,9 +701,6 @@ static int splitk_target() {
     return t;
 }
 static inline size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
-extern "C" size_t d2s_colsum_workspace_bytes(int M, int N);
-extern "C" int d2s_colsum_f32(const float* X, long ldx, int M, int N, float* out, int accumulate, void* workspace,
-                              size_t workspace_bytes, hipStream_t stream);
 // Forward / dgrad GEMMs whose tile grid leaves most CUs with 0-2 workgroups (small batches, narrow outputs with a long K) also
 // split K: the choice minimises (workgroups on the busiest CU) x (K share per workgroup) / (matrix-pipe use at that residency) plus a
 // per-slice cost for the extra slab traffic.  Large grids get 1 (no split).

@@ -12,6 +12,7 @@
 // Grid: key tile of 128 x (image, head).  fp32 only, no atomics, no memset, fixed summation orders: two calls on equal inputs give the
 // same bits.
 #include "d2s_common.h"
+#include "d2s_hip_graph_rank.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 // H * rows floats of traffic, nothing next to the qkv rows each workgroup streams.
 // fp32 only, no atomics, fixed summation orders: two launches on equal inputs give the same bits.
 #include "d2s_common.h"
+#include "d2s_hip_ltp.h"
 
 namespace {
 

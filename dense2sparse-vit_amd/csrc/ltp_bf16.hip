@@ -14,6 +14,7 @@
 // Grid: key tile x (image, head), per-head partials plus a fold - ltp.hip's, for ltp.hip's reasons.
 // No atomics, no memset, fixed summation orders: two launches on equal inputs give the same bits.
 #include "d2s_common.h"
+#include "d2s_hip_ltp_bf16.h"
 
 namespace {
 

@@ -10,6 +10,7 @@
 // (197 rows) is spread over 4 workgroups.  A slot without a chunk ends at once.
 // Latency / HBM work, no atomics, no memset: every output element is written exactly once, 16 bytes (fp32) and 8 bytes (bf16) per lane.
 #include "d2s_common.h"
+#include "d2s_hip_ragged_stage_bf16.h"
 
 namespace {
 

@@ -7,6 +7,7 @@
 //   ragged_teacher_rows_kernel                    the teacher's token of every packed row and the row weights of the token distillation
 // Latency / HBM work, no atomics, no memset: every output element is written exactly once.
 #include "d2s_common.h"
+#include "d2s_hip_ragged_threshold.h"
 
 namespace {
 

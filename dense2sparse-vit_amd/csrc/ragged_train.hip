@@ -6,6 +6,7 @@
 //   ragged_cls_scatter_kernel  the backward of the head's gather of the CLS rows (d2s_gather_rows_i32 with cu_seqlens as the index)
 // Latency / HBM work, no atomics, no memset: every output row is written exactly once, 16 bytes per lane.
 #include "d2s_common.h"
+#include "d2s_hip_ragged_train.h"
 
 namespace {
 

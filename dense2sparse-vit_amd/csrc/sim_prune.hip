@@ -22,6 +22,7 @@
 //           counting, every list compacted by wave ballots.
 // No atomics, no memset, no scratch, nothing read back by the host: deterministic and legal inside a captured step.
 #include "d2s_common.h"
+#include "d2s_hip_sim_prune.h"
 #include <limits.h>
 
 namespace {

@@ -10,6 +10,7 @@
 //             row of dx written exactly once.
 // All accesses to token rows are 16 bytes per lane; results are bit-identical run to run.
 #include "d2s_common.h"
+#include "d2s_hip_squeeze.h"
 #include <limits.h>
 
 namespace {

@@ -24,6 +24,8 @@
 // load converts each value to fp32 (exact) and everything after the load is the same fp32 code in the same order, so
 // d2s_tome_match_bf16(q16) is d2s_tome_match(float(q16)) bit for bit.
 #include "d2s_common.h"
+#include "d2s_hip_ext.h"
+#include "d2s_hip_tome_train_bf16.h"
 #include <type_traits>
 
 namespace {

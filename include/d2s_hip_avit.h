@@ -4,8 +4,8 @@
  * d2s_hip.h is the frozen core of the C ABI, d2s_hip_ext.h, d2s_hip_squeeze.h, d2s_hip_ats.h, d2s_hip_ragged_train.h and
  * d2s_hip_ragged_threshold.h are closed as well; these entries follow the same style (one `int d2s_...(` declaration at the start of a
  * line, one comment per entry) and d2s_hip.h's conventions: device pointers owned by the caller, 0 on success or D2S_ERR_* (< 0), nothing
- * throws, nothing allocates, work enqueued on `stream`.  The Python binding keeps this list apart too (d2s.lib._SIGS_AVIT /
- * avit_symbols()).
+ * throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * The batch is ragged and packed: image b owns rows cu_seqlens[b] .. cu_seqlens[b+1]-1 of `total`, the first of them its CLS token;
  * row_src [total] is the original token index of every row (0 at CLS, 1 .. N-1 at the patches).  Inside the kernels a segment is clamped

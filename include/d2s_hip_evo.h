@@ -3,8 +3,8 @@
  * d2s_hip.h is the frozen core of the C ABI, d2s_hip_ext.h, d2s_hip_squeeze.h, d2s_hip_ats.h, d2s_hip_ragged_train.h,
  * d2s_hip_ragged_threshold.h and d2s_hip_avit.h are closed as well; these entries follow the same style (one `int d2s_...(` declaration at
  * the start of a line, one comment per entry) and d2s_hip.h's conventions: device pointers owned by the caller, 0 on success or
- * D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding keeps this list apart too
- * (d2s.lib._SIGS_EVO / evo_symbols()).
+ * D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * X [B, 1+T, D] is the full token tensor (CLS first), g [B, T] the global score of the T patch tokens, kept [B, k] / dropped [B, T-k] the
  * ascending int64 id lists of a slow-fast block (together a partition of 0 .. T-1; a row whose id is outside [0, T) is skipped, nothing

@@ -3,8 +3,8 @@
  * d2s_hip.h is the frozen core of the C ABI: its list of entries no longer changes.  This file holds the two entries that followed it and is
  * closed as well (a later feature brings a header of its own: d2s_hip_squeeze.h); they are declared in the same style
  * (one `int d2s_...(` declaration at the start of a line, one comment per entry) and under d2s_hip.h's conventions: device pointers owned
- * by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding keeps
- * the two lists apart as well (d2s.lib._SIGS / exported_symbols() for the core, d2s.lib._SIGS_EXT / extension_symbols() for this file).
+ * by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  */
 #ifndef D2S_HIP_EXT_H
 #define D2S_HIP_EXT_H

@@ -3,7 +3,8 @@
  * d2s_hip.h is the frozen core of the C ABI, d2s_hip_ext.h, d2s_hip_squeeze.h, d2s_hip_ats.h, d2s_hip_ragged_train.h,
  * d2s_hip_ragged_threshold.h, d2s_hip_avit.h and d2s_hip_evo.h are closed as well; this entry follows the same style (one declaration at the
  * start of a line, one comment per entry).  It is host arithmetic only: nothing is launched, nothing allocated, no stream is taken.
- * The Python binding keeps this list apart too (d2s.lib._SIGS_GEMM_PLAN / gemm_plan_symbols()).
+ * The Python binding
+ * lists it under this file's name in its one table, d2s.lib.ABI.
  *
  * Two argument rules of d2s_gemm_f32 that d2s_hip.h does not spell out, both D2S_ERR_ARG before any launch, in every mode:
  *   - layouts 0 / 1 (NT / NN) with accumulate != 0 and an epilogue other than 0 or 8: accumulation IS epilogue 8 (C += A op(B)); it does

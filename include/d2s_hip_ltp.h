@@ -3,8 +3,8 @@
  *
  * d2s_hip.h is the frozen core of the C ABI and the older d2s_hip_*.h headers are closed as well; these entries follow the same style
  * (one `int d2s_...(` or `size_t d2s_...(` declaration at the start of a line, one comment per entry) and d2s_hip.h's conventions: device
- * pointers owned by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The
- * Python binding keeps this list apart too (d2s.lib._SIGS_LTP / ltp_symbols()).
+ * pointers owned by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * fp32 only, no atomics, fixed summation orders: two launches on equal inputs give the same bits.  Every argument error is reported
  * before any launch, and a segment of a packed batch is clamped to [0, total) inside the kernels, so nothing is dereferenced outside the

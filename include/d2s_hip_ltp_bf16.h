@@ -5,7 +5,8 @@
  * d2s_hip.h is the frozen core of the C ABI and the older d2s_hip_*.h headers are closed as well, and so is this one at its two entries;
  * they follow the same style (one `int d2s_...(` or `size_t d2s_...(` declaration at the start of a line, one comment per entry) and
  * d2s_hip.h's conventions: device pointers owned by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work
- * enqueued on `stream`.  The Python binding keeps this list apart too (d2s.lib._SIGS_LTP_BF16 / ltp_bf16_symbols()).
+ * enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * No atomics, no memset, fixed summation orders: two launches on equal inputs give the same bits.  Every argument error is D2S_ERR_ARG
  * and is reported before any launch, and a segment of a packed batch is clamped to [0, total) inside the kernels, so nothing is

@@ -4,7 +4,8 @@
  * d2s_hip.h is the frozen core of the C ABI, d2s_hip_ext.h, d2s_hip_squeeze.h, d2s_hip_ats.h and d2s_hip_ragged_train.h are closed as well;
  * these entries follow the same style (one `int d2s_...(` declaration at the start of a line, one comment per entry) and d2s_hip.h's
  * conventions: device pointers owned by the caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on
- * `stream`.  The Python binding keeps this list apart too (d2s.lib._SIGS_RAGGED_THRESHOLD / ragged_threshold_symbols()).
+ * `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * The batch is ragged and packed, as in d2s_hip_ragged_train.h: image b owns rows cu_seqlens[b] .. cu_seqlens[b+1]-1 of `total`, the first
  * of them its CLS token; row_src [total] is the ORIGINAL token index of every row (patch id + 1, 0 for CLS); an image of one row (CLS only)

@@ -2,8 +2,8 @@
  *
  * d2s_hip.h is the frozen core of the C ABI and d2s_hip_ext.h is closed as well; these entries follow the same style (one `int d2s_...(`
  * declaration at the start of a line, one comment per entry) and d2s_hip.h's conventions: device pointers owned by the caller, 0 on
- * success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding keeps this list apart
- * too (d2s.lib._SIGS_SQUEEZE / squeeze_symbols()).
+ * success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * Common to the three: x [B,n,D] fp32 is one stage's input, [CLS | T scored tokens] with n = T + 1; kept [B,k] and dropped [B,m], m = T - k,
  * are the selector's int64 stage-relative ids; a plan is dst [B,m] int32 (a POSITION in kept, not a token id) and sim [B,m] fp32.

@@ -4,8 +4,8 @@
  *
  * d2s_hip.h is the frozen core of the C ABI and every later header is closed as well; these entries follow the same style (one
  * `int d2s_...(` declaration at the start of a line, one comment per entry) and d2s_hip.h's conventions: device pointers owned by the
- * caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding keeps this
- * list apart too (d2s.lib._SIGS_TOME_TRAIN_BF16 / tome_train_bf16_symbols()).
+ * caller, 0 on success or D2S_ERR_* (< 0), nothing throws, nothing allocates, work enqueued on `stream`.  The Python binding
+ * lists them under this file's name in its one table, d2s.lib.ABI.
  *
  * Neither entry uses atomics or needs its output cleared: every output element is written exactly once, two launches are bit-identical.
  */

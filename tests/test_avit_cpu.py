@@ -4,7 +4,6 @@ a halting score against float64 autograd), the condition on the inputs the GPU t
 command line, build_models, the constructor, TrainStep's refusals and the checkpoint config."""
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -19,7 +18,6 @@ from oracle import d2s_oracle as O
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MICRO = dict(img_size=64, patch_size=16, embed_dim=128, depth=4, num_heads=2, mlp_ratio=4.0, qkv_bias=True, num_classes=10)
 NEW = ["d2s_avit_halt", "d2s_avit_halt_bwd", "d2s_avit_penalty_bwd", "d2s_avit_penalty_fwd"]
-DECL = r"^(?:int|size_t|long) (d2s_\w+)\("
 EPS = 0.01
 
 # The model cases of the GPU tests: the micro geometry (D 128, H 2, depth 4, N 17) with B = 4, gate constants picked on the CPU with the
@@ -128,24 +126,8 @@ def test_closed_form_gradient_of_the_halting_scores_against_autograd(name):
 def test_avit_header_and_binding_tables():
     from d2s import lib, ops, functional_avit
     text = open(os.path.join(REPO, "include", "d2s_hip_avit.h")).read()
-    declared = re.findall(DECL, text, flags=re.M)
-    assert sorted(declared) == NEW == lib.avit_symbols()
-    assert len(set(declared)) == len(declared)
-    older = (lib.exported_symbols(), lib.extension_symbols(), lib.squeeze_symbols(), lib.ats_symbols(), lib.ragged_train_symbols(),
-             lib.ragged_threshold_symbols())
-    for name in NEW:
-        assert all(name not in table for table in older), name
-    assert '#include "d2s_hip.h"' in text
-    decl = lambda h: re.findall(DECL, open(os.path.join(REPO, "include", h)).read(), flags=re.M)
-    assert len(decl("d2s_hip.h")) == 120 and sorted(decl("d2s_hip.h")) == lib.exported_symbols()     # the six older tables are what they were
-    assert sorted(decl("d2s_hip_ext.h")) == ["d2s_attn_keyw_fwd_bf16", "d2s_tome_match_bf16"] == lib.extension_symbols()
-    assert len(decl("d2s_hip_squeeze.h")) == 3 and sorted(decl("d2s_hip_squeeze.h")) == lib.squeeze_symbols()
-    assert decl("d2s_hip_ats.h") == ["d2s_ats_select"] == lib.ats_symbols()
-    assert len(decl("d2s_hip_ragged_train.h")) == 4 and sorted(decl("d2s_hip_ragged_train.h")) == lib.ragged_train_symbols()
-    assert len(decl("d2s_hip_ragged_threshold.h")) == 4 and sorted(decl("d2s_hip_ragged_threshold.h")) == lib.ragged_threshold_symbols()
-    for name in NEW:
-        res, argt = lib._SIGS_AVIT[name]
-        assert res is lib.I and argt
+    assert NEW == lib.symbols("d2s_hip_avit.h") and "D2S_ERR_ARG" in text
+    assert all(lib.signature(name)[0] is lib.I and lib.signature(name)[1] for name in NEW)
     for fn in ("avit_state", "avit_halt", "avit_halt_bwd", "avit_penalty_fwd", "avit_penalty_bwd"):
         assert callable(getattr(ops, fn))
     assert callable(functional_avit.AViTHaltFn.apply) and callable(functional_avit.AViTPenaltyFn.apply)

@@ -17,7 +17,6 @@ from oracle import d2s_oracle as O
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MICRO = dict(img_size=64, patch_size=16, embed_dim=128, depth=4, num_heads=2, mlp_ratio=4.0, qkv_bias=True, num_classes=10)
 NEW = ["d2s_evo_gather_bwd", "d2s_evo_scatter_bwd", "d2s_evo_scatter_fwd", "d2s_evo_select"]
-DECL = r"^(?:int|size_t|long) (d2s_\w+)\("
 
 # The model cases of the GPU tests: the micro geometry of tests/test_avit_gpu.py (D 128, H 2, depth 4, T 16) with B = 4; one case on an 80
 # pixel image (T 25) with keep 0.3 and every block slow-fast but the first, one with evo_start = depth (the dense trunk).  The seeds were
@@ -110,28 +109,9 @@ def test_closed_form_backwards_against_autograd(B, T, k, D):
 def test_evo_header_and_binding_tables():
     from d2s import lib, ops, functional_evo
     text = open(os.path.join(REPO, "include", "d2s_hip_evo.h")).read()
-    declared = re.findall(DECL, text, flags=re.M)
-    assert sorted(declared) == NEW == lib.evo_symbols()
-    assert len(set(declared)) == len(declared)
+    assert NEW == lib.symbols("d2s_hip_evo.h")
     assert len(re.findall(r"^/\* ", text, flags=re.M)) == 1 + len(NEW)            # the file's comment and one per entry
-    older = (lib.exported_symbols(), lib.extension_symbols(), lib.squeeze_symbols(), lib.ats_symbols(), lib.ragged_train_symbols(),
-             lib.ragged_threshold_symbols(), lib.avit_symbols())
-    for name in NEW:
-        assert all(name not in table for table in older), name
-    assert '#include "d2s_hip.h"' in text
-    decl = lambda h: re.findall(DECL, open(os.path.join(REPO, "include", h)).read(), flags=re.M)
-    assert len(decl("d2s_hip.h")) == 120 and sorted(decl("d2s_hip.h")) == lib.exported_symbols()     # the seven older tables are what they were
-    assert sorted(decl("d2s_hip_ext.h")) == ["d2s_attn_keyw_fwd_bf16", "d2s_tome_match_bf16"] == lib.extension_symbols()
-    assert len(decl("d2s_hip_squeeze.h")) == 3 and sorted(decl("d2s_hip_squeeze.h")) == lib.squeeze_symbols()
-    assert decl("d2s_hip_ats.h") == ["d2s_ats_select"] == lib.ats_symbols()
-    assert len(decl("d2s_hip_ragged_train.h")) == 4 and sorted(decl("d2s_hip_ragged_train.h")) == lib.ragged_train_symbols()
-    assert len(decl("d2s_hip_ragged_threshold.h")) == 4 and sorted(decl("d2s_hip_ragged_threshold.h")) == lib.ragged_threshold_symbols()
-    assert sorted(decl("d2s_hip_avit.h")) == ["d2s_avit_halt", "d2s_avit_halt_bwd", "d2s_avit_penalty_bwd", "d2s_avit_penalty_fwd"] == lib.avit_symbols()
-    for name in NEW:
-        res, argt = lib._SIGS_EVO[name]
-        assert res is lib.I and argt
-        params = re.search(name + r"\((.*?)\);", text, flags=re.S).group(1).split(",")
-        assert len(params) == len(argt) + 1 and "d2s_stream_t stream" in params[-1], name     # the table's arity is the header's
+    assert all(lib.signature(name)[0] is lib.I and lib.signature(name)[1] for name in NEW)
     for fn in ("evo_select", "evo_scatter_fwd", "evo_scatter_bwd", "evo_gather_bwd"):
         assert callable(getattr(ops, fn))
     assert callable(functional_evo.EvoGatherFn.apply) and callable(functional_evo.EvoScatterFn.apply)

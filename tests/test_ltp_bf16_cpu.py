@@ -17,33 +17,18 @@ from tests.test_ltp_cpu import MICRO, SCALE, make_policy
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["d2s_ltp_score_bf16", "d2s_ltp_score_bf16_workspace_bytes"]
-DECL = r"^(?:int|size_t|long) (d2s_\w+)\("
 
 
-# ---- the header and the binding tables ----
+# ---- the header and the binding (tests/test_abi_cpu.py compares the two entry by entry) ----
 def test_header_declares_the_two_entries_and_the_older_tables_are_what_they_were():
     from d2s import lib, ops
     text = open(os.path.join(REPO, "include", "d2s_hip_ltp_bf16.h")).read()
-    declared = re.findall(DECL, text, flags=re.M)
-    assert sorted(declared) == NEW == lib.ltp_bf16_symbols() and len(set(declared)) == len(declared) == 2
+    assert NEW == lib.symbols("d2s_hip_ltp_bf16.h")
     assert len(re.findall(r"^/\* ", text, flags=re.M)) == 1 + len(NEW)            # the file's comment and one per entry
-    assert '#include "d2s_hip.h"' in text and "D2S_ERR_ARG" in text
-    older = (lib.exported_symbols(), lib.extension_symbols(), lib.squeeze_symbols(), lib.ats_symbols(), lib.ragged_train_symbols(),
-             lib.ragged_threshold_symbols(), lib.avit_symbols(), lib.evo_symbols(), lib.gemm_plan_symbols(), lib.ragged_bf16_symbols(),
-             lib.ltp_symbols(), lib.tome_train_bf16_symbols(), lib.ragged_stage_bf16_symbols())
-    for name in NEW:
-        assert all(name not in table for table in older), name
-    decl = lambda h: re.findall(DECL, open(os.path.join(REPO, "include", h)).read(), flags=re.M)
-    counts = [("d2s_hip.h", 120), ("d2s_hip_ext.h", 2), ("d2s_hip_squeeze.h", 3), ("d2s_hip_ats.h", 1), ("d2s_hip_ragged_train.h", 4),
-              ("d2s_hip_ragged_threshold.h", 4), ("d2s_hip_avit.h", 4), ("d2s_hip_evo.h", 4), ("d2s_hip_gemm_plan.h", 1),
-              ("d2s_hip_ragged_bf16.h", 2), ("d2s_hip_ltp.h", 5), ("d2s_hip_tome_train_bf16.h", 2), ("d2s_hip_ragged_stage_bf16.h", 2)]
-    for (header, count), table in zip(counts, older):
-        assert len(decl(header)) == count and sorted(decl(header)) == table, header
-    handle = lib.load()
-    assert all(hasattr(handle, n) for t in older for n in t) and all(hasattr(handle, n) and callable(lib._fn(n)) for n in NEW)
+    assert "D2S_ERR_ARG" in text
     # the signatures: the fp32 score pair's
-    assert lib._SIGS_LTP_BF16["d2s_ltp_score_bf16"] == lib._SIGS_LTP["d2s_ltp_score_f32"]
-    assert lib._SIGS_LTP_BF16["d2s_ltp_score_bf16_workspace_bytes"] == lib._SIGS_LTP["d2s_ltp_score_workspace_bytes"]
+    assert lib.signature("d2s_ltp_score_bf16") == lib.signature("d2s_ltp_score_f32")
+    assert lib.signature("d2s_ltp_score_bf16_workspace_bytes") == lib.signature("d2s_ltp_score_workspace_bytes")
     assert lib.query("d2s_ltp_score_bf16_workspace_bytes", 197 * 128, 6) == 197 * 128 * 6 * 4
     assert lib.query("d2s_ltp_score_bf16_workspace_bytes", 0, 6) == 0 and lib.query("d2s_ltp_score_bf16_workspace_bytes", 5, 0) == 0
     src = open(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "ltp_bf16.hip")).read()

@@ -20,7 +20,6 @@ from oracle import d2s_oracle as O
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["d2s_ltp_score_f32", "d2s_ltp_score_workspace_bytes", "d2s_ltp_select", "d2s_ltp_soft_mask_bwd", "d2s_ltp_soft_mask_fwd"]
-DECL = r"^(?:int|size_t|long) (d2s_\w+)\("
 SCALE = 0.125
 
 
@@ -162,23 +161,10 @@ def test_soft_mask_closed_form_against_autograd(B, N, seed):
 def test_ltp_header_and_binding_tables():
     from d2s import lib, ops
     text = open(os.path.join(REPO, "include", "d2s_hip_ltp.h")).read()
-    declared = re.findall(DECL, text, flags=re.M)
-    assert sorted(declared) == NEW == lib.ltp_symbols() and len(set(declared)) == len(declared) == 5
+    assert NEW == lib.symbols("d2s_hip_ltp.h")
     assert len(re.findall(r"^/\* ", text, flags=re.M)) == 1 + len(NEW)            # the file's comment and one per entry
-    assert '#include "d2s_hip.h"' in text and "D2S_ERR_ARG" in text
-    older = (lib.exported_symbols(), lib.extension_symbols(), lib.squeeze_symbols(), lib.ats_symbols(), lib.ragged_train_symbols(),
-             lib.ragged_threshold_symbols(), lib.avit_symbols(), lib.evo_symbols(), lib.gemm_plan_symbols(), lib.ragged_bf16_symbols())
-    for name in NEW:
-        assert all(name not in table for table in older), name
-    decl = lambda h: re.findall(DECL, open(os.path.join(REPO, "include", h)).read(), flags=re.M)
-    counts = [("d2s_hip.h", 120), ("d2s_hip_ext.h", 2), ("d2s_hip_squeeze.h", 3), ("d2s_hip_ats.h", 1), ("d2s_hip_ragged_train.h", 4),
-              ("d2s_hip_ragged_threshold.h", 4), ("d2s_hip_avit.h", 4), ("d2s_hip_evo.h", 4), ("d2s_hip_gemm_plan.h", 1),
-              ("d2s_hip_ragged_bf16.h", 2)]
-    for (header, count), table in zip(counts, older):                             # the older tables are what they were
-        assert len(decl(header)) == count and sorted(decl(header)) == table, header
-    handle = lib.load()
-    assert all(hasattr(handle, n) for n in NEW)
-    assert lib._SIGS_LTP["d2s_ltp_score_workspace_bytes"][0] is lib.Z and all(lib._SIGS_LTP[n][0] is lib.I for n in NEW if n.endswith(("f32", "select", "fwd", "bwd")))
+    assert "D2S_ERR_ARG" in text
+    assert lib.signature("d2s_ltp_score_workspace_bytes")[0] is lib.Z and all(lib.signature(n)[0] is lib.I for n in NEW if n.endswith(("f32", "select", "fwd", "bwd")))
     assert lib.query("d2s_ltp_score_workspace_bytes", 197 * 128, 6) == 197 * 128 * 6 * 4
     assert lib.query("d2s_ltp_score_workspace_bytes", 0, 6) == 0 and lib.query("d2s_ltp_score_workspace_bytes", 5, 0) == 0
     src = open(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "ltp.hip")).read()
