@@ -229,4 +229,68 @@ inline bool epilogue_vec_ok(const GemmArgs& p) {
     return ok;
 }
 
+// ---- host side of a call: gemm_f32.hip has the C entries, check_args, run_gemm and the exact path; gemm_split.hip the plans and matrix
+// launches of the bf16 / bf16x3 paths ----
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// CUs of the current device; 256 (the MI355X's) where none answers, so that the size queries are host arithmetic without a GPU
+inline int gemm_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        return n;
+    }();
+    return cus;
+}
+
+// Workgroups the wgrad launch aims for (tiles x K slices, rounded down): 3 per CU.  Run alone, exactly 2 per CU is best (tools/gemm_bench.py,
+// split-K target sweep in round 1: 512 beats 768 / 1024 by 4-15 % - fewer, longer K slices mean less slab traffic for the ordered
+// combine - and any count that is not a multiple of the CU count loses 10-40 % to imbalance).  Inside the training step the weight
+// gradients run on their own stream BESIDE the dgrad / attention kernels (d2s.ops.async_weight_grads), where shorter workgroups interleave
+// better: 3 per CU measured best there (step: 256 -> 3483, 384 -> 3470, 512 -> 3513, 768 -> 3556, 1024 -> 3526, 1536 -> 3508, 2048 -> 3490
+// images/s on one box).
+inline int splitk_target() { return 3 * gemm_cus(); }
+inline int splitk_slices(int tiles, int K) {
+    int slices = splitk_target() / tiles;
+    const int max_slices = (K + 255) / 256;
+    if (slices > max_slices) slices = max_slices;
+    if (slices < 1) slices = 1;
+    return slices;
+}
+
+// What a call carries beside the kernels' argument block.  The C entries fill both by field name and hand them to run_gemm.
+struct GemmCall {
+    int layout;                 // 0 = NT (A[M,K], B[N,K]); 1 = NN (A[M,K], B[K,N]); 2 = TN (A[K,M], B[K,N]: the weight gradient, A = dy, B = x)
+    int mode;                   // 0 exact fp32, 1 bf16x3, 2 bf16
+    int accumulate;             // C += result (TN; on NT / NN it is EPI_ACCUM and goes with epilogue 0 or 8 only)
+    float* colsum_out;          // TN: the bias gradient, column sums of dy (may be null)
+    const void* dy16;           // TN, mode 2: dy in bf16 [K][M] (row stride lda); A may then be null
+    const void* x16;            // TN, mode 2: the layer input x in bf16 [K][N] (row stride ldb); B may then be null
+    void* workspace; size_t workspace_bytes;
+    hipStream_t stream;
+};
+
+// NT / NN in modes 1 and 2: where each operand's bf16 pieces come from, which matrix kernel multiplies them, the workspace
+enum SplitA { A_PRESPLIT, A_IN_KERNEL, A_FROM_A16 };      // a split pass writes A's pieces; the kernel converts fp32 A itself; a16 is the piece
+enum SplitKernel { SK_PIECES_X3, SK_PIECES_X1, SK_PIECES_AF32, SK_DMA_256x256, SK_DMA_256x128 };
+struct SplitPlan {
+    int split, Kp;              // pieces per operand (3 / 1), K rounded up to 32
+    SplitA a_from; bool b_from_b16; SplitKernel kernel;
+    size_t b_offset, bytes;     // workspace: A's pieces at 0, B's at b_offset
+};
+SplitPlan split_plan(const GemmArgs& p, int split);
+int launch_split(const GemmArgs& p, const GemmCall& c, const SplitPlan& pl);
+
+// TN in mode 2 (the bf16 weight gradient): K slices into fp32 slabs, the matrix kernel, the workspace
+enum WgradKernel { WK_TOKEN_MAJOR, WK_DMA_PIECES, WK_PIECES };
+struct Wgrad16Plan {
+    int Kp;                                     // K rounded up to 64
+    int slices_asked, k_per_slice, slices;      // asked for by the split-K rule; a slice's share in whole 64-deep K blocks; slices that leaves
+    WgradKernel kernel; bool vec_epilogue;
+    int colsum_parts;                           // partial rows of the bias gradient that the caller folds
+    size_t piece_offset, b_offset, colsum_offset, bytes;   // workspace: slabs at 0, A's pieces, B's pieces (from piece_offset), column-sum partials
+};
+Wgrad16Plan wgrad16_plan(const GemmArgs& slabs, const GemmCall& c);
+int launch_wgrad16_matrix(const GemmArgs& slabs, const GemmCall& c, const Wgrad16Plan& pl);
+
 }  // namespace d2s_gemm

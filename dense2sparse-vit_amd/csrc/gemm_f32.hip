@@ -648,21 +648,22 @@ inline Tile pick_tile(int M, int N) {
     return best;
 }
 
+// the run-time tile as template arguments: calls f with the TileC that names it
+template <int BM, int BN> struct TileC { static constexpr int bm = BM, bn = BN; };
+template <class F>
+inline void with_tile(const Tile& t, F f) {
+    if (t.bm == 128 && t.bn == 128) f(TileC<128, 128>{});
+    else if (t.bm == 128) f(TileC<128, 64>{});
+    else if (t.bn == 128) f(TileC<64, 128>{});
+    else f(TileC<64, 64>{});
+}
 template <int ALAY, int BLAY, bool FAST>
 inline void launch_gemm_f(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p) {
-    dim3 block(256);
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 128, FAST>), grid, block, 0, stream, p);
-    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 128, 64, FAST>), grid, block, 0, stream, p);
-    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 128, FAST>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, 64, 64, FAST>), grid, block, 0, stream, p);
+    with_tile(t, [&](auto tc) { hipLaunchKernelGGL((gemm_f32_kernel<ALAY, BLAY, decltype(tc)::bm, decltype(tc)::bn, FAST>), grid, dim3(256), 0, stream, p); });
 }
 template <int BLAY>
 inline void launch_gemm_rk(const Tile& t, dim3 grid, hipStream_t stream, const GemmArgs& p) {
-    dim3 block(256);
-    if (t.bm == 128 && t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 128>), grid, block, 0, stream, p);
-    else if (t.bm == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 128, 64>), grid, block, 0, stream, p);
-    else if (t.bn == 128) hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 128>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, 64, 64>), grid, block, 0, stream, p);
+    with_tile(t, [&](auto tc) { hipLaunchKernelGGL((gemm_f32_rk_kernel<BLAY, decltype(tc)::bm, decltype(tc)::bn>), grid, dim3(256), 0, stream, p); });
 }
 // k-contiguous A operands (NT / NN layouts) of guard-free shapes with the 16-byte epilogue use the [row][k] LDS image (ds_*_b128), every
 // other call the [k][row] image.  Measured on the model's shapes at B = 128 (tools/gemm_bench.py, profiles/r02_c_gemm_rk_vs_krow.txt): +20...30 %
@@ -676,31 +677,6 @@ inline void launch_gemm(const Tile& t, dim3 grid, hipStream_t stream, const Gemm
 
 }  // namespace
 
-namespace d2s_gemm {
-size_t split_workspace_bytes(int split, int M, int N, int K);
-int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace, size_t workspace_bytes, hipStream_t stream);
-size_t split_tn_pieces_bytes(int split, int M, int N, int K);
-int split_tn_colsum_partials(int K);
-bool split_tn_use_dma(int M, int N, int K);
-int split_tn_dma_slices(int M, int N, int K);
-int launch_split_gemm_tn(const GemmArgs& p, int split, int slices, void* pieces_ws, float* colsum_part, hipStream_t stream, int* colsum_parts);
-}
-// Workgroups the wgrad launch aims for (tiles x K slices, rounded down): 3 per CU.  Run alone, exactly 2 per CU is best (tools/gemm_bench.py,
-// split-K target sweep in round 1: 512 beats 768 / 1024 by 4-15 % - fewer, longer K slices mean less slab traffic for the ordered
-// combine - and any count that is not a multiple of the CU count loses 10-40 % to imbalance).  Inside the training step the weight
-// gradients run on their own stream BESIDE the dgrad / attention kernels (d2s.ops.async_weight_grads), where shorter workgroups interleave
-// better: 3 per CU measured best there (step: 256 -> 3483, 384 -> 3470, 512 -> 3513, 768 -> 3556, 1024 -> 3526, 1536 -> 3508, 2048 -> 3490
-// images/s on one box).
-static int splitk_target() {
-    static const int t = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        return 3 * cus;
-    }();
-    return t;
-}
-static inline size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // Forward / dgrad GEMMs whose tile grid leaves most CUs with 0-2 workgroups (small batches, narrow outputs with a long K) also
 // split K: the choice minimises (workgroups on the busiest CU) x (K share per workgroup) / (matrix-pipe use at that residency) plus a
 // per-slice cost for the extra slab traffic.  Large grids get 1 (no split).
@@ -719,19 +695,12 @@ static int nt_slices(int tiles, int K) {
     }
     return best;
 }
-static int splitk_slices(int tiles, int K) {
-    int slices = splitk_target() / tiles;
-    const int max_slices = (K + 255) / 256;
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    return slices;
-}
 
-// Tile and K slices of the exact kernels of this file (mode 0; the weight gradient, layout 2, also in mode 1), written once: the launch
-// (gemm_impl), the workspace query and the plan query (d2s_gemm_f32_plan) all read them here.  The weight gradient always runs 128x128
+// Tile, K slices and workspace of the exact kernels of this file (mode 0; the weight gradient, layout 2, also in mode 1), written once: the
+// launch (run_gemm), the workspace query and the plan query (d2s_gemm_f32_plan) all read them here.  The weight gradient always runs 128x128
 // tiles (64x64 wgrad tiles for the small 384x384 weights: measured slower).  `slices` is the count after k_per_slice was rounded up
-// to whole K-steps, i.e. the z extent of the grid.
-struct ExactPlan { Tile tile; int tiles, slices, k_per_slice; };
+// to whole K-steps, i.e. the z extent of the grid.  Workspace when K is split: the C slabs, for layout 2 also the fused bias-gradient slabs.
+struct ExactPlan { Tile tile; int tiles, slices, k_per_slice; size_t bytes; };
 static ExactPlan exact_plan(int layout, int M, int N, int K) {
     ExactPlan pl;
     pl.tile = layout == 2 ? Tile{128, 128, 1.f} : pick_tile(M, N);
@@ -741,6 +710,7 @@ static ExactPlan exact_plan(int layout, int M, int N, int K) {
     kper = ((kper + BK - 1) / BK) * BK;
     pl.k_per_slice = kper;
     pl.slices = (K + kper - 1) / kper;
+    pl.bytes = pl.slices <= 1 ? 0 : ((size_t)pl.slices * M * N + (layout == 2 ? (size_t)pl.slices * M : 0)) * sizeof(float);
     return pl;
 }
 
@@ -758,19 +728,12 @@ extern "C" {
 // matrix cores (transposing split + K-sliced pieces kernel + the same ordered slab combine), in mode 1 it stays on the exact kernel.
 // The mode is an argument of every call (no process-global state): a bf16 teacher can run beside an fp32 student, from any thread.
 size_t d2s_gemm_f32_workspace_bytes(int layout, int M, int N, int K, int mode) {
-    if (layout != 2 && mode != 0) return split_workspace_bytes(mode == 1 ? 3 : 1, M, N, K);   // bf16 piece matrices
-    if (layout != 2) {
-        const int sl = exact_plan(layout, M, N, K).slices;
-        return sl > 1 ? (size_t)sl * M * N * sizeof(float) : 0;
-    }
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    if (mode != 2) {      // C slabs + fused bias-gradient slabs
-        const int slices = exact_plan(2, M, N, K).slices;
-        return slices <= 1 ? 0 : ((size_t)slices * M * N + (size_t)slices * M) * sizeof(float);
-    }
-    // mode 2: C slabs + bf16 pieces of both operands + scratch of the separate bias-gradient pass (see gemm_impl)
-    const int slices = split_tn_use_dma(M, N, K) ? split_tn_dma_slices(M, N, K) : splitk_slices(tiles, K);
-    return ws_align(((size_t)(slices + 1) * M * N) * sizeof(float)) + ws_align(split_tn_pieces_bytes(1, M, N, K)) + (size_t)split_tn_colsum_partials(K) * M * sizeof(float);
+    GemmArgs p{};      // a plan's `bytes` depends on the shape alone
+    p.M = M; p.N = N; p.K = K;
+    if (layout != 2 && mode != 0) return split_plan(p, mode == 1 ? 3 : 1).bytes;       // bf16 piece matrices
+    // layout 2, mode 2: C slabs + bf16 pieces of both operands + partial rows of the bias gradient
+    if (layout == 2 && mode == 2) return wgrad16_plan(p, GemmCall{}).bytes;
+    return exact_plan(layout, M, N, K).bytes;
 }
 
 // What d2s_gemm_f32 (d2s_linear_wgrad_f32 for layout 2, with M = n_out, N = n_in, K = tokens) launches for a problem: tile_m | tile_n << 16 |
@@ -783,158 +746,167 @@ size_t d2s_gemm_f32_plan(int layout, int M, int N, int K, int mode) {
     return (size_t)pl.tile.bm | ((size_t)pl.tile.bn << 16) | ((size_t)pl.slices << 32);
 }
 
-// layout 0 = NT (A[M,K], B[N,K]); 1 = NN (A[M,K], B[K,N]); 2 = TN (A[K,M], B[K,N]).
-// epilogue: see enum Epi.  accumulate != 0: C += result (TN; on NT / NN it is EPI_ACCUM and goes with epilogue 0 or 8 only).
-// remap_*: see GemmArgs (EPI_BIAS_ROWADD only).
-static int gemm_impl(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                     int K, int epilogue, const float* bias, const float* aux, long ldaux, float* aux_out, int aux_rows,
-                     int remap_rows_per_img, int remap_skip, int accumulate, void* workspace, size_t workspace_bytes,
-                     hipStream_t stream, float* colsum_out, int mode, const void* a16 = nullptr, void* c16 = nullptr, const void* b16 = nullptr,
-                     const float* rowscale = nullptr, int rows_per_group = 0) {
-    // layout 2 (weight gradient): a16 is the bf16 form of the SECOND operand (the layer input x); B may then be NULL
-    // layout 2: b16 is the bf16 form of the FIRST operand (dy); A may then be NULL
-    if (b16 && (mode != 2 || (layout != 2 && (K % 32 != 0 || !aligned16(b16))) || (layout == 2 && (reinterpret_cast<uintptr_t>(b16) & 7)))) return D2S_ERR_ARG;
-    if ((!A && !(a16 && layout != 2) && !(b16 && layout == 2)) || (!B && !(a16 && layout == 2) && !(b16 && layout != 2)) || (!C && !c16) || M <= 0 || N <= 0 || K <= 0 || layout < 0 || layout > 2 || mode < 0 || mode > 2) return D2S_ERR_ARG;
-    if ((a16 || c16) && (mode != 2 || (layout != 2 && accumulate) || remap_rows_per_img > 0)) return D2S_ERR_ARG;   // bf16 operands / copies exist in bf16 mode only
-    if (layout == 2 && c16) return D2S_ERR_ARG;
-    if (layout == 2 && a16) {
-        if ((reinterpret_cast<uintptr_t>(a16) & 7) != 0) return D2S_ERR_ARG;
+}  // extern "C"
+
+// Every rule that answers D2S_ERR_ARG, on the call as its entry filled it (p.epi is still the C-ABI code; p.vec_epilogue holds
+// epilogue_vec_ok(p) for the calls that gemm_split.hip's NT / NN path runs).  It runs before any launch and before the workspace is looked
+// at.  ARGS_REFUSED_LATE: the rules of gemm_split.hip's paths, which have always been tested after the workspace - a call that also
+// brings too little workspace is answered D2S_ERR_WORKSPACE (run_gemm).
+enum ArgCheck { ARGS_OK, ARGS_REFUSED, ARGS_REFUSED_LATE };
+static ArgCheck check_args(const GemmArgs& p, const GemmCall& c) {
+    const bool tn = c.layout == 2, bf16 = c.mode == 2;
+    if (c.layout < 0 || c.layout > 2 || c.mode < 0 || c.mode > 2 || p.M <= 0 || p.N <= 0 || p.K <= 0 || (!p.C && !p.c16)) return ARGS_REFUSED;
+    if (tn) {       // weight gradient: in bf16 mode either operand may come in bf16 (8-byte aligned), alone or beside its fp32 form
+        if ((c.dy16 || c.x16) && (!bf16 || ((reinterpret_cast<uintptr_t>(c.dy16) | reinterpret_cast<uintptr_t>(c.x16)) & 7))) return ARGS_REFUSED;
+        if ((!p.A && !c.dy16) || (!p.B && !c.x16) || p.c16) return ARGS_REFUSED;
+    } else {        // bf16 operands / copies exist in bf16 mode only: dense, 16-byte aligned, K (N for the copy) in whole 32-blocks
+        if ((p.a16 || p.b16 || p.c16) && !bf16) return ARGS_REFUSED;
+        if ((p.a16 || p.c16) && (c.accumulate || p.remap_rows_per_img > 0)) return ARGS_REFUSED;
+        if (((p.a16 || p.b16) && p.K % 32 != 0) || !aligned16(p.a16) || !aligned16(p.b16) || (p.c16 && (p.N % 32 != 0 || !aligned16(p.c16)))) return ARGS_REFUSED;
+        if ((!p.A && !p.a16) || (!p.B && !p.b16)) return ARGS_REFUSED;
     }
-    if ((a16 && layout != 2 && (K % 32 != 0 || !aligned16(a16))) || (c16 && (N % 32 != 0 || !aligned16(c16)))) return D2S_ERR_ARG;
-    int aux_bf16 = 0;       // bf16 data path: the GELU pre-activation saved / read in bf16 (d2s_gemm_f32_bf16io, codes 9 / 10)
-    if (epilogue == EPI_BIAS_GELU_Z16 || epilogue == EPI_MUL_GELU_GRAD_Z16) {
-        const float* z = epilogue == EPI_BIAS_GELU_Z16 ? aux_out : aux;
-        if (mode != 2 || layout == 2 || !z || (reinterpret_cast<uintptr_t>(z) & 7) || N % 4 != 0 || (epilogue == EPI_MUL_GELU_GRAD_Z16 && ldaux % 4 != 0) ||
-            (epilogue == EPI_BIAS_GELU_Z16 && ldc % 4 != 0))
-            return D2S_ERR_ARG;
-        aux_bf16 = 1;
-        epilogue = epilogue == EPI_BIAS_GELU_Z16 ? EPI_BIAS_GELU : EPI_MUL_GELU_GRAD;
+    int epi = p.epi;
+    if (epi == EPI_BIAS_GELU_Z16 || epi == EPI_MUL_GELU_GRAD_Z16) {      // bf16 data path: the GELU pre-activation saved / read in bf16
+        const float* z = epi == EPI_BIAS_GELU_Z16 ? p.aux_out : p.aux;
+        if (!bf16 || tn || !z || (reinterpret_cast<uintptr_t>(z) & 7) || p.N % 4 != 0 || (epi == EPI_MUL_GELU_GRAD_Z16 && p.ldaux % 4 != 0) ||
+            (epi == EPI_BIAS_GELU_Z16 && p.ldc % 4 != 0))
+            return ARGS_REFUSED;
+        epi = epi == EPI_BIAS_GELU_Z16 ? EPI_BIAS_GELU : EPI_MUL_GELU_GRAD;
     }
-    if (epilogue == EPI_BIAS_RESID_ROWSCALE) {      // reachable through d2s_gemm_f32_rowscale only
-        if (!rowscale || rows_per_group <= 0 || layout == 2 || accumulate || !aux) return D2S_ERR_ARG;
-    } else if (epilogue < EPI_NONE || epilogue > EPI_ACCUM) return D2S_ERR_ARG;
-    if ((epilogue == EPI_BIAS_RESID || epilogue == EPI_MUL_GELU_GRAD || epilogue == EPI_MUL_RELU_MASK ||
-         epilogue == EPI_BIAS_ROWADD) && !aux)
-        return D2S_ERR_ARG;
+    if (epi == EPI_BIAS_RESID_ROWSCALE) {      // reachable through d2s_gemm_f32_rowscale only
+        if (!p.rowscale || p.rows_per_group <= 0 || tn || c.accumulate || !p.aux) return ARGS_REFUSED;
+    } else if (epi < EPI_NONE || epi > EPI_ACCUM) return ARGS_REFUSED;
+    if ((epi == EPI_BIAS_RESID || epi == EPI_MUL_GELU_GRAD || epi == EPI_MUL_RELU_MASK || epi == EPI_BIAS_ROWADD) && !p.aux) return ARGS_REFUSED;
     // accumulate on the NT / NN layouts is the epilogue EPI_ACCUM: it does not combine with a bias, residual or activation epilogue
     // (the single-pass store would drop that epilogue, the split-K combine would drop the accumulation)
-    if (layout != 2 && accumulate && epilogue != EPI_NONE && epilogue != EPI_ACCUM) return D2S_ERR_ARG;
+    if (!tn && c.accumulate && epi != EPI_NONE && epi != EPI_ACCUM) return ARGS_REFUSED;
     // the output row remap belongs to the patch embedding's EPI_BIAS_ROWADD store; no other epilogue applies it
-    if (remap_rows_per_img > 0 && epilogue != EPI_BIAS_ROWADD) return D2S_ERR_ARG;
-    GemmArgs p;
-    p.aux_bf16 = aux_bf16;
-    p.A = A; p.B = B; p.C = C; p.bias = bias; p.aux = aux; p.aux_out = aux_out;
-    p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux;
-    p.M = M; p.N = N; p.K = K; p.epi = epilogue; p.aux_rows = aux_rows > 0 ? aux_rows : 1;
-    p.remap_rows_per_img = remap_rows_per_img; p.remap_skip = remap_skip;
-    p.colsum = nullptr; p.colsum_accumulate = accumulate;
-    p.a16 = a16; p.c16 = c16; p.b16 = b16;
-    p.rowscale = rowscale; p.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
-    {
-        p.stagger = 0;
-        p.vec_epilogue = 0;
+    if (p.remap_rows_per_img > 0 && epi != EPI_BIAS_ROWADD) return ARGS_REFUSED;
+    if (c.mode != 0 && (!tn || bf16)) {      // gemm_split.hip: bf16 pieces [rows][Kp], K rounded up to 32 (NT / NN) or 64 (TN)
+        const long Kp = tn ? (p.K + 63) / 64 * 64 : (p.K + 31) / 32 * 32;
+        if (p.M * Kp * 2 >= (1L << 32) || p.N * Kp * 2 >= (1L << 32)) return ARGS_REFUSED_LATE;      // per-thread byte offsets are 32-bit
+        if ((p.c16 || !p.C) && (!p.vec_epilogue || !bf16)) return ARGS_REFUSED_LATE;      // the bf16 copy is written by the 16-byte epilogue only
     }
-    const int alay = layout == 2 ? 1 : 0, blay = layout == 0 ? 0 : 1;
-    p.vecA = aligned16(A) && (lda % 4 == 0) && (alay == 0 ? (K % 4 == 0) : (M % 4 == 0));
-    p.vecB = aligned16(B) && (ldb % 4 == 0) && (blay == 0 ? (K % 4 == 0) : (N % 4 == 0));
-    if (mode != 0 && layout != 2) {
-        if (accumulate) p.epi = EPI_ACCUM;
-        p.k_per_slice = K;
-        p.slab_stride = 0;
-        return launch_split_gemm(p, layout == 1 ? 1 : 0, mode == 1 ? 3 : 1, workspace, workspace_bytes, stream);
-    }
-    if (layout == 2 && mode == 2) {
-        // wgrad in bf16 mode: transposing split of dy and x into K-contiguous bf16 pieces, K-sliced pieces kernel into fp32 slabs,
-        // the same ordered slab combine as the exact path; the bias gradient is a separate exact fp32 column-sum pass over dy.
-        const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-        int slices = split_tn_use_dma(M, N, K) ? split_tn_dma_slices(M, N, K) : splitk_slices(tiles, K);
-        const int Kp = ((K + 63) / 64) * 64;
-        int kper = (((Kp + slices - 1) / slices + 63) / 64) * 64;
-        slices = (Kp + kper - 1) / kper;      // never more than the query assumed
-        const size_t slab_bytes = ws_align(((size_t)(slices + 1) * M * N) * sizeof(float));
-        const size_t piece_bytes = ws_align(split_tn_pieces_bytes(1, M, N, K));
-        const size_t cs_bytes = (size_t)split_tn_colsum_partials(K) * M * sizeof(float);
-        if (!workspace || workspace_bytes < slab_bytes + piece_bytes + cs_bytes) return D2S_ERR_WORKSPACE;
-        unsigned char* wsb = static_cast<unsigned char*>(workspace);
-        p.k_per_slice = kper;
-        p.epi = EPI_NONE;
-        p.C = reinterpret_cast<float*>(wsb);
-        p.ldc = N;
-        p.slab_stride = (long)M * N;
-        p.remap_rows_per_img = 0;
-        float* cs_part = colsum_out ? reinterpret_cast<float*>(wsb + slab_bytes + piece_bytes) : nullptr;
-        int cs_parts = 0;
-        int rc = launch_split_gemm_tn(p, 1, slices, wsb + slab_bytes, cs_part, stream, &cs_parts);
-        if (rc != D2S_OK) return rc;
-        const long total = (long)M * N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                           reinterpret_cast<const float*>(wsb), C, ldc, M, N, slices, (long)M * N, accumulate,
-                           static_cast<const float*>(nullptr), static_cast<float*>(nullptr));
-        if (colsum_out)   // ordered fold of the per-64-token partials that the split pass of dy produced (exact fp32)
-            hipLaunchKernelGGL(colsum_fold_wide_kernel, dim3((M + 15) / 16), dim3(1024), 0, stream, cs_part, M, cs_parts,
-                               colsum_out, accumulate);
-        return d2s_check_launch();
-    }
-    const ExactPlan plan = exact_plan(layout, M, N, K);
-    const Tile tile = plan.tile;
-    const int tiles = plan.tiles, slices = plan.slices;
-    p.k_per_slice = plan.k_per_slice;
-    p.slab_stride = 0;
-    float* realC = C;
-    if (accumulate && layout != 2 && p.epi == EPI_NONE) p.epi = EPI_ACCUM;
-    const GemmArgs real = p;              // output and epilogue operands as the caller gave them (used by the NT / NN slab combine)
-    if (slices > 1 && layout != 2) {
-        const size_t need = (size_t)slices * M * N * sizeof(float);
-        if (!workspace || workspace_bytes < need) return D2S_ERR_WORKSPACE;
-        p.C = static_cast<float*>(workspace);
-        p.ldc = N;
-        p.slab_stride = (long)M * N;
-        p.remap_rows_per_img = 0;
-    } else if (slices > 1) {
-        const size_t need = ((size_t)slices * M * N + (size_t)slices * M) * sizeof(float);
-        if (!workspace || workspace_bytes < need) return D2S_ERR_WORKSPACE;
-        p.C = static_cast<float*>(workspace);
-        p.ldc = N;
-        p.slab_stride = (long)M * N;
-        p.remap_rows_per_img = 0;
-        if (colsum_out) p.colsum = static_cast<float*>(workspace) + (size_t)slices * M * N;
+    return ARGS_OK;
+}
+
+// the matrix kernel writes one [M][N] slab per K slice into the workspace; a combine folds them into the output afterwards
+static void redirect_to_slabs(GemmArgs& p, void* workspace) {
+    p.C = static_cast<float*>(workspace);
+    p.ldc = p.N;
+    p.slab_stride = (long)p.M * p.N;
+    p.remap_rows_per_img = 0;
+}
+
+// Ordered combine of `slices` slabs at the head of the workspace into `out`: NT / NN with the epilogue that the single-pass kernel would
+// have applied; TN plain or accumulating, 16 bytes per thread where the output allows and the caller lets it, with the fused bias-gradient
+// slabs (colsum_slabs, may be null) folded by the tail threads.
+static void combine_slabs(const GemmArgs& out, const GemmCall& c, int slices, const float* colsum_slabs, bool may_vec) {
+    const float* ws = static_cast<const float*>(c.workspace);
+    const long mn = (long)out.M * out.N, tail = colsum_slabs ? out.M : 0;
+    const dim3 block(256);
+    if (c.layout != 2) {
+        hipLaunchKernelGGL(splitk_reduce_epi_kernel, dim3((unsigned)((mn + 255) / 256)), block, 0, c.stream, out, ws, slices, mn);
+    } else if (may_vec && (out.N % 4 == 0) && (out.ldc % 4 == 0) && aligned16(out.C) && aligned16(ws) && (mn % 4 == 0)) {
+        const long total = (long)out.M * (out.N / 4) + tail;
+        hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, c.stream, ws, out.C, out.ldc, out.M, out.N,
+                           slices, mn, c.accumulate, colsum_slabs, colsum_slabs ? c.colsum_out : nullptr);
     } else {
-        if (accumulate) p.epi = EPI_ACCUM;
-        p.colsum = colsum_out;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn + tail + 255) / 256)), block, 0, c.stream, ws, out.C, out.ldc, out.M, out.N,
+                           slices, mn, c.accumulate, colsum_slabs, colsum_slabs ? c.colsum_out : nullptr);
+    }
+}
+
+// the exact kernels of this file: `out` is the call as the caller gave it
+static int launch_exact(const GemmArgs& out, const GemmCall& c, const ExactPlan& pl) {
+    GemmArgs p = out;
+    p.k_per_slice = pl.k_per_slice;
+    if (pl.slices > 1) {
+        redirect_to_slabs(p, c.workspace);
+        if (c.colsum_out) p.colsum = p.C + (size_t)pl.slices * p.M * p.N;      // TN: the fused bias-gradient slabs follow the C slabs
+    } else {
+        if (c.accumulate) p.epi = EPI_ACCUM;
+        p.colsum = c.colsum_out;
     }
     p.vec_epilogue = (epilogue_vec_ok(p) && (p.slab_stride % 4 == 0)) ? 1 : 0;
-    dim3 grid(tiles, 1, slices), block(256);
+    const dim3 grid(pl.tiles, 1, pl.slices);
     // guard-free instantiation: both operands 16-byte loadable, every K slice a whole number of K-steps, and at least one full
     // 4-row chunk where rows are the contiguous dimension (the clamp needs rows - 4 >= 0)
-    const bool fast = p.vecA && p.vecB && (K % BK == 0) && (alay == 0 || M >= 4) && (blay == 0 || N >= 4);
-    if (layout == 0) launch_gemm<0, 0>(tile, grid, stream, p, fast);
-    else if (layout == 1) launch_gemm<0, 1>(tile, grid, stream, p, fast);
-    else launch_gemm<1, 1>(tile, grid, stream, p, fast);
-    if (slices > 1 && layout != 2) {
-        const long total = (long)M * N;
-        hipLaunchKernelGGL(splitk_reduce_epi_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, stream, real,
-                           static_cast<const float*>(workspace), slices, (long)M * N);
-    } else if (slices > 1) {
-        if ((N % 4 == 0) && (ldc % 4 == 0) && aligned16(realC) && aligned16(workspace) && (((long)M * N) % 4 == 0)) {
-            const long total = (long)M * (N / 4) + (colsum_out ? M : 0);
-            hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, stream,
-                               static_cast<const float*>(workspace), realC, ldc, M, N, slices, (long)M * N, accumulate, p.colsum, colsum_out);
-        } else {
-            const long total = (long)M * N + (colsum_out ? M : 0);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), block, 0, stream,
-                               static_cast<const float*>(workspace), realC, ldc, M, N, slices, (long)M * N, accumulate,
-                               p.colsum, colsum_out);
-        }
-    }
+    const bool fast = p.vecA && p.vecB && (p.K % BK == 0) && (c.layout != 2 || p.M >= 4) && (c.layout == 0 || p.N >= 4);
+    if (c.layout == 0) launch_gemm<0, 0>(pl.tile, grid, c.stream, p, fast);
+    else if (c.layout == 1) launch_gemm<0, 1>(pl.tile, grid, c.stream, p, fast);
+    else launch_gemm<1, 1>(pl.tile, grid, c.stream, p, fast);
+    if (pl.slices > 1) combine_slabs(out, c, pl.slices, p.colsum, true);
     return d2s_check_launch();
 }
 
+// wgrad in bf16 mode: the matrix kernel of the plan (gemm_split.hip) into fp32 slabs, the same ordered slab combine as the exact path (in
+// its dword form, as this path has always run it); the bias gradient is an ordered fold of the partial rows that came with the slabs.
+static int launch_wgrad16(const GemmArgs& out, const GemmArgs& slabs, const GemmCall& c, const Wgrad16Plan& pl) {
+    const int rc = launch_wgrad16_matrix(slabs, c, pl);
+    if (rc != D2S_OK) return rc;
+    combine_slabs(out, c, pl.slices, nullptr, false);
+    if (c.colsum_out)
+        hipLaunchKernelGGL(colsum_fold_wide_kernel, dim3((out.M + 15) / 16), dim3(1024), 0, c.stream,
+                           reinterpret_cast<const float*>(static_cast<const unsigned char*>(c.workspace) + pl.colsum_offset), out.M, pl.colsum_parts,
+                           c.colsum_out, c.accumulate);
+    return d2s_check_launch();
+}
+
+// One call: refuse, plan, check the workspace against the plan's `bytes`, launch.
+static int run_gemm(GemmArgs p, const GemmCall& c) {
+    const bool tn = c.layout == 2, split_nt = c.mode != 0 && !tn;
+    p.vec_epilogue = split_nt && epilogue_vec_ok(p) ? 1 : 0;      // the other paths decide it once the output may have moved to slabs
+    const ArgCheck args = check_args(p, c);
+    if (args == ARGS_REFUSED) return D2S_ERR_ARG;
+    // what the kernels read beside the entry's fields
+    if (p.epi == EPI_BIAS_GELU_Z16 || p.epi == EPI_MUL_GELU_GRAD_Z16) {
+        p.aux_bf16 = 1;
+        p.epi = p.epi == EPI_BIAS_GELU_Z16 ? EPI_BIAS_GELU : EPI_MUL_GELU_GRAD;
+    }
+    if (!tn && c.accumulate) p.epi = EPI_ACCUM;
+    if (p.aux_rows <= 0) p.aux_rows = 1;
+    if (p.rows_per_group <= 0) p.rows_per_group = 1;
+    p.colsum_accumulate = c.accumulate;
+    p.vecA = aligned16(p.A) && (p.lda % 4 == 0) && (tn ? (p.M % 4 == 0) : (p.K % 4 == 0));
+    p.vecB = aligned16(p.B) && (p.ldb % 4 == 0) && (c.layout == 0 ? (p.K % 4 == 0) : (p.N % 4 == 0));
+    const bool no_ws = !c.workspace;
+    if (split_nt) {
+        const SplitPlan pl = split_plan(p, c.mode == 1 ? 3 : 1);
+        if (no_ws || c.workspace_bytes < pl.bytes) return D2S_ERR_WORKSPACE;
+        return args == ARGS_OK ? launch_split(p, c, pl) : D2S_ERR_ARG;
+    }
+    if (tn && c.mode == 2) {
+        GemmArgs slabs = p;
+        redirect_to_slabs(slabs, c.workspace);
+        slabs.epi = EPI_NONE;
+        const Wgrad16Plan pl = wgrad16_plan(slabs, c);
+        if (no_ws || c.workspace_bytes < pl.bytes) return D2S_ERR_WORKSPACE;
+        return args == ARGS_OK ? launch_wgrad16(p, slabs, c, pl) : D2S_ERR_ARG;
+    }
+    const ExactPlan pl = exact_plan(c.layout, p.M, p.N, p.K);
+    if (pl.slices > 1 && (no_ws || c.workspace_bytes < pl.bytes)) return D2S_ERR_WORKSPACE;
+    return launch_exact(p, c, pl);
+}
+
+extern "C" {
+
+// layout 0 = NT (A[M,K], B[N,K]); 1 = NN (A[M,K], B[K,N]); 2 = TN (A[K,M], B[K,N]).
+// epilogue: see enum Epi.  accumulate != 0: C += result (TN; on NT / NN it is EPI_ACCUM and goes with epilogue 0 or 8 only).
+// remap_*: see GemmArgs (EPI_BIAS_ROWADD only).
 int d2s_gemm_f32(int layout, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                  int K, int epilogue, const float* bias, const float* aux, long ldaux, float* aux_out, int aux_rows,
                  int remap_rows_per_img, int remap_skip, int accumulate, int mode, void* workspace, size_t workspace_bytes,
                  hipStream_t stream) {
-    return gemm_impl(layout, A, lda, B, ldb, C, ldc, M, N, K, epilogue, bias, aux, ldaux, aux_out, aux_rows, remap_rows_per_img,
-                     remap_skip, accumulate, workspace, workspace_bytes, stream, nullptr, mode);
+    GemmArgs p{};
+    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K;
+    p.epi = epilogue; p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.aux_out = aux_out; p.aux_rows = aux_rows;
+    p.remap_rows_per_img = remap_rows_per_img; p.remap_skip = remap_skip;
+    GemmCall c{};
+    c.layout = layout; c.mode = mode; c.accumulate = accumulate;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return run_gemm(p, c);
 }
 
 // d2s_gemm_f32 in mode 2 (bf16 operands) with bf16 side channels: a_bf16 (optional) = the A operand already rounded to bf16, dense
@@ -947,8 +919,15 @@ int d2s_gemm_f32_bf16io(int layout, const float* A, long lda, const float* B, lo
                         int epilogue, const float* bias, const float* aux, long ldaux, float* aux_out, const void* a_bf16, const void* b_bf16,
                         void* c_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (layout == 2) return D2S_ERR_ARG;      // weight gradients with a bf16 input: d2s_linear_wgrad_f32_bf16x
-    return gemm_impl(layout, A, lda, B, ldb, C, ldc, M, N, K, epilogue, bias, aux, ldaux, aux_out, 0, 0, 0, 0, workspace, workspace_bytes,
-                     stream, nullptr, 2, a_bf16, c_bf16, b_bf16);
+    GemmArgs p{};
+    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K;
+    p.epi = epilogue; p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.aux_out = aux_out;
+    p.a16 = a_bf16; p.b16 = b_bf16; p.c16 = c_bf16;
+    GemmCall c{};
+    c.layout = layout; c.mode = 2;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return run_gemm(p, c);
 }
 
 // Stochastic depth in the residual GEMMs (proj, fc2): C = rowscale[m / rows_per_group] * (A B^T + bias[n]) + aux[m][n], epilogue kind
@@ -958,8 +937,15 @@ int d2s_gemm_f32_rowscale(int layout, const float* A, long lda, const float* B, 
                           const float* bias, const float* aux, long ldaux, const float* rowscale, int rows_per_group, int mode,
                           const void* a_bf16, const void* b_bf16, void* c_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (layout == 2 || !rowscale || rows_per_group <= 0) return D2S_ERR_ARG;
-    return gemm_impl(layout, A, lda, B, ldb, C, ldc, M, N, K, EPI_BIAS_RESID_ROWSCALE, bias, aux, ldaux, nullptr, 0, 0, 0, 0, workspace,
-                     workspace_bytes, stream, nullptr, mode, a_bf16, c_bf16, b_bf16, rowscale, rows_per_group);
+    GemmArgs p{};
+    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K;
+    p.epi = EPI_BIAS_RESID_ROWSCALE; p.bias = bias; p.aux = aux; p.ldaux = ldaux; p.rowscale = rowscale; p.rows_per_group = rows_per_group;
+    p.a16 = a_bf16; p.b16 = b_bf16; p.c16 = c_bf16;
+    GemmCall c{};
+    c.layout = layout; c.mode = mode;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return run_gemm(p, c);
 }
 
 // nn.Linear backward w.r.t. its parameters in one pass over dy:  dW[n_out, n_in] (+)= dy^T x,  db[n_out] (+)= column sums of dy.
@@ -969,8 +955,14 @@ size_t d2s_linear_wgrad_workspace_bytes(int tokens, int n_out, int n_in, int mod
 }
 int d2s_linear_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, float* dW, long lddw, float* db, int tokens,
                          int n_out, int n_in, int accumulate, int mode, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    return gemm_impl(2, dy, lddy, x, ldx, dW, lddw, n_out, n_in, tokens, EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0,
-                     accumulate, workspace, workspace_bytes, stream, db, mode);
+    GemmArgs p{};
+    p.A = dy; p.lda = lddy; p.B = x; p.ldb = ldx; p.C = dW; p.ldc = lddw;
+    p.M = n_out; p.N = n_in; p.K = tokens;
+    p.epi = EPI_NONE;
+    GemmCall c{};
+    c.layout = 2; c.mode = mode; c.accumulate = accumulate; c.colsum_out = db;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return run_gemm(p, c);
 }
 // The same in mode 2 with the layer input given in bf16 only (x_bf16 [tokens][n_in], row stride ldx elements): what the bf16 data path
 // saved for the backward instead of the fp32 activation.  dy is fp32 (its exact column sums are the bias gradient) or, when the kernel that
@@ -981,8 +973,14 @@ int d2s_linear_wgrad_f32(const float* dy, long lddy, const float* x, long ldx, f
 int d2s_linear_wgrad_f32_bf16x(const float* dy, const void* dy_bf16, long lddy, const void* x_bf16, long ldx, float* dW, long lddw, float* db,
                                int tokens, int n_out, int n_in, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (!x_bf16 || (!dy && !dy_bf16)) return D2S_ERR_ARG;
-    return gemm_impl(2, dy, lddy, nullptr, ldx, dW, lddw, n_out, n_in, tokens, EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0,
-                     accumulate, workspace, workspace_bytes, stream, db, 2, x_bf16, nullptr, dy_bf16);
+    GemmArgs p{};
+    p.A = dy; p.lda = lddy; p.ldb = ldx; p.C = dW; p.ldc = lddw;
+    p.M = n_out; p.N = n_in; p.K = tokens;
+    p.epi = EPI_NONE;
+    GemmCall c{};
+    c.layout = 2; c.mode = 2; c.accumulate = accumulate; c.colsum_out = db; c.dy16 = dy_bf16; c.x16 = x_bf16;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return run_gemm(p, c);
 }
 
 // dst[C][R] = src[R][C]^T (dense row-major): the k-contiguous copy of a Linear weight for the input-gradient GEMM.

@@ -383,15 +383,6 @@ __global__ __launch_bounds__(256, 2) void gemm_pieces_nt_kernel(GemmArgs p, Piec
 //     the buffer goes straight back to the DMA.
 // An LDS-DMA instruction writes wave-uniform base + lane * 16 B, so the LDS image is lane-linear [row][BK bf16]; the bank swizzle
 // (16-byte chunk index XOR row / rows-per-256-B) is applied to the per-lane SOURCE address and again on the fragment read.
-inline int gemm_cus() {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
-    return cus;
-}
-
 template <int BK>
 __device__ __forceinline__ int dma_swz(int row) {
     constexpr int CPR = BK / 8, RPB = 256 / (BK * 2);      // 16-byte chunks per row, rows per 256-byte bank row
@@ -659,29 +650,40 @@ inline void launch_dma(const GemmArgs& pv, const PieceArgs& q, hipStream_t strea
     hipLaunchKernelGGL((gemm_bf16_dma_kernel<WGN, BK, NS, TOK>), dim3(grid), dim3(WGN * 128), lds, stream, pv, q);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// gemm_pieces_nt_kernel's dynamic LDS: the operand images of one K-step of 32 (measured faster than 16 on every model shape), or the
+// epilogue's staging where that is larger
+inline size_t pieces_lds_bytes(int split) {
+    const size_t lds = (size_t)split * (SBM + SBN) * (32 + 8) * sizeof(__bf16), stage = 4 * epi_stage_floats(2) * sizeof(float);
+    return lds < stage ? stage : lds;
+}
+
+// stage 1 for one call: A's pieces from p.A [M][K] (unless the kernel converts A itself or the caller gave them), then B's from p.B, [N][K]
+// or, for the dgrad layout, [K][N] (unless the caller gave them)
+template <int SPLIT>
+inline void launch_split_passes(const GemmArgs& p, const GemmCall& c, const SplitPlan& pl, __bf16* Ap, __bf16* Bp) {
+    const int Kp = pl.Kp;
+    const long ea = (long)p.M * (Kp / 4), eb = (long)p.N * (Kp / 4);
+    dim3 block(256);
+    if (pl.a_from == A_PRESPLIT) hipLaunchKernelGGL(split_rows_kernel<SPLIT>, dim3((unsigned)((ea + 255) / 256)), block, 0, c.stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA);
+    if (pl.b_from_b16) { /* nothing to convert */ }
+    else if (c.layout == 1) hipLaunchKernelGGL(split_cols_kernel<SPLIT>, dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, c.stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
+    else hipLaunchKernelGGL(split_rows_kernel<SPLIT>, dim3((unsigned)((eb + 255) / 256)), block, 0, c.stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB);
+}
 
 }  // namespace
 
 namespace d2s_gemm {
 
-size_t split_workspace_bytes(int split, int M, int N, int K) {
-    const size_t Kp = (size_t)((K + 31) / 32) * 32;
-    return align256((size_t)split * M * Kp * sizeof(__bf16)) + align256((size_t)split * N * Kp * sizeof(__bf16));
-}
-
-// C[M,N] = epi(A[M,K] * B^T) with B given as [N][K] (b_cols = 0) or as [K][N] (b_cols = 1, the dgrad layout).
-int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    const int Kp = ((p.K + 31) / 32) * 32;
-    if (!workspace || workspace_bytes < split_workspace_bytes(split, p.M, p.N, p.K)) return D2S_ERR_WORKSPACE;
-    if ((long)p.M * Kp * 2 >= (1L << 32) || (long)p.N * Kp * 2 >= (1L << 32)) return D2S_ERR_ARG;   // per-thread byte offsets are 32-bit
-    __bf16* Ap = static_cast<__bf16*>(workspace);
-    __bf16* Bp = reinterpret_cast<__bf16*>(static_cast<unsigned char*>(workspace) + align256((size_t)split * p.M * Kp * sizeof(__bf16)));
+// NT / NN in modes 1 (split = 3) and 2 (split = 1): every branch choice of the call.  p.vec_epilogue holds epilogue_vec_ok(p) (run_gemm);
+// the size query passes a GemmArgs with nothing but M, N, K - `bytes` depends on nothing else.
+SplitPlan split_plan(const GemmArgs& p, int split) {
+    SplitPlan pl;
+    pl.split = split;
+    pl.Kp = ((p.K + 31) / 32) * 32;
+    pl.b_offset = align256((size_t)split * p.M * pl.Kp * sizeof(__bf16));
+    pl.bytes = pl.b_offset + align256((size_t)split * p.N * pl.Kp * sizeof(__bf16));
     // the caller's cached bf16 form of the B operand, always [N][K] k-contiguous (for the dgrad layout: W^T), K % 32 == 0
-    const bool have_b16 = p.b16 != nullptr && split == 1;
-    if (have_b16) Bp = static_cast<__bf16*>(const_cast<void*>(p.b16));
-    const long ea = (long)p.M * (Kp / 4), eb = (long)p.N * (Kp / 4);
-    dim3 block(256);
+    pl.b_from_b16 = p.b16 != nullptr && split == 1;
     // The activation operand can be converted inside the matrix kernel (read as fp32 with 16-byte loads, no split pass over it) instead
     // of being pre-split.  bf16x3 (mode 1): alone, a GEMM with <= 4 column tiles runs 9-12 % faster that way and one with 9-12 column tiles
     // 4 % slower (each panel element is re-split per column tile); inside the training step pre-splitting is 0.5-1 % faster overall, so
@@ -692,10 +694,10 @@ int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace,
     // Without a caller-provided bf16 A the kernel needs a conversion pass over A first (6 bytes per element of A against the 2 of reading
     // it in the matrix kernel): that pays from N ~ 900 on (measured: DeiT-B fc1 / qkv yes, proj / fc2 no).
     const bool have_a16 = p.a16 != nullptr && split == 1;      // the caller's bf16 copy of A is the piece matrix (Kp == K)
-    const bool dma_shape = split == 1 && p.M >= 2048 && p.N >= 128 && epilogue_vec_ok(p) && (have_a16 || p.N >= 1024);
+    const bool dma_shape = split == 1 && p.M >= 2048 && p.N >= 128 && p.vec_epilogue && (have_a16 || p.N >= 1024);
     bool dma_wide = false;
     if (dma_shape) {
-        if (Kp % 64 == 0 && p.N >= 256) {
+        if (pl.Kp % 64 == 0 && p.N >= 256) {
             // residency rounds of each grid (256 CUs; one 256x256 or two 256x128 workgroups per CU) x relative cost of a tile
             const long t256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256), t128 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
             const int cus = gemm_cus();
@@ -707,64 +709,34 @@ int launch_split_gemm(const GemmArgs& p, int b_cols, int split, void* workspace,
             dma_wide = c256 <= c128;
         }
     }
-    if ((p.c16 || !p.C) && (!epilogue_vec_ok(p) || split != 1)) return D2S_ERR_ARG;      // the bf16 copy is written by the 16-byte epilogue only
-    if (!p.A && !have_a16) return D2S_ERR_ARG;
-    if (have_a16) Ap = static_cast<__bf16*>(const_cast<void*>(p.a16));
     const bool af32 = !have_a16 && p.vecA && split == 1 && col_tiles <= 12 && !dma_shape;
-    if (split == 3) {
-        if (!af32) hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)((ea + 255) / 256)), block, 0, stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA);
-        if (b_cols) hipLaunchKernelGGL(split_cols_kernel<3>, dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
-        else hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)((eb + 255) / 256)), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB);
-    } else {
-        if (!af32 && !have_a16) hipLaunchKernelGGL(split_rows_kernel<1>, dim3((unsigned)((ea + 255) / 256)), block, 0, stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA);
-        if (have_b16) { /* nothing to convert */ }
-        else if (b_cols) hipLaunchKernelGGL(split_cols_kernel<1>, dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
-        else hipLaunchKernelGGL(split_rows_kernel<1>, dim3((unsigned)((eb + 255) / 256)), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB);
-    }
-    if (dma_shape && !af32) {
-        GemmArgs pb = p;
-        pb.vec_epilogue = 1;
-        pb.k_per_slice = Kp;
-        pb.slab_stride = 0;
-        PieceArgs qb{Ap, Bp, Kp};
-        if (dma_wide) launch_dma<4, 64, 2>(pb, qb, stream);
-        else launch_dma<2, 32, 3>(pb, qb, stream);
-        return d2s_check_launch();
-    }
-    const int tiles = ((p.M + SBM - 1) / SBM) * ((p.N + SBN - 1) / SBN);
-    size_t lds = (size_t)split * (SBM + SBN) * (32 + 8) * sizeof(__bf16);      // K-step 32 (measured faster than 16 on every model shape)
-    if (lds < 4 * epi_stage_floats(2) * sizeof(float)) lds = 4 * epi_stage_floats(2) * sizeof(float);
-    GemmArgs pv = p;
-    pv.vec_epilogue = epilogue_vec_ok(p) ? 1 : 0;
-    pv.k_per_slice = Kp;      // one K slice over the padded reduction length
-    pv.slab_stride = 0;
-    PieceArgs q{Ap, Bp, Kp};
-    if (af32) hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, true>), dim3(tiles), block, lds, stream, pv, q);
-    else if (split == 3) hipLaunchKernelGGL((gemm_pieces_nt_kernel<3, 32, false>), dim3(tiles), block, lds, stream, pv, q);
-    else hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, false>), dim3(tiles), block, lds, stream, pv, q);
-    return d2s_check_launch();
+    pl.a_from = have_a16 ? A_FROM_A16 : af32 ? A_IN_KERNEL : A_PRESPLIT;
+    pl.kernel = split == 3 ? SK_PIECES_X3 : af32 ? SK_PIECES_AF32 : !dma_shape ? SK_PIECES_X1 : dma_wide ? SK_DMA_256x256 : SK_DMA_256x128;
+    return pl;
 }
 
-// wgrad on the bf16 matrix cores (mode 2): C slabs[z][M][N] = A^T B over K slice z, with A given as [K][M] and B as [K][N] (both
-// token-major).  Both operands go through the transposing split pass, so the matrix kernel sees K-contiguous pieces as usual.
-// The caller (gemm_f32.hip) combines the slabs in slab order.  Workspace: pieces only (the slabs are the caller's).
-// The pieces are [rows][Kp] with Kp = K rounded up to 64 (zero padded), so that either matrix kernel can slice them.
-static inline int tn_kp(int K) { return ((K + 63) / 64) * 64; }
-size_t split_tn_pieces_bytes(int split, int M, int N, int K) {
-    return align256((size_t)split * M * tn_kp(K) * sizeof(__bf16)) + align256((size_t)split * N * tn_kp(K) * sizeof(__bf16));
-}
-// 256x256 LDS-DMA tiles for weight gradients whose output fills them (every DeiT-S / DeiT-B Linear; not the predictor's narrow layers)
-bool split_tn_use_dma(int M, int N, int K) {
-    const long padded = (long)((M + 255) / 256) * 256 * ((N + 255) / 256) * 256;
-    return M >= 256 && N >= 256 && K >= 2048 && padded * 5 <= (long)M * N * 6;      // at most 20 % of the tile area past the edges
-}
-// K slices for the LDS-DMA form: about one 256x256 workgroup per CU, at least 8 slabs of 64 per slice
-int split_tn_dma_slices(int M, int N, int K) {
-    const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-    int slices = (gemm_cus() + tiles / 2) / tiles;
-    const int max_slices = tn_kp(K) / 512;
-    if (slices > max_slices) slices = max_slices;
-    return slices < 1 ? 1 : slices;
+// C[M,N] = epi(A[M,K] * B^T) with B given as [N][K] (NT) or as [K][N] (NN, the dgrad layout): the split passes the plan names, then its
+// matrix kernel over one K slice of the padded reduction length.
+int launch_split(const GemmArgs& p, const GemmCall& c, const SplitPlan& pl) {
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    __bf16* Ap = pl.a_from == A_FROM_A16 ? static_cast<__bf16*>(const_cast<void*>(p.a16)) : reinterpret_cast<__bf16*>(ws);
+    __bf16* Bp = pl.b_from_b16 ? static_cast<__bf16*>(const_cast<void*>(p.b16)) : reinterpret_cast<__bf16*>(ws + pl.b_offset);
+    if (pl.split == 3) launch_split_passes<3>(p, c, pl, Ap, Bp);
+    else launch_split_passes<1>(p, c, pl, Ap, Bp);
+    GemmArgs pv = p;      // vec_epilogue: as run_gemm set it (the LDS-DMA kernels are chosen only where it is 1)
+    pv.k_per_slice = pl.Kp;
+    pv.slab_stride = 0;
+    const PieceArgs q{Ap, Bp, pl.Kp};
+    const dim3 tiles(((p.M + SBM - 1) / SBM) * ((p.N + SBN - 1) / SBN)), block(256);
+    const size_t lds = pieces_lds_bytes(pl.split);
+    switch (pl.kernel) {
+        case SK_DMA_256x256: launch_dma<4, 64, 2>(pv, q, c.stream); break;
+        case SK_DMA_256x128: launch_dma<2, 32, 3>(pv, q, c.stream); break;
+        case SK_PIECES_AF32: hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, true>), tiles, block, lds, c.stream, pv, q); break;
+        case SK_PIECES_X3: hipLaunchKernelGGL((gemm_pieces_nt_kernel<3, 32, false>), tiles, block, lds, c.stream, pv, q); break;
+        case SK_PIECES_X1: hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, false>), tiles, block, lds, c.stream, pv, q); break;
+    }
+    return d2s_check_launch();
 }
 
 // Per-64-token partial column sums of a token-major bf16 matrix, [K / 64][R] floats, summed in the order split_cols_kernel uses (four runs
@@ -803,59 +775,86 @@ __global__ __launch_bounds__(256) void colsum_tok_kernel(const ST* __restrict__ 
     }
 }
 
-// colsum_part (optional, [split_tn_colsum_partials(K)][M] floats): per-64-token partial column sums of A (= dy), produced by the split
-// pass that reads dy anyway; the caller folds them in order into the bias gradient.
-int split_tn_colsum_partials(int K) { return tn_kp(K) / 64; }
-int launch_split_gemm_tn(const GemmArgs& p, int split, int slices, void* pieces_ws, float* colsum_part, hipStream_t stream, int* colsum_parts) {
-    *colsum_parts = split_tn_colsum_partials(p.K);      // partial rows written to colsum_part (the caller folds that many)
-    const int Kp = tn_kp(p.K);
-    if (split != 1) return D2S_ERR_ARG;
-    if ((long)p.M * Kp * 2 >= (1L << 32) || (long)p.N * Kp * 2 >= (1L << 32)) return D2S_ERR_ARG;
-    __bf16* Ap = static_cast<__bf16*>(pieces_ws);
-    __bf16* Bp = reinterpret_cast<__bf16*>(static_cast<unsigned char*>(pieces_ws) + align256((size_t)split * p.M * Kp * sizeof(__bf16)));
-    dim3 block(256);
+// wgrad on the bf16 matrix cores (mode 2): C slabs[z][M][N] = A^T B over K slice z, with A = dy given as [K][M] and B = x as [K][N] (both
+// token-major).  Unless the matrix kernel reads them as they lie, both operands go through the transposing split pass, so that it sees
+// K-contiguous pieces as usual: [rows][Kp] with Kp = K rounded up to 64 (zero padded), so that either matrix kernel can slice them.
+// The caller (gemm_f32.hip) combines the slabs in slab order and folds the bias gradient's partial rows.
+
+// 256x256 LDS-DMA tiles for weight gradients whose output fills them (every DeiT-S / DeiT-B Linear; not the predictor's narrow layers)
+static bool split_tn_use_dma(int M, int N, int K) {
+    const long padded = (long)((M + 255) / 256) * 256 * ((N + 255) / 256) * 256;
+    return M >= 256 && N >= 256 && K >= 2048 && padded * 5 <= (long)M * N * 6;      // at most 20 % of the tile area past the edges
+}
+
+// Every branch choice and workspace figure of the call.  `p` is the argument block with its output redirected to the slabs (p.C = the
+// workspace, ldc = N, slab_stride = M * N); the size query passes nothing but M, N, K - `bytes` depends on nothing else.
+Wgrad16Plan wgrad16_plan(const GemmArgs& p, const GemmCall& c) {
+    Wgrad16Plan pl;
+    pl.Kp = ((p.K + 63) / 64) * 64;
+    const bool dma = split_tn_use_dma(p.M, p.N, p.K);
+    if (dma) {      // K slices for the LDS-DMA form: about one 256x256 workgroup per CU, at least 8 slabs of 64 per slice
+        const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256), max_slices = pl.Kp / 512;
+        int slices = (gemm_cus() + tiles / 2) / tiles;
+        if (slices > max_slices) slices = max_slices;
+        pl.slices_asked = slices < 1 ? 1 : slices;
+    } else {
+        pl.slices_asked = splitk_slices(((p.M + 127) / 128) * ((p.N + 127) / 128), p.K);
+    }
+    pl.k_per_slice = (((pl.Kp + pl.slices_asked - 1) / pl.slices_asked + 63) / 64) * 64;
+    pl.slices = (pl.Kp + pl.k_per_slice - 1) / pl.k_per_slice;      // never more than asked for
+    // the slabs are sized for the slices asked for (+ 1), whatever the rounding to K blocks left of them
+    pl.piece_offset = align256((size_t)(pl.slices_asked + 1) * p.M * p.N * sizeof(float));
+    pl.b_offset = pl.piece_offset + align256((size_t)p.M * pl.Kp * sizeof(__bf16));
+    pl.colsum_offset = pl.b_offset + align256((size_t)p.N * pl.Kp * sizeof(__bf16));
+    pl.bytes = pl.colsum_offset + (size_t)(pl.Kp / 64) * p.M * sizeof(float);      // one partial row per 64 tokens
+    pl.vec_epilogue = epilogue_vec_ok(p) && p.slab_stride % 4 == 0;
     // Both operands at hand in bf16 (the bf16 data path's fc1 / qkv, and proj / fc2 where the caller kept the bf16 forms): the matrix kernel
     // reads them token-major as they lie (gemm_bf16_dma_kernel<.., TOK>) - no transposing pass, no piece matrices.
-    if (p.b16 && p.a16 && p.K % 64 == 0 && p.M % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
-        (reinterpret_cast<uintptr_t>(p.b16) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.a16) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && split_tn_use_dma(p.M, p.N, p.K) &&
-        epilogue_vec_ok(p) && p.slab_stride % 4 == 0 && p.k_per_slice % 64 == 0 && (long)p.K * p.lda * 2 < (1L << 32) && (long)p.K * p.ldb * 2 < (1L << 32)) {
-        GemmArgs pt = p;
-        pt.colsum = nullptr;
+    const bool tok = c.dy16 && c.x16 && p.K % 64 == 0 && p.M % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && aligned16(c.dy16) &&
+                     aligned16(c.x16) && aligned16(p.A) && dma && pl.vec_epilogue && (long)p.K * p.lda * 2 < (1L << 32) && (long)p.K * p.ldb * 2 < (1L << 32);
+    pl.kernel = tok ? WK_TOKEN_MAJOR : dma && pl.vec_epilogue ? WK_DMA_PIECES : WK_PIECES;      // k_per_slice is whole 64-deep blocks, as both DMA forms need
+    // the bias gradient: per-64-token partial sums of dy from the pass that reads it, or, token-major with dy in bf16 only, one row per K
+    // slice from the matrix kernel itself
+    pl.colsum_parts = tok && !p.A ? pl.slices : pl.Kp / 64;
+    return pl;
+}
+
+int launch_wgrad16_matrix(const GemmArgs& p, const GemmCall& c, const Wgrad16Plan& pl) {
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    float* colsum_part = c.colsum_out ? reinterpret_cast<float*>(ws + pl.colsum_offset) : nullptr;
+    // the one place where the bf16 forms become operands: dy16 stands for A (rows of M features), x16 for B (rows of N features)
+    const __bf16* dy16 = static_cast<const __bf16*>(c.dy16);
+    const __bf16* x16 = static_cast<const __bf16*>(c.x16);
+    const int Kp = pl.Kp;
+    dim3 block(256);
+    GemmArgs pv = p;                      // C / ldc / slab_stride / epi: the slabs (run_gemm)
+    pv.k_per_slice = pl.k_per_slice;
+    pv.vec_epilogue = pl.vec_epilogue ? 1 : 0;
+    if (pl.kernel == WK_TOKEN_MAJOR) {
         if (colsum_part && p.A)       // the fp32 gradient exists too: the bias gradient stays its exact column sum
-            hipLaunchKernelGGL(colsum_tok_kernel<float>, dim3((p.M + 255) / 256, p.K / 64), block, 0, stream, p.A, p.lda, p.M, colsum_part);
-        else if (colsum_part) {      // bf16-only gradient: summed by the matrix kernel itself, one partial row per K slice
-            pt.colsum = colsum_part;
-            *colsum_parts = slices;
-        }
-        pt.vec_epilogue = 1;
-        pt.a16 = nullptr; pt.c16 = nullptr; pt.b16 = nullptr;
-        PieceArgs qt{static_cast<const __bf16*>(p.b16), static_cast<const __bf16*>(p.a16), p.K};
-        launch_dma<4, 64, 2, true>(pt, qt, stream);
+            hipLaunchKernelGGL(colsum_tok_kernel<float>, dim3((p.M + 255) / 256, p.K / 64), block, 0, c.stream, p.A, p.lda, p.M, colsum_part);
+        else pv.colsum = colsum_part;      // bf16-only gradient: summed by the matrix kernel itself, one partial row per K slice
+        launch_dma<4, 64, 2, true>(pv, PieceArgs{dy16, x16, p.K}, c.stream);
         return d2s_check_launch();
     }
-    if (p.b16 && !p.A)   // bf16 data path: dy handed over in bf16 ONLY (the gradient a GEMM epilogue / attention backward wrote in that form); its
+    __bf16* Ap = reinterpret_cast<__bf16*>(ws + pl.piece_offset);
+    __bf16* Bp = reinterpret_cast<__bf16*>(ws + pl.b_offset);
+    const dim3 ga((p.M + 63) / 64, (Kp + 63) / 64), gb((p.N + 63) / 64, (Kp + 63) / 64);
+    if (dy16 && !p.A)    // bf16 data path: dy handed over in bf16 ONLY (the gradient a GEMM epilogue / attention backward wrote in that form); its
                          // column sums - the bias gradient - are then sums of the bf16 values, as under torch.autocast
-        hipLaunchKernelGGL((split_cols_kernel<1, __bf16>), dim3((p.M + 63) / 64, (Kp + 63) / 64), block, 0, stream, static_cast<const __bf16*>(p.b16), p.lda, Ap,
-                           p.M, p.K, Kp, (int)((p.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.b16) & 7) == 0)), colsum_part);
+        hipLaunchKernelGGL((split_cols_kernel<1, __bf16>), ga, block, 0, c.stream, dy16, p.lda, Ap, p.M, p.K, Kp,
+                           (int)((p.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(dy16) & 7) == 0)), colsum_part);
     else
-        hipLaunchKernelGGL(split_cols_kernel<1>, dim3((p.M + 63) / 64, (Kp + 63) / 64), block, 0, stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA, colsum_part);
-    if (p.a16)      // weight gradient on the bf16 data path: the layer input x ([tokens][n_in]) was saved in bf16 only
-        hipLaunchKernelGGL((split_cols_kernel<1, __bf16>), dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, stream, static_cast<const __bf16*>(p.a16), p.ldb, Bp,
-                           p.N, p.K, Kp, (int)((p.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.a16) & 7) == 0)), static_cast<float*>(nullptr));
+        hipLaunchKernelGGL(split_cols_kernel<1>, ga, block, 0, c.stream, p.A, p.lda, Ap, p.M, p.K, Kp, p.vecA, colsum_part);
+    if (x16)        // weight gradient on the bf16 data path: the layer input x ([tokens][n_in]) was saved in bf16 only
+        hipLaunchKernelGGL((split_cols_kernel<1, __bf16>), gb, block, 0, c.stream, x16, p.ldb, Bp, p.N, p.K, Kp,
+                           (int)((p.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(x16) & 7) == 0)), static_cast<float*>(nullptr));
     else
-        hipLaunchKernelGGL(split_cols_kernel<1>, dim3((p.N + 63) / 64, (Kp + 63) / 64), block, 0, stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
-    GemmArgs pv = p;                      // p.C / p.ldc / p.slab_stride / p.k_per_slice / p.epi were set by the caller
-    pv.vec_epilogue = (epilogue_vec_ok(p) && (p.slab_stride % 4 == 0)) ? 1 : 0;
-    pv.a16 = nullptr; pv.c16 = nullptr; pv.b16 = nullptr;
-    PieceArgs q{Ap, Bp, Kp};
-    if (split_tn_use_dma(p.M, p.N, p.K) && pv.vec_epilogue && p.k_per_slice % 64 == 0) {
-        launch_dma<4, 64, 2>(pv, q, stream);
-        return d2s_check_launch();
-    }
-    const int tiles = ((p.M + SBM - 1) / SBM) * ((p.N + SBN - 1) / SBN);
-    size_t lds = (size_t)split * (SBM + SBN) * (32 + 8) * sizeof(__bf16);
-    if (lds < 4 * epi_stage_floats(2) * sizeof(float)) lds = 4 * epi_stage_floats(2) * sizeof(float);
-    hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, false>), dim3(tiles, 1, slices), block, lds, stream, pv, q);
+        hipLaunchKernelGGL(split_cols_kernel<1>, gb, block, 0, c.stream, p.B, p.ldb, Bp, p.N, p.K, Kp, p.vecB, static_cast<float*>(nullptr));
+    const PieceArgs q{Ap, Bp, Kp};
+    if (pl.kernel == WK_DMA_PIECES) launch_dma<4, 64, 2>(pv, q, c.stream);
+    else hipLaunchKernelGGL((gemm_pieces_nt_kernel<1, 32, false>), dim3(((p.M + SBM - 1) / SBM) * ((p.N + SBN - 1) / SBN), 1, pl.slices), block,
+                            pieces_lds_bytes(1), c.stream, pv, q);
     return d2s_check_launch();
 }
 

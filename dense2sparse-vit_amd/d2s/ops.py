@@ -154,15 +154,20 @@ class Bf16Weights:
                 _W16[(w.data_ptr(), True)] = (None, weights_epoch, w._version, shape, wt16)
 
 
-def gemm(layout, A, lda, B, ldb, C, ldc, M, N, K, epi=EPI_NONE, bias=None, aux=None, ldaux=0, aux_out=None, aux_rows=0,
-         remap_rows=0, remap_skip=0, accumulate=False, a16=None, c16=None, b16=None, rowscale=None, rows_per_group=0):
-    mode = get_gemm_mode()
+def _gemm_workspace(layout, M, N, K, mode, device):
+    """The workspace of a d2s_gemm_f32 / d2s_linear_wgrad_f32 call (layout TN: M = n_out, N = n_in, K = tokens), None where it needs none;
+    the size query is made once per problem."""
     qk = (layout, M, N, K, mode)
     need = _WS_NEED.get(qk)
     if need is None:
         need = _WS_NEED[qk] = lib.query("d2s_gemm_f32_workspace_bytes", layout, M, N, K, mode)
-    dev = C.device if C is not None else c16.device
-    ws = workspace(need, dev) if need else None
+    return workspace(need, device) if need else None
+
+
+def gemm(layout, A, lda, B, ldb, C, ldc, M, N, K, epi=EPI_NONE, bias=None, aux=None, ldaux=0, aux_out=None, aux_rows=0,
+         remap_rows=0, remap_skip=0, accumulate=False, a16=None, c16=None, b16=None, rowscale=None, rows_per_group=0):
+    mode = get_gemm_mode()
+    ws = _gemm_workspace(layout, M, N, K, mode, C.device if C is not None else c16.device)
     if epi == EPI_BIAS_RESID_ROWSCALE:      # stochastic depth: its own entry point, every arithmetic mode (bf16 side channels in mode 2 only)
         assert rowscale is not None and rows_per_group > 0 and aux is not None and not accumulate and remap_rows == 0 and aux_rows == 0
         assert rowscale.dtype == torch.float32 and rowscale.is_contiguous() and rowscale.numel() * rows_per_group >= M
@@ -323,8 +328,7 @@ def linear_wgrad(dy, x, dW, accumulate=False, db=None, x16=None, dy16=None):
     M, N = (dy if dy is not None else dy16).shape
     K = (x if x is not None else x16).shape[1]
     mode = get_gemm_mode()
-    need = lib.query("d2s_linear_wgrad_workspace_bytes", M, N, K, mode)
-    ws = workspace(need, dW.device) if need else None
+    ws = _gemm_workspace(TN, N, K, M, mode, dW.device)      # d2s_linear_wgrad_workspace_bytes(M, N, K, mode) is this query
     if x16 is not None:
         assert mode == GEMM_BF16 and x16.dtype == torch.bfloat16 and x16.is_contiguous() and tuple(x16.shape) == (M, K)
         assert dy16 is None or (dy16.dtype == torch.bfloat16 and dy16.is_contiguous() and tuple(dy16.shape) == (M, N))

@@ -193,6 +193,32 @@ def test_gemm_plan_header_and_binding_tables():
     assert res is lib.Z and argt == lib.signature("d2s_gemm_f32_workspace_bytes")[1]      # a size_t query: no stream is appended
     params = re.search(r"d2s_gemm_f32_plan\((.*?)\);", text, flags=re.S).group(1).split(",")
     assert len(params) == len(argt) and "stream" not in "".join(params)
-    # the launch, the workspace query and the plan query read tile and slices from one helper
-    src = open(os.path.join(REPO, "dense2sparse-vit_amd", "csrc", "gemm_f32.hip")).read()
-    assert src.count("exact_plan(") == 5 and src.count("pick_tile(") == 2 and src.count("nt_slices(") == 2
+    # the launch, the workspace query and the plan query read tile, slices and workspace bytes from one helper: its definition, one
+    # call in each of the three, and nothing else chooses a tile or a slice count
+    csrc = os.path.join(REPO, "dense2sparse-vit_amd", "csrc")
+    src = open(os.path.join(csrc, "gemm_f32.hip")).read()
+    assert src.count("exact_plan(") == 4 and src.count("pick_tile(") == 2 and src.count("nt_slices(") == 2
+    # the same for the two plans of the bf16 / bf16x3 paths: defined beside their kernels, called by the workspace query and by the launch
+    # (run_gemm, which hands the plan to the launcher), and nowhere else
+    split = open(os.path.join(csrc, "gemm_split.hip")).read()
+    for plan in ("split_plan(", "wgrad16_plan("):
+        assert split.count(plan) == 1 and src.count(plan) == 2, plan
+        query = src[src.index("size_t d2s_gemm_f32_workspace_bytes("):src.index("size_t d2s_gemm_f32_plan(")]
+        run = src[src.index("static int run_gemm("):src.index("int d2s_gemm_f32(int layout")]
+        assert query.count(plan) == 1 and run.count(plan) == 1, plan
+    # the weight gradient's LDS-DMA predicate: its definition and one evaluation, inside wgrad16_plan
+    assert split.count("split_tn_use_dma(") == 2 and src.count("split_tn_use_dma(") == 0
+    body = split[split.index("Wgrad16Plan wgrad16_plan("):split.index("int launch_wgrad16_matrix(")]
+    assert body.count("split_tn_use_dma(") == 1
+
+
+def test_workspace_queries_return_the_recorded_sizes():
+    """tests/golden/gemm_workspace_bytes.json: what the two queries returned before the GEMM host code was rewritten around one plan per
+    path (tools/gen_golden.py gemm_workspace; host arithmetic at the fallback CU count 256, which is also the MI355X's)."""
+    import json
+    from d2s import lib
+    rec = json.load(open(os.path.join(REPO, "tests", "golden", "gemm_workspace_bytes.json")))
+    assert len(rec["d2s_gemm_f32_workspace_bytes"]) > 1500 and len(rec["d2s_linear_wgrad_workspace_bytes"]) == 108
+    for name, rows in rec.items():
+        for *args, want in rows:
+            assert lib.query(name, *args) == want, (name, args, want)

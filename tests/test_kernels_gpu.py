@@ -591,6 +591,55 @@ def test_linear_wgrad_bf16_input(ops, tokens, n_out, n_in):
         ops.set_gemm_mode(ops.GEMM_EXACT)
 
 
+def _workspace_contract(need, call):
+    """`call(ws_ptr, ws_bytes)` -> return code: one byte less than the queried size and a null workspace are D2S_ERR_WORKSPACE (-2), the
+    queried size is accepted (0), in that order, so that the result the caller checks afterwards is the accepted call's"""
+    from d2s import lib
+    assert need > 1
+    ws = torch.empty(need, dtype=torch.uint8, device=_dev())
+    assert call(lib.ptr(ws), need - 1) == -2
+    assert call(None, need) == -2
+    assert call(lib.ptr(ws), need) == 0
+
+
+def test_gemm_workspace_contract_outside_the_exact_mode():
+    """Modes 1 and 2 of the NT / NN layouts (K = 40 is no multiple of 32: padded pieces) and the mode-2 weight gradient with more than one K
+    slice, fp32 and bf16 layer input: each call checks its workspace against the size its query names, and the accepted call's result
+    is right (float64 reference; tolerances of test_gemm_split_modes and test_linear_wgrad_bf16_mode for the mode)."""
+    from d2s import lib
+    st = lib.stream()
+    M, N, K = 64, 96, 40
+    x, w = _rand("wcx", (M, K)).to(_dev()), _rand("wcw", (N, K), 0.05).to(_dev())
+    wt = w.t().contiguous()                                              # NN: B stored [K][N]
+    ref = (x.double() @ w.double().t()).cpu().numpy()
+    for mode, rtol, atol in ((1, 1e-4, 2e-5), (2, 3e-2, 3e-2)):
+        for layout, b, ldb in ((0, w, K), (1, wt, N)):
+            out = torch.full((M, N), float("nan"), device=_dev())
+            need = lib.query("d2s_gemm_f32_workspace_bytes", layout, M, N, K, mode)
+            _workspace_contract(need, lambda ws, nbytes: lib._fn("d2s_gemm_f32")(
+                layout, lib.ptr(x), K, lib.ptr(b), ldb, lib.ptr(out), N, M, N, K, 0, None, None, 0, None, 0, 0, 0, 0, mode, ws, nbytes, st))
+            np.testing.assert_allclose(out.cpu().double().numpy(), ref, rtol=rtol, atol=atol, err_msg=f"mode {mode} layout {layout}")
+    tokens, n_out, n_in = 600, 96, 72
+    g = torch.Generator().manual_seed(tokens + n_in)
+    dy, xin = torch.randn(tokens, n_out, generator=g).to(_dev()), torch.randn(tokens, n_in, generator=g).to(_dev())
+    x16 = xin.bfloat16()
+    ref_w, ref_b, scale = (dy.double().t() @ xin.double()).cpu(), dy.double().sum(0).cpu(), math.sqrt(tokens)
+    need = lib.query("d2s_linear_wgrad_workspace_bytes", tokens, n_out, n_in, 2)
+    calls = {"fp32 x": lambda dW, db: (lambda ws, nbytes: lib._fn("d2s_linear_wgrad_f32")(
+                 lib.ptr(dy), n_out, lib.ptr(xin), n_in, lib.ptr(dW), n_in, lib.ptr(db), tokens, n_out, n_in, 0, 2, ws, nbytes, st)),
+             "bf16 x": lambda dW, db: (lambda ws, nbytes: lib._fn("d2s_linear_wgrad_f32_bf16x")(
+                 lib.ptr(dy), None, n_out, lib.ptr(x16), n_in, lib.ptr(dW), n_in, lib.ptr(db), tokens, n_out, n_in, 0, ws, nbytes, st))}
+    got = {}
+    for name, make in calls.items():
+        dW, db = torch.full((n_out, n_in), float("nan"), device=_dev()), torch.full((n_out,), float("nan"), device=_dev())
+        _workspace_contract(need, make(dW, db))
+        assert (dW.cpu().double() - ref_w).abs().max() <= 0.02 * scale, name
+        assert (dW.cpu().double() - ref_w).pow(2).mean().sqrt() <= 0.004 * scale, name
+        assert (db.cpu().double() - ref_b).abs().max() <= 2e-6 * scale * 10, name
+        got[name] = (dW, db)
+    assert torch.equal(got["fp32 x"][0], got["bf16 x"][0]) and torch.equal(got["fp32 x"][1], got["bf16 x"][1])
+
+
 @pytest.mark.parametrize("M,N,K", [(600, 384, 1536), (3168, 384, 1536), (257, 96, 2048), (1000, 200, 1024)])
 def test_gemm_small_grid_split_k_epilogues(ops, M, N, K):
     """Forward / dgrad GEMMs with a small tile grid and a long K split K and apply their epilogue in the ordered slab combine

@@ -523,7 +523,31 @@ def gen_checkpoint_ingestion(dv):
     print("checkpoint.npz", {k: tuple(v.shape) for k, v in out.items()})
 
 
+def gen_gemm_workspace_bytes():
+    """What the BUILT library's two GEMM workspace queries return (host arithmetic; the CU count falls back to 256 without a GPU), recorded
+    before a change to the GEMM host code so that the changed library can be held to the same numbers: `gen_golden.py gemm_workspace`."""
+    import json
+    from d2s import lib
+    from tests import gemm_cases as C
+    deit = [(D, no, ni) for D in (192, 384, 768) for (no, ni) in ((3 * D, D), (D, D), (4 * D, D), (D, 4 * D))]
+    shapes = list(C.all_shapes())
+    shapes += [(rows, no, ni) for (_, no, ni) in deit for rows in (197, 99, 197 * 32, 197 * 128)]           # forward / dgrad: M = rows
+    shapes += [(no, ni, rows) for (_, no, ni) in deit for rows in (197, 99, 197 * 32, 197 * 128)]           # weight gradient: K = rows
+    # K no multiple of 32 / of 64 (padded pieces), and long reductions where rounding to K blocks lowers the slice count
+    shapes += [(64, 96, 40), (96, 72, 600), (130, 132, 1000), (2048, 1024, 100), (4096, 256, 72), (384, 384, 21800), (384, 384, 25216 + 32),
+               (256, 256, 2080), (300, 260, 4100), (1536, 384, 2049)]
+    gemm = [[lay, M, N, K, mode, lib.query("d2s_gemm_f32_workspace_bytes", lay, M, N, K, mode)]
+            for (M, N, K) in sorted(set(shapes)) for lay in (0, 1, 2) for mode in (0, 1, 2)]
+    wgrad = [[t, no, ni, mode, lib.query("d2s_linear_wgrad_workspace_bytes", t, no, ni, mode)]
+             for (_, no, ni) in deit for t in (2048, 25216, 50000) for mode in (0, 1, 2)]
+    with open(os.path.join(OUT, "gemm_workspace_bytes.json"), "w") as f:
+        json.dump({"d2s_gemm_f32_workspace_bytes": gemm, "d2s_linear_wgrad_workspace_bytes": wgrad}, f, separators=(",", ":"))
+    print("gemm_workspace_bytes.json", len(gemm), len(wgrad))
+
+
 def main():
+    if sys.argv[1:] == ["gemm_workspace"]:      # needs the built library only, not the reference
+        return gen_gemm_workspace_bytes()
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
